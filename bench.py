@@ -46,6 +46,7 @@ MFCC_FLOP_PER_FRAME = 25_000                 # FFT-512 + window 
 PEAK_TFLOPS = {"bf16": 2500.0, "bf16x3": 2500.0, "f16mx": 2500.0, "f32": 157.3}   # MI355X_MICROARCH.md dense MFMA peaks
 MFMA_PASSES = {"bf16": 1, "bf16x3": 3, "f16mx": 1.5, "f32": 1}                        # MFMA passes per algorithmic FLOP
 TOLERANCE = 1e-4                             # north_star: max-abs x-vector deviation vs the fp32 reference path
+DUMP_LIMIT_BYTES = 64 << 20                  # --dump-outputs: at most this much in all
 KERNELS = {"bf16": "tdnn_bf16r16_kernel (K=1536 layers) + tdnn_bf16h_kernel (K<=768 layers)",
            "bf16x3": "tdnn_x3r_kernel<.., SPLIT> (tdnn2-4) + tdnn_x3s_kernel (tdnn5 + pooling) + tdnn_x3r_kernel (tdnn1)",
            "f16mx": "tdnn_mx_kernel (csrc/tdnn_mx.hip): v_mfma_f32_16x16x32_f16 + 2 x v_mfma_scale_f32_16x16x128_f8f6f4 (fp4 x fp4, fp4 x fp6) per 128 K",
@@ -67,7 +68,10 @@ def parse_args(argv=None):
     ap.add_argument("--gemm", default="f16mx", choices=["bf16", "bf16x3", "f16mx", "f32"])
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-gather", action="store_true")
-    ap.add_argument("--dump-xvectors", default=None, help="rank 0 saves the x-vectors of the last timed step (all ranks' when gathered) as .npy (tests)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="rank 0 writes what the timed path returned in its last timed step as DIR/<name>.npy: xvectors.npy, float32 "
+                         "(all ranks' when gathered; a fixed seeded sample of rows beyond DUMP_LIMIT_BYTES). The inputs depend on the "
+                         "arguments only, so two builds can be compared output for output")
     ap.add_argument("--no-extra", action="store_true", help="skip the side measurements (other modes, latency, PLDA)")
     ap.add_argument("--no-parity", action="store_true", help="measurement runs of timing-only ablation builds (tools/mx): no oracle comparison, no finite check")
     ap.add_argument("--mx-loader", action="store_true", help="A/B: f16mx on the loader-wave kernel (csrc/tdnn_mxl.hip) instead of the 256 x 256 eight-wave kernel")
@@ -75,7 +79,10 @@ def parse_args(argv=None):
     ap.add_argument("--atomic-pooling", action="store_true", help="fp64-atomic fused pooling instead of the reproducible form")
     ap.add_argument("--n1-json", default=None, help="a file holding the JSON line of the N = 1 run of this bench: the N > 1 line then carries "
                                                     "`scaling_summary` (value / (N x value at N = 1)); the driver computes efficiency itself, this is a convenience")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 # --------------------------------------------------------------------------------------------- self-launch (N > 1)
@@ -189,6 +196,7 @@ def main(argv=None):
             probe_region_ms = 1e3 * dt_i / args.steps
         else:
             regions.append({"dt": dt_i, "dt_local": dt_local, "gemm": ops_prof.finish(restore=False)})
+            y_timed = y                              # (the clock-probe region behind the timed ones is not a timed step)
     ops_prof.restore()
     order = sorted(range(len(regions)), key=lambda i: regions[i]["dt"])
     med = order[len(order) // 2]
@@ -207,8 +215,8 @@ def main(argv=None):
         if world > 1:
             torch.distributed.destroy_process_group()
         return
-    if args.dump_xvectors:
-        np.save(args.dump_xvectors, y.detach().cpu().numpy())
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"xvectors": y_timed})
 
     value = world * B * args.steps / dt
     out = {
@@ -279,6 +287,24 @@ def main(argv=None):
     print(json.dumps(out))
     if world > 1:
         torch.distributed.destroy_process_group()
+
+
+def dump_outputs(out_dir, arrays, limit=DUMP_LIMIT_BYTES):
+    """{name: (rows, ...) tensor} -> out_dir/<name>.npy, float64 kept, anything else as float32. Beyond `limit` bytes in all, each
+    array keeps the same share of its rows, picked with a fixed seed and kept in order: the same arguments dump the same rows."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    host = {}
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy()
+        host[name] = a if a.dtype == np.float64 else a.astype(np.float32)
+    total = sum(a.nbytes for a in host.values())
+    for name, a in host.items():
+        if total > limit:
+            keep = a.shape[0] * limit // total
+            a = a[np.sort(np.random.default_rng(0).choice(a.shape[0], keep, replace=False))]
+            print(f"bench: --dump-outputs keeps a seeded sample of {keep} of the {host[name].shape[0]} rows of {name}", file=sys.stderr)
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 class _GemmProfiler:

@@ -30,11 +30,11 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 @pytest.mark.parametrize("N", [2, 4])
 def test_bench_ranks_on_one_gpu_gather_every_shard(tmp_path, N):
     B, sec = 48, 3.0
-    dump = str(tmp_path / "xv.npy")
+    dump = str(tmp_path / "outputs")
     env = dict(os.environ, KTF_SHARE_GPU="1", KTF_DIST_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     env.pop("WORLD_SIZE", None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(N), "--steps", "2", "--warmup", "1", "--no-extra", "--no-cpu-baseline",
-           "--no-parity", "--batch", str(B), "--seconds", str(sec), "--gemm", "f32", "--dump-xvectors", dump]
+           "--no-parity", "--batch", str(B), "--seconds", str(sec), "--gemm", "f32", "--dump-outputs", dump]
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     line = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
@@ -44,7 +44,7 @@ def test_bench_ranks_on_one_gpu_gather_every_shard(tmp_path, N):
     assert pr["ranks"] == N and 0 < pr["min"] <= pr["max"] and abs(pr["max"] - line["ms_per_step"]) < 1e-6 * pr["max"]
     assert line["config"]["collective_backend"] == "gloo"
     assert line["value"] > 0 and abs(line["value"] - N * B / (line["ms_per_step"] * 1e-3)) < 1e-6 * line["value"]
-    got = np.load(dump)
+    got = np.load(os.path.join(dump, "xvectors.npy"))
     assert got.shape == (N * B, 128)
     # the same extraction in this process: rank r's waveforms come from generator seed 1234 + r (bench.py)
     cfg = synth.extractor_cfg(dither=0.0)
