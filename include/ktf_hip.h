@@ -490,6 +490,47 @@ int ktf_plda_score_f64(const double* test_tr, int64_t N, const double* enroll_tr
 int ktf_plda_score_f32(const float* test_tr, int64_t N, const float* enroll_tr, int64_t M, int32_t dim, const float* psi,
                        float* scores, void* stream);
 
+/* ------------------------------------------------------------------ dense PLDA scoring with conversation-dependent PCA
+ * Kaldi `ivector-plda-scoring-dense` (the scoring stage of x-vector diarization); the reference ships its golden table
+ * (testdata/plda/plda_scores.py, RefPldaScores.ark, --target-energy 0.1) and no implementation. For every recording r of a call
+ * (rows x[first_r .. first_r + lengths[r]), the vectors PLDA.call takes):
+ *   1. m = mean, Sigma = centred covariance, in fp64 (the n x n Gram matrix when n <= dim: the same non-zero spectrum);
+ *   2. its eigenvalues lam (descending) and eigenvectors: batched cyclic Jacobi, at most KTF_PLDA_DENSE_MAX_SWEEPS sweeps;
+ *   3. d as EstPca chooses it, off-by-one included: tot = sum lam; e = 0; d = 1; while (e / tot <= target) e += lam[d++ - 1];
+ *      then clamped to the numerical rank, the count of lam > floor * lam[0] (floor KTF_PLDA_DENSE_RANK_FLOOR_F64 / _F32 by the
+ *      dtype of x; rank 0 when lam[0] <= floor * the mean squared row norm, i.e. rows equal up to rounding) -- this project's only deviation from Kaldi, whose SVD fills directions of zero variance arbitrarily (with
+ *      n = 2 Kaldi's d is always 2, the rank 1). Rank 0 (n = 1, or all rows equal): the recording is scored without PCA;
+ *   4. M = the first d eigenvectors as rows; Plda::ApplyTransform(M) in fp64 gives the model (T', offset', psi') of dimension d;
+ *   5. every row x: y = T' M x + offset', length norm (normalize_length / simple_length_norm) in dimension d, num_examples = 1;
+ *   6. scores_r[i][j] = LLR(y_i | class of y_j), the formula of ktf_plda_*, with psi'.
+ * Steps 1-4 are fp64 whatever the dtype; 5 is fp64 rounded to the dtype; 6 runs in the dtype.
+ * target_energy == KTF_PLDA_DENSE_NO_PCA: no PCA, every block is ktf_plda_*'s scores of the recording's rows, bit for bit. Otherwise
+ * 0 <= target_energy < 1.
+ * x (S, dim) with 1 <= dim <= KTF_PLDA_DENSE_MAX_DIM; lengths: HOST array of R >= 1 counts, each >= 1, summing to S (argument
+ * checks and sizes); lengths_dev: the same R values on the device (the per-recording table is built from them on the device).
+ * A, offset, psi: the model as ktf_plda_* takes it; mean64 (dim), Tinv64 (dim x dim, the inverse of A), psi64 (dim): the model in
+ * fp64 (not read without PCA). Out: scores = the R blocks lengths[r]^2, row-major, one after another; dims (R, device int32) =
+ * the retained d per recording, 0 where it was scored without PCA; *status (device int32) = the number of eigenproblems that did
+ * not converge or subspaces whose within-class covariance was not positive definite: nonzero means the scores are not to be
+ * used. Reading it is the caller's (one word at the end of the call). workspace: a device buffer of at least
+ * ktf_plda_dense_workspace_bytes() bytes (returns a negative KTF_* code on bad arguments). Nothing is copied to or from the host. */
+#define KTF_PLDA_DENSE_NO_PCA (-1.0)
+#define KTF_PLDA_DENSE_MAX_DIM 512
+#define KTF_PLDA_DENSE_MAX_SWEEPS 30
+#define KTF_PLDA_DENSE_JACOBI_LDS 128            /* eigenproblems up to this size run in LDS (fp64), larger ones in the workspace */
+#define KTF_PLDA_DENSE_RANK_FLOOR_F64 1e-10
+#define KTF_PLDA_DENSE_RANK_FLOOR_F32 1e-6       /* fp32 inputs carry ~6e-8 relative rounding: a direction of relative variance
+                                                  * 1e-6 (amplitude 1e-3) is projected with >= 1e-4 relative error */
+int64_t ktf_plda_dense_workspace_bytes(const int32_t* lengths, int32_t R, int32_t dim, double target_energy);
+int ktf_plda_dense_f64(const double* x, int64_t S, int32_t dim, const int32_t* lengths, const int32_t* lengths_dev, int32_t R,
+                       double target_energy, const double* A, const double* offset, const double* psi, const double* mean64,
+                       const double* Tinv64, const double* psi64, int32_t normalize_length, int32_t simple_length_norm,
+                       double* scores, int32_t* dims, void* workspace, size_t workspace_bytes, int32_t* status, void* stream);
+int ktf_plda_dense_f32(const float* x, int64_t S, int32_t dim, const int32_t* lengths, const int32_t* lengths_dev, int32_t R,
+                       double target_energy, const float* A, const float* offset, const float* psi, const double* mean64,
+                       const double* Tinv64, const double* psi64, int32_t normalize_length, int32_t simple_length_norm,
+                       float* scores, int32_t* dims, void* workspace, size_t workspace_bytes, int32_t* status, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -3,6 +3,7 @@
 // Replaces: layers/stats/stats_pooling.py:179-295, models/kaldi/xvector_extractor.py:174-184,
 //           layers/plda/plda.py:163-263 of the reference.
 #include "common.h"
+#include "plda_common.h"
 
 // tf.nn.relu of the variance (stats_pooling.py:238, 293): a NaN -- the 0 / 0 of a window without a sampled frame -- stays a NaN (fmax
 // would return 0 and the standard deviation sqrt(epsilon))
@@ -411,156 +412,24 @@ __global__ __launch_bounds__(XT_THREADS) void xvec_tail_reduce_kernel(const floa
 }
 
 // ------------------------------------------------------------------------------------ PLDA
-template <typename R>
-__device__ __forceinline__ R wsum(R v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-template <typename R>
-__device__ __forceinline__ R rsqrt_(R v);
-template <> __device__ __forceinline__ float rsqrt_<float>(float v) { return sqrtf(v); }
-template <> __device__ __forceinline__ double rsqrt_<double>(double v) { return sqrt(v); }
-template <typename R>
-__device__ __forceinline__ R rlog_(R v);
-template <> __device__ __forceinline__ float rlog_<float>(float v) { return logf(v); }
-template <> __device__ __forceinline__ double rlog_<double>(double v) { return log(v); }
-
-// transformVector (plda.py:163-196): one workgroup per input vector; one wave per output row (strided).
+// (device code in plda_common.h, shared with plda_dense.hip)
+// transformVector (plda.py:163-196): one workgroup per input vector.
 template <typename R>
 __global__ __launch_bounds__(256) void plda_transform_kernel(const R* __restrict__ x, int dim, const R* __restrict__ A,
                                                              const R* __restrict__ offset, const R* __restrict__ psi,
                                                              int normalize, int simple, R* __restrict__ out) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smraw[];
-    R* xs = reinterpret_cast<R*>(smraw);
-    R* ys = xs + dim;
-    R* red = ys + dim;
-    const int b = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    for (int i = threadIdx.x; i < dim; i += 256) xs[i] = x[(int64_t)b * dim + i];
-    __syncthreads();
-    for (int r = wave; r < dim; r += 4) {
-        R acc = 0;
-        for (int c = lane; c < dim; c += 64) acc += A[(int64_t)r * dim + c] * xs[c];
-        acc = wsum<R>(acc);
-        if (lane == 0) ys[r] = acc + offset[r];
-    }
-    __syncthreads();
-    R f = 1;
-    if (normalize) {
-        R part = 0;
-        for (int r = threadIdx.x; r < dim; r += 256) {
-            const R v = ys[r];
-            part += simple ? v * v : v * v / (psi[r] + (R)1);
-        }
-        part = wsum<R>(part);
-        if (lane == 0) red[wave] = part;
-        __syncthreads();
-        const R tot = red[0] + red[1] + red[2] + red[3];
-        f = simple ? rsqrt_<R>((R)dim) / rsqrt_<R>(tot) : rsqrt_<R>((R)dim / tot);
-    }
-    for (int r = threadIdx.x; r < dim; r += 256) out[(int64_t)b * dim + r] = ys[r] * f;
+    const int64_t b = blockIdx.x;
+    plda_transform_row<R>(x + b * dim, dim, A, offset, psi, normalize, simple, out + b * dim, smraw);
 }
 
-// logLikelihoodRatio (plda.py:198-245): a 64 x 64 block of (test i, class j) pairs per workgroup, sixteen pairs per thread (rows
-// ti + 16 a, classes tj + 16 b), the dimensions staged through LDS 64 at a time.
-// Per dimension the reference forms  mean = psi / (psi + 1) * y_j,  var1 = 1 + psi / (psi + 1),  var2 = 1 + psi  and sums
-// (y_i - mean)^2 / var1 and y_i^2 / var2. Neither variance depends on the pair and the second sum not on j: a tile computes the
-// per-dimension constants k = psi / (psi + 1), 1 / var1, 1 / var2 once (its only divisions), stages the class rows as k * y_j, sums
-// y_i^2 / var2 once per row, and a pair costs one subtraction, one multiplication and one fused multiply-add per dimension, on operands
-// that four pairs share (it was three fp64 divisions and three LDS reads per pair and dimension: 0.32 ms for 1024 x 1024 trials of
-// dimension 128). Rows are padded by one element: the rows a wave reads side by side would otherwise sit in the same LDS banks.
-#define PLDA_TILE 64
-#define PLDA_DC 64
-#define PLDA_LDS_BYTES(R) (sizeof(R) * (2 * PLDA_TILE * (PLDA_DC + 1) + 2 * PLDA_DC + 8))        // 67,648 B in fp64
+// logLikelihoodRatio (plda.py:198-245): one 64 x 64 block of (test i, class j) pairs per workgroup.
 template <typename R>
 __global__ __launch_bounds__(256) void plda_score_kernel(const R* __restrict__ y, int64_t B, const R* __restrict__ yc,
                                                          int64_t Bc, int dim, const R* __restrict__ psi,
                                                          R* __restrict__ scores) {
-    // rows i: vectors y (B of them, "test"); columns j: vectors yc (Bc of them, the classes); PLDA.call uses y == yc
-    constexpr int LD = PLDA_DC + 1;
     extern __shared__ __attribute__((aligned(16))) unsigned char smraw[];      // PLDA_LDS_BYTES(R)
-    R* yi = reinterpret_cast<R*>(smraw);       // test rows, this chunk of dimensions
-    R* yj = yi + PLDA_TILE * LD;               // class rows times k
-    R* iv1 = yj + PLDA_TILE * LD;
-    R* iv2 = iv1 + PLDA_DC;
-    R* red = iv2 + PLDA_DC;                    // 8
-    const int ti = threadIdx.x >> 4, tj = threadIdx.x & 15;
-    const int64_t i0 = (int64_t)blockIdx.y * PLDA_TILE, j0 = (int64_t)blockIdx.x * PLDA_TILE;
-    // constant terms: sum log(var1) and sum log(var2)
-    R l1 = 0, l2 = 0;
-    for (int d = threadIdx.x; d < dim; d += 256) {
-        const R p = psi[d];
-        l1 += rlog_<R>((R)1 + p / (p + (R)1));
-        l2 += rlog_<R>((R)1 + p);
-    }
-    l1 = wsum<R>(l1); l2 = wsum<R>(l2);
-    if ((threadIdx.x & 63) == 0) { red[threadIdx.x >> 6] = l1; red[4 + (threadIdx.x >> 6)] = l2; }
-    R a[4][4], c[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-        c[u] = 0;
-#pragma unroll
-        for (int v = 0; v < 4; ++v) a[u][v] = 0;
-    }
-    for (int d0 = 0; d0 < dim; d0 += PLDA_DC) {
-        const int dc = min(PLDA_DC, dim - d0);
-        __syncthreads();                                       // (the previous chunk has been consumed)
-        for (int e = threadIdx.x; e < PLDA_TILE * PLDA_DC; e += 256) {
-            const int r = e / PLDA_DC, dd = e - r * PLDA_DC;
-            R vi = 0, vj = 0;
-            if (dd < dc) {
-                const R p = psi[d0 + dd];
-                if (i0 + r < B) vi = y[(i0 + r) * dim + d0 + dd];
-                if (j0 + r < Bc) vj = p * yc[(j0 + r) * dim + d0 + dd] / (p + (R)1);
-            }
-            yi[r * LD + dd] = vi;
-            yj[r * LD + dd] = vj;
-        }
-        if (threadIdx.x < PLDA_DC) {
-            const R p = threadIdx.x < dc ? psi[d0 + threadIdx.x] : (R)0;
-            iv1[threadIdx.x] = (R)1 / ((R)1 + p / (p + (R)1));
-            iv2[threadIdx.x] = (R)1 / ((R)1 + p);
-        }
-        __syncthreads();
-        // sum_d y_i^2 / var2: the sixteen threads of a row group take every sixteenth dimension (added up across the lanes at the end)
-        for (int dd = tj; dd < dc; dd += 16) {
-            const R w2 = iv2[dd];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const R v = yi[(ti + 16 * u) * LD + dd];
-                c[u] += v * v * w2;
-            }
-        }
-        for (int dd = 0; dd < dc; ++dd) {
-            const R w1 = iv1[dd];
-            R vi[4], vj[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                vi[u] = yi[(ti + 16 * u) * LD + dd];
-                vj[u] = yj[(tj + 16 * u) * LD + dd];
-            }
-#pragma unroll
-            for (int u = 0; u < 4; ++u)
-#pragma unroll
-                for (int v = 0; v < 4; ++v) {
-                    const R diff = vi[u] - vj[v];
-                    a[u][v] += diff * diff * w1;
-                }
-        }
-    }
-    const R logdet1 = red[0] + red[1] + red[2] + red[3];       // (written before the first barrier of the chunk loop; dim >= 1)
-    const R logdet2 = red[4] + red[5] + red[6] + red[7];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-#pragma unroll
-        for (int o = 8; o > 0; o >>= 1) c[u] += __shfl_xor(c[u], o, 64);
-        const int64_t i = i0 + ti + 16 * u;
-#pragma unroll
-        for (int v = 0; v < 4; ++v) {
-            const int64_t j = j0 + tj + 16 * v;
-            if (i < B && j < Bc) scores[i * Bc + j] = (R)(-0.5) * (logdet1 + a[u][v]) - (R)(-0.5) * (logdet2 + c[u]);
-        }
-    }
+    plda_score_tile<R>(y, B, yc, Bc, dim, psi, scores, (int64_t)blockIdx.y * PLDA_TILE, (int64_t)blockIdx.x * PLDA_TILE, smraw);
 }
 
 template <typename R>

@@ -137,7 +137,15 @@ PROTOTYPES = {
     "ktf_plda_f32": (C.c_int, [_P, _i64, _i32, _P, _P, _P, _i32, _i32, _P, _P, _P]),
     "ktf_plda_score_f64": (C.c_int, [_P, _i64, _P, _i64, _i32, _P, _P, _P]),
     "ktf_plda_score_f32": (C.c_int, [_P, _i64, _P, _i64, _i32, _P, _P, _P]),
+    "ktf_plda_dense_workspace_bytes": (_i64, [_P, _i32, _i32, C.c_double]),
+    "ktf_plda_dense_f64": (C.c_int, [_P, _i64, _i32, _P, _P, _i32, C.c_double, _P, _P, _P, _P, _P, _P, _i32, _i32, _P, _P, _P,
+                                     C.c_size_t, _P, _P]),
+    "ktf_plda_dense_f32": (C.c_int, [_P, _i64, _i32, _P, _P, _i32, C.c_double, _P, _P, _P, _P, _P, _P, _i32, _i32, _P, _P, _P,
+                                     C.c_size_t, _P, _P]),
 }
+PLDA_DENSE_NO_PCA = -1.0            # ktf_plda_dense_*: target_energy for "no PCA"
+PLDA_DENSE_MAX_DIM = 512
+PLDA_DENSE_MAX_SWEEPS = 30
 
 _lib = None
 

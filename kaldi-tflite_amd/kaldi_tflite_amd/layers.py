@@ -1119,6 +1119,8 @@ class PLDA(Layer):
         self.assertParamShapes()
         self.offset = (-1.0 * (self.transformMat @ self.mean.reshape(self.dim, 1))).reshape(-1).astype(npdt)
         self._dev = None
+        self._dense_dev = self._dense_ws = None
+        self.last_dense_dims = None               # score_dense: retained PCA dimension per recording (device int32)
 
     @staticmethod
     def _torch_dtype(dt):
@@ -1181,6 +1183,65 @@ class PLDA(Layer):
         if self._dev is None or self._dev[0].device != t.device:
             self._prepare(t)
         return ops.plda_score(t, e, self._dev[2])
+
+    def score_dense(self, inputs, lengths=None, target_energy=0.1):
+        """Extension: Kaldi's `ivector-plda-scoring-dense`, the scoring stage of diarization. `inputs` (S, dim) or (S, 1, dim), the
+        vectors `call` takes, are the rows of R recordings laid end to end, `lengths[r]` rows each (None: one recording). Each
+        recording gets its own PCA (retaining `target_energy` of its variance as Kaldi's EstPca counts it, clamped to the
+        numerical rank), the model is projected into that subspace, and every pair of its rows is scored.
+        target_energy None: no PCA, every block is `call`'s scores of that recording's rows, bit for bit.
+        -> a list of R (n_r, n_r) tensors in the layer's dtype, views of one allocation; a single (S, S) tensor when lengths is None.
+        `last_dense_dims` then holds the retained dimension per recording (device int32; 0 = scored without PCA)."""
+        shape = tuple(inputs.shape)
+        if len(shape) not in (2, 3) or (len(shape) == 3 and shape[1] != 1):
+            raise ValueError(f"expected (rows, dim) or (rows, 1, dim) input, got {shape}")
+        if shape[-1] != self.dim:
+            raise ValueError(f"expected input vector dimension to be {self.dim}, got {shape[-1]}")
+        if self.dim > L.PLDA_DENSE_MAX_DIM:
+            raise ValueError(f"dense scoring needs dim <= {L.PLDA_DENSE_MAX_DIM}, got {self.dim} (PLDA.call serves any dim)")
+        if target_energy is not None:
+            if isinstance(target_energy, bool) or not isinstance(target_energy, (int, float, np.floating, np.integer)):
+                raise ValueError(f"target_energy must be a number in [0, 1) or None, got {target_energy!r}")
+            if not 0.0 <= float(target_energy) < 1.0:
+                raise ValueError(f"target_energy must be in [0, 1) (None: no PCA), got {target_energy}")
+        S = shape[0]
+        single = lengths is None
+        if single:
+            lens = [S]
+        else:
+            arr = np.asarray(lengths.tolist() if isinstance(lengths, torch.Tensor) else lengths)
+            if arr.ndim != 1 or (arr.size and arr.dtype.kind not in "iu"):
+                raise ValueError(f"lengths must be a 1-D sequence of integers, got {lengths!r}")
+            lens = [int(n) for n in arr]
+        if not lens or min(lens) < 1:
+            raise ValueError(f"every recording needs at least one row, got lengths {lens}")
+        if sum(lens) != S:
+            raise ValueError(f"lengths add up to {sum(lens)} rows, the input has {S}")
+        x = self._prepare(inputs)
+        A, off, psi = self._dev
+        if getattr(self, "_dense_dev", None) is None or self._dense_dev[0].device != x.device:
+            T = np.asarray(self.transformMat, np.float64)
+            f = lambda a: torch.as_tensor(np.array(a, np.float64), device=x.device)  # noqa: E731
+            self._dense_dev = (f(self.mean), f(np.linalg.inv(T)), f(self.psi))
+        if getattr(self, "_dense_ws", None) is None:
+            from .models import _Workspace
+            self._dense_ws = _Workspace()
+        ws = self._dense_ws
+        scores, dims, status = ops.plda_dense(x, lens, target_energy, A, off, psi, *self._dense_dev, self.normalizeLength,
+                                              self.simpleLengthNorm,
+                                              scratch=lambda role, shp, dt: ws.get(role, shp, dt, x.device, padded=False))
+        self.last_dense_dims = dims
+        bad = int(status.item())                   # the call's one device -> host read
+        if bad:
+            raise L.KtfBackendError(f"PLDA.score_dense: {bad} per-recording eigenproblem(s) did not converge within "
+                                    f"{L.PLDA_DENSE_MAX_SWEEPS} Jacobi sweeps or gave a singular subspace model")
+        if single:
+            return scores.view(S, S)
+        out, o = [], 0
+        for n in lens:
+            out.append(scores[o:o + n * n].view(n, n))
+            o += n * n
+        return out
 
     def call(self, inputs):
         x = self._prepare(inputs)

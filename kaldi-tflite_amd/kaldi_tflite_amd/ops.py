@@ -393,6 +393,44 @@ def plda_score(test_tr, enroll_tr, psi):
     return scores
 
 
+def plda_dense_workspace_bytes(lengths, dim, target_energy):
+    """Bytes of scratch ktf_plda_dense_* needs (lengths: host ints; target_energy None = no PCA)."""
+    lib = L.load()
+    lens = np.ascontiguousarray(lengths, dtype=np.int32)
+    t = L.PLDA_DENSE_NO_PCA if target_energy is None else float(target_energy)
+    n = lib.ktf_plda_dense_workspace_bytes(lens.ctypes.data_as(C.c_void_p), len(lens), int(dim), t)
+    if n < 0:
+        L.check(int(n), "ktf_plda_dense_workspace_bytes")
+    return int(n)
+
+
+def plda_dense(x, lengths, target_energy, A, offset, psi, mean64, Tinv64, psi64, normalize_length, simple_length_norm,
+               scratch=None):
+    """Dense per-recording scoring (ktf_plda_dense_*). x (S, dim) on the device, lengths host ints (R), target_energy None = no PCA.
+    -> (scores: the R blocks n_r x n_r packed in one 1-D tensor, dims (R,) int32, status (1,) int32 -- the device word the caller
+    reads once). `scratch(role, shape, dtype)` hands out workspace tensors (a fresh allocation each call without it)."""
+    lib = L.load()
+    S, dim = x.shape
+    lens = np.ascontiguousarray(lengths, dtype=np.int32)
+    R = len(lens)
+    t = L.PLDA_DENSE_NO_PCA if target_energy is None else float(target_energy)
+    nbytes = plda_dense_workspace_bytes(lens, dim, target_energy)
+    get = scratch or (lambda role, shape, dtype: torch.empty(shape, dtype=dtype, device=x.device))
+    ws = get("plda_dense_ws", (nbytes,), torch.uint8)
+    status = get("plda_dense_status", (1,), torch.int32)
+    lens_dev = get("plda_dense_lengths", (R,), torch.int32)
+    lens_dev.copy_(torch.from_numpy(lens))
+    scores = torch.empty((int(np.sum(lens.astype(np.int64) ** 2)),), dtype=x.dtype, device=x.device)
+    dims = torch.empty((R,), dtype=torch.int32, device=x.device)
+    fn = lib.ktf_plda_dense_f64 if x.dtype == torch.float64 else lib.ktf_plda_dense_f32
+    with L.on_device(x.device):
+        rc = fn(L.ptr(x), S, dim, lens.ctypes.data_as(C.c_void_p), L.ptr(lens_dev), R, t, L.ptr(A), L.ptr(offset), L.ptr(psi),
+                L.ptr(mean64), L.ptr(Tinv64), L.ptr(psi64), int(normalize_length), int(simple_length_norm), L.ptr(scores),
+                L.ptr(dims), L.ptr(ws), ws.numel(), L.ptr(status), L.stream_ptr())
+    L.check(rc, "ktf_plda_dense")
+    return scores, dims, status
+
+
 def split_bf16(src, D, planes, lens=None):
     """fp32 (B,T,ld_src) rows -> planes (2,B,T,ld) bf16: hi = bf16(v), lo = bf16(v - hi); pad columns zero. `lens`: only the rows
     t < lens[b] are converted (the consumers never read the rest)."""
