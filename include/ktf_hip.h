@@ -531,6 +531,30 @@ int ktf_plda_dense_f32(const float* x, int64_t S, int32_t dim, const int32_t* le
                        const double* Tinv64, const double* psi64, int32_t normalize_length, int32_t simple_length_norm,
                        float* scores, int32_t* dims, void* workspace, size_t workspace_bytes, int32_t* status, void* stream);
 
+/* ------------------------------------------------------------------ agglomerative clustering of dense PLDA scores
+ * Kaldi `agglomerative-cluster` (AgglomerativeClusterer, single pass), the stage of x-vector diarization after
+ * ktf_plda_dense_*. For every recording r (its n = lengths[r] rows): costs C = read_costs ? scores : -scores, of which only the
+ * strict upper triangle (i < j) is read (the diagonal and the lower triangle may hold anything, NaN included). Every row starts
+ * as its own cluster (ids 1 .. n, size 1); Sigma(a, b) = the sum of the costs between two clusters, avg = Sigma / dtype(size_a *
+ * size_b). While more than min_clusters clusters are active, the eligible pair (avg <= threshold and size_a + size_b <=
+ * ceil(fp32(n) * fp32(max_spk_fraction))) with the smallest (avg, lo_id, hi_id) is merged into a cluster with the next id
+ * (n + 1, n + 2, ...), Sigma(k, new) = Sigma(k, a) + Sigma(k, b). Labels 1 .. K go to the final clusters in ascending id.
+ * All arithmetic is in the dtype of scores (fp32: Kaldi's BaseFloat), threshold is rounded to it.
+ * scores: the R blocks lengths[r]^2, row-major, one after another (ktf_plda_dense_*'s output). lengths: HOST array of R >= 1
+ * counts, each in 1 .. KTF_AHC_MAX_N (argument checks and sizes); lengths_dev: the same R values on the device. min_clusters_dev:
+ * R device int32 (NULL: 1 for every recording). 0 < max_spk_fraction <= 1. Out: labels (S = sum of lengths, device int32, one
+ * per row), num_clusters (R, device int32). workspace: a device buffer of at least ktf_ahc_workspace_bytes() bytes (returns a
+ * negative KTF_* code on bad arguments; dtype_bytes 4 or 8). Nothing is copied to or from the host. */
+#define KTF_AHC_MAX_N 32767                     /* Kaldi's default first-pass-max-utterances: below it Kaldi runs one pass */
+#define KTF_AHC_LDS_SLOTS 5120                  /* recordings up to this size keep the merge loop's per-slot state in LDS */
+int64_t ktf_ahc_workspace_bytes(const int32_t* lengths, int32_t R, int32_t dtype_bytes);
+int ktf_ahc_f64(const double* scores, const int32_t* lengths, const int32_t* lengths_dev, int32_t R, int32_t read_costs,
+                double threshold, const int32_t* min_clusters_dev, double max_spk_fraction, int32_t* labels, int32_t* num_clusters,
+                void* workspace, size_t workspace_bytes, void* stream);
+int ktf_ahc_f32(const float* scores, const int32_t* lengths, const int32_t* lengths_dev, int32_t R, int32_t read_costs,
+                double threshold, const int32_t* min_clusters_dev, double max_spk_fraction, int32_t* labels, int32_t* num_clusters,
+                void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -142,10 +142,15 @@ PROTOTYPES = {
                                      C.c_size_t, _P, _P]),
     "ktf_plda_dense_f32": (C.c_int, [_P, _i64, _i32, _P, _P, _i32, C.c_double, _P, _P, _P, _P, _P, _P, _i32, _i32, _P, _P, _P,
                                      C.c_size_t, _P, _P]),
+    "ktf_ahc_workspace_bytes": (_i64, [_P, _i32, _i32]),
+    "ktf_ahc_f64": (C.c_int, [_P, _P, _P, _i32, _i32, C.c_double, _P, C.c_double, _P, _P, _P, C.c_size_t, _P]),
+    "ktf_ahc_f32": (C.c_int, [_P, _P, _P, _i32, _i32, C.c_double, _P, C.c_double, _P, _P, _P, C.c_size_t, _P]),
 }
 PLDA_DENSE_NO_PCA = -1.0            # ktf_plda_dense_*: target_energy for "no PCA"
 PLDA_DENSE_MAX_DIM = 512
 PLDA_DENSE_MAX_SWEEPS = 30
+AHC_MAX_N = 32767                   # ktf_ahc_*: rows per recording
+AHC_LDS_SLOTS = 5120                # ... up to which the merge loop's state sits in LDS
 
 _lib = None
 

@@ -431,6 +431,40 @@ def plda_dense(x, lengths, target_energy, A, offset, psi, mean64, Tinv64, psi64,
     return scores, dims, status
 
 
+def ahc_workspace_bytes(lengths, dtype_bytes):
+    """Bytes of scratch ktf_ahc_* needs (lengths: host ints)."""
+    lib = L.load()
+    lens = np.ascontiguousarray(lengths, dtype=np.int32)
+    n = lib.ktf_ahc_workspace_bytes(lens.ctypes.data_as(C.c_void_p), len(lens), int(dtype_bytes))
+    if n < 0:
+        L.check(int(n), "ktf_ahc_workspace_bytes")
+    return int(n)
+
+
+def ahc(scores, lengths, threshold, min_clusters, max_spk_fraction, read_costs, scratch=None):
+    """Agglomerative clustering (ktf_ahc_*) of R packed blocks: scores 1-D, the blocks lengths[r]^2 one after another (as
+    plda_dense returns them), lengths host ints, min_clusters None (1) or host ints (R). -> (labels (S,) int32, counts (R,) int32).
+    `scratch(role, shape, dtype)` hands out workspace tensors (a fresh allocation each call without it)."""
+    lib = L.load()
+    lens = np.ascontiguousarray(lengths, dtype=np.int32)
+    R = len(lens)
+    nbytes = ahc_workspace_bytes(lens, scores.element_size())
+    get = scratch or (lambda role, shape, dtype: torch.empty(shape, dtype=dtype, device=scores.device))
+    ws = get("ahc_ws", (nbytes,), torch.uint8)
+    meta = get("ahc_lengths", (2 * R,), torch.int32)          # lengths, then min_clusters
+    host = np.concatenate([lens, np.ones(R, np.int32) if min_clusters is None else np.asarray(min_clusters, np.int32)])
+    meta.copy_(torch.from_numpy(host))
+    labels = torch.empty((int(lens.astype(np.int64).sum()),), dtype=torch.int32, device=scores.device)
+    counts = torch.empty((R,), dtype=torch.int32, device=scores.device)
+    fn = lib.ktf_ahc_f64 if scores.dtype == torch.float64 else lib.ktf_ahc_f32
+    with L.on_device(scores.device):
+        rc = fn(L.ptr(scores), lens.ctypes.data_as(C.c_void_p), L.ptr(meta), R, int(bool(read_costs)), float(threshold),
+                L.ptr(meta[R:]) if min_clusters is not None else None, float(max_spk_fraction), L.ptr(labels), L.ptr(counts),
+                L.ptr(ws), ws.numel(), L.stream_ptr())
+    L.check(rc, "ktf_ahc")
+    return labels, counts
+
+
 def split_bf16(src, D, planes, lens=None):
     """fp32 (B,T,ld_src) rows -> planes (2,B,T,ld) bf16: hi = bf16(v), lo = bf16(v - hi); pad columns zero. `lens`: only the rows
     t < lens[b] are converted (the consumers never read the rest)."""
