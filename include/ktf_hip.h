@@ -555,6 +555,36 @@ int ktf_ahc_f32(const float* scores, const int32_t* lengths, const int32_t* leng
                 double threshold, const int32_t* min_clusters_dev, double max_spk_fraction, int32_t* labels, int32_t* num_clusters,
                 void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------ sliding-window x-vectors of diarization
+ * The project's restatement of the front half of Kaldi's diarization recipe (speech segments -> per-segment sliding CMN ->
+ * overlapping subsegments). R recordings' frames lie end to end in one frame stream: recording r owns frames [offsets[r],
+ * offsets[r + 1]) (offsets: R + 1 device int32, offsets[0] = 0), frames[r] = offsets[r + 1] - offsets[r] on the HOST (argument checks).
+ * seg_work / win_work: 2 * F device int32 each (F = sum of frames): recording r's (start, end) pairs at slot offsets[r]. counts: 2R
+ * device int32, segments per recording then windows per recording. Frame numbers are relative to the recording, ends exclusive.
+ *
+ * Segments of the energy VAD: the threshold and the vote of ktf_vad_cmvn (VAD.call, layers/dsp/vad.py:156-203) over each
+ * recording's own frames[r] frames of mfcc (F, D); a segment is a maximal run of voiced frames. Writes seg_work and counts[0, R). */
+int ktf_diar_segments(const float* mfcc, int32_t D, const int32_t* frames, const int32_t* offsets, int32_t R, const KtfVadCfg* vad,
+                      int32_t* seg_work, int32_t* counts, void* stream);
+/* Windows of the counts[r] segments of seg_work: for a segment [s, e) of L frames, [a, a + W) while L > W + M (a += P, L -= P), then
+ * [a, e): 1 + max(0, ceil((L - W - M) / P)) windows. Needs W > 0, 0 < P <= W, M >= 0. Writes win_work and counts[R, 2R). */
+int ktf_diar_windows(const int32_t* seg_work, const int32_t* frames, const int32_t* offsets, int32_t R, int32_t W, int32_t P, int32_t M,
+                     int32_t* win_work, int32_t* counts, void* stream);
+/* The compact tables: segments (G, 3) and windows (S, 3) device int32 rows (recording, start, end), recording 0's first; G and S are
+ * the sums of the counts (the host reads them in between). */
+int ktf_diar_compact(const int32_t* seg_work, const int32_t* win_work, const int32_t* counts, const int32_t* frames, const int32_t* offsets,
+                     int32_t R, int64_t G, int64_t S, int32_t* segments, int32_t* windows, void* stream);
+/* CMN of every segment's rows of mfcc (F, D) as one utterance: the values of ktf_cmvn_f32 (CMVN.call, layers/normalization/
+ * cmvn.py:186-250) on those rows alone, bit for bit, written to out (F, D) at the same frames (other rows untouched). SAME padding
+ * only. work: F * D floats (segments too long for the LDS). */
+int ktf_diar_segment_cmn(const float* mfcc, int32_t D, const int32_t* frames, const int32_t* offsets, int32_t R, const int32_t* segments,
+                         int64_t G, const KtfCmvnCfg* cmvn, float* out, float* work, void* stream);
+/* Windows [w0, w0 + n) of the table (S, 3) -> out (n, Tw, ldo) of out_dtype (KTF_F32 / KTF_BF16, round to nearest even): row t < len
+ * of window i is row start + t of cmn (F, D), every other element zero; lens[i] = len = min(end - start, Tw). ldo a multiple of 8, cmn
+ * and out 16-byte aligned, cmn allocated with 4 floats beyond F * D (16-byte loads). */
+int ktf_diar_gather(const float* cmn, int32_t D, const int32_t* frames, const int32_t* offsets, int32_t R, const int32_t* windows, int64_t S,
+                    int64_t w0, int64_t n, int32_t Tw, void* out, int32_t out_dtype, int32_t ldo, int32_t* lens, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -145,6 +145,11 @@ PROTOTYPES = {
     "ktf_ahc_workspace_bytes": (_i64, [_P, _i32, _i32]),
     "ktf_ahc_f64": (C.c_int, [_P, _P, _P, _i32, _i32, C.c_double, _P, C.c_double, _P, _P, _P, C.c_size_t, _P]),
     "ktf_ahc_f32": (C.c_int, [_P, _P, _P, _i32, _i32, C.c_double, _P, C.c_double, _P, _P, _P, C.c_size_t, _P]),
+    "ktf_diar_segments": (C.c_int, [_P, _i32, _P, _P, _i32, C.POINTER(VadCfg), _P, _P, _P]),
+    "ktf_diar_windows": (C.c_int, [_P, _P, _P, _i32, _i32, _i32, _i32, _P, _P, _P]),
+    "ktf_diar_compact": (C.c_int, [_P, _P, _P, _P, _P, _i32, _i64, _i64, _P, _P, _P]),
+    "ktf_diar_segment_cmn": (C.c_int, [_P, _i32, _P, _P, _i32, _P, _i64, C.POINTER(CmvnCfg), _P, _P, _P]),
+    "ktf_diar_gather": (C.c_int, [_P, _i32, _P, _P, _i32, _P, _i64, _i64, _i64, _i32, _P, _i32, _i32, _P, _P]),
 }
 PLDA_DENSE_NO_PCA = -1.0            # ktf_plda_dense_*: target_energy for "no PCA"
 PLDA_DENSE_MAX_DIM = 512

@@ -1,5 +1,6 @@
-"""Extension: the clustering stage of x-vector diarization on the device. Kaldi's `agglomerative-cluster` (single pass) over the
-blocks `PLDA.score_dense` returns, batched over recordings."""
+"""Extension: x-vector diarization on the device. Kaldi's `agglomerative-cluster` (single pass) over the blocks `PLDA.score_dense`
+returns, batched over recordings; RTTM lines from window labels and the wav -> RTTM composition `diarize`
+(INTEGRATION.md §2d)."""
 
 import numbers
 
@@ -102,3 +103,93 @@ def agglomerative_cluster(scores, threshold=None, num_speakers=None, max_spk_fra
         out.append(labels[o:o + n])
         o += n
     return out, counts
+
+
+def _labels_host(labels, S):
+    """labels: one (S,) tensor / array, or a list of per-recording ones laid end to end -> (S,) host int64."""
+    parts = list(labels) if isinstance(labels, (list, tuple)) else [labels]
+    arrs = [np.asarray(p.cpu() if isinstance(p, torch.Tensor) else p).reshape(-1) for p in parts]
+    out = np.concatenate(arrs) if arrs else np.zeros(0, np.int64)
+    if out.size != S:
+        raise ValueError(f"{out.size} labels for {S} windows")
+    if out.size and out.dtype.kind not in "iu":
+        raise ValueError(f"labels must be integers, got {out.dtype}")
+    return out.astype(np.int64)
+
+
+def rttm_pieces(starts, ends, labels):
+    """Kaldi make_rttm.py's rule on one recording's windows in start order (times in any unit): where a window ends after the next
+    one starts, both boundaries move to the midpoint (a window whose start already moved keeps that start); then consecutive pieces
+    that touch (end == next start) and carry the same label merge. -> [(start, end, label)]."""
+    st = [float(v) for v in starts]
+    en = [float(v) for v in ends]
+    for i in range(len(st) - 1):
+        if en[i] > st[i + 1]:
+            mid = (en[i] + st[i + 1]) / 2.0
+            en[i] = st[i + 1] = mid
+    out = []
+    for a, b, lab in zip(st, en, labels):
+        if out and out[-1][1] == a and out[-1][2] == lab:
+            out[-1][1] = b
+        else:
+            out.append([a, b, lab])
+    return [tuple(p) for p in out]
+
+
+def rttm(res, labels, reco_ids=None, channel=1):
+    """RTTM lines of `res` (XvectorExtractor.extract_windows' result) and one label per window: one (S,) tensor, or per-recording
+    tensors laid end to end (agglomerative_cluster's list). Per recording, windows in start order, rttm_pieces' rule, then one line
+    `SPEAKER <reco> <channel> <start> <duration> <NA> <NA> <label> <NA> <NA>` per piece, seconds with three decimals. reco_ids: R
+    names (default reco0, reco1, ...). Reads the window table and the labels back to the host; returns a list of str."""
+    R = len(res.lengths)
+    if reco_ids is None:
+        reco_ids = [f"reco{r}" for r in range(R)]
+    reco_ids = list(reco_ids)
+    if len(reco_ids) != R:
+        raise ValueError(f"{len(reco_ids)} reco_ids for {R} recordings")
+    win = res.windows.cpu().numpy().astype(np.int64).reshape(-1, 3)
+    lab = _labels_host(labels, win.shape[0])
+    shift = float(res.frame_shift)
+    lines = []
+    for r in range(R):
+        sel = np.nonzero(win[:, 0] == r)[0]
+        if sel.size == 0:
+            continue
+        order = sel[np.argsort(win[sel, 1], kind="stable")]
+        for a, b, k in rttm_pieces(win[order, 1], win[order, 2], lab[order]):
+            lines.append(f"SPEAKER {reco_ids[r]} {channel} {a * shift:.3f} {(b - a) * shift:.3f} <NA> <NA> {int(k)} <NA> <NA>")
+    return lines
+
+
+class Diarization:
+    """diarize's result: windows (extract_windows' WindowXvectors), labels (S,) int32 and counts (R,) int32 (speakers per recording, 0
+    for a recording without windows) on the GPU, rttm (list of str)."""
+
+    def __init__(self, windows, labels, counts, rttm_lines):
+        self.windows, self.labels, self.counts, self.rttm = windows, labels, counts, rttm_lines
+
+
+def diarize(ext, plda, wavs, target_energy=0.1, threshold=None, num_speakers=None, max_spk_fraction=1.0, segments=None, window=1.5,
+            period=0.75, min_segment=0.5, reco_ids=None):
+    """wav -> RTTM: ext.extract_windows -> plda.score_dense (the recordings with windows) -> agglomerative_cluster -> rttm.
+    num_speakers: None (threshold mode), an int, or R ints (one per recording of wavs). Recordings without windows are left out of
+    scoring and clustering and produce no lines."""
+    res = ext.extract_windows(wavs, window=window, period=period, min_segment=min_segment, segments=segments)
+    R = len(res.lengths)
+    live = [r for r in range(R) if res.lengths[r] > 0]
+    dev = res.xvectors.device
+    counts = torch.zeros((R,), dtype=torch.int32, device=dev)
+    if not live:
+        labels = torch.zeros((0,), dtype=torch.int32, device=dev)
+        return Diarization(res, labels, counts, [])
+    ns = num_speakers
+    if ns is not None and not isinstance(ns, (numbers.Integral, np.integer)):
+        arr = list(ns.tolist() if isinstance(ns, torch.Tensor) else ns)
+        if len(arr) != R:
+            raise ValueError(f"num_speakers must be an int or {R} ints, got {num_speakers!r}")
+        ns = [arr[r] for r in live]
+    scores = plda.score_dense(res.xvectors, lengths=[res.lengths[r] for r in live], target_energy=target_energy)
+    labels, cnt = agglomerative_cluster(scores, threshold=threshold, num_speakers=ns, max_spk_fraction=max_spk_fraction)
+    labels = torch.cat(labels) if len(labels) > 1 else labels[0]
+    counts[torch.as_tensor(live, device=dev)] = cnt
+    return Diarization(res, labels, counts, rttm(res, labels, reco_ids))

@@ -731,6 +731,79 @@ def XvectorExtractorFromConfig(cfgPath, name=None, gemm="f32"):
     return XvectorExtractor(ext, name=name, gemm=gemm)
 
 
+class WindowXvectors:
+    """XvectorExtractor.extract_windows' result. xvectors (S, lda_dim) fp32, the windows of recording 0 then recording 1 ...; lengths: R
+    host ints, windows per recording (PLDA.score_dense's `lengths=`, may hold 0); windows (S, 3) and segments (G, 3) int32 rows
+    (recording, first frame, end frame) -- all on the GPU; frame_shift: seconds per frame."""
+
+    def __init__(self, xvectors, lengths, windows, segments, frame_shift):
+        self.xvectors, self.lengths, self.windows, self.segments, self.frame_shift = xvectors, lengths, windows, segments, frame_shift
+
+
+def seconds_to_frames(x, shift):
+    """floor(x / shift + 0.5): the frame of a time in seconds (sliding-window extraction)."""
+    return int(math.floor(float(x) / float(shift) + 0.5))
+
+
+def window_count(L, W, P, M):
+    """Windows of a segment of L >= 1 frames: 1 + max(0, ceil((L - W - M) / P))."""
+    return 1 + max(0, -(-(L - W - M) // P))
+
+
+def _is_real(v):
+    return isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, (bool, np.bool_))
+
+
+def window_frames(shift, window, period, min_segment):
+    """(W, P, M) in frames; ValueError unless window > 0, 0 < period <= window, min_segment >= 0 (and W, P >= 1 after rounding)."""
+    for name, v in (("window", window), ("period", period), ("min_segment", min_segment)):
+        if not _is_real(v) or not math.isfinite(float(v)):
+            raise ValueError(f"{name} must be a finite number of seconds, got {v!r}")
+    if not float(window) > 0:
+        raise ValueError(f"window must be > 0, got {window}")
+    if not 0 < float(period) <= float(window):
+        raise ValueError(f"period must be in (0, window], got {period} (window {window})")
+    if not float(min_segment) >= 0:
+        raise ValueError(f"min_segment must be >= 0, got {min_segment}")
+    W, P, M = (seconds_to_frames(v, shift) for v in (window, period, min_segment))
+    if W < 1 or P < 1:
+        raise ValueError(f"window and period must be at least one frame ({shift} s), got {window} and {period}")
+    return W, min(P, W), M
+
+
+def caller_segments(segments, frames, shift):
+    """Kaldi `segments` pairs (start_s, end_s) per recording -> lists of (start, end) frames, each end clamped to the recording's
+    frame count; ValueError for a pair that is unsorted, overlaps its predecessor or is empty after clamping."""
+    if not isinstance(segments, (list, tuple)) or len(segments) != len(frames):
+        raise ValueError(f"segments must be a list of {len(frames)} lists of (start_s, end_s) pairs")
+    out = []
+    for r, (segs, T) in enumerate(zip(segments, frames)):
+        rows, prev = [], 0
+        for pair in segs:
+            if len(pair) != 2 or not all(_is_real(v) and math.isfinite(float(v)) for v in pair):
+                raise ValueError(f"recording {r}: a segment must be a (start_s, end_s) pair of numbers, got {pair!r}")
+            if float(pair[1]) < float(pair[0]):
+                raise ValueError(f"recording {r}: segment {pair!r} ends before it starts")
+            s, e = seconds_to_frames(pair[0], shift), min(seconds_to_frames(pair[1], shift), T)
+            if s < prev:
+                raise ValueError(f"recording {r}: segment {pair!r} overlaps the one before it or is out of order")
+            if s < 0 or e <= s:
+                raise ValueError(f"recording {r}: segment {pair!r} is empty after conversion to frames (recording of {T} frames)")
+            rows.append((s, e))
+            prev = e
+        out.append(rows)
+    return out
+
+
+def _one_device(groups):
+    """The device of extract_windows' recordings (after device_samples: host input is on the current GPU by then); ValueError when
+    they are on different devices -- every buffer of the call is allocated on one, before anything is launched."""
+    devs = {x.device for x, _, _ in groups}
+    if len(devs) != 1:
+        raise ValueError(f"the recordings must all be on one GPU (or on the host), got {sorted(str(d) for d in devs)}")
+    return groups[0][0].device
+
+
 class XvectorExtractor:
     """models/kaldi/xvector_extractor.py:74 — wav (batch, samples) in int16 scale -> length-normalised x-vector(s).
 
@@ -916,12 +989,16 @@ class XvectorExtractor:
     def _extract_routed(self, inputs, out=None):
         _, feats, lens = self._features(inputs)
         self.last_lens = lens                                          # voiced-frame counts of the last call (workspace view)
+        return self._route_xvectors(feats, lens, out), feats, lens
+
+    def _route_xvectors(self, feats, lens, out=None):
+        """CMVN'd features + frame counts -> x-vectors, short utterances routed to the tighter mode (route_short_utterances)."""
         B, T = feats.shape[0], feats.shape[1]
         seq = self.xvec
         nshort = seq.frames_floor(seq.gemm)
         if not (self.route_short_utterances and nshort > 0 and T >= nshort and seq.gemm in seq.SHORT_MODE
                 and seq.batch_gemm(B, T) == _GEMM[seq.gemm]):
-            return self._xvectors(feats, lens, out), feats, lens
+            return self._xvectors(feats, lens, out)
         # Per-utterance routing: the batch runs in the model's mode with the utterances of fewer than `nshort` voiced frames masked out
         # (length 0: their tiles leave at once), then once more in the tighter mode with only those utterances live; the second tail
         # writes just their rows. The masks are made on the device (ktf_route_short, one small launch behind VAD / CMVN). Whether the
@@ -947,14 +1024,14 @@ class XvectorExtractor:
         if not capturing:
             self.last_short_count = self._await_short_count(feats.device)
             if self.last_short_count == 0 and not self._warming_for_capture:
-                return y, feats, lens
+                return y
         short_mode = seq.SHORT_MODE[seq.gemm]
         if self._tail_fusable() and self.fuse_tail:
             self._xvectors(feats, lens_short, y, mode=short_mode, skip_empty=True)
         else:                                                          # (tails that write every row: select afterwards)
             y2 = self._xvectors(feats, lens_short, None, mode=short_mode)
             y.copy_(torch.where((lens_short > 0)[:, None], y2, y))
-        return y, feats, lens
+        return y
 
     def _await_short_count(self, dev):
         """The number of short utterances ktf_route_short wrote to pinned memory for this call: the host polls the sequence number
@@ -1030,6 +1107,139 @@ class XvectorExtractor:
             return False
         layer = steps[at][1]
         return self.ldaMat.shape[1] <= 256 and layer.units == self.ldaMat.shape[0] and layer.kernelFlags == 0
+
+    def _recordings(self, wavs):
+        """wavs -> [(samples (B, N) on the device, in_kind, first recording index)]: an (R, N) tensor is one group (one front-end
+        launch), a list is one group per recording."""
+        fr = self.framing
+        if isinstance(wavs, (list, tuple)):
+            items = list(wavs)
+            if not items:
+                raise ValueError("wavs must hold at least one recording")
+            groups = []
+            for r, w in enumerate(items):
+                x, kind = fr.device_samples(w)
+                if x.dim() != 1:
+                    raise ValueError(f"recording {r} must be 1-D, got shape {tuple(x.shape)}")
+                groups.append((x.unsqueeze(0), kind, r))
+            return groups
+        x, kind = fr.device_samples(wavs)
+        if x.dim() == 1:
+            x = x.unsqueeze(0)
+        if x.dim() != 2 or x.shape[0] == 0:
+            raise ValueError(f"wavs must be one 1-D recording, a list of them or an (R, N) tensor, got shape {tuple(x.shape)}")
+        return [(x, kind, 0)]
+
+    def extract_windows(self, wavs, window=1.5, period=0.75, min_segment=0.5, segments=None, max_windows_per_pass=1024):
+        """Extension: x-vectors of the sliding windows of whole recordings, the input of diarization (PLDA.score_dense ->
+        ktf.diarization.agglomerative_cluster -> ktf.diarization.rttm). The project's rules, modelled on Kaldi's diarization recipe
+        (INTEGRATION.md §2d):
+        - MFCC once per recording (the frames of `features(recording)`, bit for bit);
+        - speech segments: maximal runs of the energy VAD's voiced frames over each recording's own frames, or `segments[r]`, a list of
+          (start_s, end_s) pairs per recording (frames floor(x / shift + 0.5), ends clamped to the recording);
+        - the extractor's CMVN over each segment's rows as one utterance (ktf.layers.CMVN on those rows, bit for bit; SAME padding);
+        - windows of W = window, advanced by P = period while more than W + M (M = min_segment) frames are left, then the rest;
+        - each window's x-vector as __call__ computes one for an utterance of its length (same modes and short-utterance routing), in
+          passes of at most `max_windows_per_pass` windows. In exact fp32 a window's x-vector does not depend on the pass.
+        wavs: one 1-D recording, a list of R 1-D recordings of any lengths or an (R, N) tensor (fp32 in int16 scale or int16 PCM).
+        -> WindowXvectors (xvectors, lengths, windows, segments, frame_shift). One device-to-host read (the per-recording counts) with
+        VAD segments, none with caller segments -- while W + M is below the mode's frames_floor (f16mx: 400 frames, so windows up to
+        3.5 s with the default min_segment). Longer windows take __call__'s per-utterance route, which adds one poll of pinned host
+        memory per pass. verify_fraction, compile() and multi-GPU do not apply to this path (all recordings on one device)."""
+        L.require_gpu()
+        fr, mf = self.framing, self.mfcc
+        shift = fr.frameShift / float(fr.sampleFreq)
+        W, P, M = window_frames(shift, window, period, min_segment)
+        if isinstance(max_windows_per_pass, (bool, np.bool_)) or not isinstance(max_windows_per_pass, (int, np.integer)) \
+                or max_windows_per_pass < 1:
+            raise ValueError(f"max_windows_per_pass must be an int >= 1, got {max_windows_per_pass!r}")
+        if self.cmvn.padding != "SAME":
+            raise ValueError("extract_windows needs the extractor's CMVN with SAME padding (VALID would drop the segments' edge frames)")
+        groups = self._recordings(wavs)
+        dev = _one_device(groups)
+        frames = []
+        for x, _, r0 in groups:
+            N = x.shape[1]
+            if N < fr.minSamples():
+                raise ValueError(f"recording {r0} has {N} samples, fewer than a frame ({fr.frameSize})")
+            frames += [fr.numFrames(N)] * x.shape[0]
+        R = len(frames)
+        if segments is not None:
+            segs_f = caller_segments(segments, frames, shift)
+        if not mf.built or mf._M != fr.frameWidth:
+            mf.build((None, None, fr.frameWidth))
+        D = mf.numMfccs
+        off = np.zeros(R + 1, np.int64)
+        off[1:] = np.cumsum(frames)
+        F = int(off[-1])
+        if F * max(D, 2) >= 2 ** 31:
+            raise ValueError(f"{F} frames in one call: too many (split the recordings over calls)")
+        with L.launch_scope(dev):
+            ws = self._ws
+            ws.enter(dev)
+            get = lambda role, shape, dt: ws.get(role, shape, dt, dev, padded=False)      # noqa: E731
+            off_dev = torch.as_tensor(off.astype(np.int32), device=dev)
+            mfcc = get("dw_mfcc", (F * D + 4,), torch.float32)         # (4 floats of slack: the gather's 16-byte loads)
+            tables = mf.tables(dev)
+            for x, kind, r0 in groups:                                   # MFCC: one launch per group of equal-length recordings
+                B, N = x.shape
+                T = frames[r0]
+                cfg = L.FrontendCfg.from_buffer_copy(mf._cfg)
+                cfg.frame_size, cfg.frame_shift = fr.frameWidth, fr.frameShift
+                cfg.pad_mode = 0 if fr.snipEdges else 1
+                cfg.row_stride = 0 if x.is_contiguous() else x.stride(0)
+                o = int(off[r0]) * D
+                ops.frontend(x, kind, cfg, tables, L.OUT_MFCC, N, B, T, seed=mf.next_seed(), out=mfcc[o:o + B * T * D].view(B, T, D))
+            mf2 = mfcc[:F * D].view(F, D)
+            counts = get("dw_counts", (2 * R,), torch.int32)
+            seg_work = get("dw_seg", (2 * F + 2,), torch.int32)
+            win_work = get("dw_win", (2 * F + 2,), torch.int32)
+            if segments is None:
+                ops.diar_segments(mf2, frames, off_dev, self.vad.cfg(), seg_work, counts)
+                ops.diar_windows(seg_work, frames, off_dev, W, P, M, win_work, counts)
+                cnt = counts.cpu().numpy()                               # the call's one device-to-host read
+                nseg, nwin = cnt[:R].tolist(), cnt[R:].tolist()
+            else:
+                host = np.zeros(2 * F + 2, np.int32)
+                for r, rows in enumerate(segs_f):
+                    if rows:
+                        host[2 * off[r]:2 * off[r] + 2 * len(rows)] = np.asarray(rows, np.int32).reshape(-1)
+                nseg = [len(rows) for rows in segs_f]
+                nwin = [sum(window_count(e - s, W, P, M) for s, e in rows) for rows in segs_f]
+                seg_work.copy_(torch.from_numpy(host), non_blocking=False)
+                counts.copy_(torch.as_tensor(nseg + nwin, dtype=torch.int32))
+                ops.diar_windows(seg_work, frames, off_dev, W, P, M, win_work, counts)
+            G, S = int(sum(nseg)), int(sum(nwin))
+            segs, wins = ops.diar_compact(seg_work, win_work, counts, frames, off_dev, G, S)
+            odim = self.ldaMat.shape[1]
+            y = torch.empty((S, odim), dtype=torch.float32, device=dev)
+            if S:
+                cmn = get("dw_cmn", (F * D + 4,), torch.float32)
+                work = get("dw_cmn_work", (F * D + 4,), torch.float32)
+                ops.diar_segment_cmn(mf2, frames, off_dev, segs, self.cmvn.cfg(), cmn, work)
+                self._window_xvectors(cmn, D, frames, off_dev, wins, W + M, int(max_windows_per_pass), y)
+        return WindowXvectors(y, [int(n) for n in nwin], wins, segs, shift)
+
+    def _window_xvectors(self, cmn, D, frames, off_dev, wins, Tw, chunk, y):
+        """The windows' rows gathered into padded batches of at most `chunk` windows of Tw frames -> y (S, lda_dim), as __call__
+        extracts a batch of utterances: the model's mode with short windows routed to SHORT_MODE (route_short_utterances), or the whole
+        batch in SHORT_MODE at once when no window can reach the mode's frame floor."""
+        seq = self.xvec
+        S = wins.shape[0]
+        floor = seq.frames_floor(seq.gemm)
+        short = seq.SHORT_MODE.get(seq.gemm) if (self.route_short_utterances and 0 < floor and Tw < floor) else None
+        Dp = ops.round_up(D, 32)
+        dev = y.device
+        for w0 in range(0, S, chunk):
+            n = min(chunk, S - w0)
+            dt = L.act_torch_dtype(seq.batch_gemm(n, Tw, mode=short))
+            feats = self._ws.get(f"dw_feats_{str(dt)[6:]}", (n, Tw, Dp), dt, dev, padded=False)      # (every element written)
+            lens = self._ws.get("dw_lens", (n,), torch.int32, dev, padded=False)
+            ops.diar_gather(cmn, D, frames, off_dev, wins, w0, n, feats, lens)
+            out = y[w0:w0 + n]
+            res = self._xvectors(feats[:, :, :D], lens, out, mode=short) if short else self._route_xvectors(feats[:, :, :D], lens, out)
+            if res.data_ptr() != out.data_ptr():
+                out.copy_(res)
 
     def __call__(self, inputs, training=False):
         if hasattr(inputs, "shape") and len(inputs.shape) == 2 and inputs.shape[0] == 0:

@@ -777,3 +777,58 @@ def plda(x, A, offset, psi, normalize_length, simple_length_norm, want_scores=Tr
                 L.ptr(tr), L.ptr(scores), L.stream_ptr())
     L.check(rc, "ktf_plda")
     return scores, tr
+
+
+# ----------------------------------------------------------------------------- sliding-window diarization front end (ktf_diar_*)
+def _host_i32(a):
+    return np.ascontiguousarray(a, dtype=np.int32)
+
+
+def diar_segments(mfcc, frames, offsets, vad_cfg, seg_work, counts):
+    """Energy-VAD speech segments of R recordings laid end to end in mfcc (F, D) (ktf_diar_segments). frames: host ints (R),
+    offsets: device int32 (R + 1). Writes seg_work (2F int32) and counts[:R]."""
+    fr = _host_i32(frames)
+    with L.on_device(mfcc.device):
+        rc = L.load().ktf_diar_segments(L.ptr(mfcc), mfcc.shape[-1], fr.ctypes.data_as(C.c_void_p), L.ptr(offsets), len(fr),
+                                        C.byref(vad_cfg), L.ptr(seg_work), L.ptr(counts), L.stream_ptr())
+    L.check(rc, "ktf_diar_segments")
+
+
+def diar_windows(seg_work, frames, offsets, W, P, M, win_work, counts):
+    """Windows of every segment in seg_work (ktf_diar_windows): writes win_work (2F int32) and counts[R:]."""
+    fr = _host_i32(frames)
+    with L.on_device(seg_work.device):
+        rc = L.load().ktf_diar_windows(L.ptr(seg_work), fr.ctypes.data_as(C.c_void_p), L.ptr(offsets), len(fr), int(W), int(P), int(M),
+                                       L.ptr(win_work), L.ptr(counts), L.stream_ptr())
+    L.check(rc, "ktf_diar_windows")
+
+
+def diar_compact(seg_work, win_work, counts, frames, offsets, G, S):
+    """-> (segments (G, 3), windows (S, 3)) int32 device tables (ktf_diar_compact)."""
+    fr = _host_i32(frames)
+    dev = seg_work.device
+    segs = torch.empty((G, 3), dtype=torch.int32, device=dev)
+    wins = torch.empty((S, 3), dtype=torch.int32, device=dev)
+    with L.on_device(dev):
+        rc = L.load().ktf_diar_compact(L.ptr(seg_work), L.ptr(win_work), L.ptr(counts), fr.ctypes.data_as(C.c_void_p), L.ptr(offsets), len(fr),
+                                       int(G), int(S), L.ptr(segs), L.ptr(wins), L.stream_ptr())
+    L.check(rc, "ktf_diar_compact")
+    return segs, wins
+
+
+def diar_segment_cmn(mfcc, frames, offsets, segments, cmvn_cfg, out, work):
+    """CMN of every segment's rows of mfcc (F, D) into out (F, D) at the same rows (ktf_diar_segment_cmn)."""
+    fr = _host_i32(frames)
+    with L.on_device(mfcc.device):
+        rc = L.load().ktf_diar_segment_cmn(L.ptr(mfcc), mfcc.shape[-1], fr.ctypes.data_as(C.c_void_p), L.ptr(offsets), len(fr), L.ptr(segments),
+                                           segments.shape[0], C.byref(cmvn_cfg), L.ptr(out), L.ptr(work), L.stream_ptr())
+    L.check(rc, "ktf_diar_segment_cmn")
+
+
+def diar_gather(cmn, D, frames, offsets, windows, w0, n, out, lens):
+    """Windows [w0, w0 + n) of the table -> out (n, Tw, ldo) float32 / bfloat16 and lens (n,) (ktf_diar_gather)."""
+    fr = _host_i32(frames)
+    with L.on_device(cmn.device):
+        rc = L.load().ktf_diar_gather(L.ptr(cmn), int(D), fr.ctypes.data_as(C.c_void_p), L.ptr(offsets), len(fr), L.ptr(windows), windows.shape[0],
+                                      int(w0), int(n), out.shape[1], L.ptr(out), L.ktf_dtype(out.dtype), out.stride(1), L.ptr(lens), L.stream_ptr())
+    L.check(rc, "ktf_diar_gather")
