@@ -490,6 +490,48 @@ int ktf_plda_score_f64(const double* test_tr, int64_t N, const double* enroll_tr
 int ktf_plda_score_f32(const float* test_tr, int64_t N, const float* enroll_tr, int64_t M, int32_t dim, const float* psi,
                        float* scores, void* stream);
 
+/* ------------------------------------------------------------------ speaker verification
+ * Kaldi's verification recipes (sitw, sre16 v2, voxceleb): ivector-mean over spk2utt, then ivector-subtract-global-mean,
+ * transform-vec and ivector-normalize-length (ktf_xvec_post_f32), then ivector-plda-scoring --num-utts over a trial list.
+ *
+ * ivector-mean: speaker s owns utts[offsets[s] .. offsets[s + 1]) (a CSR map: offsets S + 1 and utts device int32), rows of raw
+ * (U, D) fp32. means[s] (S, D) fp32 = the fp64 sum of its rows in list order, divided by the count and rounded once to fp32;
+ * num_utts[s] (S, device int32) = the count. A speaker with an empty or out-of-range list, or naming a row outside [0, U), gets a
+ * NaN row and num_utts 0 (callers check the map on the host: this only keeps the kernel inside its arrays). n_idx: length of utts. */
+int ktf_spk_mean_f32(const float* raw, int64_t U, int32_t D, const int32_t* offsets, int64_t S, const int32_t* utts, int64_t n_idx,
+                     float* means, int32_t* num_utts, void* stream);
+
+/* PLDA::TransformIvector(config, ivector, num_examples, ...) (plda.py:163-196 transformVector(inputs, num_examples)): ktf_plda_*'s
+ * transform with a count per row, num_examples (B, device, the dtype of x). The length normalisation factor becomes
+ * sqrt(dim / sum_d y_d^2 / (psi_d + 1 / n)); simple_length_norm ignores n. With every count 1: ktf_plda_*'s transformed rows, bit
+ * for bit. Counts must be > 0 (not checked on the device). */
+int ktf_plda_transform_n_f64(const double* x, int64_t B, int32_t dim, const double* A, const double* offset, const double* psi,
+                             const double* num_examples, int32_t normalize_length, int32_t simple_length_norm, double* transformed,
+                             void* stream);
+int ktf_plda_transform_n_f32(const float* x, int64_t B, int32_t dim, const float* A, const float* offset, const float* psi,
+                             const float* num_examples, int32_t normalize_length, int32_t simple_length_norm, float* transformed,
+                             void* stream);
+/* PLDA::LogLikelihoodRatio(transformed_enroll, n, transformed_test) (plda.py:198-245 logLikelihoodRatio(inputs, num_examples)) on
+ * the rectangular block of ktf_plda_score_*, class j (enroll column) averaging enroll_num_examples[j] = n_j examples (M, device, the
+ * dtype): mean_jd = n_j psi_d / (n_j psi_d + 1) e_jd, var_jd = 1 + psi_d / (n_j psi_d + 1); the no-class term keeps 1 + psi. With
+ * every count 1: ktf_plda_score_*'s scores, bit for bit. */
+int ktf_plda_score_n_f64(const double* test_tr, int64_t N, const double* enroll_tr, int64_t M, int32_t dim, const double* psi,
+                         const double* enroll_num_examples, double* scores, void* stream);
+int ktf_plda_score_n_f32(const float* test_tr, int64_t N, const float* enroll_tr, int64_t M, int32_t dim, const float* psi,
+                         const float* enroll_num_examples, float* scores, void* stream);
+/* ivector-plda-scoring --num-utts over a trial list: scores[t] = the LLR of ktf_plda_score_n_* for the pair trials[2t] = class j
+ * (row of enroll_tr, 0 <= j < M), trials[2t + 1] = test i (row of test_tr, 0 <= i < N); trials: T pairs of device int32. A pair
+ * outside those ranges scores NaN (nothing outside the arrays is read). A score's bits depend on its two vectors, psi and n_j only,
+ * not on its position in the list or the order of the list. workspace: a device buffer of at least
+ * ktf_plda_trials_workspace_bytes(N, M, dim, sizeof dtype) bytes (returns a negative KTF_* code on bad arguments). */
+int64_t ktf_plda_trials_workspace_bytes(int64_t N, int64_t M, int32_t dim, int32_t dtype_bytes);
+int ktf_plda_trials_f64(const double* test_tr, int64_t N, const double* enroll_tr, int64_t M, int32_t dim, const double* psi,
+                        const double* enroll_num_examples, const int32_t* trials, int64_t T, double* scores, void* workspace,
+                        size_t workspace_bytes, void* stream);
+int ktf_plda_trials_f32(const float* test_tr, int64_t N, const float* enroll_tr, int64_t M, int32_t dim, const float* psi,
+                        const float* enroll_num_examples, const int32_t* trials, int64_t T, float* scores, void* workspace,
+                        size_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------------ dense PLDA scoring with conversation-dependent PCA
  * Kaldi `ivector-plda-scoring-dense` (the scoring stage of x-vector diarization); the reference ships its golden table
  * (testdata/plda/plda_scores.py, RefPldaScores.ark, --target-energy 0.1) and no implementation. For every recording r of a call

@@ -1168,21 +1168,103 @@ class PLDA(Layer):
             self._dev = (f(self.transformMat), f(self.offset), f(self.psi))
         return x
 
-    def transform(self, inputs):
-        """Extension: transformVector alone (plda.py:163-196) -> (B, dim) transformed vectors."""
+    def transform(self, inputs, num_examples=None):
+        """Extension: transformVector alone (plda.py:163-196) -> (B, dim) transformed vectors. num_examples: the number of
+        examples each vector averages (Kaldi's TransformIvector(num_examples); the speaker model of verification.speaker_means):
+        None (1, the plain path), a scalar, a host array of B or a device tensor of B. Counts must be > 0: checked directly on the
+        host, or on the device with one reduction and one read. With every count 1 the result is the plain path's, bit for bit."""
         x = self._prepare(inputs)
         A, off, psi = self._dev
-        return ops.plda(x, A, off, psi, self.normalizeLength, self.simpleLengthNorm, want_scores=False)[1]
+        if num_examples is None:
+            return ops.plda(x, A, off, psi, self.normalizeLength, self.simpleLengthNorm, want_scores=False)[1]
+        n = self._counts(num_examples, x.shape[0], x.device, "num_examples")
+        return ops.plda_transform_n(x, A, off, psi, n, self.normalizeLength, self.simpleLengthNorm)
 
-    def score(self, test_transformed, enroll_transformed):
-        """Extension: rectangular trial block, scores[i, j] = LLR(test_i | class of enroll_j) on TRANSFORMED vectors
-        (the reference scores a batch against itself only); row blocks of a large trial matrix shard across GPUs
-        (parallel.plda_trials)."""
+    def _counts(self, n, rows, device, what):
+        """num_examples as a (rows,) device tensor of the layer's dtype, every value checked > 0 (NaN refused)."""
+        if isinstance(n, torch.Tensor) and n.is_cuda:
+            if n.device != device:
+                raise ValueError(f"{what} is on {n.device}, the vectors on {device}")
+            if n.dim() == 0:
+                n = n.reshape(1).expand(rows)
+            if n.dim() != 1 or n.shape[0] != rows:
+                raise ValueError(f"{what} must be a scalar or hold {rows} counts, got shape {tuple(n.shape)}")
+            c = n.to(self.paramDtype).contiguous()
+            if rows and bool((~(c > 0)).any().item()):                      # the one device -> host read
+                raise ValueError(f"{what} must all be > 0")
+            return c
+        a = np.asarray(n.numpy() if isinstance(n, torch.Tensor) else n, dtype=np.float64)
+        if a.ndim == 0:
+            a = np.full((rows,), float(a))
+        if a.ndim != 1 or a.shape[0] != rows:
+            raise ValueError(f"{what} must be a scalar or hold {rows} counts, got shape {a.shape}")
+        if not np.all(a > 0):
+            raise ValueError(f"{what} must all be > 0, got {a[~(a > 0)][:4].tolist()}")
+        return torch.as_tensor(a, dtype=self.paramDtype).to(device)
+
+    def _scoring_inputs(self, test_transformed, enroll_transformed):
         t = test_transformed.reshape(test_transformed.shape[0], -1).to(self.paramDtype).contiguous()
         e = enroll_transformed.reshape(enroll_transformed.shape[0], -1).to(self.paramDtype).contiguous()
+        if e.device != t.device:
+            raise ValueError(f"test vectors on {t.device}, enrollment vectors on {e.device}")
         if self._dev is None or self._dev[0].device != t.device:
             self._prepare(t)
-        return ops.plda_score(t, e, self._dev[2])
+        return t, e
+
+    def score(self, test_transformed, enroll_transformed, enroll_num_examples=None):
+        """Extension: rectangular trial block, scores[i, j] = LLR(test_i | class of enroll_j) on TRANSFORMED vectors
+        (the reference scores a batch against itself only); row blocks of a large trial matrix shard across GPUs
+        (parallel.plda_trials). enroll_num_examples: examples per class j (Kaldi's LogLikelihoodRatio(n), ivector-plda-scoring
+        --num-utts), checked as transform's num_examples; None keeps the count-free path (every count 1 gives its bits)."""
+        t, e = self._scoring_inputs(test_transformed, enroll_transformed)
+        if enroll_num_examples is None:
+            return ops.plda_score(t, e, self._dev[2])
+        n = self._counts(enroll_num_examples, e.shape[0], t.device, "enroll_num_examples")
+        return ops.plda_score_n(t, e, self._dev[2], n)
+
+    def score_trials(self, test_transformed, enroll_transformed, trials_enroll, trials_test, enroll_num_examples=None):
+        """Extension: ivector-plda-scoring over a trial list. scores[t] = LLR(test_{trials_test[t]} | class enroll_{trials_enroll[t]})
+        with the class's count (enroll_num_examples, as in score; None: 1 each) -> (T,) in the layer's dtype. Only the listed pairs
+        are scored: a trial's bits depend on its two vectors and the count, not on the list's order. The indices are host arrays
+        (checked there) or device integer tensors (checked with one reduction and one read); either way every index must lie in
+        range (a pair outside the arrays that reached the kernel would score NaN, nothing outside them is read)."""
+        t, e = self._scoring_inputs(test_transformed, enroll_transformed)
+        N, M = t.shape[0], e.shape[0]
+        pairs = self._trial_pairs(trials_enroll, trials_test, M, N, t.device)
+        n = self._counts(1.0 if enroll_num_examples is None else enroll_num_examples, M, t.device, "enroll_num_examples")
+        return ops.plda_trials(t, e, self._dev[2], n, pairs)
+
+    @staticmethod
+    def _trial_pairs(trials_enroll, trials_test, M, N, device):
+        """(T, 2) device int32 rows (class j, test i), every index checked in range."""
+        dev_in = [isinstance(a, torch.Tensor) and a.is_cuda for a in (trials_enroll, trials_test)]
+        if all(dev_in):
+            je, it = trials_enroll, trials_test
+            for a in (je, it):
+                if a.device != device:
+                    raise ValueError(f"trial indices on {a.device}, the vectors on {device}")
+                if a.dim() != 1 or a.dtype.is_floating_point or a.dtype == torch.bool or a.is_complex():
+                    raise ValueError(f"trial indices must be 1-D integer tensors, got {a.dtype} {tuple(a.shape)}")
+            if je.shape[0] != it.shape[0]:
+                raise ValueError(f"{je.shape[0]} enrollment indices, {it.shape[0]} test indices")
+            if je.shape[0] and bool(((je < 0) | (je >= M) | (it < 0) | (it >= N)).any().item()):     # the one device -> host read
+                raise ValueError(f"a trial index is out of range (classes 0..{M - 1}, tests 0..{N - 1})")
+            return torch.stack((je.to(torch.int32), it.to(torch.int32)), dim=1).contiguous()
+        if any(dev_in):
+            raise ValueError("trials_enroll and trials_test must both be on the host or both on the device")
+        arrs = []
+        for a, hi, what in ((trials_enroll, M, "trials_enroll"), (trials_test, N, "trials_test")):
+            a = np.asarray(a.numpy() if isinstance(a, torch.Tensor) else a)
+            if a.size == 0:
+                a = a.reshape(0).astype(np.int64)
+            if a.ndim != 1 or a.dtype.kind not in "iu":
+                raise ValueError(f"{what} must be a 1-D sequence of integers, got {a.dtype} {a.shape}")
+            if a.size and (a.min() < 0 or a.max() >= hi):
+                raise ValueError(f"{what} has an index outside 0..{hi - 1}")
+            arrs.append(a.astype(np.int32))
+        if arrs[0].shape != arrs[1].shape:
+            raise ValueError(f"{arrs[0].size} enrollment indices, {arrs[1].size} test indices")
+        return torch.as_tensor(np.ascontiguousarray(np.stack(arrs, axis=1).reshape(-1, 2))).to(device)
 
     def score_dense(self, inputs, lengths=None, target_energy=0.1):
         """Extension: Kaldi's `ivector-plda-scoring-dense`, the scoring stage of diarization. `inputs` (S, dim) or (S, 1, dim), the

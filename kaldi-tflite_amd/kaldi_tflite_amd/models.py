@@ -991,14 +991,15 @@ class XvectorExtractor:
         self.last_lens = lens                                          # voiced-frame counts of the last call (workspace view)
         return self._route_xvectors(feats, lens, out), feats, lens
 
-    def _route_xvectors(self, feats, lens, out=None):
-        """CMVN'd features + frame counts -> x-vectors, short utterances routed to the tighter mode (route_short_utterances)."""
+    def _route_xvectors(self, feats, lens, out=None, raw=None):
+        """CMVN'd features + frame counts -> x-vectors, short utterances routed to the tighter mode (route_short_utterances).
+        raw: (B, units) fp32 that receives the tdnn6 outputs of the same passes (embeddings), or None."""
         B, T = feats.shape[0], feats.shape[1]
         seq = self.xvec
         nshort = seq.frames_floor(seq.gemm)
         if not (self.route_short_utterances and nshort > 0 and T >= nshort and seq.gemm in seq.SHORT_MODE
                 and seq.batch_gemm(B, T) == _GEMM[seq.gemm]):
-            return self._xvectors(feats, lens, out)
+            return self._xvectors(feats, lens, out, raw=raw)
         # Per-utterance routing: the batch runs in the model's mode with the utterances of fewer than `nshort` voiced frames masked out
         # (length 0: their tiles leave at once), then once more in the tighter mode with only those utterances live; the second tail
         # writes just their rows. The masks are made on the device (ktf_route_short, one small launch behind VAD / CMVN). Whether the
@@ -1020,17 +1021,20 @@ class XvectorExtractor:
                 tl.short_seq = 0
             tl.short_seq = (tl.short_seq % 0x3FFFFFFF) + 1
             ops.route_short(lens, nshort, lens_main, lens_short, tl.short_flag, tl.short_seq)
-        y = self._xvectors(feats, lens_main, out)
+        y = self._xvectors(feats, lens_main, out, raw=raw)
         if not capturing:
             self.last_short_count = self._await_short_count(feats.device)
             if self.last_short_count == 0 and not self._warming_for_capture:
                 return y
         short_mode = seq.SHORT_MODE[seq.gemm]
         if self._tail_fusable() and self.fuse_tail:
-            self._xvectors(feats, lens_short, y, mode=short_mode, skip_empty=True)
+            self._xvectors(feats, lens_short, y, mode=short_mode, skip_empty=True, raw=raw)
         else:                                                          # (tails that write every row: select afterwards)
-            y2 = self._xvectors(feats, lens_short, None, mode=short_mode)
+            raw2 = None if raw is None else torch.empty_like(raw)
+            y2 = self._xvectors(feats, lens_short, None, mode=short_mode, raw=raw2)
             y.copy_(torch.where((lens_short > 0)[:, None], y2, y))
+            if raw is not None:
+                raw.copy_(torch.where((lens_short > 0)[:, None], raw2, raw))
         return y
 
     def _await_short_count(self, dev):
@@ -1055,20 +1059,17 @@ class XvectorExtractor:
                 break
         return int(flag[0])
 
-    def _xvectors(self, feats, lens, out=None, mode=None, skip_empty=False):
+    def _xvectors(self, feats, lens, out=None, mode=None, skip_empty=False, raw=None):
         """CMVN'd features + voiced-frame counts -> x-vectors (B, lda_dim). `mode`: the TDNN arithmetic of this pass (default: the
-        model's); `skip_empty`: utterances with lens == 0 are not computed and their rows of `out` stay (fused tail only)."""
+        model's); `skip_empty`: utterances with lens == 0 are not computed and their rows of `out` (and `raw`) stay (fused tail only).
+        `raw`: (B, units) fp32 that also receives the tdnn6 outputs (the fused tail's h_out), or None."""
         one_launch = self.fuse_tail and self._tail_fusable() and (skip_empty or feats.shape[0] < self.fuse_tail_below or
                                                                   self.xvec.batch_gemm(feats.shape[0], feats.shape[1], mode=mode) == L.GEMM_F32)
         if skip_empty and not one_launch:
             raise RuntimeError("internal: skip_empty needs the fused tail")
         h = self.xvec.run_ragged(feats, lens, defer_tail=one_launch, mode=mode)          # (B, 1, 512), or the deferred tail
         dev = feats.device
-        key = str(dev)
-        if key not in self._post_dev:
-            self._post_dev[key] = (ops.to_device_f32(self.xvecGlobalMean, dev), ops.to_device_f32(self.ldaMat, dev),
-                                   ops.to_device_f32(self.ldaOffset.reshape(-1), dev))
-        mean, A, off = self._post_dev[key]
+        mean, A, off = self._post_params(dev)
         if isinstance(h, DeferredTail):
             # pooling finalize + tdnn6 + mean subtraction + LDA + length normalisation in one launch (ktf_xvec_tail_f32)
             t = h
@@ -1090,13 +1091,60 @@ class XvectorExtractor:
                 if out is None:
                     out = torch.empty((B, odim), dtype=torch.float32, device=dev)
                 return ops.xvec_tail(t.pooled, t.sums, t.slots, t.lens, t.T, t.D, t.include_std, t.eps, w6, b6, t.layer.units, mean, A, off,
-                                     partial, counters, out, group=group, slot_rows=t.slot_rows, skip_empty=skip_empty)
+                                     partial, counters, out, h_out=raw, group=group, slot_rows=t.slot_rows, skip_empty=skip_empty)
             raise ValueError(f"LDA input dim {A.shape[0]} != embedding dim {t.layer.units}")
         B = h.shape[0]
         h2 = h.reshape(B, h.shape[-1])
         if not h2.is_contiguous():
             h2 = h2.contiguous()
+        if raw is not None:
+            raw.copy_(h2)
         return ops.xvec_post(h2, mean, A, off, out=out)
+
+    def _post_params(self, dev):
+        key = str(dev)
+        if key not in self._post_dev:
+            self._post_dev[key] = (ops.to_device_f32(self.xvecGlobalMean, dev), ops.to_device_f32(self.ldaMat, dev),
+                                   ops.to_device_f32(self.ldaOffset.reshape(-1), dev))
+        return self._post_dev[key]
+
+    def embeddings(self, wavs):
+        """Extension: the raw x-vectors (B, units) fp32 -- the tdnn6.affine output, Kaldi's xvector.ark, before mean subtraction,
+        LDA and length normalisation -- of the utterances `__call__` takes, by the same route (the model's mode, short-utterance
+        routing, fused or three-launch tail; the fused tail writes them alongside the x-vectors in its one launch). Always 2-D.
+        postprocess(embeddings(w)) is __call__(w) within 1e-5. Eager only: compile() and verify_fraction do not
+        apply."""
+        L.require_gpu()
+        units = self.ldaMat.shape[0]
+        if hasattr(wavs, "shape") and len(wavs.shape) == 2 and wavs.shape[0] == 0:
+            return torch.empty((0, units), dtype=torch.float32, device=ops.default_device())
+        dev = wavs.device if (isinstance(wavs, torch.Tensor) and wavs.is_cuda) else ops.default_device()
+        with L.launch_scope(dev):
+            _, feats, lens = self._features(wavs)
+            self.last_lens = lens
+            raw = torch.empty((feats.shape[0], units), dtype=torch.float32, device=feats.device)
+            self._route_xvectors(feats, lens, raw=raw)
+        return raw
+
+    def postprocess(self, raw):
+        """Extension: raw x-vectors (B, units) or (units,) -> mean subtraction, LDA with offset and length normalisation
+        (ktf_xvec_post_f32) -> (B, lda_dim) fp32 (the input's rank). The second half of __call__, for vectors the caller combined
+        first (verification.speaker_means: Kaldi averages the raw x-vectors of a speaker's utterances)."""
+        L.require_gpu()
+        x = raw if isinstance(raw, torch.Tensor) else torch.as_tensor(np.asarray(raw, np.float32))
+        if not x.is_cuda:
+            x = x.to(ops.default_device())
+        one = x.dim() == 1
+        x = x.reshape(1, -1) if one else x
+        if x.dim() != 2 or x.shape[1] != self.ldaMat.shape[0]:
+            raise ValueError(f"expected (B, {self.ldaMat.shape[0]}) raw x-vectors, got {tuple(raw.shape)}")
+        x = x.to(torch.float32).contiguous()
+        if x.shape[0] == 0:
+            return torch.empty((0, self.ldaMat.shape[1]), dtype=torch.float32, device=x.device)
+        with L.launch_scope(x.device):
+            mean, A, off = self._post_params(x.device)
+            y = ops.xvec_post(x, mean, A, off)
+        return y.reshape(-1) if one else y
 
     def _tail_fusable(self):
         """ktf_xvec_tail_f32 serves LDA outputs up to 256 wide (one thread per output), an embedding layer whose width is the LDA's

@@ -393,6 +393,70 @@ def plda_score(test_tr, enroll_tr, psi):
     return scores
 
 
+# ----------------------------------------------------------------------------- speaker verification (ktf_spk_mean_f32, ktf_plda_*_n_*)
+def spk_mean(raw, offsets, utts, S, means=None, num_utts=None):
+    """Kaldi ivector-mean: raw (U, D) fp32, the CSR map offsets (S + 1) / utts on the device (int32) -> (means (S, D) fp32,
+    num_utts (S,) int32)."""
+    U, D = raw.shape
+    if means is None:
+        means = torch.empty((S, D), dtype=torch.float32, device=raw.device)
+    if num_utts is None:
+        num_utts = torch.empty((S,), dtype=torch.int32, device=raw.device)
+    with L.on_device(raw.device):
+        rc = L.load().ktf_spk_mean_f32(L.ptr(raw), U, D, L.ptr(offsets), S, L.ptr(utts), utts.numel(), L.ptr(means), L.ptr(num_utts),
+                                       L.stream_ptr())
+    L.check(rc, "ktf_spk_mean_f32")
+    return means, num_utts
+
+
+def plda_transform_n(x, A, offset, psi, num_examples, normalize_length, simple_length_norm):
+    """transformVector(x, num_examples): x (B, dim), num_examples (B,) on the device in x's dtype -> (B, dim)."""
+    lib = L.load()
+    B, dim = x.shape
+    tr = torch.empty_like(x)
+    fn = lib.ktf_plda_transform_n_f64 if x.dtype == torch.float64 else lib.ktf_plda_transform_n_f32
+    with L.on_device(x.device):
+        rc = fn(L.ptr(x), B, dim, L.ptr(A), L.ptr(offset), L.ptr(psi), L.ptr(num_examples), int(normalize_length),
+                int(simple_length_norm), L.ptr(tr), L.stream_ptr())
+    L.check(rc, "ktf_plda_transform_n")
+    return tr
+
+
+def plda_score_n(test_tr, enroll_tr, psi, enroll_num_examples):
+    """scores (N, M) with class j averaging enroll_num_examples[j] examples (device, the dtype of the vectors)."""
+    lib = L.load()
+    N, dim = test_tr.shape
+    M = enroll_tr.shape[0]
+    scores = torch.empty((N, M), dtype=test_tr.dtype, device=test_tr.device)
+    fn = lib.ktf_plda_score_n_f64 if test_tr.dtype == torch.float64 else lib.ktf_plda_score_n_f32
+    with L.on_device(test_tr.device):
+        rc = fn(L.ptr(test_tr), N, L.ptr(enroll_tr), M, dim, L.ptr(psi), L.ptr(enroll_num_examples), L.ptr(scores), L.stream_ptr())
+    L.check(rc, "ktf_plda_score_n")
+    return scores
+
+
+def plda_trials(test_tr, enroll_tr, psi, enroll_num_examples, pairs, workspace=None):
+    """scores (T,) of the trial list pairs (T, 2) device int32 rows (class j, test i). workspace(nbytes) -> a uint8 device tensor
+    (None: a fresh one)."""
+    lib = L.load()
+    N, dim = test_tr.shape
+    M = enroll_tr.shape[0]
+    T = pairs.shape[0]
+    scores = torch.empty((T,), dtype=test_tr.dtype, device=test_tr.device)
+    if T == 0:
+        return scores
+    nbytes = int(lib.ktf_plda_trials_workspace_bytes(N, M, dim, test_tr.element_size()))
+    if nbytes < 0:
+        L.check(nbytes, "ktf_plda_trials_workspace_bytes")
+    ws = workspace(nbytes) if workspace is not None else torch.empty((nbytes,), dtype=torch.uint8, device=test_tr.device)
+    fn = lib.ktf_plda_trials_f64 if test_tr.dtype == torch.float64 else lib.ktf_plda_trials_f32
+    with L.on_device(test_tr.device):
+        rc = fn(L.ptr(test_tr), N, L.ptr(enroll_tr), M, dim, L.ptr(psi), L.ptr(enroll_num_examples), L.ptr(pairs), T, L.ptr(scores),
+                L.ptr(ws), ws.numel(), L.stream_ptr())
+    L.check(rc, "ktf_plda_trials")
+    return scores
+
+
 def plda_dense_workspace_bytes(lengths, dim, target_energy):
     """Bytes of scratch ktf_plda_dense_* needs (lengths: host ints; target_energy None = no PCA)."""
     lib = L.load()
