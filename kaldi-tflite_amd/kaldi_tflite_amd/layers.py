@@ -996,9 +996,8 @@ class TDNN(Layer):
         the four MX planes -> csrc/tdnn_mx.hip -> fp32 rows."""
         from . import mx
         B, T, D = x.shape
-        src = x if (x.dtype == torch.float32 and x.stride(2) == 1 and x.stride(0) == T * x.stride(1)) else x.to(torch.float32).contiguous()
         planes = mx.Planes.empty(B, T, D, x.device)
-        ops.mx_planes(src, D, None, planes)
+        ops.mx_planes(_f32_rows(x), D, None, planes)
         wh, wq, bias = self.device_weights_mx(x.device, loader=False)
         d = self.desc(L.GEMM_F16MX, torch.float32, torch.float32)
         if self.outputTimesteps(T) <= 0:               # VALID padding of an input shorter than the context: no output row
@@ -1006,6 +1005,13 @@ class TDNN(Layer):
         y = torch.empty((B, self.outputTimesteps(T), ops.round_up(self.units, 4)), dtype=torch.float32, device=x.device)
         ops.tdnn_mx(planes, None, d, wh, wq, bias, None, None, y)
         return y[:, :, : self.units]
+
+
+def _f32_rows(x):
+    """(B, T, D) x as fp32 rows of one stride per utterance: x itself if it is that already, else a contiguous copy."""
+    if x.dtype == torch.float32 and x.stride(2) == 1 and x.stride(0) == x.shape[1] * x.stride(1):
+        return x
+    return x.to(torch.float32).contiguous()
 
 
 # =============================================================================== stats

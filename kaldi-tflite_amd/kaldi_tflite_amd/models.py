@@ -19,7 +19,7 @@ import torch
 from . import _lib as L
 from . import ops
 from .io import KaldiNnet3Reader, ReadKaldiArray
-from .layers import TDNN, BatchNorm, CMVN, Framing, MFCC, ReLU, StatsPooling, VAD, _GEMM, WEIGHTS_EPOCH
+from .layers import TDNN, BatchNorm, CMVN, Framing, MFCC, ReLU, StatsPooling, VAD, _GEMM, WEIGHTS_EPOCH, _f32_rows
 from .mx import Planes
 
 
@@ -125,6 +125,36 @@ class DeferredTail:
         self.pooled, self.sums, self.slots, self.lens, self.T, self.slot_rows = pooled, sums, slots, lens, T, slot_rows
 
 
+class _RunState:
+    """What one Sequential.run_ragged call carries from step to step: the activations `x` (`x_pair`: they hold KTF_BF16P pairs; `mxp` /
+    `planes`: they live as f16mx / split-bf16 planes, x is then a shape carrier), their lengths, the BatchNorm an f16mx layer left to the
+    next one to fold (`pending_bn`), the flat-row bookkeeping of the current lengths, and the tail deferred to the caller."""
+
+    def __init__(self, ws, x, lens, gemm, pairs, tail_at, tail):
+        self.ws, self.dev, self.x, self.lens, self.gemm, self.pairs = ws, x.device, x, lens, gemm, pairs
+        self.tail_at, self.tail, self.deferred = tail_at, tail, None
+        self.mxp = self.planes = self.pending_bn = None
+        self.x_pair = self.pooled = self.skip = False
+        self._rows, self._rows_for = None, None
+
+    def rows(self, B, T):
+        """The FlatRows of the current (lens, B, T): made when the first flat layer runs, made again when a layer has changed the lengths
+        (set_lens) OR the frame count -- a dense batch (lens None) has no lengths to replace, only T changes (tools/fuzz_models.py seeds
+        202 / 203: stale rows behind a VALID-padded layer of a dense batch)."""
+        if self._rows is None or self._rows_for != (B, T):
+            self._rows = ops.flat_rows(self.lens, B, T, lambda role, shape, dt: self.ws.get(role, shape, dt, self.dev, padded=False))
+            self._rows_for = (B, T)
+        return self._rows
+
+    def set_lens(self, lens):
+        """A VALID-padded or subsampling layer (or the pooling) has replaced the lengths: the flat rows made for the old ones are stale."""
+        self.lens, self._rows = lens, None
+
+    def defer(self, sp, B, D, T, **pooled_or_sums):
+        """The StatsPooling `sp` in front of the deferred tail has run: the DeferredTail run_ragged returns."""
+        self.deferred = DeferredTail(self.tail, B, D, sp.includeStd, sp.epsilon, lens=self.lens, T=T, **pooled_or_sums)
+
+
 class Sequential:
     """Keras-Sequential stand-in: `.layers`, `.name`, `mdl(x, training=False)`, `get_layer`, `summary`.
     `gemm` selects the TDNN arithmetic of the fused runner: "f32" (exact fp32 MFMA, default = the reference's
@@ -189,7 +219,7 @@ class Sequential:
         self.deterministic = True    # ... with per-block partial sums added in a fixed order (bitwise reproducible runs)
         self.dtype = "float32"
         self._ws_own = _Workspace()
-        self._tl = threading.local()  # per host thread: a workspace override (XvectorExtractor.compile), the deferred tail of the call in flight
+        self._tl = threading.local()  # per host thread: a workspace override (XvectorExtractor.compile)
         self._build()
 
     def _build(self):
@@ -305,14 +335,6 @@ class Sequential:
     def _ws(self, ws):                       # XvectorExtractor.compile: private workspaces for the capturing thread only
         self._tl.ws = None if ws is self._ws_own else ws
 
-    @property
-    def _deferred(self):
-        return getattr(self._tl, "deferred", None)
-
-    @_deferred.setter
-    def _deferred(self, d):
-        self._tl.deferred = d
-
     def _mx_use_loader(self, B, T):
         """f16mx: the loader-wave kernel for this batch? (`mx_loader` None: rounds of 256 workgroups x rows per tile, two N-tiles)"""
         if self.mx_loader is not None:
@@ -328,45 +350,9 @@ class Sequential:
         if not (self.flat_rows and B * T > 0 and l.padding == "SAME" and l.subsamplingFactor == 1 and l.activation in (None, "linear", "relu")
                 and B <= 4095 and B * T * ldx * 2 < 2 ** 32):
             return False
-        # tiles that are mostly padding (fewer than 80 % of the 16-row blocks computed hold a row of a full-length utterance), or at least
-        # 1.5 % fewer tiles even if the VAD dropped no frame (a ragged batch saves half a tile per utterance on top)
-        return bool(5 * (-(-T // 16)) < 4 * (-(-T // 256)) * 16 or (self.flat_rows_long and -(-(B * T) // 256) * 200 <= B * (-(-T // 256)) * 197))
-
-    def _pooled_by_gemm(self, l, relu, bn, nxt, x_or_planes, lens, gemm, split, dev, T, defer_to=None, row_starts=None):
-        """[affine, relu, batchnorm] -> reducing StatsPooling inside the GEMM epilogue: the layer output is never written.
-        `split`: the input is a (2,B,T,ld) pair of bf16 planes read by the split-plane kernel; `row_starts`: ... on flat row tiles
-        (reproducible form only). Returns the pooled (1, B, od) view."""
-        sp = nxt[1]
-        D = l.units
-        od = 2 * D if sp.includeStd else D
-        ld = ops.round_up(od, 32)
-        B = x_or_planes.shape[1] if x_or_planes.dim() == 4 else x_or_planes.shape[0]
-        flat = row_starts is not None
-        slots = (ops.flat_stats_slots(T) if flat else ops.stats_slots(T)) if self.deterministic else 0
-        sums = self._ws.get("sums", (B, max(slots, 1), 2, D), torch.float64, dev, padded=False)
-        sbuf = self._ws.get("pooled", (B, ld), torch.float32, dev, padded=od if ld != od else False)
-        kint = bool(split and l.kernelWidth > 1)
-        wt = bool(split)
-        w, w_lo, bias = l.device_weights(dev, gemm, k_interleaved=kint, w_tiled=wt)
-        scale, shift = bn.affine_device(dev) if bn is not None else (None, None)
-        xdt = x_or_planes.dtype
-        d = l.desc(gemm, xdt, xdt if split else L.act_torch_dtype(gemm), act="relu" if relu else None,
-                   flags=(L.TDNN_DET_STATS if slots else 0) | (L.TDNN_K_INTERLEAVED if kint else 0) | (L.TDNN_W_TILED if wt else 0))
-        if flat:
-            ops.tdnn_split_flat_stats(x_or_planes, row_starts, d, w, w_lo, bias, scale, shift, sums, zero=not slots)
-            if slots:
-                ops.stats_finalize_flat(sums, row_starts, T, D, sp.includeStd, sp.epsilon, sbuf, slots)
-            else:
-                ops.stats_finalize(sums, lens, T, D, sp.includeStd, sp.epsilon, sbuf)
-            if defer_to is not None:     # (the fused tail reads finished pooled rows here: its own finalize knows per-utterance slots only)
-                self._deferred = DeferredTail(defer_to, B, D, sp.includeStd, sp.epsilon, pooled=sbuf, lens=lens, T=T)
-            return sbuf[:, :od].unsqueeze(0)
-        (ops.tdnn_split_stats if split else ops.tdnn_stats)(x_or_planes, lens, d, w, w_lo, bias, scale, shift, sums, zero=not slots)
-        if defer_to is not None:         # the caller's fused tail finalizes the sums itself
-            self._deferred = DeferredTail(defer_to, B, D, sp.includeStd, sp.epsilon, sums=sums, slots=slots, lens=lens, T=T)
-            return sbuf[:, :od].unsqueeze(0)
-        ops.stats_finalize(sums, lens, T, D, sp.includeStd, sp.epsilon, sbuf, slots=slots)
-        return sbuf[:, :od].unsqueeze(0)
+        # tiles that are mostly padding (fewer than 80 % of the 16-row blocks computed hold a row of a full-length utterance), or fewer
+        # tiles even if the VAD dropped no frame (a ragged batch saves half a tile per utterance on top)
+        return bool(5 * (-(-T // 16)) < 4 * (-(-T // 256)) * 16 or (self.flat_rows_long and _fewer_flat_tiles(B, T)))
 
     def _tail_step(self, steps):
         """Index of the last step if it is a plain affine (context [0], no activation / BatchNorm) right after a reducing
@@ -387,264 +373,219 @@ class Sequential:
         steps = self._plan()
         if steps is None:
             raise NotImplementedError("this layer stack is not supported by the fused ragged runner")
-        dev = x.device
-        self._ws.enter(dev)
+        self._ws.enter(x.device)
         gemm, pairs = self._batch_route(x.shape[0], x.shape[1], mode=mode)
-        x_pair = False                                   # x holds KTF_BF16P pairs (in a float32 tensor)
-        rows_T = [None]                                  # the frame count the flat-row bookkeeping below was made for
-
-        def flat_rows_for(rs, B_, T_):
-            """The flat-row bookkeeping of the current (lens, B, T): made when the first flat layer runs, made again when a VALID-padded or
-            subsampling layer has changed the lengths (the callers reset it) OR the frame count -- a dense batch (lens None) has no lengths to
-            replace, only T changes (tools/fuzz_models.py seeds 202 / 203: stale rows behind a VALID-padded layer of a dense batch)."""
-            if rs is None or rows_T[0] != (B_, T_):
-                rs = ops.flat_rows(lens, B_, T_, lambda role, shape, dt: self._ws.get(role, shape, dt, dev, padded=False))
-                rows_T[0] = (B_, T_)
-            return rs
-        row_starts = None                                # prefix sums of lens for the layers on flat row tiles: made when the first one runs,
-                                                         # again when a VALID-padded or subsampling layer has changed the lengths
-        act_dtype = L.act_torch_dtype(gemm)
         tail_at = self._tail_step(steps) if defer_tail else -1
-        self._deferred = None        # set by a pooling step whose consumer is the deferred tail
-        pooled = False
-        skip = False
-        # split-bf16 mode: frame-level activations travel between the wide layers as hi/lo bf16 planes (2,B,T,ld) instead
-        # of fp32, so the GEMM K-loop carries no conversion (ktf_tdnn_split); `planes` holds them while they exist
-        use_planes = gemm == L.GEMM_BF16X3 and self.split_planes
-        planes = None
-        pending_bn = None            # F16MX: the BatchNorm of the previous layer, to be folded into the next layer's weights
-        mxp = None                   # F16MX: the current activations as the four MX planes (mx.Planes)
+        c = _RunState(self._ws, x, lens, gemm, pairs, tail_at, steps[tail_at][1] if tail_at >= 0 else None)
         for si, st in enumerate(steps):
-            if skip:
-                skip = False
+            if c.skip:                                   # (pooled in the epilogue of the layer in front of it)
+                c.skip = False
                 continue
+            if si == tail_at and c.deferred is not None:
+                return c.deferred
             nxt = steps[si + 1] if si + 1 < len(steps) else None
             # layer si reads what layer si-1 wrote: two arenas alternate; outputs with pad columns and the single rows
             # after the pooling get arenas of their own, so that in steady state no role changes shape (a change costs a fill)
-            out_role = f"act{si & 1}" + ("s" if pooled else "")
-            if st[0] == "tdnn" and st[1].units % 32:
-                out_role += "p"
-            if si == tail_at and self._deferred is not None:
-                return self._deferred
+            out_role = f"act{si & 1}" + ("s" if c.pooled else "") + ("p" if st[0] == "tdnn" and st[1].units % 32 else "")
+            own = can_pool = False                       # own: a frame-level layer on the kernels of the call's mode
             if st[0] == "tdnn":
-                _, l, relu, bn = st
+                _, l, relu, _ = st
                 if relu and l.activation not in (None, "linear"):
                     raise ValueError("cannot fuse a ReLU after a TDNN that already has an activation")
-                can_pool = (self.fuse_stats and not pooled and nxt is not None and nxt[0] == "stats" and
+                can_pool = (self.fuse_stats and not c.pooled and nxt is not None and nxt[0] == "stats" and
                             nxt[1].inputPeriod == 1 and l.units > 128 and l.padding == "SAME" and l.subsamplingFactor == 1)
-                if not pooled:                           # (frame-level layers: behind the pooling everything is fp32 by design)
+                if not c.pooled:                         # (frame-level layers: behind the pooling everything is fp32 by design)
                     l.warn_fallback(gemm, relu)
-            if gemm == L.GEMM_F16MX and st[0] == "tdnn" and not pooled and l.effective_gemm(gemm, relu) == gemm:
-                # one half pass + two block-scaled residual passes (csrc/tdnn_mx.hip): activations travel as four chunk-major
-                # planes (half value, e2m1 images of the residual and of the value, block scales) holding the ReLU outputs; a
-                # layer's BatchNorm is folded into the weights of the next layer of the route
-                if mxp is None:                          # first layer of the route: fp32 rows -> planes
-                    B, T, D = x.shape
-                    src = x if (x.dtype == torch.float32 and x.stride(2) == 1 and x.stride(0) == T * x.stride(1)) \
-                        else x.to(torch.float32).contiguous()
-                    mxp = Planes.buffers(self._ws.get, "mx_in", B, T, D, dev)
-                    ops.mx_planes(src, D, lens, mxp)
-                B, T, _ = mxp.shape
-                fold, pending_bn = pending_bn, None
-                plain = l.padding == "SAME" and l.subsamplingFactor == 1      # (VALID padding / subsampling: the 256-row kernel only)
-                Tout = l.outputTimesteps(T)
-                use_loader = plain and self._mx_use_loader(B, T)
-                kern = "loader" if use_loader else "tile"
-                wh, wq, bias = l.device_weights_mx(dev, fold=fold, kernel=kern)
-                mxf = L.TDNN_MX_LOADER if use_loader else 0
-                d = l.desc(gemm, torch.float32, torch.float32, act="relu" if relu else None, flags=mxf)      # (the MX entry points read no dtype field)
-                nch_in = ops.round_up(l.inputDim, 32) // 32
-                mx_flat = (self.mx_flat_rows and plain and not use_loader and B * T > 0 and B <= 4095 and B * T * nch_in * 64 < 2 ** 32
-                           and B * T * (ops.round_up(l.units, 32) // 32) < 2 ** 31
-                           and -(-(B * T) // 256) * 200 <= B * (-(-T // 256)) * 197)          # at least 1.5 % fewer tiles even if no frame was dropped
-                if mx_flat:
-                    row_starts = flat_rows_for(row_starts, B, T)
-                if can_pool and mx_flat and self.flat_pooling:      # ... on flat row tiles (partial sums per run of an utterance's rows: flat_pooling)
-                    sp = nxt[1]
-                    od = 2 * l.units if sp.includeStd else l.units
-                    slots = ops.flat_stats_slots(T) if self.deterministic else 0
-                    sums = self._ws.get("sums", (B, max(slots, 1), 2, l.units), torch.float64, dev, padded=False)
-                    sbuf = self._ws.get("pooled", (B, ops.round_up(od, 32)), torch.float32, dev)
-                    scale, shift = bn.affine_device(dev) if bn is not None else (None, None)
-                    d.flags = L.TDNN_DET_STATS if slots else 0
-                    ops.tdnn_mx_flat_stats(mxp, row_starts, d, wh, wq, bias, scale, shift, sums, zero=not slots)
-                    if slots:
-                        ops.stats_finalize_flat(sums, row_starts, T, l.units, sp.includeStd, sp.epsilon, sbuf, slots)
-                    else:
-                        ops.stats_finalize(sums, lens, T, l.units, sp.includeStd, sp.epsilon, sbuf)
-                    if si + 2 == tail_at:            # (the fused tail reads finished pooled rows: its own finalize knows per-utterance slots only)
-                        self._deferred = DeferredTail(steps[tail_at][1], B, l.units, sp.includeStd, sp.epsilon, pooled=sbuf, lens=lens, T=T)
-                    x = sbuf[:, :od].unsqueeze(0)
-                    lens, pooled, skip, mxp = None, True, True, None
-                    continue
-                if can_pool:                             # ... -> reducing StatsPooling inside the epilogue (BatchNorm applied there)
-                    sp = nxt[1]
-                    od = 2 * l.units if sp.includeStd else l.units
-                    slots = ops.stats_slots(T, mx_flags=mxf) if self.deterministic else 0
-                    srows = ops.mx_slot_rows(mxf)
-                    sums = self._ws.get("sums", (B, max(slots, 1), 2, l.units), torch.float64, dev, padded=False)
-                    sbuf = self._ws.get("pooled", (B, ops.round_up(od, 32)), torch.float32, dev)
-                    scale, shift = bn.affine_device(dev) if bn is not None else (None, None)
-                    d.flags = mxf | (L.TDNN_DET_STATS if slots else 0)
-                    ops.tdnn_mx_stats(mxp, lens, d, wh, wq, bias, scale, shift, sums, zero=not slots)
-                    if si + 2 == tail_at:            # the caller's fused tail finalizes the sums itself
-                        self._deferred = DeferredTail(steps[tail_at][1], B, l.units, sp.includeStd, sp.epsilon, sums=sums, slots=slots,
-                                                      lens=lens, T=T, slot_rows=srows)
-                    else:
-                        ops.stats_finalize(sums, lens, T, l.units, sp.includeStd, sp.epsilon, sbuf, slots=slots, slot_rows=srows)
-                    x = sbuf[:, :od].unsqueeze(0)
-                    lens, pooled, skip, mxp = None, True, True, None
-                    continue
-                nl = nxt[1] if nxt is not None and nxt[0] == "tdnn" else None
-                in_route = nl is not None and nl.effective_gemm(gemm, nxt[2]) == gemm and nl.inputDim == l.units
-                defer_bn = bn is not None and in_route
-                scale, shift = (None, None) if (bn is None or defer_bn) else bn.affine_device(dev)
-                if in_route:
-                    out = Planes.buffers(self._ws.get, out_role + "mx", B, Tout, l.units, dev)
-                    if mx_flat:
-                        ops.tdnn_mx_flat(mxp, row_starts, d, wh, wq, bias, scale, shift, out)
-                    else:
-                        ops.tdnn_mx(mxp, lens, d, wh, wq, bias, scale, shift, out)
-                    mxp = out
-                    x = out.xh                            # (shape carrier only)
-                else:
-                    ldy = ops.round_up(l.units, 32)
-                    ybuf = self._ws.get(out_role, (B, Tout, ldy), torch.float32, dev, padded=ldy != l.units)
-                    ops.tdnn_mx(mxp, lens, d, wh, wq, bias, scale, shift, ybuf)
-                    mxp = None
-                    x = ybuf[:, :, : l.units]
-                if lens is not None and not plain:
-                    lens, row_starts = ops.tdnn_out_lens(lens, d, torch.empty_like(lens)), None
-                if defer_bn:
-                    pending_bn = bn
+                    own = l.effective_gemm(gemm, relu) == gemm
+            if own and gemm == L.GEMM_F16MX:
+                self._step_mx(c, si, st, nxt, can_pool, out_role)
                 continue
-            if mxp is not None:
+            if c.mxp is not None:
                 raise RuntimeError("internal: MX planes reached a layer that cannot read them")
-            if pending_bn is not None:
+            if c.pending_bn is not None:
                 raise RuntimeError("internal: a deferred BatchNorm reached a layer that cannot fold it")
-            if use_planes and st[0] == "tdnn" and not pooled and l.units > 128 and l.effective_gemm(gemm, relu) == gemm:
-                if planes is None:                                   # first wide layer: split its fp32 input once
-                    B, T, D = x.shape
-                    planes = self._ws.get("split_in", (2, B, T, ops.round_up(D, 32)), torch.bfloat16, dev)
-                    src = x if (x.dtype == torch.float32 and x.stride(2) == 1 and x.stride(0) == T * x.stride(1)) else x.to(torch.float32).contiguous()
-                    ops.split_bf16(src, D, planes, lens)
-                B, T = planes.shape[1], planes.shape[2]
-                if can_pool:
-                    flat = self.flat_pooling and self._flat_tiles(l, B, T, planes.shape[3])
-                    if flat:
-                        row_starts = flat_rows_for(row_starts, B, T)
-                    x = self._pooled_by_gemm(l, relu, bn, nxt, planes, lens, gemm, True, dev, T,
-                                             defer_to=steps[tail_at][1] if si + 2 == tail_at else None, row_starts=row_starts if flat else None)
-                    lens, pooled, skip, planes = None, True, True, None
-                    continue
-                kint = bool(l.kernelWidth > 1)
-                kflag = (L.TDNN_K_INTERLEAVED if kint else 0) | L.TDNN_W_TILED
-                w, w_lo, bias = l.device_weights(dev, gemm, k_interleaved=kint, w_tiled=True)
-                scale, shift = bn.affine_device(dev) if bn is not None else (None, None)
-                Tout = l.outputTimesteps(T)
-                ldy = ops.round_up(l.units, 32)
-                out_lens = None
-                if lens is not None and (l.padding == "VALID" or l.subsamplingFactor != 1):
-                    out_lens = torch.empty_like(lens)
-                keep = (nxt is not None and nxt[0] == "tdnn" and nxt[1].units > 128 and         # the consumer reads planes too
-                        nxt[1].effective_gemm(gemm, nxt[2]) == gemm)
-                # utterances that fill their 256-row tiles badly (a 1.5 s window: 148 rows): M-tiles over the batch's valid rows laid
-                # end to end (ktf_tdnn_split_flat), same bits
-                flat = self._flat_tiles(l, B, T, planes.shape[3])
-                if flat:
-                    row_starts = flat_rows_for(row_starts, B, T)
-                split = (lambda d_, y_, ylo_: ops.tdnn_split_flat(planes, row_starts, d_, w, w_lo, bias, scale, shift, y_, ylo_)) if flat else \
-                        (lambda d_, y_, ylo_: ops.tdnn_split(planes, lens, d_, w, w_lo, bias, scale, shift, y_, ylo_, out_lens))
-                if keep:
-                    ybuf = self._ws.get(out_role, (2, B, Tout, ldy), torch.bfloat16, dev, padded=ldy != l.units)
-                    split(l.desc(gemm, torch.bfloat16, torch.bfloat16, act="relu" if relu else None, flags=kflag), ybuf[0], ybuf[1])
-                    planes = ybuf
-                    x = ybuf[0][:, :, : l.units]                     # shape carrier only (the values live in `planes`)
-                else:
-                    ybuf = self._ws.get(out_role, (B, Tout, ldy), torch.float32, dev, padded=ldy != l.units)
-                    split(l.desc(gemm, torch.bfloat16, torch.float32, act="relu" if relu else None, flags=kflag), ybuf, None)
-                    planes = None
-                    x = ybuf[:, :, : l.units]
-                if out_lens is not None:
-                    lens, row_starts = out_lens, None
+            if own and gemm == L.GEMM_BF16X3 and self.split_planes and l.units > 128:
+                self._step_planes(c, si, st, nxt, can_pool, out_role)
                 continue
-            if planes is not None:
+            if c.planes is not None:
                 raise RuntimeError("internal: split planes reached a layer that cannot read them")
             if st[0] == "tdnn":
-                if (can_pool and gemm in (L.GEMM_BF16, L.GEMM_BF16X3) and l.effective_gemm(gemm, relu) == gemm):
-                    xdt = L.act_torch_dtype(gemm)
-                    if x.dtype != xdt or x.stride(2) != 1 or x.stride(1) % 8 != 0 or x.stride(1) < ops.round_up(x.shape[-1], 32):
-                        x = _padded_copy(x, xdt)
-                    x = self._pooled_by_gemm(l, relu, bn, nxt, x, lens, gemm, False, dev, x.shape[1],
-                                             defer_to=steps[tail_at][1] if si + 2 == tail_at else None)
-                    lens, pooled, skip = None, True, True
-                    continue
-                g = L.GEMM_F32 if pooled else l.effective_gemm(gemm, relu)
-                ydt = torch.float32 if (pooled or g != gemm) else act_dtype
-                # the pair route (small batches of a reduced-precision model): this layer reads pairs if its producer wrote them,
-                # and writes them if its consumer is a frame-level layer that can read them
-                pair_in, x_pair = x_pair, False
-                pair_ok = lambda t, r: t.activation in (None, "linear") or (t.activation == "relu" and not r)  # noqa: E731
-                pair_out = (pairs and not pooled and g == L.GEMM_F32 and pair_ok(l, relu) and nxt is not None and nxt[0] == "tdnn"
-                            and pair_ok(nxt[1], nxt[2]) and nxt[1].inputDim == l.units)
-                if pair_in:
-                    g = L.GEMM_BF16X4
-                    if can_pool:                         # [affine, relu, batchnorm] -> reducing StatsPooling inside the pair kernel's epilogue
-                        sp = nxt[1]
-                        B, T, _ = x.shape
-                        od = 2 * l.units if sp.includeStd else l.units
-                        slots = ops.tdnn_stats_slots(T, g) if self.deterministic else 0
-                        srows = ops.tdnn_slot_rows(g)
-                        sums = self._ws.get("sums", (B, max(slots, 1), 2, l.units), torch.float64, dev, padded=False)
-                        sbuf = self._ws.get("pooled", (B, ops.round_up(od, 32)), torch.float32, dev)
-                        if x.stride(2) != 1 or x.stride(1) % 8 != 0 or x.stride(1) < ops.round_up(x.shape[-1], 32):
-                            x = _padded_copy(x, torch.float32)
-                        w, _, bias = l.device_weights(dev, g)
-                        scale, shift = bn.affine_device(dev) if bn is not None else (None, None)
-                        d = l.desc(g, L.PAIR, torch.float32, act="relu" if relu else None, flags=L.TDNN_DET_STATS if slots else 0)
-                        ops.tdnn_stats(x, lens, d, w, None, bias, scale, shift, sums, zero=not slots)
-                        if si + 2 == tail_at:            # the caller's fused tail finalizes the sums itself
-                            self._deferred = DeferredTail(steps[tail_at][1], B, l.units, sp.includeStd, sp.epsilon, sums=sums, slots=slots,
-                                                          lens=lens, T=T, slot_rows=srows)
-                        else:
-                            ops.stats_finalize(sums, lens, T, l.units, sp.includeStd, sp.epsilon, sbuf, slots=slots, slot_rows=srows)
-                        x = sbuf[:, :od].unsqueeze(0)
-                        lens, pooled, skip = None, True, True
-                        continue
-                if x.dtype != L.act_torch_dtype(g) or x.stride(2) != 1 or \
-                        x.stride(1) % 8 != 0 or x.stride(1) < ops.round_up(x.shape[-1], 32):
-                    x = _padded_copy(x, L.act_torch_dtype(g))
-                B, T, _ = x.shape
-                Tout = l.outputTimesteps(T)
-                ldy = ops.round_up(l.units, 32)
-                ybuf = self._ws.get(out_role, (B, Tout, ldy), ydt, dev, padded=ldy != l.units)
-                out_lens = None
-                if lens is not None and (l.padding == "VALID" or l.subsamplingFactor != 1):
-                    out_lens = torch.empty_like(lens)
-                sc_sh = bn.affine_device(dev) if bn is not None else None
-                l.forward(x, lens=lens, relu=relu, bn=sc_sh, gemm=g, out_dtype=ydt, ldy=ldy, out=ybuf, out_lens=out_lens,
-                          pair_in=pair_in, pair_out=pair_out)
-                x_pair = pair_out
-                if out_lens is not None:
-                    lens, row_starts = out_lens, None
-                x = ybuf[:, :, : l.units]
+                self._step_generic(c, si, st, nxt, can_pool, out_role)
             elif st[0] == "stats":
-                l = st[1]
-                B, T, D = x.shape
-                od = 2 * D if l.includeStd else D
-                sbuf = self._ws.get("pooled", (B, ops.round_up(od, 32)), torch.float32, dev)
-                l.reduce_all(x, D, lens=lens, out=sbuf)
-                if si + 1 == tail_at:
-                    return DeferredTail(steps[tail_at][1], B, D, l.includeStd, l.epsilon, pooled=sbuf, lens=lens, T=T)      # (lens: KTF_TAIL_SKIP_EMPTY of the
-                                                                                                                         # short-utterance pass reads them)
-                x = sbuf[:, :od].unsqueeze(0)       # (1, B, od): the pooled vectors form ONE B-row matrix
-                lens = None
-                pooled = True
+                self._step_stats(c, si, st[1])
             else:
-                x = st[1](x.to(torch.float32).contiguous())
-        if pooled:
-            return x.reshape(x.shape[1], 1, x.shape[2])
-        return x
+                c.x = st[1](c.x.to(torch.float32).contiguous())
+        if c.pooled:
+            return c.x.reshape(c.x.shape[1], 1, c.x.shape[2])
+        return c.x
+
+    def _step_mx(self, c, si, st, nxt, can_pool, out_role):
+        """f16mx: one half pass + two block-scaled residual passes (csrc/tdnn_mx.hip). Activations travel as four chunk-major planes (half
+        value, e2m1 images of the residual and of the value, block scales) holding the ReLU outputs; a layer's BatchNorm is folded into
+        the weights of the next layer of the route."""
+        _, l, relu, bn = st
+        if c.mxp is None:                                # first layer of the route: fp32 rows -> planes
+            B, T, D = c.x.shape
+            src = _f32_rows(c.x)
+            c.mxp = Planes.buffers(c.ws.get, "mx_in", B, T, D, c.dev)
+            ops.mx_planes(src, D, c.lens, c.mxp)
+        B, T, _ = c.mxp.shape
+        fold, c.pending_bn = c.pending_bn, None
+        plain = l.padding == "SAME" and l.subsamplingFactor == 1      # (VALID padding / subsampling: the 256-row kernel only)
+        use_loader = plain and self._mx_use_loader(B, T)
+        wh, wq, bias = l.device_weights_mx(c.dev, fold=fold, kernel="loader" if use_loader else "tile")
+        mxf = L.TDNN_MX_LOADER if use_loader else 0
+        nch_in = ops.round_up(l.inputDim, 32) // 32
+        # plane outputs of the 256-row kernel on flat row tiles (ktf_tdnn_mx_flat), same bits
+        flat = (self.mx_flat_rows and plain and not use_loader and B * T > 0 and B <= 4095 and B * T * nch_in * 64 < 2 ** 32
+                and B * T * (ops.round_up(l.units, 32) // 32) < 2 ** 31 and _fewer_flat_tiles(B, T))
+        rows = c.rows(B, T) if flat else None
+        act = "relu" if relu else None
+        if can_pool:                                     # BatchNorm applied in the epilogue; on flat row tiles if flat_pooling
+            rows = rows if self.flat_pooling else None
+            slots = (ops.flat_stats_slots(T) if rows is not None else ops.stats_slots(T, mx_flags=mxf)) if self.deterministic else 0
+            d = l.desc(c.gemm, torch.float32, torch.float32, act=act, flags=mxf | (L.TDNN_DET_STATS if slots else 0))
+            scale, shift = bn.affine_device(c.dev) if bn is not None else (None, None)
+            fn, where = (ops.tdnn_mx_flat_stats, rows) if rows is not None else (ops.tdnn_mx_stats, c.lens)
+            self._pool_in_epilogue(c, si, l, nxt[1], B, T, lambda sums, zero: fn(c.mxp, where, d, wh, wq, bias, scale, shift, sums, zero=zero),
+                                   slots, ops.mx_slot_rows(mxf), rows)
+            return
+        nl = nxt[1] if nxt is not None and nxt[0] == "tdnn" else None
+        in_route = nl is not None and nl.effective_gemm(c.gemm, nxt[2]) == c.gemm and nl.inputDim == l.units
+        defer_bn = bn is not None and in_route
+        scale, shift = (None, None) if (bn is None or defer_bn) else bn.affine_device(c.dev)
+        d = l.desc(c.gemm, torch.float32, torch.float32, act=act, flags=mxf)      # (the MX entry points read no dtype field)
+        Tout = l.outputTimesteps(T)
+        if in_route:
+            out = Planes.buffers(c.ws.get, out_role + "mx", B, Tout, l.units, c.dev)
+            if rows is not None:
+                ops.tdnn_mx_flat(c.mxp, rows, d, wh, wq, bias, scale, shift, out)
+            else:
+                ops.tdnn_mx(c.mxp, c.lens, d, wh, wq, bias, scale, shift, out)
+            c.mxp, c.x = out, out.xh                     # (x: shape carrier only)
+        else:
+            ldy = ops.round_up(l.units, 32)
+            ybuf = c.ws.get(out_role, (B, Tout, ldy), torch.float32, c.dev, padded=ldy != l.units)
+            ops.tdnn_mx(c.mxp, c.lens, d, wh, wq, bias, scale, shift, ybuf)
+            c.mxp, c.x = None, ybuf[:, :, : l.units]
+        if c.lens is not None and not plain:
+            c.set_lens(ops.tdnn_out_lens(c.lens, d, torch.empty_like(c.lens)))
+        c.pending_bn = bn if defer_bn else None
+
+    def _step_planes(self, c, si, st, nxt, can_pool, out_role):
+        """split-bf16: frame-level activations travel between the wide layers as hi/lo bf16 planes (2,B,T,ld) instead of fp32, so the
+        GEMM K-loop carries no conversion (ktf_tdnn_split)."""
+        _, l, relu, bn = st
+        if c.planes is None:                             # first wide layer: split its fp32 input once
+            B, T, D = c.x.shape
+            c.planes = c.ws.get("split_in", (2, B, T, ops.round_up(D, 32)), torch.bfloat16, c.dev)
+            ops.split_bf16(_f32_rows(c.x), D, c.planes, c.lens)
+        planes = c.planes
+        B, T = planes.shape[1], planes.shape[2]
+        # utterances that fill their 256-row tiles badly (a 1.5 s window: 148 rows): M-tiles over the batch's valid rows laid end to end
+        # (ktf_tdnn_split_flat), same bits; a pooling layer there if flat_pooling
+        rows = c.rows(B, T) if (self.flat_pooling or not can_pool) and self._flat_tiles(l, B, T, planes.shape[3]) else None
+        kflag = (L.TDNN_K_INTERLEAVED if l.kernelWidth > 1 else 0) | L.TDNN_W_TILED
+        w, w_lo, bias = l.device_weights(c.dev, c.gemm, k_interleaved=l.kernelWidth > 1, w_tiled=True)
+        scale, shift = bn.affine_device(c.dev) if bn is not None else (None, None)
+        act = "relu" if relu else None
+        if can_pool:
+            slots = (ops.flat_stats_slots(T) if rows is not None else ops.stats_slots(T)) if self.deterministic else 0
+            d = l.desc(c.gemm, torch.bfloat16, torch.bfloat16, act=act, flags=kflag | (L.TDNN_DET_STATS if slots else 0))
+            fn, where = (ops.tdnn_split_flat_stats, rows) if rows is not None else (ops.tdnn_split_stats, c.lens)
+            self._pool_in_epilogue(c, si, l, nxt[1], B, T, lambda sums, zero: fn(planes, where, d, w, w_lo, bias, scale, shift, sums, zero=zero),
+                                   slots, rows=rows, pad_cols=True)
+            return
+        Tout, ldy = l.outputTimesteps(T), ops.round_up(l.units, 32)
+        out_lens = torch.empty_like(c.lens) if c.lens is not None and (l.padding == "VALID" or l.subsamplingFactor != 1) else None
+        keep = (nxt is not None and nxt[0] == "tdnn" and nxt[1].units > 128 and         # the consumer reads planes too
+                nxt[1].effective_gemm(c.gemm, nxt[2]) == c.gemm)
+        ydt = torch.bfloat16 if keep else torch.float32
+        ybuf = c.ws.get(out_role, ((2,) if keep else ()) + (B, Tout, ldy), ydt, c.dev, padded=ldy != l.units)
+        y, y_lo = (ybuf[0], ybuf[1]) if keep else (ybuf, None)
+        d = l.desc(c.gemm, torch.bfloat16, ydt, act=act, flags=kflag)
+        if rows is not None:
+            ops.tdnn_split_flat(planes, rows, d, w, w_lo, bias, scale, shift, y, y_lo)
+        else:
+            ops.tdnn_split(planes, c.lens, d, w, w_lo, bias, scale, shift, y, y_lo, out_lens)
+        c.planes = ybuf if keep else None
+        c.x = y[:, :, : l.units]                         # (planes kept: shape carrier only)
+        if out_lens is not None:
+            c.set_lens(out_lens)
+
+    def _step_generic(self, c, si, st, nxt, can_pool, out_role):
+        """Every other layer: the fp32 / one-pass bf16 kernels (ktf_tdnn), and the pair route -- small batches of a reduced-precision
+        model: a layer reads KTF_BF16P pairs if its producer wrote them, and writes them if its consumer is a frame-level layer that can."""
+        _, l, relu, bn = st
+        gemm = c.gemm
+        pair_in, c.x_pair = c.x_pair, False
+        if can_pool and (pair_in or (gemm in (L.GEMM_BF16, L.GEMM_BF16X3) and l.effective_gemm(gemm, relu) == gemm)):
+            g = L.GEMM_BF16X4 if pair_in else gemm       # pooled in the epilogue of the pair / one-pass bf16 / split-bf16 kernel
+            x = _gemm_rows(c.x, L.act_torch_dtype(g))
+            slots = (ops.tdnn_stats_slots(x.shape[1], g) if pair_in else ops.stats_slots(x.shape[1])) if self.deterministic else 0
+            w, w_lo, bias = l.device_weights(c.dev, g)
+            scale, shift = bn.affine_device(c.dev) if bn is not None else (None, None)
+            d = l.desc(g, L.PAIR if pair_in else x.dtype, x.dtype, act="relu" if relu else None, flags=L.TDNN_DET_STATS if slots else 0)
+            self._pool_in_epilogue(c, si, l, nxt[1], x.shape[0], x.shape[1],
+                                   lambda sums, zero: ops.tdnn_stats(x, c.lens, d, w, w_lo, bias, scale, shift, sums, zero=zero),
+                                   slots, ops.tdnn_slot_rows(g) if pair_in else 128, pad_cols=not pair_in)
+            return
+        g = L.GEMM_F32 if c.pooled else l.effective_gemm(gemm, relu)
+        ydt = torch.float32 if (c.pooled or g != gemm) else L.act_torch_dtype(gemm)
+        pair_ok = lambda t, r: t.activation in (None, "linear") or (t.activation == "relu" and not r)  # noqa: E731
+        pair_out = (c.pairs and not c.pooled and g == L.GEMM_F32 and pair_ok(l, relu) and nxt is not None and nxt[0] == "tdnn"
+                    and pair_ok(nxt[1], nxt[2]) and nxt[1].inputDim == l.units)
+        if pair_in:
+            g = L.GEMM_BF16X4
+        x = _gemm_rows(c.x, L.act_torch_dtype(g))
+        B, T = x.shape[0], x.shape[1]
+        Tout, ldy = l.outputTimesteps(T), ops.round_up(l.units, 32)
+        ybuf = c.ws.get(out_role, (B, Tout, ldy), ydt, c.dev, padded=ldy != l.units)
+        out_lens = torch.empty_like(c.lens) if c.lens is not None and (l.padding == "VALID" or l.subsamplingFactor != 1) else None
+        l.forward(x, lens=c.lens, relu=relu, bn=bn.affine_device(c.dev) if bn is not None else None, gemm=g, out_dtype=ydt, ldy=ldy,
+                  out=ybuf, out_lens=out_lens, pair_in=pair_in, pair_out=pair_out)
+        c.x_pair = pair_out
+        if out_lens is not None:
+            c.set_lens(out_lens)
+        c.x = ybuf[:, :, : l.units]
+
+    def _step_stats(self, c, si, sp):
+        """A reducing StatsPooling that no GEMM epilogue took: a pass of its own over the frame-level rows."""
+        B, T, D = c.x.shape
+        od = 2 * D if sp.includeStd else D
+        sbuf = c.ws.get("pooled", (B, ops.round_up(od, 32)), torch.float32, c.dev)
+        sp.reduce_all(c.x, D, lens=c.lens, out=sbuf)
+        if si + 1 == c.tail_at:                          # (lens: KTF_TAIL_SKIP_EMPTY of the short-utterance pass reads them)
+            c.defer(sp, B, D, T, pooled=sbuf)
+        c.x = sbuf[:, :od].unsqueeze(0)                  # (1, B, od): the pooled vectors form ONE B-row matrix
+        c.set_lens(None)
+        c.pooled = True
+
+    def _pool_in_epilogue(self, c, si, l, sp, B, T, launch, slots, slot_rows=128, rows=None, pad_cols=False):
+        """[affine, relu, batchnorm] of step si -> the reducing StatsPooling `sp` behind it, inside the GEMM epilogue (the layer output is
+        never written). `launch(sums, zero)` runs the layer into fp64 partial sums: `slots` per utterance of `slot_rows` rows each
+        (KTF_TDNN_DET_STATS), or one slot accumulated in any order (slots 0); `rows`: the FlatRows of flat row tiles (partial sums per run
+        of an utterance's rows), None: per-utterance tiles. `pad_cols`: a new shape of the pooled view zeroes its pad columns only.
+        Leaves the pooled (1, B, od) view in c.x and skips the pooling step."""
+        D = l.units
+        od = 2 * D if sp.includeStd else D
+        ld = ops.round_up(od, 32)
+        sums = c.ws.get("sums", (B, max(slots, 1), 2, D), torch.float64, c.dev, padded=False)
+        sbuf = c.ws.get("pooled", (B, ld), torch.float32, c.dev, padded=(od if ld != od else False) if pad_cols else True)
+        launch(sums, not slots)
+        to_tail = si + 2 == c.tail_at
+        if to_tail and rows is None:                     # the caller's fused tail finalizes the sums itself
+            c.defer(sp, B, D, T, sums=sums, slots=slots, slot_rows=slot_rows)
+        else:
+            if rows is not None and slots:
+                ops.stats_finalize_flat(sums, rows, T, D, sp.includeStd, sp.epsilon, sbuf, slots)
+            else:
+                ops.stats_finalize(sums, c.lens, T, D, sp.includeStd, sp.epsilon, sbuf, slots=slots, slot_rows=slot_rows)
+            if to_tail:                                  # (flat rows: the fused tail's own finalize knows per-utterance slots only)
+                c.defer(sp, B, D, T, pooled=sbuf)
+        c.x, c.mxp, c.planes = sbuf[:, :od].unsqueeze(0), None, None
+        c.set_lens(None)
+        c.pooled = c.skip = True
 
     def __call__(self, inputs, training=False):
         x = inputs
@@ -663,6 +604,20 @@ class Sequential:
         return x
 
     call = __call__
+
+
+def _fewer_flat_tiles(B, T):
+    """Flat row tiles (a batch's valid rows laid end to end) take at least 1.5 % fewer 256-row tiles than per-utterance ones, even if
+    no frame was dropped."""
+    return -(-(B * T) // 256) * 200 <= B * (-(-T // 256)) * 197
+
+
+def _gemm_rows(x, dtype):
+    """x if the GEMM can read it as it is (`dtype`, unit column stride, a row stride that is a multiple of 8 and covers the padded
+    width), else a padded copy."""
+    if x.dtype != dtype or x.stride(2) != 1 or x.stride(1) % 8 != 0 or x.stride(1) < ops.round_up(x.shape[-1], 32):
+        return _padded_copy(x, dtype)
+    return x
 
 
 def _padded_copy(x, dtype):
