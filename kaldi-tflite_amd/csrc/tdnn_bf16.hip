@@ -1135,94 +1135,67 @@ __global__ __launch_bounds__(256, 2) void tdnn_bf16h_kernel(TdnnParams p, int mt
 
 // ------------------------------------------------------------------------------------ launcher
 int tdnn_launch_16(const TdnnParams& p, const KtfTdnnDesc* d, int64_t B, int64_t Tout, int64_t ldy, double* stats_sums, hipStream_t st) {
-    const unsigned ntiles = (unsigned)ktf_cdiv(d->units, 128);
-    {
-        KTF_REQUIRE(d->w_dtype == KTF_BF16, "ktf_tdnn: bf16 gemm needs bf16 weights");
-        KTF_REQUIRE(d->y_dtype == KTF_BF16 || d->y_dtype == KTF_F32, "ktf_tdnn: bf16 gemm writes bf16 or fp32");
-        const bool x3 = d->gemm == KTF_GEMM_BF16X3;
-        dim3 grid(ntiles, (unsigned)ktf_cdiv(Tout, BF_BM), (unsigned)B);
-        // K-step: 64 when the per-context width allows it, else 32
-        const bool k64 = (d->din_pad % 64) == 0;
-#define BF_LAUNCH(BK, XF, X3)                                                                               \
-    do {                                                                                                    \
-        const size_t lds = (size_t)2 * 128 * BfCfg<BK>::PITCH * 2 * (X3 ? 2 : 1) * sizeof(unsigned short);  \
-        KTF_NOTE_KERNEL("tdnn_bf16_kernel<" #BK ", " #XF ", " #X3 ">");                                      \
-        if (lds > 64 * 1024)                                                                                \
-            KTF_LDS_ONCE((int)lds, tdnn_bf16_kernel<BK, XF, X3>); \
-        hipLaunchKernelGGL((tdnn_bf16_kernel<BK, XF, X3>), grid, dim3(256), lds, st, p);                     \
-    } while (0)
-        if (x3) {
-            if (k64) BF_LAUNCH(64, true, true); else BF_LAUNCH(32, true, true);
-        } else if (d->x_dtype == KTF_F32) {
-            if (k64) BF_LAUNCH(64, true, false); else BF_LAUNCH(32, true, false);
+    KTF_REQUIRE(d->w_dtype == KTF_BF16, "ktf_tdnn: bf16 gemm needs bf16 weights");
+    const bool k64 = (d->din_pad % 64) == 0;             // K-step: 64 when the per-context width allows it, else 32
+    // the 128x128 kernel; its two names per operand form are the ones ktf_tdnn_last_kernel() reports
+    auto plain = [&](auto XF, auto X3, const char* name64, const char* name32) {
+        const dim3 grid((unsigned)ktf_cdiv(d->units, 128), (unsigned)ktf_cdiv(Tout, BF_BM), (unsigned)B);
+        tdnn_pick<64, 32>(k64 ? 64 : 32, [&](auto BK) {
+            constexpr int lds = 2 * 128 * BfCfg<BK>::PITCH * 2 * (X3 ? 2 : 1) * sizeof(unsigned short);
+            tdnn_launch_kernel<tdnn_bf16_kernel<BK, XF, X3>>(BK == 64 ? name64 : name32, grid, dim3(256), lds, lds > 64 * 1024 ? lds : 0, st, p);
+        });
+    };
+    if (d->gemm == KTF_GEMM_BF16X3) {
+        plain(std::true_type{}, std::true_type{}, "tdnn_bf16_kernel<64, true, true>", "tdnn_bf16_kernel<32, true, true>");
+    } else if (d->x_dtype == KTF_F32) {
+        plain(std::true_type{}, std::false_type{}, "tdnn_bf16_kernel<64, true, false>", "tdnn_bf16_kernel<32, true, false>");
+    } else {
+        KTF_REQUIRE(d->x_dtype == KTF_BF16, "ktf_tdnn: bad x_dtype");
+        if (d->units > 128 && ldy % 4 == 0) {
+            // W must be padded to a multiple of 256 rows for this kernel (documented in ktf_hip.h)
+            const int mtiles = ktf_cdiv(Tout, R_BM), ntiles_r = ktf_cdiv(d->units, R_BN);
+            const int64_t gtiles = B * (int64_t)mtiles;
+            const int64_t nblocks = grouped_blocks(gtiles, ntiles_r);
+            KTF_REQUIRE(nblocks < (1ll << 31), "ktf_tdnn: grid too large");
+            // 128x256 tiles with two workgroups per CU win while the fixed per-tile phases are comparable to the K-loop
+            // (K <= 768); deeper K amortises them and the 256x256 tile moves fewer bytes per flop
+            const bool htile = p.ktot <= 768;
+            if (htile && (d->act == KTF_ACT_RELU || d->act == KTF_ACT_NONE)) {
+                const int mt_h = ktf_cdiv(Tout, H_BM);
+                const int64_t gt_h = B * (int64_t)mt_h;
+                const int64_t nb_h = grouped_blocks(gt_h, ntiles_r);
+                KTF_REQUIRE(nb_h < (1ll << 31), "ktf_tdnn: grid too large");
+                tdnn_pick<KTF_ACT_RELU, KTF_ACT_NONE>(d->act, [&](auto A) {
+                    tdnn_pick<true, false>(stats_sums != nullptr, [&](auto ST) {
+                        tdnn_launch_kernel<tdnn_bf16h_kernel<A, ST>>("tdnn_bf16h_kernel", dim3((unsigned)nb_h), dim3(256), H_LDS_BYTES, H_LDS_BYTES,
+                                                                      st, p, mt_h, ntiles_r, (int)gt_h, stats_sums);
+                    });
+                });
+            } else if (d->act == KTF_ACT_RELU || d->act == KTF_ACT_NONE) {      // 16x16x32 MFMAs; sigmoid / tanh stay on the 32x32x16 kernel
+                tdnn_pick<KTF_ACT_RELU, KTF_ACT_NONE>(d->act, [&](auto A) {
+                    tdnn_pick<true, false>(stats_sums != nullptr, [&](auto ST) {
+                        tdnn_launch_kernel<tdnn_bf16r16_kernel<A, ST>>("tdnn_bf16r16_kernel", dim3((unsigned)nblocks), dim3(512), R16_LDS_BYTES,
+                                                                        R16_LDS_BYTES, st, p, mtiles, ntiles_r, (int)gtiles, stats_sums);
+                    });
+                });
+            } else {
+                tdnn_pick<KTF_ACT_NONE, KTF_ACT_RELU, KTF_ACT_SIGMOID, KTF_ACT_TANH>(d->act, [&](auto A) {
+                    tdnn_pick<true, false>(stats_sums != nullptr, [&](auto ST) {
+                        tdnn_launch_kernel<tdnn_bf16r_kernel<A, ST>>("tdnn_bf16r_kernel", dim3((unsigned)nblocks), dim3(512), R_LDS_BYTES, R_LDS_BYTES,
+                                                                      st, p, mtiles, ntiles_r, (int)gtiles, stats_sums);
+                    });
+                });
+            }
+        } else if (k64 && ldy % 4 == 0) {
+            const int mtiles = ktf_cdiv(Tout, G_BM), ntiles_g = ktf_cdiv(d->units, G_BN);
+            const int64_t gtiles = B * (int64_t)mtiles;
+            const int64_t nblocks = grouped_blocks(gtiles, ntiles_g);
+            KTF_REQUIRE(nblocks < (1ll << 31), "ktf_tdnn: grid too large");
+            tdnn_launch_kernel<tdnn_bf16g_kernel>("tdnn_bf16g_kernel", dim3((unsigned)nblocks), dim3(256), G_LDS_BYTES, G_LDS_BYTES, st, p, mtiles,
+                                                  ntiles_g, (int)gtiles);
         } else {
-            KTF_REQUIRE(d->x_dtype == KTF_BF16, "ktf_tdnn: bad x_dtype");
-            if (d->units > 128 && ldy % 4 == 0) {
-                // W must be padded to a multiple of 256 rows for this kernel (documented in ktf_hip.h)
-                const int mtiles = ktf_cdiv(Tout, R_BM), ntiles_r = ktf_cdiv(d->units, R_BN);
-                const int64_t gtiles = B * (int64_t)mtiles;
-                const int64_t nblocks = ((gtiles + 7) / 8) * 8 * ntiles_r;
-                KTF_REQUIRE(nblocks < (1ll << 31), "ktf_tdnn: grid too large");
-#define R_LAUNCH(A)                                                                                                    \
-    do {                                                                                                               \
-        KTF_NOTE_KERNEL("tdnn_bf16r_kernel");                                                                          \
-        if (stats_sums) {                                                                                              \
-            KTF_LDS_ONCE(R_LDS_BYTES, tdnn_bf16r_kernel<A, true>); \
-            hipLaunchKernelGGL((tdnn_bf16r_kernel<A, true>), dim3((unsigned)nblocks), dim3(512), R_LDS_BYTES, st, p, mtiles, ntiles_r, (int)gtiles, stats_sums); \
-        } else {                                                                                                       \
-            KTF_LDS_ONCE(R_LDS_BYTES, tdnn_bf16r_kernel<A, false>); \
-            hipLaunchKernelGGL((tdnn_bf16r_kernel<A, false>), dim3((unsigned)nblocks), dim3(512), R_LDS_BYTES, st, p, mtiles, ntiles_r, (int)gtiles, (double*)nullptr); \
-        }                                                                                                              \
-    } while (0)
-                // 128x256 tiles with two workgroups per CU win while the fixed per-tile phases are comparable to the K-loop
-                // (K <= 768); deeper K amortises them and the 256x256 tile moves fewer bytes per flop
-                const bool htile = p.ktot <= 768;
-                if (htile && (d->act == KTF_ACT_RELU || d->act == KTF_ACT_NONE)) {
-                    const int mt_h = ktf_cdiv(Tout, H_BM);
-                    const int64_t gt_h = B * (int64_t)mt_h;
-                    const int64_t nb_h = ((gt_h + 7) / 8) * 8 * ntiles_r;
-                    KTF_REQUIRE(nb_h < (1ll << 31), "ktf_tdnn: grid too large");
-#define H_LAUNCH(A, ST)                                                                                                \
-    do {                                                                                                               \
-        KTF_NOTE_KERNEL("tdnn_bf16h_kernel");                                                                          \
-        KTF_LDS_ONCE(H_LDS_BYTES, tdnn_bf16h_kernel<A, ST>);                                                           \
-        hipLaunchKernelGGL((tdnn_bf16h_kernel<A, ST>), dim3((unsigned)nb_h), dim3(256), H_LDS_BYTES, st, p, mt_h, ntiles_r, (int)gt_h, stats_sums); \
-    } while (0)
-                    if (d->act == KTF_ACT_RELU) { if (stats_sums) H_LAUNCH(KTF_ACT_RELU, true); else H_LAUNCH(KTF_ACT_RELU, false); }
-                    else { if (stats_sums) H_LAUNCH(KTF_ACT_NONE, true); else H_LAUNCH(KTF_ACT_NONE, false); }
-#undef H_LAUNCH
-                    KTF_CHECK_LAUNCH("ktf_tdnn");
-                    return KTF_OK;
-                }
-                if (d->act == KTF_ACT_RELU || d->act == KTF_ACT_NONE) {       // 16x16x32 MFMAs; sigmoid / tanh stay on the 32x32x16 kernel
-#define S_LAUNCH(A, ST)                                                                                                \
-    do {                                                                                                               \
-        KTF_NOTE_KERNEL("tdnn_bf16r16_kernel");                                                                        \
-        KTF_LDS_ONCE(R16_LDS_BYTES, tdnn_bf16r16_kernel<A, ST>);                                                       \
-        hipLaunchKernelGGL((tdnn_bf16r16_kernel<A, ST>), dim3((unsigned)nblocks), dim3(512), R16_LDS_BYTES, st, p, mtiles, ntiles_r, (int)gtiles, stats_sums); \
-    } while (0)
-                    if (d->act == KTF_ACT_RELU) { if (stats_sums) S_LAUNCH(KTF_ACT_RELU, true); else S_LAUNCH(KTF_ACT_RELU, false); }
-                    else { if (stats_sums) S_LAUNCH(KTF_ACT_NONE, true); else S_LAUNCH(KTF_ACT_NONE, false); }
-#undef S_LAUNCH
-                    KTF_CHECK_LAUNCH("ktf_tdnn");
-                    return KTF_OK;
-                }
-                if (d->act == KTF_ACT_NONE) R_LAUNCH(KTF_ACT_NONE);
-                else if (d->act == KTF_ACT_RELU) R_LAUNCH(KTF_ACT_RELU);
-                else if (d->act == KTF_ACT_SIGMOID) R_LAUNCH(KTF_ACT_SIGMOID);
-                else R_LAUNCH(KTF_ACT_TANH);
-#undef R_LAUNCH
-            } else if (k64 && ldy % 4 == 0) {
-                const int mtiles = ktf_cdiv(Tout, G_BM), ntiles_g = ktf_cdiv(d->units, G_BN);
-                const int64_t gtiles = B * (int64_t)mtiles;
-                const int64_t nblocks = ((gtiles + 7) / 8) * 8 * ntiles_g;
-                KTF_REQUIRE(nblocks < (1ll << 31), "ktf_tdnn: grid too large");
-                KTF_NOTE_KERNEL("tdnn_bf16g_kernel");
-                KTF_LDS_ONCE(G_LDS_BYTES, tdnn_bf16g_kernel);
-                hipLaunchKernelGGL(tdnn_bf16g_kernel, dim3((unsigned)nblocks), dim3(256), G_LDS_BYTES, st, p, mtiles, ntiles_g, (int)gtiles);
-            } else if (k64) BF_LAUNCH(64, false, false); else BF_LAUNCH(32, false, false);
+            plain(std::false_type{}, std::false_type{}, "tdnn_bf16_kernel<64, false, false>", "tdnn_bf16_kernel<32, false, false>");
         }
-#undef BF_LAUNCH
     }
     KTF_CHECK_LAUNCH("ktf_tdnn");
     return KTF_OK;

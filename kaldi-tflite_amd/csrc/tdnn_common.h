@@ -11,6 +11,7 @@
 // Replaces: layers/tdnn/tdnn.py:251-280 (+ keras ReLU, batchnorm.py:78-88) of the reference.
 #pragma once
 #include <stdlib.h>
+#include <type_traits>
 
 #include "common.h"
 
@@ -172,7 +173,59 @@ __device__ __forceinline__ void store_tile32_t(const f32x16& acc, const TdnnPara
 
 // name of the kernel family the calling thread's last ktf_tdnn* call launched (ktf_tdnn_last_kernel; dispatch tests)
 extern thread_local const char* g_ktf_last_kernel;
-#define KTF_NOTE_KERNEL(name) (g_ktf_last_kernel = (name))
+
+// Opts kernel K in to `bytes` of dynamic LDS, once per kernel and device. K is a template argument so that every kernel has a flag
+// of its own: most of them share one signature.
+template <auto K>
+static void tdnn_lds_once(int bytes) {
+    KTF_LDS_ONCE(bytes, K);
+}
+
+// Every TDNN GEMM launch: records `name` for ktf_tdnn_last_kernel(), opts K in to `lds_attr` bytes of dynamic LDS (0: no opt-in,
+// for kernels within the default 64 KiB) and launches it with `lds` bytes (MX: the opt-in covers the largest K, the launch its own).
+template <auto K, typename... Args>
+static void tdnn_launch_kernel(const char* name, dim3 grid, dim3 block, int lds, int lds_attr, hipStream_t st, Args... args) {
+    g_ktf_last_kernel = name;
+    if (lds_attr > 0) tdnn_lds_once<K>(lds_attr);
+    hipLaunchKernelGGL(K, grid, block, lds, st, args...);
+}
+
+// Compile-time dispatch: f(std::integral_constant<T, V>{}) for the first V of the list that equals v, else for the last one (the
+// launchers pass values they have validated, so the last entry is the remaining case). Template arguments keep the list's type.
+template <auto V, auto... Vs, typename F>
+static void tdnn_pick(decltype(V) v, F&& f) {
+    if constexpr (sizeof...(Vs) == 0) f(std::integral_constant<decltype(V), V>{});
+    else if (v == V) f(std::integral_constant<decltype(V), V>{});
+    else tdnn_pick<Vs...>(v, f);
+}
+
+// Blocks of a grouped tile walk: the M-tiles (gtiles over the batch) in groups of 8, times the N-tiles
+static inline int64_t grouped_blocks(int64_t gtiles, int64_t ntiles) { return ((gtiles + 7) / 8) * 8 * ntiles; }
+
+// Column width of the 64-row small tiles with K-step 64 (tdnn_f32s_kernel, tdnn_x4s_kernel): one workgroup per CU (the ring takes most
+// of the LDS), so the cost is (rounds of 256 workgroups) x (time of one, ~ width + fixed part); 96 columns only where W's rows, padded to
+// a multiple of 128, cover the last tile. `mtiles`: 64-row tiles over the batch.
+static inline int small_tile_width(int units, int64_t mtiles) {
+    int best = 32;
+    int64_t best_cost = INT64_MAX;
+    for (int bn = 32; bn <= 96; bn += 32) {
+        if (bn == 96 && (int64_t)ktf_cdiv(units, 96) * 96 > (int64_t)ktf_cdiv(units, 128) * 128) continue;
+        const int64_t cost = ktf_cdiv(ktf_cdiv(units, bn) * mtiles, 256) * (bn + 16);
+        if (cost < best_cost) best_cost = cost, best = bn;
+    }
+    return best;
+}
+
+// The descriptor checks of ktf_tdnn* and ktf_tdnn_mx*; each adds the limits of its own kernels. `who` names the entry point.
+static inline int tdnn_check_desc(const KtfTdnnDesc* d, const float* scale, const float* shift, const char* who) {
+    KTF_REQUIRE(d->units > 0 && d->din > 0, "%s: units/din must be > 0", who);
+    KTF_REQUIRE(d->din_pad >= d->din && d->din_pad % 32 == 0, "%s: din_pad %d must be a multiple of 32 with din <= din_pad", who, d->din_pad);
+    KTF_REQUIRE(d->nctx >= 1 && d->nctx <= 16, "%s: nctx %d outside [1,16]", who, d->nctx);
+    for (int i = 1; i < d->nctx; ++i) KTF_REQUIRE(d->ctx[i] > d->ctx[i - 1], "%s: context must be strictly ascending", who);
+    KTF_REQUIRE(d->subsampling > 0, "%s: subsampling_factor should be > 0", who);
+    KTF_REQUIRE((scale == nullptr) == (shift == nullptr), "%s: scale and shift go together", who);
+    return KTF_OK;
+}
 
 // per-family launchers (validation of the family's own constraints + launch); `p` is filled by tdnn_gemm.hip
 int tdnn_launch_f32(const TdnnParams& p, const KtfTdnnDesc* d, int64_t B, int64_t Tout, hipStream_t st);

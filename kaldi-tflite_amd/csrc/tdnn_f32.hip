@@ -571,57 +571,34 @@ __global__ __launch_bounds__(64) void tdnn_f32_rowvec_kernel(TdnnParams p) {
 
 // ------------------------------------------------------------------------------------ launcher
 int tdnn_launch_f32(const TdnnParams& p, const KtfTdnnDesc* d, int64_t B, int64_t Tout, hipStream_t st) {
-        KTF_REQUIRE(d->x_dtype == KTF_F32 && d->w_dtype == KTF_F32, "ktf_tdnn: F32 gemm needs fp32 x and w");
-        // W must cover round_up(units, 128) rows (the host pads to 256)
-        const int64_t wg128 = (int64_t)ktf_cdiv(d->units, 128) * ktf_cdiv(Tout, 128) * B;
-        const bool lat = !(d->flags & KTF_TDNN_REF_TILES);   // flag: the register-staged 32x32x2 tile kernels (bitwise reference of the DMA-staged ones)
-        if (lat && B * Tout <= 8) {
-            dim3 grid((unsigned)ktf_cdiv(d->units, RV_UNITS), (unsigned)Tout, (unsigned)B);
-            KTF_NOTE_KERNEL("tdnn_f32_rowvec_kernel");
-            hipLaunchKernelGGL(tdnn_f32_rowvec_kernel, grid, dim3(64), 0, st, p);
-        } else if (lat && wg128 < 256) {
-            const int64_t wg64 = (int64_t)ktf_cdiv(d->units, FS_BM) * ktf_cdiv(Tout, FS_BM) * B;
-#define FS_LAUNCH(BK_, BN_, NB_)                                                                                       \
-    do {                                                                                                               \
-        const int lds = FS_NSTAGE * (FS_BM + BN_) * BK_ * 4;                                                           \
-        dim3 grid_((unsigned)ktf_cdiv(d->units, BN_), (unsigned)ktf_cdiv(Tout, FS_BM), (unsigned)B);                   \
-        KTF_NOTE_KERNEL("tdnn_f32s_kernel<" #BK_ ", " #BN_ ">");                                                        \
-        KTF_LDS_ONCE(lds, tdnn_f32s_kernel<BK_, BN_, NB_>);                                                            \
-        hipLaunchKernelGGL((tdnn_f32s_kernel<BK_, BN_, NB_>), grid_, dim3(64 * 4 * (BN_ / 16 / NB_)), lds, st, p);      \
-    } while (0)
-            if (d->din_pad % 64 == 0) {
-                // tile width: one workgroup per CU (the ring takes most of the LDS), so the cost is (rounds of 256 workgroups) x
-                // (time of one, ~ width + fixed part); 96 columns only where the padded W rows cover the last tile
-                const int64_t mt = (int64_t)ktf_cdiv(Tout, FS_BM) * B;
-                int best = 32;
-                int64_t best_cost = INT64_MAX;
-                for (int bn = 32; bn <= 96; bn += 32) {
-                    if (bn == 96 && (int64_t)ktf_cdiv(d->units, 96) * 96 > (int64_t)ktf_cdiv(d->units, 128) * 128) continue;
-                    const int64_t cost = ktf_cdiv(ktf_cdiv(d->units, bn) * mt, 256) * (bn + 16);
-                    if (cost < best_cost) best_cost = cost, best = bn;
-                }
-                (void)wg64;
-                if (best == 32) FS_LAUNCH(64, 32, 1);
-                else if (best == 64) FS_LAUNCH(64, 64, 1);
-                else FS_LAUNCH(64, 96, 3);
-            } else {
-                FS_LAUNCH(32, 64, 1);
-            }
-#undef FS_LAUNCH
-        } else if (lat) {
-            dim3 grid((unsigned)ktf_cdiv(d->units, FT_BM), (unsigned)ktf_cdiv(Tout, FT_BM), (unsigned)B);
-            KTF_NOTE_KERNEL("tdnn_f32t_kernel");
-            KTF_LDS_ONCE(FT_LDS_BYTES, tdnn_f32t_kernel<32>);
-            hipLaunchKernelGGL(tdnn_f32t_kernel<32>, grid, dim3(512), FT_LDS_BYTES, st, p);
-        } else if (wg128 >= 256) {
-            dim3 grid((unsigned)ktf_cdiv(d->units, 128), (unsigned)ktf_cdiv(Tout, 128), (unsigned)B);
-            KTF_NOTE_KERNEL("tdnn_f32_kernel<2, 16>");
-            hipLaunchKernelGGL((tdnn_f32_kernel<2, 16>), grid, dim3(256), 0, st, p);
-        } else {
-            dim3 grid((unsigned)ktf_cdiv(d->units, 64), (unsigned)ktf_cdiv(Tout, 64), (unsigned)B);
-            KTF_NOTE_KERNEL("tdnn_f32_kernel<1, 32>");
-            hipLaunchKernelGGL((tdnn_f32_kernel<1, 32>), grid, dim3(256), 0, st, p);
-        }
+    // W must cover round_up(units, 128) rows (the host pads to 256)
+    const int64_t wg128 = (int64_t)ktf_cdiv(d->units, 128) * ktf_cdiv(Tout, 128) * B;
+    const bool lat = !(d->flags & KTF_TDNN_REF_TILES);   // flag: the register-staged 32x32x2 tile kernels (bitwise reference of the DMA-staged ones)
+    const dim3 grid128((unsigned)ktf_cdiv(d->units, 128), (unsigned)ktf_cdiv(Tout, 128), (unsigned)B);
+    if (lat && B * Tout <= 8) {
+        const dim3 grid((unsigned)ktf_cdiv(d->units, RV_UNITS), (unsigned)Tout, (unsigned)B);
+        tdnn_launch_kernel<tdnn_f32_rowvec_kernel>("tdnn_f32_rowvec_kernel", grid, dim3(64), 0, 0, st, p);
+    } else if (lat && wg128 < 256) {
+        auto small = [&](auto BK, auto BN) {
+            constexpr int NB = BN == 96 ? 3 : 1, lds = FS_NSTAGE * (FS_BM + BN) * BK * 4;
+            const char* name = BK == 32 ? "tdnn_f32s_kernel<32, 64>" : BN == 32 ? "tdnn_f32s_kernel<64, 32>"
+                             : BN == 64 ? "tdnn_f32s_kernel<64, 64>" : "tdnn_f32s_kernel<64, 96>";
+            const dim3 grid((unsigned)ktf_cdiv(d->units, BN), (unsigned)ktf_cdiv(Tout, FS_BM), (unsigned)B);
+            tdnn_launch_kernel<tdnn_f32s_kernel<BK, BN, NB>>(name, grid, dim3(64 * 4 * (BN / 16 / NB)), lds, lds, st, p);
+        };
+        if (d->din_pad % 64 == 0)
+            tdnn_pick<32, 64, 96>(small_tile_width(d->units, (int64_t)ktf_cdiv(Tout, FS_BM) * B),
+                                  [&](auto BN) { small(std::integral_constant<int, 64>{}, BN); });
+        else
+            small(std::integral_constant<int, 32>{}, std::integral_constant<int, 64>{});
+    } else if (lat) {
+        tdnn_launch_kernel<tdnn_f32t_kernel<32>>("tdnn_f32t_kernel", grid128, dim3(512), FT_LDS_BYTES, FT_LDS_BYTES, st, p);
+    } else if (wg128 >= 256) {
+        tdnn_launch_kernel<tdnn_f32_kernel<2, 16>>("tdnn_f32_kernel<2, 16>", grid128, dim3(256), 0, 0, st, p);
+    } else {
+        const dim3 grid((unsigned)ktf_cdiv(d->units, 64), (unsigned)ktf_cdiv(Tout, 64), (unsigned)B);
+        tdnn_launch_kernel<tdnn_f32_kernel<1, 32>>("tdnn_f32_kernel<1, 32>", grid, dim3(256), 0, 0, st, p);
+    }
     KTF_CHECK_LAUNCH("ktf_tdnn");
     return KTF_OK;
 }

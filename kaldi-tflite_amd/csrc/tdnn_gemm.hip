@@ -151,11 +151,8 @@ static int tdnn_launch(const void* x, int64_t B, int64_t T, int64_t ldx, const i
     KTF_REQUIRE(B >= 0 && T >= 0, "ktf_tdnn: negative size");
     KTF_REQUIRE(!(d->flags & ~(KTF_TDNN_REF_TILES | KTF_TDNN_DET_STATS | KTF_TDNN_K_INTERLEAVED | KTF_TDNN_W_TILED | KTF_TDNN_MX_LOADER)),
                 "ktf_tdnn: unknown bits in KtfTdnnDesc.flags (0x%x)", (unsigned)d->flags);
-    KTF_REQUIRE(d->units > 0 && d->din > 0, "ktf_tdnn: units/din must be > 0");
-    KTF_REQUIRE(d->nctx >= 1 && d->nctx <= 16, "ktf_tdnn: nctx %d outside [1,16]", d->nctx);
-    for (int i = 1; i < d->nctx; ++i) KTF_REQUIRE(d->ctx[i] > d->ctx[i - 1], "ktf_tdnn: context must be strictly ascending");
-    KTF_REQUIRE(d->subsampling > 0, "ktf_tdnn: subsampling_factor should be > 0");
-    KTF_REQUIRE(d->din_pad >= d->din && d->din_pad % 32 == 0 && d->din_pad <= ldx, "ktf_tdnn: din_pad %d must be a multiple of 32 with din <= din_pad <= ldx", d->din_pad);
+    if (const int rc = tdnn_check_desc(d, scale, shift, "ktf_tdnn"); rc != KTF_OK) return rc;
+    KTF_REQUIRE(d->din_pad <= ldx, "ktf_tdnn: din_pad %d > ldx", d->din_pad);
     KTF_REQUIRE(ldx % 8 == 0, "ktf_tdnn: ldx must be a multiple of 8");
     KTF_REQUIRE(ldy >= d->units, "ktf_tdnn: ldy < units");
     KTF_REQUIRE(d->act >= KTF_ACT_NONE && d->act <= KTF_ACT_SOFTMAX, "ktf_tdnn: bad activation %d", d->act);
@@ -166,7 +163,6 @@ static int tdnn_launch(const void* x, int64_t B, int64_t T, int64_t ldx, const i
     if (y_pair) KTF_REQUIRE((d->gemm == KTF_GEMM_F32 || d->gemm == KTF_GEMM_BF16X4) && (y || stats_sums) && !act_pass,
                             "ktf_tdnn: a KTF_BF16P output comes from KTF_GEMM_F32 or KTF_GEMM_BF16X4 (no fused pooling, fused activations only)");
     KTF_REQUIRE(y_pair || d->y_dtype == KTF_F32 || d->y_dtype == KTF_BF16, "ktf_tdnn: bad y_dtype");
-    KTF_REQUIRE((scale == nullptr) == (shift == nullptr), "ktf_tdnn: scale and shift go together");
     KTF_REQUIRE(T < (1ll << 30) && B < 65536, "ktf_tdnn: T or B too large");
     const int64_t Tout = ktf_tdnn_out_len(T, d);
     if (B == 0) return KTF_OK;
@@ -401,44 +397,38 @@ __global__ void stats_finalize_kernel(const double* __restrict__ sums, int64_t s
     }
 }
 
-extern "C" int ktf_stats_finalize(const double* sums, const int32_t* lens, int64_t T, int64_t B, int32_t D,
-                                  int32_t include_std, float eps, float* out, int64_t ld_out, void* stream) {
-    KTF_REQUIRE(sums && out, "ktf_stats_finalize: null argument");
-    KTF_REQUIRE(B >= 0 && D > 0 && ld_out >= (include_std ? 2 : 1) * (int64_t)D, "ktf_stats_finalize: bad sizes");
+// The three entry points below: `slots` == 0 reads the sums of the fp64 atomics, else the partial sums of `slot_rows`-row blocks, per
+// utterance of `lens` or over the flat rows of `row_starts`
+static int stats_finalize(const char* who, const double* sums, int64_t slots, int slot_rows, const int32_t* lens, const int32_t* row_starts,
+                          int64_t T, int64_t B, int32_t D, int32_t include_std, float eps, float* out, int64_t ld_out, void* stream) {
+    KTF_REQUIRE(sums && out, "%s: null argument", who);
+    KTF_REQUIRE(B >= 0 && D > 0 && ld_out >= (include_std ? 2 : 1) * (int64_t)D, "%s: bad sizes", who);
     if (B == 0) return KTF_OK;
     int blocks = ktf_cdiv(B * D, 256);
     if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(stats_finalize_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, sums, (int64_t)0, 128, lens, T, B, D, include_std, eps, out, ld_out);
-    KTF_CHECK_LAUNCH("ktf_stats_finalize");
+    hipLaunchKernelGGL(stats_finalize_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, sums, slots, slot_rows, lens, T, B, D, include_std, eps, out,
+                       ld_out, row_starts);
+    KTF_CHECK_LAUNCH(who);
     return KTF_OK;
+}
+
+extern "C" int ktf_stats_finalize(const double* sums, const int32_t* lens, int64_t T, int64_t B, int32_t D,
+                                  int32_t include_std, float eps, float* out, int64_t ld_out, void* stream) {
+    return stats_finalize("ktf_stats_finalize", sums, 0, 128, lens, nullptr, T, B, D, include_std, eps, out, ld_out, stream);
 }
 
 extern "C" int ktf_stats_finalize_slots(const double* sums, int64_t slots, int32_t slot_rows, const int32_t* lens, int64_t T, int64_t B, int32_t D,
                                         int32_t include_std, float eps, float* out, int64_t ld_out, void* stream) {
-    KTF_REQUIRE(sums && out, "ktf_stats_finalize_slots: null argument");
-    KTF_REQUIRE(B >= 0 && D > 0 && ld_out >= (include_std ? 2 : 1) * (int64_t)D, "ktf_stats_finalize_slots: bad sizes");
     KTF_REQUIRE(slot_rows > 0 && slots * slot_rows >= T, "ktf_stats_finalize_slots: %lld slots of %d rows do not cover %lld rows", (long long)slots, slot_rows, (long long)T);
-    if (B == 0) return KTF_OK;
-    int blocks = ktf_cdiv(B * D, 256);
-    if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(stats_finalize_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, sums, slots, (int)slot_rows, lens, T, B, D, include_std, eps, out, ld_out);
-    KTF_CHECK_LAUNCH("ktf_stats_finalize_slots");
-    return KTF_OK;
+    return stats_finalize("ktf_stats_finalize_slots", sums, slots, slot_rows, lens, nullptr, T, B, D, include_std, eps, out, ld_out, stream);
 }
 
 extern "C" int ktf_stats_finalize_flat(const double* sums, int64_t slots, const int32_t* row_starts, int64_t T, int64_t B, int32_t D,
                                        int32_t include_std, float eps, float* out, int64_t ld_out, void* stream) {
-    KTF_REQUIRE(sums && out && row_starts, "ktf_stats_finalize_flat: null argument");
-    KTF_REQUIRE(B >= 0 && D > 0 && ld_out >= (include_std ? 2 : 1) * (int64_t)D, "ktf_stats_finalize_flat: bad sizes");
+    KTF_REQUIRE(row_starts, "ktf_stats_finalize_flat: null argument");
     KTF_REQUIRE(slots == 0 || slots >= ktf_flat_stats_slots(T), "ktf_stats_finalize_flat: %lld slots, utterances of up to %lld rows touch %lld blocks",
                 (long long)slots, (long long)T, (long long)ktf_flat_stats_slots(T));
-    if (B == 0) return KTF_OK;
-    int blocks = ktf_cdiv(B * D, 256);
-    if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(stats_finalize_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, sums, slots, 128, (const int32_t*)nullptr, T, B, D, include_std, eps,
-                       out, ld_out, row_starts);
-    KTF_CHECK_LAUNCH("ktf_stats_finalize_flat");
-    return KTF_OK;
+    return stats_finalize("ktf_stats_finalize_flat", sums, slots, 128, nullptr, row_starts, T, B, D, include_std, eps, out, ld_out, stream);
 }
 
 extern "C" int ktf_affine_act_f32(const float* x, int64_t rows, int32_t D, int32_t act, const float* scale,

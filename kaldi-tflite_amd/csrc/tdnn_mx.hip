@@ -560,14 +560,11 @@ static int mx_launch(const void* xh, const void* xl4, const void* x4, const void
     KTF_REQUIRE(d->gemm == KTF_GEMM_F16MX, "%s: needs KTF_GEMM_F16MX", who);
     KTF_REQUIRE(B >= 0 && T >= 0 && B < 65536, "%s: bad size", who);
     KTF_REQUIRE(B == 0 || T == 0 || (xh && xl4 && x4 && xs), "%s: null argument", who);
-    KTF_REQUIRE(d->units > 0 && d->din > 0 && d->din_pad % 32 == 0 && d->din_pad >= d->din, "%s: bad units / din / din_pad", who);
-    KTF_REQUIRE(d->nctx >= 1 && d->nctx <= 16, "%s: nctx %d outside [1,16]", who, d->nctx);
-    for (int i = 1; i < d->nctx; ++i) KTF_REQUIRE(d->ctx[i] > d->ctx[i - 1], "%s: context must be strictly ascending", who);
-    KTF_REQUIRE(d->subsampling >= 1 && d->subsampling <= 64, "%s: subsampling %d outside [1,64]", who, d->subsampling);
+    if (const int rc = tdnn_check_desc(d, scale, shift, who); rc != KTF_OK) return rc;
+    KTF_REQUIRE(d->subsampling <= 64, "%s: subsampling %d outside [1,64]", who, d->subsampling);
     const bool plain = !d->valid && d->subsampling == 1;
     KTF_REQUIRE(plain || !stats, "%s: the fused pooling takes SAME padding without subsampling", who);
     KTF_REQUIRE(d->act == KTF_ACT_NONE || d->act == KTF_ACT_RELU, "%s: fuses ReLU or no activation", who);
-    KTF_REQUIRE((scale == nullptr) == (shift == nullptr), "%s: scale and shift go together", who);
     KTF_REQUIRE(T * (int64_t)d->din_pad * 2 < (1ll << 31) - (1ll << 20), "%s: T * din_pad too large", who);
     KTF_REQUIRE((((int64_t)d->din_pad / 32 * d->nctx + 3) / 4) * 4 <= MX_KQ_MAX_STEPS || (d->flags & KTF_TDNN_MX_LOADER), "%s: more than %d K-steps (din_pad / 32 * contexts)", who, MX_KQ_MAX_STEPS);
     if (B == 0 || T == 0 || ktf_tdnn_out_len(T, d) <= 0) return KTF_OK;       // (no output row: VALID padding of an input shorter than the context)
@@ -617,47 +614,29 @@ static int mx_launch(const void* xh, const void* xl4, const void* x4, const void
         }
         const int ntiles = ktf_cdiv(d->units, 256);
         const int64_t ftiles = ktf_cdiv(B * T, 256);
-        const int64_t fblocks = ((ftiles + 7) / 8) * 8 * ntiles;
-        KTF_NOTE_KERNEL("tdnn_mx_kernel<flat>");
-#define MX_LAUNCH_FLAT(A, O)                                                                                           \
-    {                                                                                                                  \
-        if (p.nk & 3) {                                                                                                \
-            KTF_LDS_ONCE(MX_LDS_TOTAL(MX_KQ_MAX_STEPS), tdnn_mx_kernel<A, O, true, true>);                                              \
-            hipLaunchKernelGGL((tdnn_mx_kernel<A, O, true, true>), dim3((unsigned)fblocks), dim3(512), MX_LDS_TOTAL(p.nss * 4), st, p, (int)B, ntiles, (int)ftiles, stats); \
-        } else {                                                                                                       \
-            KTF_LDS_ONCE(MX_LDS_TOTAL(MX_KQ_MAX_STEPS), tdnn_mx_kernel<A, O, false, true>);                                             \
-            hipLaunchKernelGGL((tdnn_mx_kernel<A, O, false, true>), dim3((unsigned)fblocks), dim3(512), MX_LDS_TOTAL(p.nss * 4), st, p, (int)B, ntiles, (int)ftiles, stats); \
-        }                                                                                                              \
-    }
-        if (o == MX_OUT_STATS) {
-            if (d->act == KTF_ACT_RELU) MX_LAUNCH_FLAT(KTF_ACT_RELU, MX_OUT_STATS) else MX_LAUNCH_FLAT(KTF_ACT_NONE, MX_OUT_STATS)
-        } else {
-            if (d->act == KTF_ACT_RELU) MX_LAUNCH_FLAT(KTF_ACT_RELU, MX_OUT_PLANES) else MX_LAUNCH_FLAT(KTF_ACT_NONE, MX_OUT_PLANES)
-        }
-#undef MX_LAUNCH_FLAT
+        const int64_t fblocks = grouped_blocks(ftiles, ntiles);
+        tdnn_pick<MX_OUT_STATS, MX_OUT_PLANES>(o, [&](auto O) {
+            tdnn_pick<KTF_ACT_RELU, KTF_ACT_NONE>(d->act, [&](auto A) {
+                tdnn_pick<true, false>((p.nk & 3) != 0, [&](auto PADK) {
+                    tdnn_launch_kernel<tdnn_mx_kernel<A, O, PADK, true>>("tdnn_mx_kernel<flat>", dim3((unsigned)fblocks), dim3(512), MX_LDS_TOTAL(p.nss * 4),
+                                                                         MX_LDS_TOTAL(MX_KQ_MAX_STEPS), st, p, (int)B, ntiles, (int)ftiles, stats);
+                });
+            });
+        });
         KTF_CHECK_LAUNCH(who);
         return KTF_OK;
     }
     const int mtiles = ktf_cdiv(p.Tout, 256), ntiles = ktf_cdiv(d->units, 256);
     const int64_t gtiles = B * mtiles;
-    const int64_t nblocks = ((gtiles + 7) / 8) * 8 * ntiles;
-#define MX_LAUNCH(A, O)                                                                                                \
-    {                                                                                                                  \
-        KTF_NOTE_KERNEL("tdnn_mx_kernel");                                                                             \
-        if (p.nk & 3) {                                                                                                \
-            KTF_LDS_ONCE(MX_LDS_TOTAL(MX_KQ_MAX_STEPS), tdnn_mx_kernel<A, O, true>);                                                    \
-            hipLaunchKernelGGL((tdnn_mx_kernel<A, O, true>), dim3((unsigned)nblocks), dim3(512), MX_LDS_TOTAL(p.nss * 4), st, p, mtiles, ntiles, (int)gtiles, stats); \
-        } else {                                                                                                       \
-            KTF_LDS_ONCE(MX_LDS_TOTAL(MX_KQ_MAX_STEPS), tdnn_mx_kernel<A, O, false>);                                                   \
-            hipLaunchKernelGGL((tdnn_mx_kernel<A, O, false>), dim3((unsigned)nblocks), dim3(512), MX_LDS_TOTAL(p.nss * 4), st, p, mtiles, ntiles, (int)gtiles, stats); \
-        }                                                                                                              \
-    }
-    if (d->act == KTF_ACT_RELU) {
-        if (o == MX_OUT_STATS) MX_LAUNCH(KTF_ACT_RELU, MX_OUT_STATS) else if (o == MX_OUT_F32) MX_LAUNCH(KTF_ACT_RELU, MX_OUT_F32) else MX_LAUNCH(KTF_ACT_RELU, MX_OUT_PLANES)
-    } else {
-        if (o == MX_OUT_STATS) MX_LAUNCH(KTF_ACT_NONE, MX_OUT_STATS) else if (o == MX_OUT_F32) MX_LAUNCH(KTF_ACT_NONE, MX_OUT_F32) else MX_LAUNCH(KTF_ACT_NONE, MX_OUT_PLANES)
-    }
-#undef MX_LAUNCH
+    const int64_t nblocks = grouped_blocks(gtiles, ntiles);
+    tdnn_pick<KTF_ACT_RELU, KTF_ACT_NONE>(d->act, [&](auto A) {
+        tdnn_pick<MX_OUT_STATS, MX_OUT_F32, MX_OUT_PLANES>(o, [&](auto O) {
+            tdnn_pick<true, false>((p.nk & 3) != 0, [&](auto PADK) {
+                tdnn_launch_kernel<tdnn_mx_kernel<A, O, PADK>>("tdnn_mx_kernel", dim3((unsigned)nblocks), dim3(512), MX_LDS_TOTAL(p.nss * 4),
+                                                               MX_LDS_TOTAL(MX_KQ_MAX_STEPS), st, p, mtiles, ntiles, (int)gtiles, stats);
+            });
+        });
+    });
     KTF_CHECK_LAUNCH(who);
     return KTF_OK;
 }

@@ -582,18 +582,11 @@ int mxl_launch(const MxParams& p, int64_t B, int act, int out_kind, double* stat
         q.mtiles = 0;
         q.gtiles = ktf_cdiv(B * p.T, XL_ROWS);
     }
-    const int64_t nblocks = (((int64_t)q.gtiles + 7) / 8) * 8 * q.ntiles;
-#define XL_LAUNCH(A, O)                                                                                                \
-    {                                                                                                                  \
-        KTF_NOTE_KERNEL("tdnn_mxl_kernel");                                                                            \
-        KTF_LDS_ONCE(XL_LDS_BYTES, tdnn_mxl_kernel<A, O>);                                                             \
-        hipLaunchKernelGGL((tdnn_mxl_kernel<A, O>), dim3((unsigned)nblocks), dim3(768), XL_LDS_BYTES, st, q);          \
-    }
-    if (act == KTF_ACT_RELU) {
-        if (out_kind == MX_OUT_STATS) XL_LAUNCH(KTF_ACT_RELU, MX_OUT_STATS) else if (out_kind == MX_OUT_F32) XL_LAUNCH(KTF_ACT_RELU, MX_OUT_F32) else XL_LAUNCH(KTF_ACT_RELU, MX_OUT_PLANES)
-    } else {
-        if (out_kind == MX_OUT_STATS) XL_LAUNCH(KTF_ACT_NONE, MX_OUT_STATS) else if (out_kind == MX_OUT_F32) XL_LAUNCH(KTF_ACT_NONE, MX_OUT_F32) else XL_LAUNCH(KTF_ACT_NONE, MX_OUT_PLANES)
-    }
-#undef XL_LAUNCH
+    const int64_t nblocks = grouped_blocks(q.gtiles, q.ntiles);
+    tdnn_pick<KTF_ACT_RELU, KTF_ACT_NONE>(act, [&](auto A) {
+        tdnn_pick<MX_OUT_STATS, MX_OUT_F32, MX_OUT_PLANES>(out_kind, [&](auto O) {
+            tdnn_launch_kernel<tdnn_mxl_kernel<A, O>>("tdnn_mxl_kernel", dim3((unsigned)nblocks), dim3(768), XL_LDS_BYTES, XL_LDS_BYTES, st, q);
+        });
+    });
     return KTF_OK;
 }

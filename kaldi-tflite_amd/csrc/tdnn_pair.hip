@@ -216,37 +216,21 @@ __global__ __launch_bounds__(64 * 4 * (BN / 16 / NB)) void tdnn_x4s_kernel(TdnnP
 #define X4_SLOT_ROWS 64
 
 int tdnn_launch_x4(const TdnnParams& p, const KtfTdnnDesc* d, int64_t B, int64_t Tout, double* stats, hipStream_t st) {
-#define X4_LAUNCH(BK_, BN_, NB_)                                                                                       \
-    do {                                                                                                               \
-        const int lds = FS_NSTAGE * (FS_BM + BN_) * BK_ * 4;                                                           \
-        dim3 grid_((unsigned)ktf_cdiv(d->units, BN_), (unsigned)ktf_cdiv(Tout, FS_BM), (unsigned)B);                   \
-        KTF_NOTE_KERNEL("tdnn_x4s_kernel<" #BK_ ", " #BN_ ">");                                                         \
-        if (stats) {                                                                                                   \
-            KTF_LDS_ONCE(lds, tdnn_x4s_kernel<BK_, BN_, NB_, true>);                                                   \
-            hipLaunchKernelGGL((tdnn_x4s_kernel<BK_, BN_, NB_, true>), grid_, dim3(64 * 4 * (BN_ / 16 / NB_)), lds, st, p, stats); \
-        } else {                                                                                                       \
-            KTF_LDS_ONCE(lds, tdnn_x4s_kernel<BK_, BN_, NB_, false>);                                                  \
-            hipLaunchKernelGGL((tdnn_x4s_kernel<BK_, BN_, NB_, false>), grid_, dim3(64 * 4 * (BN_ / 16 / NB_)), lds, st, p, stats); \
-        }                                                                                                              \
-    } while (0)
-    if (d->din_pad % 64 == 0) {
-        // tile width as for the fp32 small tiles (tdnn_launch_f32): rounds of 256 workgroups x (width + fixed part); 96 columns
-        // only where the padded W rows (the host pads to 128) cover the last tile
-        const int64_t mt = (int64_t)ktf_cdiv(Tout, FS_BM) * B;
-        int best = 32;
-        int64_t best_cost = INT64_MAX;
-        for (int bn = 32; bn <= 96; bn += 32) {
-            if (bn == 96 && (int64_t)ktf_cdiv(d->units, 96) * 96 > (int64_t)ktf_cdiv(d->units, 128) * 128) continue;
-            const int64_t cost = ktf_cdiv(ktf_cdiv(d->units, bn) * mt, 256) * (bn + 16);
-            if (cost < best_cost) best_cost = cost, best = bn;
-        }
-        if (best == 32) X4_LAUNCH(64, 32, 1);
-        else if (best == 64) X4_LAUNCH(64, 64, 1);
-        else X4_LAUNCH(64, 96, 3);
-    } else {
-        X4_LAUNCH(32, 64, 1);
-    }
-#undef X4_LAUNCH
+    // tile width as for the fp32 small tiles (tdnn_launch_f32; the host pads W's rows to 128 here)
+    auto small = [&](auto BK, auto BN) {
+        constexpr int NB = BN == 96 ? 3 : 1, lds = FS_NSTAGE * (FS_BM + BN) * BK * 4;
+        const char* name = BK == 32 ? "tdnn_x4s_kernel<32, 64>" : BN == 32 ? "tdnn_x4s_kernel<64, 32>"
+                         : BN == 64 ? "tdnn_x4s_kernel<64, 64>" : "tdnn_x4s_kernel<64, 96>";
+        const dim3 grid((unsigned)ktf_cdiv(d->units, BN), (unsigned)ktf_cdiv(Tout, FS_BM), (unsigned)B);
+        tdnn_pick<true, false>(stats != nullptr, [&](auto STATS) {
+            tdnn_launch_kernel<tdnn_x4s_kernel<BK, BN, NB, STATS>>(name, grid, dim3(64 * 4 * (BN / 16 / NB)), lds, lds, st, p, stats);
+        });
+    };
+    if (d->din_pad % 64 == 0)
+        tdnn_pick<32, 64, 96>(small_tile_width(d->units, (int64_t)ktf_cdiv(Tout, FS_BM) * B),
+                              [&](auto BN) { small(std::integral_constant<int, 64>{}, BN); });
+    else
+        small(std::integral_constant<int, 32>{}, std::integral_constant<int, 64>{});
     KTF_CHECK_LAUNCH("ktf_tdnn");
     return KTF_OK;
 }

@@ -515,82 +515,43 @@ __global__ __launch_bounds__(512) void tdnn_x3s_kernel(TdnnParams p, int mtiles,
 // ------------------------------------------------------------------------------------ launcher
 int tdnn_launch_split(const TdnnParams& p, const KtfTdnnDesc* d, int64_t B, int64_t Tout, int64_t ldy, bool split_in, double* stats_sums,
                       hipStream_t st) {
-    {
-        {
-            const int mtiles = ktf_cdiv(Tout, R_BM), ntiles_r = ktf_cdiv(d->units, R_BN);
-            const int64_t gtiles = B * (int64_t)mtiles;
-            const int64_t nblocks = ((gtiles + 7) / 8) * 8 * ntiles_r;
-            KTF_REQUIRE(nblocks < (1ll << 31), "ktf_tdnn: grid too large");
-#define X_LAUNCH(A)                                                                                                    \
-    do {                                                                                                               \
-        KTF_NOTE_KERNEL("tdnn_x3r_kernel");                                                                            \
-        if (stats_sums) {                                                                                              \
-            KTF_LDS_ONCE(X_LDS_BYTES, tdnn_x3r_kernel<A, true>);                                                       \
-            hipLaunchKernelGGL((tdnn_x3r_kernel<A, true>), dim3((unsigned)nblocks), dim3(512), X_LDS_BYTES, st, p, mtiles, ntiles_r, (int)gtiles, stats_sums); \
-        } else {                                                                                                       \
-            KTF_LDS_ONCE(X_LDS_BYTES, tdnn_x3r_kernel<A, false>);                                                      \
-            hipLaunchKernelGGL((tdnn_x3r_kernel<A, false>), dim3((unsigned)nblocks), dim3(512), X_LDS_BYTES, st, p, mtiles, ntiles_r, (int)gtiles, stats_sums); \
-        }                                                                                                              \
-    } while (0)
-            // mostly-padding tiles (fewer than 80 % of the 16-row blocks computed hold a row of a full-length utterance): the SKIP form
-            const bool skip = 5 * (int64_t)ktf_cdiv(Tout, 16) < 4 * (int64_t)mtiles * 16;
-#define XS_LAUNCH1(A, ST)                                                                                              \
-    do {                                                                                                               \
-        KTF_NOTE_KERNEL("tdnn_x3s_kernel");                                                                   \
-        if (skip) {                                                                                                    \
-            KTF_LDS_ONCE(XS_LDS_BYTES, tdnn_x3s_kernel<A, ST, true>);                                        \
-            hipLaunchKernelGGL((tdnn_x3s_kernel<A, ST, true>), dim3((unsigned)nblocks), dim3(512), XS_LDS_BYTES, st, p, mtiles, ntiles_r, (int)gtiles, stats_sums); \
-        } else {                                                                                                       \
-            KTF_LDS_ONCE(XS_LDS_BYTES, tdnn_x3s_kernel<A, ST>);                                                        \
-            hipLaunchKernelGGL((tdnn_x3s_kernel<A, ST>), dim3((unsigned)nblocks), dim3(512), XS_LDS_BYTES, st, p, mtiles, ntiles_r, (int)gtiles, stats_sums); \
-        }                                                                                                              \
-    } while (0)
-#define XS_LAUNCH(A)                                                                                                   \
-    do {                                                                                                               \
-        if (stats_sums) XS_LAUNCH1(A, true); else XS_LAUNCH1(A, false);                                                \
-    } while (0)
-            // hi / lo planes in: the 16x16x32 plane kernel; fp32 activations in: the kernel that splits them in registers
-            if (split_in && p.row_starts) {              // ktf_tdnn_split_flat: M-tiles over the batch's valid rows laid end to end
-                KTF_REQUIRE(!d->valid && d->subsampling == 1, "ktf_tdnn_split_flat: SAME padding, no subsampling");
-                KTF_REQUIRE(d->act == KTF_ACT_NONE || d->act == KTF_ACT_RELU, "ktf_tdnn_split_flat: fuses ReLU or no activation");
-                KTF_REQUIRE(B <= 4095 && B * p.T * p.ldx * 2 < (1ll << 32), "ktf_tdnn_split_flat: B <= 4095 and B * T * ldx * 2 < 2^32");
-                const int64_t ftiles = ktf_cdiv(B * p.T, R_BM);
-                const int64_t fblocks = ((ftiles + 7) / 8) * 8 * ntiles_r;
-                KTF_REQUIRE(fblocks < (1ll << 31), "ktf_tdnn: grid too large");
-                constexpr int lds_ = XS_LDS_BYTES + XS_FLAT_BYTES;
-                KTF_NOTE_KERNEL("tdnn_x3s_kernel<flat>");
-                if (stats_sums) {
-                    KTF_NOTE_KERNEL("tdnn_x3s_kernel<flat, pooled>");
-                    if (d->act == KTF_ACT_RELU) {
-                        KTF_LDS_ONCE(lds_, tdnn_x3s_kernel<KTF_ACT_RELU, true, false, true>);
-                        hipLaunchKernelGGL((tdnn_x3s_kernel<KTF_ACT_RELU, true, false, true>), dim3((unsigned)fblocks), dim3(512), lds_, st, p, (int)B, ntiles_r, (int)ftiles, stats_sums);
-                    } else {
-                        KTF_LDS_ONCE(lds_, tdnn_x3s_kernel<KTF_ACT_NONE, true, false, true>);
-                        hipLaunchKernelGGL((tdnn_x3s_kernel<KTF_ACT_NONE, true, false, true>), dim3((unsigned)fblocks), dim3(512), lds_, st, p, (int)B, ntiles_r, (int)ftiles, stats_sums);
-                    }
-                } else
-                if (d->act == KTF_ACT_RELU) {
-                    KTF_LDS_ONCE(lds_, tdnn_x3s_kernel<KTF_ACT_RELU, false, false, true>);
-                    hipLaunchKernelGGL((tdnn_x3s_kernel<KTF_ACT_RELU, false, false, true>), dim3((unsigned)fblocks), dim3(512), lds_, st, p, (int)B, ntiles_r, (int)ftiles, nullptr);
-                } else {
-                    KTF_LDS_ONCE(lds_, tdnn_x3s_kernel<KTF_ACT_NONE, false, false, true>);
-                    hipLaunchKernelGGL((tdnn_x3s_kernel<KTF_ACT_NONE, false, false, true>), dim3((unsigned)fblocks), dim3(512), lds_, st, p, (int)B, ntiles_r, (int)ftiles, nullptr);
-                }
-            } else
-            if (split_in) {
-                if (d->act == KTF_ACT_NONE) XS_LAUNCH(KTF_ACT_NONE);
-                else if (d->act == KTF_ACT_RELU) XS_LAUNCH(KTF_ACT_RELU);
-                else if (d->act == KTF_ACT_SIGMOID) XS_LAUNCH(KTF_ACT_SIGMOID);
-                else XS_LAUNCH(KTF_ACT_TANH);
-            } else
-            if (d->act == KTF_ACT_NONE) X_LAUNCH(KTF_ACT_NONE);
-            else if (d->act == KTF_ACT_RELU) X_LAUNCH(KTF_ACT_RELU);
-            else if (d->act == KTF_ACT_SIGMOID) X_LAUNCH(KTF_ACT_SIGMOID);
-            else X_LAUNCH(KTF_ACT_TANH);
-#undef XS_LAUNCH
-#undef XS_LAUNCH1
-#undef X_LAUNCH
-        }
+    const int mtiles = ktf_cdiv(Tout, R_BM), ntiles_r = ktf_cdiv(d->units, R_BN);
+    const int64_t gtiles = B * (int64_t)mtiles;
+    const int64_t nblocks = grouped_blocks(gtiles, ntiles_r);
+    KTF_REQUIRE(nblocks < (1ll << 31), "ktf_tdnn: grid too large");
+    // hi / lo planes in: the 16x16x32 plane kernel; fp32 activations in: the kernel that splits them in registers
+    if (split_in && p.row_starts) {              // ktf_tdnn_split_flat: M-tiles over the batch's valid rows laid end to end
+        KTF_REQUIRE(!d->valid && d->subsampling == 1, "ktf_tdnn_split_flat: SAME padding, no subsampling");
+        KTF_REQUIRE(d->act == KTF_ACT_NONE || d->act == KTF_ACT_RELU, "ktf_tdnn_split_flat: fuses ReLU or no activation");
+        KTF_REQUIRE(B <= 4095 && B * p.T * p.ldx * 2 < (1ll << 32), "ktf_tdnn_split_flat: B <= 4095 and B * T * ldx * 2 < 2^32");
+        const int64_t ftiles = ktf_cdiv(B * p.T, R_BM);
+        const int64_t fblocks = grouped_blocks(ftiles, ntiles_r);
+        KTF_REQUIRE(fblocks < (1ll << 31), "ktf_tdnn: grid too large");
+        constexpr int lds = XS_LDS_BYTES + XS_FLAT_BYTES;
+        tdnn_pick<true, false>(stats_sums != nullptr, [&](auto ST) {
+            tdnn_pick<KTF_ACT_RELU, KTF_ACT_NONE>(d->act, [&](auto A) {
+                tdnn_launch_kernel<tdnn_x3s_kernel<A, ST, false, true>>(ST ? "tdnn_x3s_kernel<flat, pooled>" : "tdnn_x3s_kernel<flat>", dim3((unsigned)fblocks),
+                                                                          dim3(512), lds, lds, st, p, (int)B, ntiles_r, (int)ftiles, stats_sums);
+            });
+        });
+    } else if (split_in) {
+        // mostly-padding tiles (fewer than 80 % of the 16-row blocks computed hold a row of a full-length utterance): the SKIP form
+        const bool skip = 5 * (int64_t)ktf_cdiv(Tout, 16) < 4 * (int64_t)mtiles * 16;
+        tdnn_pick<KTF_ACT_NONE, KTF_ACT_RELU, KTF_ACT_SIGMOID, KTF_ACT_TANH>(d->act, [&](auto A) {
+            tdnn_pick<true, false>(stats_sums != nullptr, [&](auto ST) {
+                tdnn_pick<true, false>(skip, [&](auto SKIP) {
+                    tdnn_launch_kernel<tdnn_x3s_kernel<A, ST, SKIP>>("tdnn_x3s_kernel", dim3((unsigned)nblocks), dim3(512), XS_LDS_BYTES, XS_LDS_BYTES, st, p,
+                                                                     mtiles, ntiles_r, (int)gtiles, stats_sums);
+                });
+            });
+        });
+    } else {
+        tdnn_pick<KTF_ACT_NONE, KTF_ACT_RELU, KTF_ACT_SIGMOID, KTF_ACT_TANH>(d->act, [&](auto A) {
+            tdnn_pick<true, false>(stats_sums != nullptr, [&](auto ST) {
+                tdnn_launch_kernel<tdnn_x3r_kernel<A, ST>>("tdnn_x3r_kernel", dim3((unsigned)nblocks), dim3(512), X_LDS_BYTES, X_LDS_BYTES, st, p, mtiles,
+                                                           ntiles_r, (int)gtiles, stats_sums);
+            });
+        });
     }
     KTF_CHECK_LAUNCH("ktf_tdnn");
     return KTF_OK;
