@@ -627,6 +627,39 @@ int ktf_diar_segment_cmn(const float* mfcc, int32_t D, const int32_t* frames, co
 int ktf_diar_gather(const float* cmn, int32_t D, const int32_t* frames, const int32_t* offsets, int32_t R, const int32_t* windows, int64_t S,
                     int64_t w0, int64_t n, int32_t Tw, void* out, int32_t out_dtype, int32_t ldo, int32_t* lens, void* stream);
 
+/* ------------------------------------------------------------------ i-vector extraction
+ * Kaldi's sid/extract_ivectors.sh core: gmm-global-get-post | scale-post | ivector-extract. The reference ships the extractor's
+ * reader (io/kaldi/ivector_extractor_reader.py) and no extraction. Frames of all utterances lie end to end in x (F, D) fp32, row
+ * stride ldx; utterance b owns rows [offsets[b], offsets[b + 1]) (offsets: B + 1 device int32).
+ *
+ * gmm-global-get-post --n=num_gselect --min-post=min_post (DiagGmm::LogLikelihoods, then VectorToPosteriorEntry): per frame the
+ * log-likelihoods l_i = gconst_i + x . mi_i - x^2 . iv_i / 2 as one fp32 GEMM of [x, x^2] against W (2D x I, row-major: row d is
+ * means_invvars[:, d], row D + d is -inv_vars[:, d] / 2), never written out. Kept: the min(num_gselect, I) largest l (ties: the
+ * lower index); p = exp(l - max) over the kept set; the smallest dropped while p < min_post * (sum of the kept p), at least one
+ * kept; renormalised. gauss / post: (F, num_gselect) device int32 / fp32, sorted by posterior, unused slots (-1, 0). */
+#define KTF_IVECTOR_MAX_FEAT_DIM 128
+#define KTF_IVECTOR_MAX_GAUSS 8192
+#define KTF_IVECTOR_MAX_GSELECT 64
+#define KTF_IVECTOR_MAX_DIM 1024
+int ktf_ivector_post_f32(const float* x, int64_t F, int32_t D, int64_t ldx, const float* W, const float* gconst, int32_t I,
+                         int32_t num_gselect, float min_post, int32_t* gauss, float* post, void* stream);
+/* scale-post posterior_scale, then ivector-extract --acoustic-weight --max-count (IvectorExtractorUtteranceStats::AccStats without
+ * second-order stats, IvectorExtractor::GetIvectorDistMean / GetIvectorDistPrior, the solve, ivector(0) -= prior_offset):
+ *   p' = fp32(p * posterior_scale); t = acoustic_weight * sum p' (fp64); scale = fp32(acoustic_weight * (max_count > 0 && t > max_count
+ *   ? max_count / t : 1)); gamma_i = sum_t fp32(p' * scale), F_i = sum_t fp32(p' * scale) x_t (fp64, each Gaussian's sum in frame
+ *   order); linear = sum_i sigma_inv_M_i^T F_i + prior_offset e0; Q = I + sum_i gamma_i U_i; ivector = Q^-1 linear (Cholesky, fp64),
+ *   ivector(0) -= prior_offset. An utterance with no frames gets zeros.
+ * gauss / post: (F, n) as ktf_ivector_post_f32 writes them (slots with an index outside [0, I) are skipped). sigma_inv_M: (I * D, S)
+ * fp64 row-major (SigmaInv_i M_i stacked), U: (I, S(S+1)/2) fp64, the lower triangle of M_i^T SigmaInv_i M_i row by row.
+ * ivectors: (B, S) fp32 (out_dtype_bytes 4) or fp64 (8). workspace: 256-byte aligned, at least
+ * ktf_ivector_workspace_bytes(B, I, D, S) bytes (returns a negative KTF_* code on bad arguments). An utterance's bits depend on its
+ * own frames alone, not on B or its position. */
+int64_t ktf_ivector_workspace_bytes(int32_t B, int32_t I, int32_t D, int32_t S);
+int ktf_ivector_extract(const float* x, int64_t F, int32_t D, int64_t ldx, const int32_t* offsets, int32_t B, const int32_t* gauss,
+                        const float* post, int32_t n, float posterior_scale, float acoustic_weight, float max_count,
+                        const double* sigma_inv_M, const double* U, int32_t I, int32_t S, double prior_offset, void* ivectors,
+                        int32_t out_dtype_bytes, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -158,12 +158,17 @@ PROTOTYPES = {
     "ktf_diar_compact": (C.c_int, [_P, _P, _P, _P, _P, _i32, _i64, _i64, _P, _P, _P]),
     "ktf_diar_segment_cmn": (C.c_int, [_P, _i32, _P, _P, _i32, _P, _i64, C.POINTER(CmvnCfg), _P, _P, _P]),
     "ktf_diar_gather": (C.c_int, [_P, _i32, _P, _P, _i32, _P, _i64, _i64, _i64, _i32, _P, _i32, _i32, _P, _P]),
+    "ktf_ivector_post_f32": (C.c_int, [_P, _i64, _i32, _i64, _P, _P, _i32, _i32, _f32, _P, _P, _P]),
+    "ktf_ivector_workspace_bytes": (_i64, [_i32, _i32, _i32, _i32]),
+    "ktf_ivector_extract": (C.c_int, [_P, _i64, _i32, _i64, _P, _i32, _P, _P, _i32, _f32, _f32, _f32, _P, _P, _i32, _i32, C.c_double,
+                                      _P, _i32, _P, C.c_size_t, _P]),
 }
 PLDA_DENSE_NO_PCA = -1.0            # ktf_plda_dense_*: target_energy for "no PCA"
 PLDA_DENSE_MAX_DIM = 512
 PLDA_DENSE_MAX_SWEEPS = 30
 AHC_MAX_N = 32767                   # ktf_ahc_*: rows per recording
 AHC_LDS_SLOTS = 5120                # ... up to which the merge loop's state sits in LDS
+IVECTOR_MAX_FEAT_DIM, IVECTOR_MAX_GAUSS, IVECTOR_MAX_GSELECT, IVECTOR_MAX_DIM = 128, 8192, 64, 1024   # ktf_ivector_*
 
 _lib = None
 

@@ -17,8 +17,9 @@ token search. Kaldi's binary stream is self-delimiting --
     "<"                           nothing: the next tag
 
 -- so an nnet3 file is decoded in ONE forward pass into (tag, payload) events (`iter_fields`), and a
-component is the run of events between two <ComponentName> tags. `KaldiIvecExtractorReader` is out of
-scope.
+component is the run of events between two <ComponentName> tags. `KaldiIvecExtractorReader` (io/kaldi/
+ivector_extractor_reader.py) feeds ktf.layers.IvectorExtractor, together with `KaldiDiagGmmReader`, an extension of this
+project for the diagonal UBM (`final.dubm`) of Kaldi's i-vector recipes.
 """
 
 import re
@@ -302,6 +303,93 @@ class KaldiPldaReader(KaldiObjReader):
         self.expectToken("<Plda>")
         self.mean, self.transformMat, self.psi = self.readVec(), self.readMat(), self.readVec()
         self.expectToken("</Plda>")
+
+
+class KaldiIvecExtractorReader(KaldiObjReader):
+    """io/kaldi/ivector_extractor_reader.py:26 — <IvectorExtractor> (I = numGauss Gaussians, D = featDim, S = ivecDim):
+    w (I, S) or empty (ivector-dependent weights), wVec (I), M: I matrices (D, S), sigmaInv: I FULL symmetric (D, D) matrices,
+    priorOffset; derived: sigmaInvM (I, D, S) = sigmaInv[i] @ M[i] and U (I, S(S+1)/2), the lower triangle of M[i]^T sigmaInvM[i]
+    row by row. readPackedMat gives the full symmetric SigmaInv of a real extractor (the reference keeps only the lower triangle,
+    which agrees on its diagonal dummies)."""
+
+    def __init__(self, ivec_path, binary=True):
+        super().__init__(ivec_path, binary)
+        self.numGauss = self.featDim = self.ivecDim = None
+        self.w = self.wVec = self.M = self.sigmaInv = self.priorOffset = self.U = self.sigmaInvM = None
+        self.read()
+        self.deriveVars()
+
+    def read(self):
+        self.expectToken("<IvectorExtractor>")
+        self.expectToken("<w>")
+        self.w = self.readMat()
+        self.expectToken("<w_vec>")
+        self.wVec = self.readVec()
+        self.expectToken("<M>")
+        self.numGauss = int(self.readInt())
+        self.M = [self.readMat() for _ in range(self.numGauss)]
+        self.expectToken("<SigmaInv>")
+        self.sigmaInv = [self.readPackedMat() for _ in range(self.numGauss)]
+        self.expectToken("<IvectorOffset>")
+        self.priorOffset = self.readDouble()
+        self.expectToken("</IvectorExtractor>")
+
+    def deriveVars(self):
+        if len(self.M) == 0:
+            raise ValueError("expected at least 1 projection matrix (M_), got 0")
+        self.featDim, self.ivecDim = int(self.M[0].shape[0]), int(self.M[0].shape[-1])
+        if any(m.shape != (self.featDim, self.ivecDim) for m in self.M) or \
+                any(s.shape != (self.featDim, self.featDim) for s in self.sigmaInv):
+            raise ValueError("inconsistent M / SigmaInv shapes")
+        self.sigmaInvM = np.matmul(self.sigmaInv, self.M)
+        S = self.ivecDim
+        r, c = np.tril_indices(S)
+        self.U = np.zeros((self.numGauss, S * (S + 1) // 2), dtype=np.float64)
+        for i0 in range(0, self.numGauss, 64):          # (64, S, S) at a time: a real extractor's full stack is GBs
+            tmp = np.matmul(np.swapaxes(np.asarray(self.M[i0:i0 + 64]), 1, 2), self.sigmaInvM[i0:i0 + 64])
+            self.U[i0:i0 + 64] = tmp[:, r, c]
+
+
+class KaldiDiagGmmReader(KaldiObjReader):
+    """Kaldi DiagGmm (`final.dubm`; an extension: the reference has no UBM reader): <DiagGMM> <GCONSTS> FV <WEIGHTS> FV
+    <MEANS_INVVARS> FM <INV_VARS> FM </DiagGMM>. weights (I), means_invvars (I, D), inv_vars (I, D) as stored (fp32 in Kaldi's
+    files); gconsts (I, fp32) are recomputed as DiagGmm::ComputeGconsts does,
+    log w - D/2 log(2 pi) + sum_d (log iv_d / 2 - mi_d^2 / iv_d / 2) in fp32, and the stored ones are kept as `storedGconsts`."""
+
+    def __init__(self, path, binary=True):
+        super().__init__(path, binary)
+        self.read()
+
+    def read(self):
+        self.expectToken("<DiagGMM>")
+        self.storedGconsts = self.readVec() if self.expectToken("<GCONSTS>", stopTokens=("<WEIGHTS>",)) else None
+        self.expectToken("<WEIGHTS>")
+        self.weights = self.readVec()
+        self.expectToken("<MEANS_INVVARS>")
+        self.means_invvars = self.readMat()
+        self.expectToken("<INV_VARS>")
+        self.inv_vars = self.readMat()
+        self.expectToken("</DiagGMM>")
+        I, D = self.means_invvars.shape
+        if self.inv_vars.shape != (I, D) or self.weights.shape != (I,) or I == 0:
+            raise ValueError(f"inconsistent DiagGMM shapes: weights {self.weights.shape}, means_invvars {self.means_invvars.shape}, "
+                             f"inv_vars {self.inv_vars.shape}")
+        self.numGauss, self.featDim = int(I), int(D)
+        self.gconsts = self.computeGconsts()
+
+    def computeGconsts(self):
+        """DiagGmm::ComputeGconsts with C++'s promotions: offset = BaseFloat(-0.5 * M_LOG_2PI * dim), gc = Log(w) + offset in
+        fp32, then per dimension gc += 0.5 * Log(iv) - 0.5 * mi * mi / iv (the right side in double, gc rounded to fp32 each step)."""
+        f = np.float32
+        iv = self.inv_vars.astype(f)
+        mi = self.means_invvars.astype(f).astype(np.float64)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            gc = np.log(self.weights.astype(f)) + f(-0.5 * np.log(2 * np.pi) * self.featDim)
+            logiv = np.log(iv).astype(np.float64)                       # Log(float) is logf
+            ivd = iv.astype(np.float64)
+            for d in range(self.featDim):
+                gc = (gc.astype(np.float64) + (0.5 * logiv[:, d] - 0.5 * mi[:, d] * mi[:, d] / ivd[:, d])).astype(f)
+        return gc.astype(f)
 
 
 def _text_array(path, dtype):

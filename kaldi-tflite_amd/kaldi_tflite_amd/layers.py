@@ -1338,3 +1338,137 @@ class PLDA(Layer):
         if self.returnTransformed:
             return scores, tr.reshape(tr.shape[0], tr.shape[1], 1)
         return scores
+
+
+# =============================================================================== i-vectors
+class IvectorExtractor(Layer):
+    """Extension (the reference reads `final.ie` and extracts nothing): Kaldi's sid/extract_ivectors.sh core on the GPU,
+
+        gmm-global-get-post --n=num_gselect --min-post=min_post final.dubm feats ark:- | scale-post ark:- posterior_scale ark:- |
+        ivector-extract --acoustic-weight=acoustic_weight --max-count=max_count final.ie feats ark:- ivectors.ark
+
+    `extractor`: a path to a Kaldi binary `final.ie` or an io.KaldiIvecExtractorReader; `diag_ubm`: a path to `final.dubm` or an
+    io.KaldiDiagGmmReader. The defaults are those of the recipe's extract_ivectors.sh (num_gselect 20, min_post 0.025);
+    gmm-global-get-post's own defaults are --n=50 --min-post=0.0. An extractor with ivector-dependent weights (a non-empty `w`)
+    raises NotImplementedError. Calls run on the device of `feats` and its current stream; the utterances are processed in chunks
+    whose workspace stays under `workspace_limit` bytes, and an utterance's i-vector bits do not depend on the chunk it falls in."""
+
+    def __init__(self, extractor, diag_ubm, num_gselect=20, min_post=0.025, posterior_scale=1.0, acoustic_weight=1.0, max_count=0.0,
+                 workspace_limit=1 << 30, name=None):
+        super().__init__(trainable=False, name=name)
+        from . import io as kio
+        ie = extractor if isinstance(extractor, kio.KaldiIvecExtractorReader) else kio.KaldiIvecExtractorReader(extractor, binary=True)
+        ubm = diag_ubm if isinstance(diag_ubm, kio.KaldiDiagGmmReader) else kio.KaldiDiagGmmReader(diag_ubm, binary=True)
+        if ie.w is not None and ie.w.size:
+            raise NotImplementedError("ivector-dependent weights (a non-empty <w>) are not supported")
+        if ubm.numGauss != ie.numGauss or ubm.featDim != ie.featDim:
+            raise ValueError(f"UBM ({ubm.numGauss} Gaussians, dim {ubm.featDim}) does not match the extractor "
+                             f"({ie.numGauss} Gaussians, dim {ie.featDim})")
+        I, D, S = ie.numGauss, ie.featDim, ie.ivecDim
+        if not (1 <= I <= L.IVECTOR_MAX_GAUSS and 1 <= D <= L.IVECTOR_MAX_FEAT_DIM and 1 <= S <= L.IVECTOR_MAX_DIM):
+            raise ValueError(f"extractor shape (I={I}, D={D}, S={S}) outside I <= {L.IVECTOR_MAX_GAUSS}, D <= "
+                             f"{L.IVECTOR_MAX_FEAT_DIM}, S <= {L.IVECTOR_MAX_DIM}")
+        if not 1 <= int(num_gselect) <= L.IVECTOR_MAX_GSELECT:
+            raise ValueError(f"num_gselect {num_gselect} outside 1 .. {L.IVECTOR_MAX_GSELECT}")
+        if not 0.0 <= float(min_post) < 1.0:
+            raise ValueError(f"min_post {min_post} outside [0, 1)")
+        if min(float(posterior_scale), float(acoustic_weight), float(max_count)) < 0:
+            raise ValueError("posterior_scale, acoustic_weight and max_count must be >= 0")
+        self.numGauss, self.featDim, self.ivecDim = I, D, S
+        self.numGselect, self.minPost = int(num_gselect), float(min_post)
+        self.posteriorScale, self.acousticWeight, self.maxCount = float(posterior_scale), float(acoustic_weight), float(max_count)
+        self.priorOffset = float(ie.priorOffset)
+        self.workspaceLimit = int(workspace_limit)
+        # host copies of the device constants: W = [means_invvars; -inv_vars / 2] (2D, I), gconst (I), sigmaInvM (I*D, S), U (I, P)
+        self._W = np.ascontiguousarray(np.concatenate([ubm.means_invvars.astype(np.float32).T,
+                                                       (np.float32(-0.5) * ubm.inv_vars.astype(np.float32)).T]))
+        self._gconst = np.ascontiguousarray(ubm.gconsts, dtype=np.float32)
+        self._sigmaInvM = np.ascontiguousarray(np.asarray(ie.sigmaInvM, dtype=np.float64).reshape(I * D, S))
+        self._U = np.ascontiguousarray(ie.U, dtype=np.float64)
+
+    def get_config(self):
+        raise NotImplementedError("IvectorExtractor holds model files, not a config")
+
+    def _consts(self, device):
+        def make():
+            f = lambda a: torch.as_tensor(a, device=device)  # noqa: E731
+            return f(self._W), f(self._gconst), f(self._sigmaInvM), f(self._U)
+        return _per_device(self, device, make)
+
+    def _frames(self, feats, lengths, mask):
+        """(B, T, D) device fp32 -> (frames (F, D) in utterance order, offsets (B + 1) host int64)."""
+        if not isinstance(feats, torch.Tensor) or not feats.is_cuda:
+            raise ValueError("feats must be a (B, T, D) tensor on a GPU")
+        if feats.dim() != 3 or feats.shape[2] != self.featDim:
+            raise ValueError(f"feats must be (B, T, {self.featDim}), got {tuple(feats.shape)}")
+        if feats.dtype != torch.float32:
+            raise ValueError(f"feats must be float32, got {feats.dtype}")
+        B, T, D = feats.shape
+        if lengths is not None and mask is not None:
+            raise ValueError("pass lengths or mask, not both")
+        if mask is not None:
+            m = mask.reshape(mask.shape[0], -1) if isinstance(mask, torch.Tensor) else torch.as_tensor(np.asarray(mask))
+            if m.dim() != 2 or tuple(m.shape) != (B, T):
+                raise ValueError(f"mask must be (B, T) or (B, T, 1) = ({B}, {T}), got {tuple(mask.shape)}")
+            m = m.to(feats.device) != 0
+        elif lengths is not None:
+            n = np.asarray(lengths.cpu() if isinstance(lengths, torch.Tensor) else lengths, dtype=np.int64).reshape(-1)
+            if n.shape[0] != B or (n < 0).any() or (n > T).any():
+                raise ValueError(f"lengths must hold {B} values in 0 .. {T}")
+            m = torch.arange(T, device=feats.device)[None, :] < torch.as_tensor(n, device=feats.device)[:, None]
+        else:
+            return feats.reshape(B * T, D) if feats.is_contiguous() else feats.contiguous().reshape(B * T, D), np.arange(B + 1) * T
+        counts = m.sum(1).cpu().numpy().astype(np.int64)
+        return feats[m].contiguous(), np.concatenate([[0], np.cumsum(counts)])
+
+    def _chunks(self, B):
+        per = ops.ivector_workspace_bytes(1, self.numGauss, self.featDim, self.ivecDim)
+        step = int(max(1, min(B, 65535, self.workspaceLimit // max(per, 1))))
+        return [(b, min(B, b + step)) for b in range(0, B, step)]
+
+    def posteriors(self, feats, lengths=None, mask=None):
+        """gmm-global-get-post alone -> (gauss (F, num_gselect) int32, post (F, num_gselect) fp32, offsets (B + 1) int64): the selected
+        frames of all utterances end to end, utterance b's rows [offsets[b], offsets[b + 1]); unused slots (-1, 0)."""
+        x, off = self._frames(feats, lengths, mask)
+        W, gc, _, _ = self._consts(x.device)
+        with L.on_device(x.device):
+            g, p = ops.ivector_post(x, W, gc, self.numGselect, self.minPost)
+        return g, p, torch.as_tensor(off, device=x.device)
+
+    def from_posteriors(self, feats, gauss, post, lengths=None, mask=None, dtype=torch.float32):
+        """scale-post | ivector-extract on posteriors the caller supplies: gauss / post (F, n) rows aligned with the selected frames
+        of feats (as `posteriors` returns them; an index outside [0, I) is skipped) -> (B, S) i-vectors of dtype."""
+        x, off = self._frames(feats, lengths, mask)
+        if gauss.shape != post.shape or gauss.dim() != 2 or gauss.shape[0] != x.shape[0]:
+            raise ValueError(f"gauss / post must both be ({x.shape[0]}, n), got {tuple(gauss.shape)} / {tuple(post.shape)}")
+        if not 1 <= gauss.shape[1] <= L.IVECTOR_MAX_GSELECT:
+            raise ValueError(f"{gauss.shape[1]} slots per frame outside 1 .. {L.IVECTOR_MAX_GSELECT}")
+        g = gauss.to(device=x.device, dtype=torch.int32).contiguous()
+        p = post.to(device=x.device, dtype=torch.float32).contiguous()
+        return self._extract(x, off, lambda lo, hi: (g[lo:hi], p[lo:hi]), dtype)
+
+    def _extract(self, x, off, posts, dtype):
+        if dtype not in (torch.float32, torch.float64):
+            raise ValueError(f"dtype must be torch.float32 or torch.float64, got {dtype}")
+        B = len(off) - 1
+        _, _, sim, U = self._consts(x.device)
+        out = torch.empty((B, self.ivecDim), dtype=dtype, device=x.device)
+        with L.on_device(x.device):
+            for b0, b1 in self._chunks(B):
+                lo, hi = int(off[b0]), int(off[b1])
+                g, p = posts(lo, hi)
+                o = torch.as_tensor((off[b0:b1 + 1] - lo).astype(np.int32), device=x.device)
+                out[b0:b1] = ops.ivector_extract(x[lo:hi], o, g, p, self.posteriorScale, self.acousticWeight, self.maxCount, sim, U,
+                                                 self.priorOffset, dtype)
+        return out
+
+    def __call__(self, feats, lengths=None, mask=None, dtype=torch.float32):
+        """feats (B, T, D) fp32 on a GPU; lengths: the first lengths[b] frames of utterance b; mask: (B, T) or (B, T, 1), nonzero =
+        voiced (select-voiced-frames, e.g. VAD(return_indexes=False)); neither: every frame. -> (B, S) i-vectors (fp32, Kaldi's
+        Vector<BaseFloat>; dtype=torch.float64 keeps the solve's precision)."""
+        x, off = self._frames(feats, lengths, mask)
+        W, gc, _, _ = self._consts(x.device)
+
+        def posts(lo, hi):
+            return ops.ivector_post(x[lo:hi], W, gc, self.numGselect, self.minPost)
+        return self._extract(x, off, posts, dtype)

@@ -896,3 +896,45 @@ def diar_gather(cmn, D, frames, offsets, windows, w0, n, out, lens):
         rc = L.load().ktf_diar_gather(L.ptr(cmn), int(D), fr.ctypes.data_as(C.c_void_p), L.ptr(offsets), len(fr), L.ptr(windows), windows.shape[0],
                                       int(w0), int(n), out.shape[1], L.ptr(out), L.ktf_dtype(out.dtype), out.stride(1), L.ptr(lens), L.stream_ptr())
     L.check(rc, "ktf_diar_gather")
+
+
+def ivector_post(x, W, gconst, num_gselect, min_post):
+    """gmm-global-get-post on frames x (F, D) fp32 (row stride x.stride(0)): W (2D, I), gconst (I) fp32 on the same device ->
+    (gauss (F, n) int32, post (F, n) fp32), ktf_ivector_post_f32."""
+    lib = L.load()
+    F, D = x.shape
+    n = int(num_gselect)
+    gauss = torch.empty((F, n), dtype=torch.int32, device=x.device)
+    post = torch.empty((F, n), dtype=torch.float32, device=x.device)
+    with L.on_device(x.device):
+        rc = lib.ktf_ivector_post_f32(L.ptr(x), F, D, x.stride(0) if F else D, L.ptr(W), L.ptr(gconst), gconst.shape[0], n,
+                                      float(min_post), L.ptr(gauss), L.ptr(post), L.stream_ptr())
+    L.check(rc, "ktf_ivector_post_f32")
+    return gauss, post
+
+
+def ivector_workspace_bytes(B, I, D, S):
+    n = int(L.load().ktf_ivector_workspace_bytes(int(B), int(I), int(D), int(S)))
+    if n < 0:
+        L.check(n, "ktf_ivector_workspace_bytes")
+    return n
+
+
+def ivector_extract(x, offsets, gauss, post, posterior_scale, acoustic_weight, max_count, sigma_inv_M, U, prior_offset,
+                    dtype=torch.float32):
+    """Stats, linear / quadratic terms and the solve (ktf_ivector_extract) for B = offsets.numel() - 1 utterances whose frames lie
+    end to end in x (F, D). -> (B, S) i-vectors of `dtype` (float32 or float64)."""
+    lib = L.load()
+    F, D = x.shape
+    B = offsets.numel() - 1
+    I, S = U.shape[0], sigma_inv_M.shape[1]
+    out = torch.empty((B, S), dtype=dtype, device=x.device)
+    nbytes = ivector_workspace_bytes(B, I, D, S)
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=x.device)
+    with L.on_device(x.device):
+        rc = lib.ktf_ivector_extract(L.ptr(x), F, D, x.stride(0) if F else D, L.ptr(offsets), B, L.ptr(gauss), L.ptr(post),
+                                     gauss.shape[1], float(posterior_scale), float(acoustic_weight), float(max_count), L.ptr(sigma_inv_M),
+                                     L.ptr(U), I, S, float(prior_offset), L.ptr(out), out.element_size(), L.ptr(ws), nbytes,
+                                     L.stream_ptr())
+    L.check(rc, "ktf_ivector_extract")
+    return out

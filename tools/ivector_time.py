@@ -1,0 +1,113 @@
+"""Times i-vector extraction (ktf.layers.IvectorExtractor) on one GPU: B utterances x T frames at I Gaussians, D feature dims, for
+each i-vector dim S given; per stage (posteriors = ktf_ivector_post_f32; extract = ktf_ivector_extract: stats, linear and quadratic
+terms, solve) and end to end as i-vectors/s, batch-1 latency, and the host NumPy restatement (tests/_ivector_ref.py) on a few
+utterances for scale. The model is random (built on the device: no files). Prints one JSON line per S.
+
+    python tools/ivector_time.py [--B 1024] [--T 1000] [--I 2048] [--D 60] [--S 400 600] [--reps 3]
+"""
+
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (ROOT, os.path.join(ROOT, "kaldi-tflite_amd"), os.path.join(ROOT, "tests")):
+    sys.path.insert(0, p)
+
+import _ivector_ref as R                                        # noqa: E402
+import kaldi_tflite_amd as ktf                                  # noqa: E402
+from kaldi_tflite_amd import _lib as L, ops                    # noqa: E402
+from kaldi_tflite_amd.io import KaldiDiagGmmReader, KaldiIvecExtractorReader   # noqa: E402
+
+
+def model(I, D, S, dev, seed=1):
+    """Reader objects filled directly (no file round trip): sigmaInvM and U derived on the device in fp64."""
+    rng = np.random.default_rng(seed)
+    (w, mi, iv), _ = R.random_models(rng, I, D, 2, full_sigma=False)
+    ubm = KaldiDiagGmmReader.__new__(KaldiDiagGmmReader)
+    ubm.weights, ubm.means_invvars, ubm.inv_vars, ubm.numGauss, ubm.featDim = w, mi, iv, I, D
+    ubm.gconsts = ubm.computeGconsts()
+    g = torch.Generator(device=dev).manual_seed(seed)
+    M = torch.randn((I, D, S), generator=g, device=dev, dtype=torch.float64) * 0.3
+    M[:, :, 0] = torch.as_tensor(mi / iv, device=dev, dtype=torch.float64) / 100.0
+    sig = torch.diag_embed(torch.rand((I, D), generator=g, device=dev, dtype=torch.float64) + 0.5)
+    sim = sig @ M
+    r, c = np.tril_indices(S)
+    U = torch.empty((I, S * (S + 1) // 2), dtype=torch.float64, device=dev)
+    for i0 in range(0, I, 128):
+        U[i0:i0 + 128] = (M[i0:i0 + 128].transpose(1, 2) @ sim[i0:i0 + 128])[:, r, c]
+    ie = KaldiIvecExtractorReader.__new__(KaldiIvecExtractorReader)
+    ie.w, ie.wVec, ie.priorOffset = np.zeros((0, 0)), np.full(I, 1.0 / I), 100.0
+    ie.numGauss, ie.featDim, ie.ivecDim = I, D, S
+    ie.M, ie.sigmaInv = M.cpu().numpy(), sig.cpu().numpy()
+    ie.sigmaInvM, ie.U = sim.cpu().numpy(), U.cpu().numpy()
+    return ie, ubm
+
+
+def timed(fn, reps):
+    best = float("inf")
+    for _ in range(reps):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out = fn()
+        torch.cuda.synchronize()
+        best = min(best, time.perf_counter() - t0)
+    return best, out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--B", type=int, default=1024)
+    ap.add_argument("--T", type=int, default=1000)
+    ap.add_argument("--I", type=int, default=2048)
+    ap.add_argument("--D", type=int, default=60)
+    ap.add_argument("--S", type=int, nargs="+", default=[400, 600])
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--host-utts", type=int, default=2)
+    a = ap.parse_args()
+    dev = torch.device("cuda:0")
+    torch.cuda.set_device(dev)
+    L.load()
+    for S in a.S:
+        ie, ubm = model(a.I, a.D, S, dev)
+        layer = ktf.layers.IvectorExtractor(ie, ubm)
+        rng = np.random.default_rng(2)
+        mean = ubm.means_invvars / ubm.inv_vars
+        comp = rng.integers(0, a.I, (a.B, a.T))
+        x = torch.as_tensor((mean[comp] + rng.standard_normal((a.B, a.T, a.D)) / np.sqrt(ubm.inv_vars[comp])).astype(np.float32),
+                            device=dev)
+        W, gc, sim, U = layer._consts(dev)
+        flat = x.reshape(-1, a.D)
+        layer(x[:2])                                                            # warm-up (LDS attributes, allocator)
+        t_post, (g, p) = timed(lambda: ops.ivector_post(flat, W, gc, layer.numGselect, layer.minPost), a.reps)
+        off = np.arange(a.B + 1) * a.T
+        t_ext, iv = timed(lambda: layer._extract(flat, off, lambda lo, hi: (g[lo:hi], p[lo:hi]), torch.float32), a.reps)
+        t_all, _ = timed(lambda: layer(x), a.reps)
+        t_b1, _ = timed(lambda: layer(x[:1]), a.reps)
+        # host restatement on a few utterances
+        h = a.host_utts
+        xs = x[:h].cpu().numpy()
+        t0 = time.perf_counter()
+        gmm = (ubm.gconsts, ubm.means_invvars, ubm.inv_vars)
+        for b in range(h):
+            gg, pp = R.posteriors(xs[b], gmm, 20, 0.025)
+            gamma, F = R.stats(xs[b], gg, pp, a.I)
+            R.extract_packed(gamma, F, ie.sigmaInvM, ie.U, ie.priorOffset)
+        t_host = (time.perf_counter() - t0) / h
+        print(json.dumps({
+            "build_id": L.load().ktf_build_id().decode(), "device": torch.cuda.get_device_name(dev),
+            "B": a.B, "T": a.T, "I": a.I, "D": a.D, "S": S, "chunks": len(layer._chunks(a.B)),
+            "posteriors_ms": round(t_post * 1e3, 3), "extract_ms": round(t_ext * 1e3, 3), "call_ms": round(t_all * 1e3, 3),
+            "ivectors_per_s": round(a.B / t_all, 1), "batch1_ms": round(t_b1 * 1e3, 3),
+            "host_numpy_s_per_utt": round(t_host, 3), "finite": bool(torch.isfinite(iv).all().item())}), flush=True)
+        del layer, x, flat, g, p, iv, W, gc, sim, U
+        torch.cuda.empty_cache()
+
+
+if __name__ == "__main__":
+    main()
