@@ -660,6 +660,41 @@ int ktf_ivector_extract(const float* x, int64_t F, int32_t D, int64_t ldx, const
                         const double* sigma_inv_M, const double* U, int32_t I, int32_t S, double prior_offset, void* ivectors,
                         int32_t out_dtype_bytes, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------ PLDA back-end training statistics
+ * The parts of Kaldi's `ivector-compute-lda`, `ivector-compute-plda` (PldaStats, PldaEstimator) and `est-pca --read-vectors=true`
+ * whose cost grows with the rows or the speakers; the D x D factorisations run on the host (kaldi_tflite_amd/training.py). All sums
+ * are fp64, split into row chunks by a rule that depends on the row count and D only and added in a fixed order (no atomics):
+ * the results are bit-identical run to run and on any device or stream. 1 <= D <= KTF_TRAIN_MAX_DIM.
+ *
+ * PldaStats::AddSamples / ivector-mean: speaker s owns utts[offsets[s] .. offsets[s + 1]) (offsets S + 1 and utts n_idx device
+ * int32) of the rows of x (N, D) fp32. means[s] (S, D) fp64 = the fp64 sum of its rows in list order / the count (not rounded to
+ * fp32, unlike ktf_spk_mean_f32); counts[s] (S, device int32). A speaker with an empty or out-of-range list, or naming a row outside
+ * [0, N), gets a NaN row and count 0 (callers check the map: this only keeps the kernel inside its arrays). */
+#define KTF_TRAIN_MAX_DIM 1024
+int ktf_train_class_means(const float* x, int64_t N, int32_t D, const int32_t* offsets, int64_t S, const int32_t* utts,
+                          int64_t n_idx, double* means, int32_t* counts, void* stream);
+/* Scratch of the two calls below for `rows` rows: a device buffer of at least this many bytes (a negative KTF_* code on bad
+ * arguments). */
+int64_t ktf_train_workspace_bytes(int64_t rows, int32_t D);
+/* mean (D, device fp64) = the column means of rows (rows, D) fp32 / fp64: the global mean of ivector-compute-lda and est-pca, and
+ * PldaStats' mean of the class means. Sums over fixed chunks of 256 rows, then the chunks in order. */
+int ktf_train_mean_f32(const float* x, int64_t rows, int32_t D, double* mean, void* workspace, size_t workspace_bytes, void* stream);
+int ktf_train_mean_f64(const double* y, int64_t rows, int32_t D, double* mean, void* workspace, size_t workspace_bytes, void* stream);
+/* G (D x D, device fp64, symmetric bit for bit) = sum_r w_r (y_{i_r} - c)(y_{i_r} - c)^T over the list positions r < rows, with
+ * i_r = idx[r] (idx: `rows` device int32; NULL: i_r = r, rows <= N), w_r = weights[r] (NULL: 1) and c = center (D, NULL: 0), all
+ * device arrays; y (N, D) fp32 (x) or fp64 (class means, EM rows). The scatter matrices of ivector-compute-lda (total and between
+ * class), est-pca's covariance and PldaStats' within-class scatter; the two SYRKs of the PLDA EM. A listed index outside [0, N)
+ * contributes nothing (callers check the list). */
+int ktf_train_gram_f32(const float* x, int64_t N, int32_t D, const int32_t* idx, int64_t rows, const double* center,
+                       const double* weights, double* G, void* workspace, size_t workspace_bytes, void* stream);
+int ktf_train_gram_f64(const double* y, int64_t N, int32_t D, const int32_t* idx, int64_t rows, const double* center,
+                       const double* weights, double* G, void* workspace, size_t workspace_bytes, void* stream);
+/* One PldaEstimator EM step's row transform in the simultaneous diagonalisation P Phi_w P^T = I, P Phi_b P^T = diag(lam):
+ * y_s = P (mu_s - mbar) (mu (S, D), mbar (D), P (D x D row-major), all device fp64), then with n = counts[s] (S, device int32)
+ * a[s][d] = n lam_d / (1 + n lam_d) y_s[d] and b[s][d] = y_s[d] / (1 + n lam_d) (a, b: (S, D) device fp64). */
+int ktf_plda_em_project(const double* mu, int64_t S, int32_t D, const double* mbar, const double* P, const double* lam,
+                        const int32_t* counts, double* a, double* b, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -421,3 +421,40 @@ def ReadKaldiArray(path, binary, dtype=np.float32):
     if kind in (b"FV", b"DV"):
         return r.readVec()
     raise ValueError(f"binary file contains unexpected header bytes, {kind.decode(errors='replace')}, expected 'FV', 'DV', 'FM', 'DM' or 'CM'")
+
+
+# ----------------------------------------------------------------------------- writers (an extension: the reference only reads)
+def _array_bytes(array, binary):
+    """One Kaldi vector / matrix as it follows "\\0B" or a token: binary "FV " / "DV " / "FM " / "DM ", then 0x04 + int32 sizes,
+    then the little-endian data; text " [ v v v ]\\n" (vector) or " [" + "\\n  v v v " per row + "]\\n" (matrix), fp32 values as
+    '%.7g', fp64 values as '%.17g' (exact on reading back)."""
+    a = np.asarray(array)
+    if a.dtype not in (np.float32, np.float64) or a.ndim not in (1, 2):
+        raise ValueError(f"expected a float32 / float64 vector or matrix, got {a.dtype} of shape {a.shape}")
+    f32 = a.dtype == np.float32
+    if binary:
+        head = (b"F" if f32 else b"D") + (b"V " if a.ndim == 1 else b"M ")
+        sizes = b"".join(b"\x04" + _I32.pack(int(n)) for n in a.shape)
+        return head + sizes + np.ascontiguousarray(a, dtype="<f4" if f32 else "<f8").tobytes()
+    fmt = "%.7g" if f32 else "%.17g"
+    if a.ndim == 1:
+        return (" [ " + "".join(fmt % v + " " for v in a) + "]\n").encode()
+    return (" [" + "".join("\n  " + "".join(fmt % v + " " for v in row) for row in a) + "]\n").encode()
+
+
+def WriteKaldiArray(path, array, binary=True):
+    """The inverse of ReadKaldiArray: a vector or matrix, fp32 -> FV / FM, fp64 -> DV / DM; binary files start with "\\0B"."""
+    with open(path, "wb") as f:
+        f.write((b"\0B" if binary else b"") + _array_bytes(array, binary))
+
+
+def WriteKaldiPlda(path, mean, transform, psi, binary=True):
+    """Kaldi's Plda::Write: "<Plda> ", mean (DV), transform (DM), psi (DV), "</Plda> " (binary: after "\\0B"). The arrays are
+    written as fp64 whatever their dtype."""
+    mean, transform, psi = (np.asarray(a, np.float64) for a in (mean, transform, psi))
+    D = mean.shape[0]
+    if mean.ndim != 1 or transform.shape != (D, D) or psi.shape != (D,):
+        raise ValueError(f"inconsistent PLDA shapes: mean {mean.shape}, transform {transform.shape}, psi {psi.shape}")
+    with open(path, "wb") as f:
+        f.write((b"\0B" if binary else b"") + b"<Plda> " + _array_bytes(mean, binary) + _array_bytes(transform, binary)
+                + _array_bytes(psi, binary) + b"</Plda> ")

@@ -938,3 +938,60 @@ def ivector_extract(x, offsets, gauss, post, posterior_scale, acoustic_weight, m
                                      L.stream_ptr())
     L.check(rc, "ktf_ivector_extract")
     return out
+
+
+# ----------------------------------------------------------------------------- back-end training (ktf_train_*, ktf_plda_em_project)
+def train_workspace(rows, D, device):
+    """A uint8 device buffer for ktf_train_mean_* / ktf_train_gram_* over up to `rows` rows of dimension D."""
+    n = int(L.load().ktf_train_workspace_bytes(int(rows), int(D)))
+    if n < 0:
+        L.check(n, "ktf_train_workspace_bytes")
+    return torch.empty((n,), dtype=torch.uint8, device=device)
+
+
+def train_class_means(x, offsets, utts, S):
+    """x (N, D) fp32, the CSR map offsets (S + 1) / utts on the device (int32) -> (means (S, D) fp64, counts (S,) int32)."""
+    N, D = x.shape
+    means = torch.empty((S, D), dtype=torch.float64, device=x.device)
+    counts = torch.empty((S,), dtype=torch.int32, device=x.device)
+    with L.on_device(x.device):
+        rc = L.load().ktf_train_class_means(L.ptr(x), N, D, L.ptr(offsets), S, L.ptr(utts), utts.numel(), L.ptr(means), L.ptr(counts),
+                                            L.stream_ptr())
+    L.check(rc, "ktf_train_class_means")
+    return means, counts
+
+
+def train_mean(y, ws):
+    """Column means (D,) fp64 of y (rows, D) fp32 or fp64."""
+    rows, D = y.shape
+    out = torch.empty((D,), dtype=torch.float64, device=y.device)
+    fn = L.load().ktf_train_mean_f64 if y.dtype == torch.float64 else L.load().ktf_train_mean_f32
+    with L.on_device(y.device):
+        rc = fn(L.ptr(y), rows, D, L.ptr(out), L.ptr(ws), ws.numel(), L.stream_ptr())
+    L.check(rc, "ktf_train_mean")
+    return out
+
+
+def train_gram(y, ws, idx=None, center=None, weights=None):
+    """G (D, D) fp64 = sum_r w_r (y[idx[r]] - c)(y[idx[r]] - c)^T; idx (device int32, None: every row), center (D,) and weights
+    (one per listed row) device fp64 or None."""
+    N, D = y.shape
+    rows = idx.numel() if idx is not None else N
+    G = torch.empty((D, D), dtype=torch.float64, device=y.device)
+    fn = L.load().ktf_train_gram_f64 if y.dtype == torch.float64 else L.load().ktf_train_gram_f32
+    with L.on_device(y.device):
+        rc = fn(L.ptr(y), N, D, L.ptr(idx), rows, L.ptr(center), L.ptr(weights), L.ptr(G), L.ptr(ws), ws.numel(), L.stream_ptr())
+    L.check(rc, "ktf_train_gram")
+    return G
+
+
+def plda_em_project(mu, mbar, P, lam, counts):
+    """One EM step's rows in the diagonal space: mu (S, D), mbar (D,), P (D, D), lam (D,) device fp64, counts (S,) int32 -> a, b."""
+    S, D = mu.shape
+    a = torch.empty_like(mu)
+    b = torch.empty_like(mu)
+    with L.on_device(mu.device):
+        rc = L.load().ktf_plda_em_project(L.ptr(mu), S, D, L.ptr(mbar), L.ptr(P), L.ptr(lam), L.ptr(counts), L.ptr(a), L.ptr(b),
+                                          L.stream_ptr())
+    L.check(rc, "ktf_plda_em_project")
+    return a, b

@@ -30,6 +30,43 @@ def _csr(spk2utt):
     return off.astype(np.int64), utt.astype(np.int64)
 
 
+def _checked_map(spk2utt, U, device, what, host_offsets=False):
+    """spk2utt -> (offsets (S + 1), utts) as device int32 tensors and, with host_offsets, the offsets as a host int64 array (else
+    None). Every speaker needs at least one utterance and every index must lie in [0, U): checked on the host, or for a device map
+    with one reduction and one read (which also brings the offsets back when asked for), before anything is launched."""
+    off, utt = _csr(spk2utt)
+    S = off.shape[0] - 1
+    if S < 0:
+        raise ValueError("spk2utt: offsets need S + 1 >= 1 entries")
+    if isinstance(off, torch.Tensor):
+        for a in (off, utt):
+            if a.device != device:
+                raise ValueError(f"spk2utt is on {a.device}, {what} on {device}")
+            if a.dim() != 1 or a.dtype.is_floating_point or a.dtype == torch.bool:
+                raise ValueError("spk2utt: offsets and utterance indices must be 1-D integer tensors")
+        n = utt.shape[0]
+        off_h = None
+        if S:
+            bad = ((off[1:] <= off[:-1]).any() | (off[0] < 0) | (off[-1] > n) | ((utt < 0) | (utt >= U)).any()).reshape(1)
+            if host_offsets:
+                back = torch.cat([bad.to(torch.int64), off.to(torch.int64)]).cpu().numpy()       # the one device -> host read
+                bad, off_h = bool(back[0]), back[1:]
+            else:
+                bad = bool(bad.item())                                                           # the one device -> host read
+            if bad:
+                raise ValueError(f"spk2utt: a speaker without utterances, or an index outside 0..{U - 1}")
+        off_d, utt_d = off.to(torch.int32).contiguous(), utt.to(torch.int32).contiguous()
+    else:
+        if S and (np.any(off[1:] <= off[:-1]) or off[0] < 0 or off[-1] > utt.size):
+            raise ValueError("spk2utt: every speaker needs at least one utterance")
+        if utt.size and (utt.min() < 0 or utt.max() >= U):
+            raise ValueError(f"spk2utt: an utterance index outside 0..{U - 1}")
+        off_h = off
+        off_d = torch.as_tensor(off.astype(np.int32)).to(device)
+        utt_d = torch.as_tensor(utt.astype(np.int32) if utt.size else np.zeros((1,), np.int32)).to(device)
+    return off_d, utt_d, (off_h if host_offsets else None)
+
+
 def speaker_means(raw, spk2utt):
     """Kaldi ivector-mean: raw x-vectors (U, D) fp32 on the device (XvectorExtractor.embeddings) and the speaker map spk2utt --
     a list of row-index lists (speaker s owns rows spk2utt[s]) or a CSR pair (offsets (S + 1), utts) of host arrays or device
@@ -40,29 +77,8 @@ def speaker_means(raw, spk2utt):
     if not isinstance(raw, torch.Tensor) or not raw.is_cuda or raw.dim() != 2:
         raise ValueError("raw must be a (U, D) device tensor")
     x = raw.to(torch.float32).contiguous()
-    U = x.shape[0]
-    off, utt = _csr(spk2utt)
-    S = off.shape[0] - 1
-    if S < 0:
-        raise ValueError("spk2utt: offsets need S + 1 >= 1 entries")
-    if isinstance(off, torch.Tensor):
-        for a in (off, utt):
-            if a.device != x.device:
-                raise ValueError(f"spk2utt is on {a.device}, raw on {x.device}")
-            if a.dim() != 1 or a.dtype.is_floating_point or a.dtype == torch.bool:
-                raise ValueError("spk2utt: offsets and utterance indices must be 1-D integer tensors")
-        n = utt.shape[0]
-        if S and bool(((off[1:] <= off[:-1]).any() | (off[0] < 0) | (off[-1] > n)
-                       | ((utt < 0) | (utt >= U)).any()).item()):                           # the one device -> host read
-            raise ValueError(f"spk2utt: a speaker without utterances, or an index outside 0..{U - 1}")
-        off_d, utt_d = off.to(torch.int32).contiguous(), utt.to(torch.int32).contiguous()
-    else:
-        if S and (np.any(off[1:] <= off[:-1]) or off[0] < 0 or off[-1] > utt.size):
-            raise ValueError("spk2utt: every speaker needs at least one utterance")
-        if utt.size and (utt.min() < 0 or utt.max() >= U):
-            raise ValueError(f"spk2utt: an utterance index outside 0..{U - 1}")
-        off_d = torch.as_tensor(off.astype(np.int32)).to(x.device)
-        utt_d = torch.as_tensor(utt.astype(np.int32) if utt.size else np.zeros((1,), np.int32)).to(x.device)
+    off_d, utt_d, _ = _checked_map(spk2utt, x.shape[0], x.device, "raw")
+    S = off_d.shape[0] - 1
     if S == 0:
         return (torch.empty((0, x.shape[1]), dtype=torch.float32, device=x.device),
                 torch.empty((0,), dtype=torch.int32, device=x.device))
