@@ -659,6 +659,32 @@ int ktf_ivector_extract(const float* x, int64_t F, int32_t D, int64_t ldx, const
                         const float* post, int32_t n, float posterior_scale, float acoustic_weight, float max_count,
                         const double* sigma_inv_M, const double* U, int32_t I, int32_t S, double prior_offset, void* ivectors,
                         int32_t out_dtype_bytes, void* workspace, size_t workspace_bytes, void* stream);
+/* gmm-gselect --n | fgmm-global-gselect-to-post --min-post (FullGmm::LogLikelihoodsPreselect, then the pruning loop of
+ * fgmm-global-gselect-to-post.cc), the posterior stage of every sid/extract_ivectors.sh. The preselection is the diagonal call
+ * above with min_post = 0: its gauss output is gmm-gselect's set (its post output is not used). Here, per frame t:
+ *   gselect (F, n) device int32 lists the Gaussians; entries outside [0, I) are skipped. For each listed g
+ *     l_g = gconst_g + means_invcovars_g . x - x^T inv_covars_g x / 2   (fp32; summed in an order that depends on D alone)
+ *   p = exp(l - max) / sum over the listed set. With min_post != 0: every p < min_post is set to 0 and the rest divided by their
+ *   sum; if that sum is 0 the arg-max (ties: the lower Gaussian index) gets 1. One pass, not the running-sum loop above.
+ *   gauss / post (F, n): the Gaussians with p != 0 sorted by posterior, descending (ties: the lower index), then (-1, 0): the
+ *   layout ktf_ivector_extract reads. A frame with nothing listed, or whose listed l are all -inf, gets n unused slots.
+ * means_invcovars (I, D), gconst (I), inv_covars (I, D, D): device fp32 row-major; inv_covars holds the FULL matrices (not
+ * Kaldi's packed triangle) and must be symmetric bit for bit (element [k][j] is read for [j][k]). workspace: 256-byte aligned, at
+ * least ktf_fgmm_workspace_bytes(F, I, D, n) bytes (a negative KTF_* code on bad arguments); F * n < 2^31. The pairs are bucketed
+ * by Gaussian and every bucket runs as an exact-fp32 MFMA GEMM against its matrix held in LDS; each pair's value is computed alone,
+ * so a frame's output bits depend on its x row and its list alone: not on F, its position, the other frames or the run. */
+int64_t ktf_fgmm_workspace_bytes(int64_t F, int32_t I, int32_t D, int32_t n);
+int ktf_fgmm_post_f32(const float* x, int64_t F, int32_t D, int64_t ldx, const int32_t* gselect, int32_t n,
+                      const float* means_invcovars, const float* inv_covars, const float* gconst, int32_t I, float min_post,
+                      int32_t* gauss, float* post, void* workspace, size_t workspace_bytes, void* stream);
+/* add-deltas (Kaldi's DeltaFeatures): x (B, T, D) fp32, element (b, t, d) at x[b * stride_b + t * stride_t + d] -> out (B, T,
+ * D * (order + 1)) contiguous. coeffs: device fp32 (order + 1, 2 * order * window + 1), row i the order-i filter centred at column
+ * order * window and zero beyond +- i * window (the caller computes them in fp32 as DeltaFeatures does). Block i of frame t is
+ * sum_j coeffs[i][j] * x[clamp(t + j, 0, len_b - 1)], j ascending, zero coefficients skipped, every step acc = fl(acc + fl(s * x))
+ * unfused. lengths: B device int32 or null (= T); rows at and beyond lengths[b] are written as zeros. */
+#define KTF_ADD_DELTAS_MAX_CONTEXT 32
+int ktf_add_deltas_f32(const float* x, int64_t B, int64_t T, int32_t D, int64_t stride_b, int64_t stride_t, const int32_t* lengths,
+                       const float* coeffs, int32_t order, int32_t window, float* out, void* stream);
 
 /* ------------------------------------------------------------------ PLDA back-end training statistics
  * The parts of Kaldi's `ivector-compute-lda`, `ivector-compute-plda` (PldaStats, PldaEstimator) and `est-pca --read-vectors=true`

@@ -392,6 +392,77 @@ class KaldiDiagGmmReader(KaldiObjReader):
         return gc.astype(f)
 
 
+class KaldiFullGmmReader(KaldiObjReader):
+    """Kaldi FullGmm (`final.ubm`; an extension like KaldiDiagGmmReader): <FullGMM> <GCONSTS> FV <WEIGHTS> FV <MEANS_INVCOVARS> FM
+    <INV_COVARS> (FP) x I </FullGMM>, the I packed lower triangles following each other without a count, fp32. weights (I),
+    means_invcovars (I, D) as stored, inv_covars (I, D, D) full symmetric fp32; <GCONSTS> may be absent (`storedGconsts` None).
+    gconsts (I, fp32) are recomputed as FullGmm::ComputeGconsts defines them, log w - D/2 log(2 pi) - (log det Sigma + mu^T
+    Sigma^-1 mu) / 2, in fp64 from the stored fp32 fields and rounded once to fp32: Kaldi's own promotions inside ComputeGconsts are
+    not known to this project, so the last bit may differ from the stored values. A non-positive-definite inv_covars[i] or
+    inconsistent shapes raise ValueError."""
+
+    def __init__(self, path, binary=True):
+        super().__init__(path, binary)
+        self.read()
+
+    def read(self):
+        self.expectToken("<FullGMM>")
+        self.storedGconsts = self.readVec() if self.expectToken("<GCONSTS>", stopTokens=("<WEIGHTS>",)) else None
+        self.expectToken("<WEIGHTS>")
+        self.weights = self.readVec()
+        self.expectToken("<MEANS_INVCOVARS>")
+        self.means_invcovars = self.readMat()
+        self.expectToken("<INV_COVARS>")
+        I, D = self.means_invcovars.shape
+        if self.weights.shape != (I,) or I == 0 or D == 0:
+            raise ValueError(f"inconsistent FullGMM shapes: weights {self.weights.shape}, means_invcovars {self.means_invcovars.shape}")
+        covs = []
+        for i in range(I):
+            covs.append(self.readPackedMat())
+            if covs[-1].shape != (D, D):
+                raise ValueError(f"inconsistent FullGMM shapes: inv_covars[{i}] is {covs[-1].shape}, feature dim {D}")
+        self.expectToken("</FullGMM>")
+        self.inv_covars = np.asarray(covs, dtype=np.float32)
+        self.numGauss, self.featDim = int(I), int(D)
+        self.gconsts = self.computeGconsts()
+
+    def _covars(self):
+        """(Sigma (I, D, D), log det Sigma (I)) in fp64; ValueError if an inverse covariance is not positive definite."""
+        ic = self.inv_covars.astype(np.float64)
+        try:
+            chol = np.linalg.cholesky(ic)
+        except np.linalg.LinAlgError as e:
+            raise ValueError(f"FullGMM: an inverse covariance is not positive definite ({e})") from None
+        if not np.isfinite(chol).all():
+            raise ValueError("FullGMM: an inverse covariance is not positive definite")
+        logdet = -2.0 * np.log(np.diagonal(chol, axis1=1, axis2=2)).sum(1)
+        return np.linalg.inv(ic), logdet
+
+    def computeGconsts(self):
+        cov, logdet = self._covars()
+        mic = self.means_invcovars.astype(np.float64)
+        mu = np.einsum("ide,ie->id", cov, mic)
+        with np.errstate(divide="ignore"):
+            gc = np.log(self.weights.astype(np.float64)) - 0.5 * self.featDim * np.log(2 * np.pi) \
+                - 0.5 * (logdet + np.einsum("id,id->i", mu, mic))
+        return gc.astype(np.float32)
+
+    def toDiag(self):
+        """fgmm-global-to-gmm (DiagGmm::CopyFromFullGmm): Sigma = inv(inv_covars) in fp64, inv_vars = 1 / diag Sigma, means_invvars
+        = (Sigma means_invcovars) inv_vars, the same weights -> an object with KaldiDiagGmmReader's attributes."""
+        cov, _ = self._covars()
+        iv = 1.0 / np.diagonal(cov, axis1=1, axis2=2)
+        mu = np.einsum("ide,ie->id", cov, self.means_invcovars.astype(np.float64))
+        d = KaldiDiagGmmReader.__new__(KaldiDiagGmmReader)
+        d.path, d.binary, d.storedGconsts = self.path, True, None
+        d.weights = np.array(self.weights, dtype=np.float32)
+        d.inv_vars = iv.astype(np.float32)
+        d.means_invvars = (mu * iv).astype(np.float32)
+        d.numGauss, d.featDim = self.numGauss, self.featDim
+        d.gconsts = d.computeGconsts()
+        return d
+
+
 def _text_array(path, dtype):
     """Kaldi text form: ' [ v v v ]' on one line is a vector; '[' ... rows ... ']' over several lines a matrix."""
     if dtype not in (np.float32, np.float64, np.int16, np.int32, np.int64):

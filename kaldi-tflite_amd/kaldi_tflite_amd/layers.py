@@ -578,6 +578,75 @@ class CMVN(Layer):
         return out
 
 
+class AddDeltas(Layer):
+    """Extension (the reference has no delta features): Kaldi's `add-deltas --delta-order=order --delta-window=window`
+    (DeltaFeatures; the sid recipes pass order 2, window 3). (B, T, D) or (T, D) fp32 on a GPU -> (B, T, D * (order + 1)): the input,
+    then its order-1 .. order-`order` regression coefficients, frames beyond an utterance's ends clamped to its first / last frame.
+    `lengths` (optional, B values): utterance b has lengths[b] frames; rows at and beyond them are written as zeros."""
+
+    def __init__(self, order=2, window=2, name=None, **kwargs):
+        super().__init__(trainable=False, name=name, **kwargs)
+        if int(order) != order or int(window) != window or order < 0 or window < 1 or order * window > L.ADD_DELTAS_MAX_CONTEXT:
+            raise ValueError(f"AddDeltas needs integers order >= 0, window >= 1, order * window <= {L.ADD_DELTAS_MAX_CONTEXT}; "
+                             f"got order={order}, window={window}")
+        self.order, self.window = int(order), int(window)
+        self._coeffs = self.coefficients(self.order, self.window)
+
+    @staticmethod
+    def coefficients(order, window):
+        """DeltaFeatures' scales in fp32: s_0 = [1]; s_i[j + k] += j * s_{i-1}[k] for j in [-window, window], divided by sum j^2.
+        -> (order + 1, 2 * order * window + 1) fp32, row i centred at column order * window and zero beyond +- i * window."""
+        f = np.float32
+        ow = order * window
+        out = np.zeros((order + 1, 2 * ow + 1), f)
+        prev = np.ones(1, f)
+        out[0, ow] = 1
+        for i in range(1, order + 1):
+            po = (len(prev) - 1) // 2
+            cur = np.zeros(len(prev) + 2 * window, f)
+            norm = f(0)
+            for j in range(-window, window + 1):
+                norm = f(norm + f(j * j))
+                for k in range(-po, po + 1):
+                    cur[j + k + po + window] = f(cur[j + k + po + window] + f(f(j) * prev[k + po]))
+            cur = (cur / norm).astype(f)
+            out[i, ow - i * window:ow + i * window + 1] = cur
+            prev = cur
+        return out
+
+    def compute_output_shape(self, input_shape):
+        out = list(input_shape)
+        out[-1] = None if out[-1] is None else out[-1] * (self.order + 1)
+        return out
+
+    def get_config(self):
+        c = super().get_config()
+        c.update({"order": self.order, "window": self.window})
+        return c
+
+    def call(self, inputs, lengths=None):
+        if not inputs.is_cuda:
+            raise ValueError("AddDeltas computes on a GPU: the input must be a tensor on one")
+        x = inputs.to(torch.float32)
+        squeeze = x.dim() == 2
+        if squeeze:
+            x = x.unsqueeze(0)
+        if x.dim() != 3 or x.shape[2] < 1:
+            raise ValueError(f"AddDeltas takes (B, T, D) or (T, D), got {tuple(inputs.shape)}")
+        B, T, D = x.shape
+        if x.stride(2) != 1 or x.stride(1) < D or (B > 1 and x.stride(0) < 0):
+            x = x.contiguous()
+        n = None
+        if lengths is not None:
+            h = np.asarray(lengths.cpu() if isinstance(lengths, torch.Tensor) else lengths, dtype=np.int64).reshape(-1)
+            if h.shape[0] != B or (h < 0).any() or (h > T).any():
+                raise ValueError(f"lengths must hold {B} values in 0 .. {T}")
+            n = torch.as_tensor(h.astype(np.int32), device=x.device)
+        coeffs = _per_device(self, x.device, lambda: torch.as_tensor(self._coeffs, device=x.device))
+        out = ops.add_deltas(x, n, coeffs, self.order, self.window)
+        return out[0] if squeeze else out
+
+
 class ReLU(Layer):
     """keras ReLU as used by models/kaldi/sequential.py:72 (stand-alone elementwise kernel)."""
 
@@ -1347,18 +1416,36 @@ class IvectorExtractor(Layer):
         gmm-global-get-post --n=num_gselect --min-post=min_post final.dubm feats ark:- | scale-post ark:- posterior_scale ark:- |
         ivector-extract --acoustic-weight=acoustic_weight --max-count=max_count final.ie feats ark:- ivectors.ark
 
-    `extractor`: a path to a Kaldi binary `final.ie` or an io.KaldiIvecExtractorReader; `diag_ubm`: a path to `final.dubm` or an
-    io.KaldiDiagGmmReader. The defaults are those of the recipe's extract_ivectors.sh (num_gselect 20, min_post 0.025);
-    gmm-global-get-post's own defaults are --n=50 --min-post=0.0. An extractor with ivector-dependent weights (a non-empty `w`)
-    raises NotImplementedError. Calls run on the device of `feats` and its current stream; the utterances are processed in chunks
-    whose workspace stays under `workspace_limit` bytes, and an utterance's i-vector bits do not depend on the chunk it falls in."""
+    or, with `full_ubm`, the posterior stage of the recipes themselves (every sid/extract_ivectors.sh):
 
-    def __init__(self, extractor, diag_ubm, num_gselect=20, min_post=0.025, posterior_scale=1.0, acoustic_weight=1.0, max_count=0.0,
-                 workspace_limit=1 << 30, name=None):
+        gmm-gselect --n=num_gselect final.dubm feats ark:- |
+        fgmm-global-gselect-to-post --min-post=min_post final.ubm feats ark:- ark:- | scale-post ... | ivector-extract ...
+
+    `extractor`: a path to a Kaldi binary `final.ie` or an io.KaldiIvecExtractorReader; `diag_ubm`: a path to `final.dubm` or an
+    io.KaldiDiagGmmReader; `full_ubm`: a path to `final.ubm` or an io.KaldiFullGmmReader. With a full UBM the diagonal one only
+    preselects num_gselect Gaussians per frame and the posteriors come from the full one; `diag_ubm=None` then stands for
+    `full_ubm.toDiag()` (fgmm-global-to-gmm). The defaults are those of the recipe's extract_ivectors.sh (num_gselect 20, min_post
+    0.025); gmm-global-get-post's own defaults are --n=50 --min-post=0.0. An extractor with ivector-dependent weights (a non-empty
+    `w`) raises NotImplementedError. Calls run on the device of `feats` and its current stream; the utterances, and with a full UBM
+    the frames, are processed in chunks whose workspace stays under `workspace_limit` bytes, and no output bit depends on the chunks."""
+
+    def __init__(self, extractor, diag_ubm=None, num_gselect=20, min_post=0.025, posterior_scale=1.0, acoustic_weight=1.0, max_count=0.0,
+                 workspace_limit=1 << 30, name=None, full_ubm=None):
         super().__init__(trainable=False, name=name)
         from . import io as kio
         ie = extractor if isinstance(extractor, kio.KaldiIvecExtractorReader) else kio.KaldiIvecExtractorReader(extractor, binary=True)
-        ubm = diag_ubm if isinstance(diag_ubm, kio.KaldiDiagGmmReader) else kio.KaldiDiagGmmReader(diag_ubm, binary=True)
+        if diag_ubm is None and full_ubm is None:
+            raise ValueError("IvectorExtractor needs diag_ubm, full_ubm or both")
+        full = None
+        if full_ubm is not None:
+            full = full_ubm if isinstance(full_ubm, kio.KaldiFullGmmReader) else kio.KaldiFullGmmReader(full_ubm, binary=True)
+            if full.numGauss != ie.numGauss or full.featDim != ie.featDim:
+                raise ValueError(f"full UBM ({full.numGauss} Gaussians, dim {full.featDim}) does not match the extractor "
+                                 f"({ie.numGauss} Gaussians, dim {ie.featDim})")
+        if diag_ubm is None:
+            ubm = full.toDiag()
+        else:
+            ubm = diag_ubm if isinstance(diag_ubm, kio.KaldiDiagGmmReader) else kio.KaldiDiagGmmReader(diag_ubm, binary=True)
         if ie.w is not None and ie.w.size:
             raise NotImplementedError("ivector-dependent weights (a non-empty <w>) are not supported")
         if ubm.numGauss != ie.numGauss or ubm.featDim != ie.featDim:
@@ -1385,6 +1472,11 @@ class IvectorExtractor(Layer):
         self._gconst = np.ascontiguousarray(ubm.gconsts, dtype=np.float32)
         self._sigmaInvM = np.ascontiguousarray(np.asarray(ie.sigmaInvM, dtype=np.float64).reshape(I * D, S))
         self._U = np.ascontiguousarray(ie.U, dtype=np.float64)
+        # the full UBM as ktf_fgmm_post_f32 takes it: means_invcovars (I, D), inv_covars (I, D, D) full, gconst (I)
+        self._full = None if full is None else tuple(np.ascontiguousarray(a, dtype=np.float32)
+                                                     for a in (full.means_invcovars, full.inv_covars, full.gconsts))
+        # the most frames whose ktf_fgmm_post_f32 workspace stays under workspace_limit (at least one)
+        self._frameStep = None if full is None else self._frame_step()
 
     def get_config(self):
         raise NotImplementedError("IvectorExtractor holds model files, not a config")
@@ -1392,8 +1484,39 @@ class IvectorExtractor(Layer):
     def _consts(self, device):
         def make():
             f = lambda a: torch.as_tensor(a, device=device)  # noqa: E731
-            return f(self._W), f(self._gconst), f(self._sigmaInvM), f(self._U)
+            full = None if self._full is None else tuple(f(a) for a in self._full)
+            return f(self._W), f(self._gconst), f(self._sigmaInvM), f(self._U), full
         return _per_device(self, device, make)
+
+    def _frame_step(self):
+        I, D, n = self.numGauss, self.featDim, self.numGselect
+        lo, hi = 1, ((1 << 31) - 1) // n
+        if ops.fgmm_workspace_bytes(hi, I, D, n) <= self.workspaceLimit:
+            return hi
+        while hi - lo > 1:
+            mid = (lo + hi) // 2
+            if ops.fgmm_workspace_bytes(mid, I, D, n) <= self.workspaceLimit:
+                lo = mid
+            else:
+                hi = mid
+        return lo
+
+    def _post(self, x):
+        """Posteriors of the frames x (F, D): gmm-global-get-post, or with a full UBM gmm-gselect | fgmm-global-gselect-to-post."""
+        W, gc, _, _, full = self._consts(x.device)
+        if full is None:
+            return ops.ivector_post(x, W, gc, self.numGselect, self.minPost)
+        mic, icov, fgc = full
+        F, step = x.shape[0], self._frameStep
+        if F <= step:
+            sel, _ = ops.ivector_post(x, W, gc, self.numGselect, 0.0)
+            return ops.fgmm_post(x, sel, mic, icov, fgc, self.minPost)
+        g = torch.empty((F, self.numGselect), dtype=torch.int32, device=x.device)
+        p = torch.empty((F, self.numGselect), dtype=torch.float32, device=x.device)
+        for lo in range(0, F, step):
+            sel, _ = ops.ivector_post(x[lo:lo + step], W, gc, self.numGselect, 0.0)
+            g[lo:lo + step], p[lo:lo + step] = ops.fgmm_post(x[lo:lo + step], sel, mic, icov, fgc, self.minPost)
+        return g, p
 
     def _frames(self, feats, lengths, mask):
         """(B, T, D) device fp32 -> (frames (F, D) in utterance order, offsets (B + 1) host int64)."""
@@ -1427,12 +1550,11 @@ class IvectorExtractor(Layer):
         return [(b, min(B, b + step)) for b in range(0, B, step)]
 
     def posteriors(self, feats, lengths=None, mask=None):
-        """gmm-global-get-post alone -> (gauss (F, num_gselect) int32, post (F, num_gselect) fp32, offsets (B + 1) int64): the selected
+        """The posterior stage alone (gmm-global-get-post, or the full-UBM pair) -> (gauss (F, num_gselect) int32, post (F, num_gselect) fp32, offsets (B + 1) int64): the selected
         frames of all utterances end to end, utterance b's rows [offsets[b], offsets[b + 1]); unused slots (-1, 0)."""
         x, off = self._frames(feats, lengths, mask)
-        W, gc, _, _ = self._consts(x.device)
         with L.on_device(x.device):
-            g, p = ops.ivector_post(x, W, gc, self.numGselect, self.minPost)
+            g, p = self._post(x)
         return g, p, torch.as_tensor(off, device=x.device)
 
     def from_posteriors(self, feats, gauss, post, lengths=None, mask=None, dtype=torch.float32):
@@ -1451,7 +1573,7 @@ class IvectorExtractor(Layer):
         if dtype not in (torch.float32, torch.float64):
             raise ValueError(f"dtype must be torch.float32 or torch.float64, got {dtype}")
         B = len(off) - 1
-        _, _, sim, U = self._consts(x.device)
+        _, _, sim, U, _ = self._consts(x.device)
         out = torch.empty((B, self.ivecDim), dtype=dtype, device=x.device)
         with L.on_device(x.device):
             for b0, b1 in self._chunks(B):
@@ -1467,8 +1589,4 @@ class IvectorExtractor(Layer):
         voiced (select-voiced-frames, e.g. VAD(return_indexes=False)); neither: every frame. -> (B, S) i-vectors (fp32, Kaldi's
         Vector<BaseFloat>; dtype=torch.float64 keeps the solve's precision)."""
         x, off = self._frames(feats, lengths, mask)
-        W, gc, _, _ = self._consts(x.device)
-
-        def posts(lo, hi):
-            return ops.ivector_post(x[lo:hi], W, gc, self.numGselect, self.minPost)
-        return self._extract(x, off, posts, dtype)
+        return self._extract(x, off, lambda lo, hi: self._post(x[lo:hi]), dtype)

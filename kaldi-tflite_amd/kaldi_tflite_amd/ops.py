@@ -940,6 +940,45 @@ def ivector_extract(x, offsets, gauss, post, posterior_scale, acoustic_weight, m
     return out
 
 
+def fgmm_workspace_bytes(F, I, D, n):
+    b = int(L.load().ktf_fgmm_workspace_bytes(int(F), int(I), int(D), int(n)))
+    if b < 0:
+        L.check(b, "ktf_fgmm_workspace_bytes")
+    return b
+
+
+def fgmm_post(x, gselect, means_invcovars, inv_covars, gconst, min_post):
+    """fgmm-global-gselect-to-post on frames x (F, D) fp32 (row stride x.stride(0)) and the lists gselect (F, n) int32 (entries
+    outside [0, I) skipped): means_invcovars (I, D), inv_covars (I, D, D) full symmetric, gconst (I), fp32 on the same device ->
+    (gauss (F, n) int32, post (F, n) fp32), ktf_fgmm_post_f32."""
+    lib = L.load()
+    F, D = x.shape
+    n = gselect.shape[1]
+    I = gconst.shape[0]
+    gauss = torch.empty((F, n), dtype=torch.int32, device=x.device)
+    post = torch.empty((F, n), dtype=torch.float32, device=x.device)
+    nbytes = fgmm_workspace_bytes(F, I, D, n)
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=x.device)
+    with L.on_device(x.device):
+        rc = lib.ktf_fgmm_post_f32(L.ptr(x), F, D, x.stride(0) if F else D, L.ptr(gselect), n, L.ptr(means_invcovars), L.ptr(inv_covars),
+                                   L.ptr(gconst), I, float(min_post), L.ptr(gauss), L.ptr(post), L.ptr(ws), nbytes, L.stream_ptr())
+    L.check(rc, "ktf_fgmm_post_f32")
+    return gauss, post
+
+
+def add_deltas(x, lengths, coeffs, order, window):
+    """add-deltas on x (B, T, D) fp32 with a unit inner stride; lengths (B,) int32 on the device or None; coeffs (order + 1,
+    2 * order * window + 1) fp32 on the device -> (B, T, D * (order + 1)) fp32, ktf_add_deltas_f32."""
+    B, T, D = x.shape
+    out = torch.empty((B, T, D * (order + 1)), dtype=torch.float32, device=x.device)
+    with L.on_device(x.device):
+        rc = L.load().ktf_add_deltas_f32(L.ptr(x), B, T, D, x.stride(0) if B > 1 else T * max(x.stride(1), D),
+                                         x.stride(1) if T > 1 else D, L.ptr(lengths), L.ptr(coeffs), int(order), int(window), L.ptr(out),
+                                         L.stream_ptr())
+    L.check(rc, "ktf_add_deltas_f32")
+    return out
+
+
 # ----------------------------------------------------------------------------- back-end training (ktf_train_*, ktf_plda_em_project)
 def train_workspace(rows, D, device):
     """A uint8 device buffer for ktf_train_mean_* / ktf_train_gram_* over up to `rows` rows of dimension D."""

@@ -2,8 +2,11 @@
 each i-vector dim S given; per stage (posteriors = ktf_ivector_post_f32; extract = ktf_ivector_extract: stats, linear and quadratic
 terms, solve) and end to end as i-vectors/s, batch-1 latency, and the host NumPy restatement (tests/_ivector_ref.py) on a few
 utterances for scale. The model is random (built on the device: no files). Prints one JSON line per S.
+--full-ubm adds a random SPD full-covariance UBM (the diagonal one is its toDiag()): the recipe's posterior stage, timed as the
+preselection (ktf_ivector_post_f32 with min_post 0), the new stage (ktf_fgmm_post_f32) and the whole call, next to the diagonal
+posterior stage on the same frames.
 
-    python tools/ivector_time.py [--B 1024] [--T 1000] [--I 2048] [--D 60] [--S 400 600] [--reps 3]
+    python tools/ivector_time.py [--B 1024] [--T 1000] [--I 2048] [--D 60] [--S 400 600] [--reps 3] [--full-ubm]
 """
 
 import argparse
@@ -19,19 +22,35 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for p in (ROOT, os.path.join(ROOT, "kaldi-tflite_amd"), os.path.join(ROOT, "tests")):
     sys.path.insert(0, p)
 
+import _fgmm_ref as G                                           # noqa: E402
 import _ivector_ref as R                                        # noqa: E402
 import kaldi_tflite_amd as ktf                                  # noqa: E402
 from kaldi_tflite_amd import _lib as L, ops                    # noqa: E402
-from kaldi_tflite_amd.io import KaldiDiagGmmReader, KaldiIvecExtractorReader   # noqa: E402
+from kaldi_tflite_amd.io import KaldiDiagGmmReader, KaldiFullGmmReader, KaldiIvecExtractorReader   # noqa: E402
 
 
-def model(I, D, S, dev, seed=1):
+def full_model(I, D, seed=3):
+    """A random SPD full UBM (tests/_fgmm_ref.random_full_ubm) as a reader object, no file round trip."""
+    (w, mic, ic), _ = G.random_full_ubm(np.random.default_rng(seed), I, D)
+    full = KaldiFullGmmReader.__new__(KaldiFullGmmReader)
+    full.path, full.storedGconsts = "<random>", None
+    full.weights, full.means_invcovars, full.inv_covars = w, mic, ic
+    full.numGauss, full.featDim = I, D
+    full.gconsts = full.computeGconsts()
+    return full
+
+
+def model(I, D, S, dev, seed=1, full=None):
     """Reader objects filled directly (no file round trip): sigmaInvM and U derived on the device in fp64."""
     rng = np.random.default_rng(seed)
     (w, mi, iv), _ = R.random_models(rng, I, D, 2, full_sigma=False)
-    ubm = KaldiDiagGmmReader.__new__(KaldiDiagGmmReader)
-    ubm.weights, ubm.means_invvars, ubm.inv_vars, ubm.numGauss, ubm.featDim = w, mi, iv, I, D
-    ubm.gconsts = ubm.computeGconsts()
+    if full is not None:
+        ubm = full.toDiag()
+        mi, iv = ubm.means_invvars, ubm.inv_vars
+    else:
+        ubm = KaldiDiagGmmReader.__new__(KaldiDiagGmmReader)
+        ubm.weights, ubm.means_invvars, ubm.inv_vars, ubm.numGauss, ubm.featDim = w, mi, iv, I, D
+        ubm.gconsts = ubm.computeGconsts()
     g = torch.Generator(device=dev).manual_seed(seed)
     M = torch.randn((I, D, S), generator=g, device=dev, dtype=torch.float64) * 0.3
     M[:, :, 0] = torch.as_tensor(mi / iv, device=dev, dtype=torch.float64) / 100.0
@@ -69,22 +88,33 @@ def main():
     ap.add_argument("--S", type=int, nargs="+", default=[400, 600])
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--host-utts", type=int, default=2)
+    ap.add_argument("--full-ubm", action="store_true")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     torch.cuda.set_device(dev)
     L.load()
+    full = full_model(a.I, a.D) if a.full_ubm else None
     for S in a.S:
-        ie, ubm = model(a.I, a.D, S, dev)
-        layer = ktf.layers.IvectorExtractor(ie, ubm)
+        ie, ubm = model(a.I, a.D, S, dev, full=full)
+        layer = ktf.layers.IvectorExtractor(ie, ubm, full_ubm=full)
         rng = np.random.default_rng(2)
         mean = ubm.means_invvars / ubm.inv_vars
         comp = rng.integers(0, a.I, (a.B, a.T))
         x = torch.as_tensor((mean[comp] + rng.standard_normal((a.B, a.T, a.D)) / np.sqrt(ubm.inv_vars[comp])).astype(np.float32),
                             device=dev)
-        W, gc, sim, U = layer._consts(dev)
+        W, gc, sim, U, fullc = layer._consts(dev)
         flat = x.reshape(-1, a.D)
         layer(x[:2])                                                            # warm-up (LDS attributes, allocator)
         t_post, (g, p) = timed(lambda: ops.ivector_post(flat, W, gc, layer.numGselect, layer.minPost), a.reps)
+        extra = {}
+        if full is not None:                                                    # the recipe's stage, on the same frames
+            mic, icov, fgc = fullc
+            t_sel, (sel, _) = timed(lambda: ops.ivector_post(flat, W, gc, layer.numGselect, 0.0), a.reps)
+            t_full, (g, p) = timed(lambda: ops.fgmm_post(flat, sel, mic, icov, fgc, layer.minPost), a.reps)
+            extra = {"preselect_ms": round(t_sel * 1e3, 3), "fgmm_post_ms": round(t_full * 1e3, 3),
+                     "fgmm_over_diag_post": round(t_full / t_post, 3), "frame_chunks": -(-flat.shape[0] // layer._frameStep),
+                     "kept_per_frame": round(float((g >= 0).sum().item()) / flat.shape[0], 2)}
+            del mic, icov, fgc, sel
         off = np.arange(a.B + 1) * a.T
         t_ext, iv = timed(lambda: layer._extract(flat, off, lambda lo, hi: (g[lo:hi], p[lo:hi]), torch.float32), a.reps)
         t_all, _ = timed(lambda: layer(x), a.reps)
@@ -104,8 +134,8 @@ def main():
             "B": a.B, "T": a.T, "I": a.I, "D": a.D, "S": S, "chunks": len(layer._chunks(a.B)),
             "posteriors_ms": round(t_post * 1e3, 3), "extract_ms": round(t_ext * 1e3, 3), "call_ms": round(t_all * 1e3, 3),
             "ivectors_per_s": round(a.B / t_all, 1), "batch1_ms": round(t_b1 * 1e3, 3),
-            "host_numpy_s_per_utt": round(t_host, 3), "finite": bool(torch.isfinite(iv).all().item())}), flush=True)
-        del layer, x, flat, g, p, iv, W, gc, sim, U
+            "host_numpy_s_per_utt": round(t_host, 3), "finite": bool(torch.isfinite(iv).all().item()), **extra}), flush=True)
+        del layer, x, flat, g, p, iv, W, gc, sim, U, fullc
         torch.cuda.empty_cache()
 
 
