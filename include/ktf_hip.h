@@ -659,6 +659,35 @@ int ktf_ivector_extract(const float* x, int64_t F, int32_t D, int64_t ldx, const
                         const float* post, int32_t n, float posterior_scale, float acoustic_weight, float max_count,
                         const double* sigma_inv_M, const double* U, int32_t I, int32_t S, double prior_offset, void* ivectors,
                         int32_t out_dtype_bytes, void* workspace, size_t workspace_bytes, void* stream);
+/* ------------------------------------------------------------------ i-vector extractor training statistics
+ * Kaldi's `ivector-extractor-acc-stats` (IvectorExtractorStats::AccStatsForUtterance, update_variances, no ivector-dependent
+ * weights) for the B utterances of a call, added in place to fp64 device accumulators. Inputs as ktf_ivector_extract (there is no
+ * acoustic_weight and no max_count). Per utterance with at least one frame: p' = fp32(p * posterior_scale); gamma_u, F_u;
+ * lin = sum_i sigma_inv_M_i^T F_ui + prior_offset e0; Q = I + sum_i gamma_ui U_i = L L^T; C_u = Q^-1; w_u = C_u lin (the offset is
+ * NOT subtracted); W_u = C_u + w_u w_u^T. Then
+ *   gamma (I) += gamma_u;  Y (I * D, S) += F_u w_u^T;  R (I, P) += gamma_u W_u (packed lower triangles, P = S(S+1)/2);
+ *   ivector_sum (S) += w_u;  ivector_scatter (P) += W_u;  totals[0] += 1;
+ *   totals[1] += lin^T w_u / 2 - sum_j log L_jj - prior_offset^2 / 2   (the utterance's term of the marginal log-likelihood).
+ * An utterance with no frames adds nothing and is not counted. The sums over the utterances of a call run in ascending utterance
+ * order inside every element (ktf_atb_f64), so the same sequence of calls gives the same bits. workspace: 256-byte aligned, at
+ * least ktf_ivector_train_workspace_bytes(B, I, D, S) bytes: the extraction workspace plus (B, P + S + 2) fp64. */
+int64_t ktf_ivector_train_workspace_bytes(int32_t B, int32_t I, int32_t D, int32_t S);
+int ktf_ivector_acc_stats(const float* x, int64_t F, int32_t D, int64_t ldx, const int32_t* offsets, int32_t B, const int32_t* gauss,
+                          const float* post, int32_t n, float posterior_scale, const double* sigma_inv_M, const double* U, int32_t I,
+                          int32_t S, double prior_offset, double* gamma, double* Y, double* R, double* ivector_sum,
+                          double* ivector_scatter, double* totals, void* workspace, size_t workspace_bytes, void* stream);
+/* Second-order statistics: Ssec (I, D, D) fp64 += sum over the frames t and slots of x with gauss = i of p' x_t x_t^T. The (frame,
+ * slot) pairs are bucketed by Gaussian with a stable counting sort and every bucket is summed row after row in ascending pair
+ * order: bit-identical run to run, each Ssec_i symmetric bit for bit. F * n < 2^31. workspace: 256-byte aligned, at least
+ * ktf_ivector_acc2_workspace_bytes(F, I, n) bytes. */
+int64_t ktf_ivector_acc2_workspace_bytes(int64_t F, int32_t I, int32_t n);
+int ktf_ivector_acc_second_order(const float* x, int64_t F, int32_t D, int64_t ldx, const int32_t* gauss, const float* post, int32_t n,
+                                 float posterior_scale, int32_t I, double* Ssec, void* workspace, size_t workspace_bytes, void* stream);
+/* C (M x N, ldc) += A^T B in fp64 on v_mfma_f64_16x16x4_f64: A (K x M, lda) and B (K x N, ldb) row-major device arrays. Every
+ * element is C + its K terms in ascending k (four per MFMA); no atomics, no split of K: the bits depend on the operands alone.
+ * 1 <= M <= 2^22, 1 <= N <= 2^21; K = 0 leaves C as it is. */
+int ktf_atb_f64(const double* A, int64_t lda, const double* B, int64_t ldb, double* C, int64_t ldc, int64_t M, int64_t N, int64_t K,
+                void* stream);
 /* gmm-gselect --n | fgmm-global-gselect-to-post --min-post (FullGmm::LogLikelihoodsPreselect, then the pruning loop of
  * fgmm-global-gselect-to-post.cc), the posterior stage of every sid/extract_ivectors.sh. The preselection is the diagonal call
  * above with min_post = 0: its gauss output is gmm-gselect's set (its post output is not used). Here, per frame t:

@@ -1,0 +1,527 @@
+// i-vector extractor training statistics: Kaldi's `ivector-extractor-acc-stats` (IvectorExtractorStats::AccStatsForUtterance with
+// update_variances, no ivector-dependent weights), batched over the utterances of one call and accumulated in place into fp64 device
+// totals. Stages (b) - (d) of the extraction (ivector_stages.h) leave gamma, F, the linear term and the Cholesky factor L of
+// Q = I + sum_i gamma_i U_i in the workspace; from there
+//
+//   ivcov_kernel     per utterance (one workgroup): sum_j log L_jj, X = L^-1 in place (blocked, 32 x 32 tiles in LDS), z = X lin',
+//                    w = X^T z (the posterior mean, the prior offset kept), W = X^T X + w w^T as a packed lower triangle, and the
+//                    scalar lin'^T w / 2 - sum_j log L_jj - offset^2 / 2 of the marginal likelihood. An utterance with no frames
+//                    gets zeros and the flag 0.
+//   atb_kernel       C += A^T B in fp64 on v_mfma_f64_16x16x4_f64: A (K x M) and B (K x N) row-major, K = the utterances of the
+//                    chunk, ascending inside every output element; no atomics, no split of K. One kernel for R (A = gamma,
+//                    B = W), Y (A = F, B = w), gamma, the prior's sum and scatter and the two scalar totals (A = the flags).
+//   sec_*_kernel     second-order statistics Ssec_i += sum_t p'_ti x_t x_t^T: the (frame, slot) pairs are bucketed by Gaussian with
+//                    a STABLE counting sort (integer histograms per chunk of pairs, exclusive scans, then one wave per chunk that
+//                    ranks equal Gaussians by lane order), so a bucket lists its pairs in ascending pair id and its fp64 sum, taken
+//                    row after row, has the same bits on every run.
+#include "ivector_stages.h"
+
+namespace {
+
+typedef double f64x4 __attribute__((ext_vector_type(4)));
+
+constexpr int COV_THREADS = 256;
+constexpr int ATB_MT = 2;           // 16-row MFMA tiles per wave
+constexpr int ATB_NT = 4;           // 16-column MFMA tiles per wave
+constexpr int ATB_WAVES = 4;        // waves per workgroup, stacked along M: a workgroup owns 128 x 64 of C
+constexpr int SEC_CH = 8192;        // pairs per bucketing chunk (one wave scatters a chunk in pair order)
+constexpr int SEC_RB = 16;          // bucket rows staged in LDS per step
+
+struct TrLayout {
+    int64_t ext, scat, w, tail, total;
+};
+
+TrLayout tr_layout(int64_t B, int64_t I, int64_t D, int64_t S) {
+    TrLayout t;
+    const int64_t P = S * (S + 1) / 2;
+    t.ext = 0;
+    int64_t at = iv_layout(B, I, D, S).total;
+    t.scat = at; at += al256(B * P * 8);
+    t.w = at;    at += al256(B * S * 8);
+    t.tail = at; at += al256(B * 2 * 8);
+    t.total = at;
+    return t;
+}
+
+// fixed tree over the workgroup's 256 partial sums
+__device__ __forceinline__ double block_sum(double v, double* red, int tid) {
+    red[tid] = v;
+    __syncthreads();
+    for (int s = COV_THREADS / 2; s > 0; s >>= 1) {
+        if (tid < s) red[tid] += red[tid + s];
+        __syncthreads();
+    }
+    const double r = red[0];
+    __syncthreads();
+    return r;
+}
+
+// Lws (B, S, S): on entry the Cholesky factor (lower triangle, the rest undefined), on exit its inverse X (lower triangle).
+// scat (B, P), wv (B, S), tail (B, 2) = (1 if the utterance has frames, the marginal-likelihood scalar).
+__global__ void __launch_bounds__(COV_THREADS) ivcov_kernel(const double* __restrict__ lin, const int* __restrict__ off, int64_t F, int S,
+                                                             double prior_offset, double* __restrict__ Lws, double* __restrict__ scat,
+                                                             double* __restrict__ wv, double* __restrict__ tail) {
+    __shared__ double Dinv[NB][NB + 1];
+    __shared__ double Ta[NB][NB + 1];
+    __shared__ double Tb[NB][NB + 1];
+    __shared__ double y[1024];
+    __shared__ double z[1024];
+    __shared__ double red[COV_THREADS];
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int64_t P = (int64_t)S * (S + 1) / 2;
+    double* sc = scat + (int64_t)b * P;
+    int64_t t0, t1;
+    utt_rows(off, b, F, &t0, &t1);
+    if (t1 == t0) {                              // no frames: contributes nothing and is not counted
+        for (int64_t e = tid; e < P; e += COV_THREADS) sc[e] = 0.0;
+        for (int i = tid; i < S; i += COV_THREADS) wv[(int64_t)b * S + i] = 0.0;
+        if (tid == 0) tail[2 * b] = tail[2 * b + 1] = 0.0;
+        return;
+    }
+    double* L = Lws + (int64_t)b * S * S;
+    double ld = 0.0;
+    for (int j = tid; j < S; j += COV_THREADS) ld += log(L[(int64_t)j * S + j]);
+    for (int i = tid; i < S; i += COV_THREADS) y[i] = lin[(int64_t)b * S + i] + (i == 0 ? prior_offset : 0.0);
+    const double logdet = block_sum(ld, red, tid);
+    const int nt = (S + NB - 1) / NB;
+    // X = L^-1 in place, block row by block row: X_ii = L_ii^-1, X_ij = -X_ii sum_{j <= k < i} L_ik X_kj (column blocks ascending:
+    // block (i, j) of L is last read by column block j)
+    for (int bi = 0; bi < nt; ++bi) {
+        const int i0 = bi * NB, nb = S - i0 < NB ? S - i0 : NB;
+        for (int e = tid; e < NB * NB; e += COV_THREADS) {
+            const int r = e / NB, c = e - r * NB;
+            Ta[r][c] = (r < nb && c <= r) ? L[(int64_t)(i0 + r) * S + i0 + c] : (r == c ? 1.0 : 0.0);   // identity past nb
+        }
+        __syncthreads();
+        if (tid < NB) {                          // column tid of the diagonal block's inverse by forward substitution
+            const int c = tid;
+            for (int r = 0; r < NB; ++r) {
+                double v = 0.0;
+                if (r >= c) {
+                    double s = r == c ? 1.0 : 0.0;
+                    for (int k = c; k < r; ++k) s = fma(-Ta[r][k], Dinv[k][c], s);
+                    v = s / Ta[r][r];
+                }
+                Dinv[r][c] = v;
+            }
+        }
+        __syncthreads();
+        for (int bj = 0; bj < bi; ++bj) {
+            const int j0 = bj * NB;
+            double acc[NB * NB / COV_THREADS] = {};
+            for (int bk = bj; bk < bi; ++bk) {
+                const int k0 = bk * NB;
+                for (int e = tid; e < NB * NB; e += COV_THREADS) {
+                    const int r = e / NB, c = e - r * NB;
+                    Ta[r][c] = r < nb ? L[(int64_t)(i0 + r) * S + k0 + c] : 0.0;
+                    Tb[r][c] = (bk > bj || c <= r) ? L[(int64_t)(k0 + r) * S + j0 + c] : 0.0;             // X_kj, lower on its diagonal
+                }
+                __syncthreads();
+#pragma unroll
+                for (int q = 0; q < NB * NB / COV_THREADS; ++q) {
+                    const int e = tid + COV_THREADS * q, r = e / NB, c = e - r * NB;
+                    double s = acc[q];
+#pragma unroll
+                    for (int k = 0; k < NB; ++k) s = fma(Ta[r][k], Tb[k][c], s);
+                    acc[q] = s;
+                }
+                __syncthreads();
+            }
+#pragma unroll
+            for (int q = 0; q < NB * NB / COV_THREADS; ++q) {
+                const int e = tid + COV_THREADS * q, r = e / NB, c = e - r * NB;
+                Ta[r][c] = acc[q];
+            }
+            __syncthreads();
+#pragma unroll
+            for (int q = 0; q < NB * NB / COV_THREADS; ++q) {
+                const int e = tid + COV_THREADS * q, r = e / NB, c = e - r * NB;
+                double s = 0.0;
+                for (int k = 0; k <= r; ++k) s = fma(Dinv[r][k], Ta[k][c], s);
+                if (r < nb) L[(int64_t)(i0 + r) * S + j0 + c] = -s;
+            }
+            __syncthreads();
+        }
+        for (int e = tid; e < NB * NB; e += COV_THREADS) {
+            const int r = e / NB, c = e - r * NB;
+            if (r < nb && c <= r) L[(int64_t)(i0 + r) * S + i0 + c] = Dinv[r][c];
+        }
+        __syncthreads();
+    }
+    // z = X lin' (a wave per row), w = X^T z (a thread per column, rows ascending)
+    for (int i = wave; i < S; i += COV_THREADS / 64) {
+        double s = 0.0;
+        for (int k = lane; k <= i; k += 64) s = fma(L[(int64_t)i * S + k], y[k], s);
+        s = wave_sum_d(s);
+        if (lane == 0) z[i] = s;
+    }
+    __syncthreads();
+    double qd = 0.0;
+    for (int j = tid; j < S; j += COV_THREADS) {
+        double s = 0.0;
+        for (int k = j; k < S; ++k) s = fma(L[(int64_t)k * S + j], z[k], s);
+        y[j] = s;
+        wv[(int64_t)b * S + j] = s;
+        qd = fma(z[j], z[j], qd);
+    }
+    const double quad = block_sum(qd, red, tid);             // (its barriers also publish y)
+    if (tid == 0) {
+        tail[2 * b] = 1.0;
+        tail[2 * b + 1] = 0.5 * quad - logdet - 0.5 * prior_offset * prior_offset;
+    }
+    // W = X^T X + w w^T, lower tiles: C_ij = sum_{k >= i} X_ki X_kj
+    for (int ti = 0; ti < nt; ++ti)
+        for (int tj = 0; tj <= ti; ++tj) {
+            const int i0 = ti * NB, j0 = tj * NB;
+            double acc[NB * NB / COV_THREADS] = {};
+            for (int bk = ti; bk < nt; ++bk) {
+                const int k0 = bk * NB;
+                for (int e = tid; e < NB * NB; e += COV_THREADS) {
+                    const int k = e / NB, c = e - k * NB;
+                    const bool row = k0 + k < S;
+                    Ta[k][c] = (row && i0 + c <= k0 + k) ? L[(int64_t)(k0 + k) * S + i0 + c] : 0.0;
+                    Tb[k][c] = (row && j0 + c <= k0 + k) ? L[(int64_t)(k0 + k) * S + j0 + c] : 0.0;
+                }
+                __syncthreads();
+#pragma unroll
+                for (int q = 0; q < NB * NB / COV_THREADS; ++q) {
+                    const int e = tid + COV_THREADS * q, r = e / NB, c = e - r * NB;
+                    double s = acc[q];
+#pragma unroll
+                    for (int k = 0; k < NB; ++k) s = fma(Ta[k][r], Tb[k][c], s);
+                    acc[q] = s;
+                }
+                __syncthreads();
+            }
+#pragma unroll
+            for (int q = 0; q < NB * NB / COV_THREADS; ++q) {
+                const int e = tid + COV_THREADS * q, r = e / NB, c = e - r * NB;
+                const int i = i0 + r, j = j0 + c;
+                if (i < S && j <= i) sc[(int64_t)i * (i + 1) / 2 + j] = acc[q] + y[i] * y[j];
+            }
+        }
+}
+
+// C (M x N, ldc) += A^T B: A (K x M, lda), B (K x N, ldb), all fp64 row-major. v_mfma_f64_16x16x4_f64: lane l holds A^T[row l & 15]
+// [k = l >> 4] and B[k = l >> 4][col l & 15]; result reg r of lane l is C[row (l >> 4) + 4 r][col l & 15]. The accumulators start
+// from C, and k runs upwards four at a time, so every element is C + its terms in ascending k whatever M, N or the grid.
+__global__ void __launch_bounds__(64 * ATB_WAVES) atb_kernel(const double* __restrict__ A, int64_t lda, const double* __restrict__ Bm,
+                                                              int64_t ldb, double* __restrict__ Cm, int64_t ldc, int64_t M, int64_t N,
+                                                              int64_t K) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int lc = lane & 15, lk = lane >> 4;
+    const int64_t m0 = ((int64_t)blockIdx.y * ATB_WAVES + wave) * (16 * ATB_MT);
+    const int64_t n0 = (int64_t)blockIdx.x * (16 * ATB_NT);
+    if (m0 >= M) return;
+    f64x4 acc[ATB_MT][ATB_NT];
+#pragma unroll
+    for (int i = 0; i < ATB_MT; ++i)
+#pragma unroll
+        for (int j = 0; j < ATB_NT; ++j)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int64_t row = m0 + 16 * i + lk + 4 * r, col = n0 + 16 * j + lc;
+                acc[i][j][r] = (row < M && col < N) ? Cm[row * ldc + col] : 0.0;
+            }
+    for (int64_t k0 = 0; k0 < K; k0 += 4) {
+        const int64_t k = k0 + lk;
+        double a[ATB_MT], bv[ATB_NT];
+#pragma unroll
+        for (int i = 0; i < ATB_MT; ++i) {
+            const int64_t m = m0 + 16 * i + lc;
+            a[i] = (k < K && m < M) ? A[k * lda + m] : 0.0;
+        }
+#pragma unroll
+        for (int j = 0; j < ATB_NT; ++j) {
+            const int64_t c = n0 + 16 * j + lc;
+            bv[j] = (k < K && c < N) ? Bm[k * ldb + c] : 0.0;
+        }
+#pragma unroll
+        for (int i = 0; i < ATB_MT; ++i)
+#pragma unroll
+            for (int j = 0; j < ATB_NT; ++j) acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[i], bv[j], acc[i][j], 0, 0, 0);
+    }
+#pragma unroll
+    for (int i = 0; i < ATB_MT; ++i)
+#pragma unroll
+        for (int j = 0; j < ATB_NT; ++j)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int64_t row = m0 + 16 * i + lk + 4 * r, col = n0 + 16 * j + lc;
+                if (row < M && col < N) Cm[row * ldc + col] = acc[i][j][r];
+            }
+}
+
+int atb(const char* who, const double* A, int64_t lda, const double* Bm, int64_t ldb, double* Cm, int64_t ldc, int64_t M, int64_t N,
+        int64_t K, hipStream_t st) {
+    hipLaunchKernelGGL(atb_kernel, dim3(ktf_cdiv(N, 16 * ATB_NT), ktf_cdiv(M, 16 * ATB_MT * ATB_WAVES)), dim3(64 * ATB_WAVES), 0, st, A, lda,
+                       Bm, ldb, Cm, ldc, M, N, K);
+    KTF_CHECK_LAUNCH(who);
+    return KTF_OK;
+}
+
+// ---------------------------------------------------------------- second-order statistics
+struct SecLayout {
+    int64_t counts, total, start, pairs, bytes;
+    int64_t nch;
+};
+
+SecLayout sec_layout(int64_t F, int64_t I, int64_t n) {
+    SecLayout l;
+    const int64_t np = F * n;
+    l.nch = (np + SEC_CH - 1) / SEC_CH;
+    int64_t at = 0;
+    l.counts = at; at += al256(l.nch * I * 4);
+    l.total = at;  at += al256(I * 4);
+    l.start = at;  at += al256((I + 1) * 4);
+    l.pairs = at;  at += al256(np * 4);
+    l.bytes = at;
+    return l;
+}
+
+// counts[chunk][g] = the chunk's pairs of Gaussian g (integer counts: the LDS atomics cannot change the result)
+__global__ void __launch_bounds__(256) sec_hist_kernel(const int* __restrict__ gauss, int64_t np, int I, int* __restrict__ counts) {
+    extern __shared__ int sec_lds[];
+    const int tid = threadIdx.x;
+    for (int g = tid; g < I; g += 256) sec_lds[g] = 0;
+    __syncthreads();
+    const int64_t e0 = (int64_t)blockIdx.x * SEC_CH;
+    for (int64_t e = e0 + tid; e < e0 + SEC_CH && e < np; e += 256) {
+        const int g = gauss[e];
+        if (g >= 0 && g < I) atomicAdd(&sec_lds[g], 1);
+    }
+    __syncthreads();
+    for (int g = tid; g < I; g += 256) counts[(int64_t)blockIdx.x * I + g] = sec_lds[g];
+}
+
+// counts[chunk][g] -> the pairs of g in earlier chunks; total[g]
+__global__ void sec_scan_kernel(int* __restrict__ counts, int64_t nch, int I, int* __restrict__ total) {
+    const int g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= I) return;
+    int run = 0;
+    for (int64_t c = 0; c < nch; ++c) {
+        const int v = counts[c * I + g];
+        counts[c * I + g] = run;
+        run += v;
+    }
+    total[g] = run;
+}
+
+// start[g] = sum of total[< g], start[I] = all pairs kept (one workgroup)
+__global__ void __launch_bounds__(256) sec_start_kernel(const int* __restrict__ total, int I, int* __restrict__ start) {
+    __shared__ int seg[256];
+    const int tid = threadIdx.x, per = (I + 255) / 256;
+    const int g0 = tid * per, g1 = g0 + per < I ? g0 + per : I;
+    int s = 0;
+    for (int g = g0; g < g1; ++g) s += total[g];
+    seg[tid] = s;
+    __syncthreads();
+    if (tid == 0) {
+        int run = 0;
+        for (int t = 0; t < 256; ++t) {
+            const int v = seg[t];
+            seg[t] = run;
+            run += v;
+        }
+        start[I] = run;
+    }
+    __syncthreads();
+    int run = seg[tid];
+    for (int g = g0; g < g1; ++g) {
+        start[g] = run;
+        run += total[g];
+    }
+}
+
+// one wave per chunk, 64 pairs per step in pair order: a pair's slot is its bucket's cursor + the number of lower lanes with the
+// same Gaussian, and the highest such lane moves the cursor on. Every slot index is < start[I] <= np by the counts above.
+__global__ void __launch_bounds__(64) sec_scatter_kernel(const int* __restrict__ gauss, int64_t np, int I, const int* __restrict__ counts,
+                                                          const int* __restrict__ start, int* __restrict__ pairs) {
+    extern __shared__ int sec_lds[];
+    const int lane = threadIdx.x;
+    for (int g = lane; g < I; g += 64) sec_lds[g] = start[g] + counts[(int64_t)blockIdx.x * I + g];
+    __syncthreads();
+    const int64_t e0 = (int64_t)blockIdx.x * SEC_CH;
+    for (int64_t eb = e0; eb < e0 + SEC_CH && eb < np; eb += 64) {
+        const int64_t e = eb + lane;
+        int g = e < np ? gauss[e] : -1;
+        if (g >= I) g = -1;
+        int rank = 0;
+        bool later = false;
+        for (int j = 0; j < 64; ++j) {
+            const int gj = __shfl(g, j);
+            if (gj == g) {
+                rank += j < lane;
+                later |= j > lane;
+            }
+        }
+        int pos = 0;
+        if (g >= 0) {
+            pos = sec_lds[g] + rank;
+            pairs[pos] = (int)e;
+        }
+        __syncthreads();
+        if (g >= 0 && !later) sec_lds[g] = pos + 1;
+        __syncthreads();
+    }
+}
+
+// Ssec[g] (D x D) += sum over the bucket's rows, in bucket order, of p' x x^T: one workgroup per Gaussian, thread (ty, tx) owns
+// elements (ty + 16 a, tx + 16 c). x_i x_j is exact in fp64 (fp32 inputs), so the result is symmetric bit for bit.
+__global__ void __launch_bounds__(256) sec_acc_kernel(const float* __restrict__ x, int D, int64_t ldx, const float* __restrict__ post, int n,
+                                                       float post_scale, const int* __restrict__ start, const int* __restrict__ pairs,
+                                                       double* __restrict__ Ssec) {
+    __shared__ double xs[SEC_RB][KTF_IVECTOR_MAX_FEAT_DIM];
+    __shared__ double wr[SEC_RB];
+    const int g = blockIdx.x, tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
+    const int r0 = start[g], r1 = start[g + 1];
+    if (r1 <= r0) return;
+    constexpr int NA = KTF_IVECTOR_MAX_FEAT_DIM / 16;
+    double acc[NA][NA];
+#pragma unroll
+    for (int a = 0; a < NA; ++a)
+#pragma unroll
+        for (int c = 0; c < NA; ++c) acc[a][c] = 0.0;
+    for (int rb = r0; rb < r1; rb += SEC_RB) {
+        const int nr = r1 - rb < SEC_RB ? r1 - rb : SEC_RB;
+        for (int e = tid; e < nr * D; e += 256) {
+            const int r = e / D, d = e - r * D;
+            const int p = pairs[rb + r];
+            xs[r][d] = (double)x[(int64_t)(p / n) * ldx + d];
+        }
+        if (tid < nr) wr[tid] = (double)(post[pairs[rb + tid]] * post_scale);
+        __syncthreads();
+        for (int r = 0; r < nr; ++r) {
+            const double w = wr[r];
+#pragma unroll
+            for (int a = 0; a < NA; ++a) {
+                if (16 * a >= D) break;
+                const int i = ty + 16 * a;
+                const double xi = i < D ? xs[r][i] : 0.0;
+#pragma unroll
+                for (int c = 0; c < NA; ++c) {
+                    if (16 * c >= D) break;
+                    const int j = tx + 16 * c;
+                    const double xj = j < D ? xs[r][j] : 0.0;
+                    acc[a][c] = fma(xi * xj, w, acc[a][c]);
+                }
+            }
+        }
+        __syncthreads();
+    }
+    double* out = Ssec + (int64_t)g * D * D;
+#pragma unroll
+    for (int a = 0; a < NA; ++a)
+#pragma unroll
+        for (int c = 0; c < NA; ++c) {
+            const int i = ty + 16 * a, j = tx + 16 * c;
+            if (i < D && j < D) out[(int64_t)i * D + j] += acc[a][c];
+        }
+}
+
+}  // namespace
+
+extern "C" int ktf_atb_f64(const double* A, int64_t lda, const double* B, int64_t ldb, double* C, int64_t ldc, int64_t M, int64_t N,
+                           int64_t K, void* stream) {
+    const char* who = "ktf_atb_f64";
+    KTF_REQUIRE(M >= 1 && N >= 1 && K >= 0, "%s: M %lld, N %lld, K %lld out of range", who, (long long)M, (long long)N, (long long)K);
+    KTF_REQUIRE(M <= ((int64_t)1 << 22) && N <= ((int64_t)1 << 21), "%s: M %lld > 2^22 or N %lld > 2^21", who, (long long)M, (long long)N);
+    KTF_REQUIRE(lda >= M && ldb >= N && ldc >= N, "%s: lda %lld < M, ldb %lld < N or ldc %lld < N", who, (long long)lda, (long long)ldb,
+                (long long)ldc);
+    KTF_REQUIRE(C && (K == 0 || (A && B)), "%s: null argument", who);
+    if (K == 0) return KTF_OK;
+    return atb(who, A, lda, B, ldb, C, ldc, M, N, K, (hipStream_t)stream);
+}
+
+extern "C" int64_t ktf_ivector_train_workspace_bytes(int32_t B, int32_t I, int32_t D, int32_t S) {
+    const int64_t ext = ktf_ivector_workspace_bytes(B, I, D, S);
+    if (ext < 0) return ext;
+    return tr_layout(B, I, D, S).total;
+}
+
+extern "C" int ktf_ivector_acc_stats(const float* x, int64_t F, int32_t D, int64_t ldx, const int32_t* offsets, int32_t B, const int32_t* gauss,
+                                     const float* post, int32_t n, float posterior_scale, const double* sigma_inv_M, const double* U, int32_t I,
+                                     int32_t S, double prior_offset, double* gamma, double* Y, double* R, double* ivector_sum,
+                                     double* ivector_scatter, double* totals, void* workspace, size_t workspace_bytes, void* stream) {
+    const char* who = "ktf_ivector_acc_stats";
+    const int64_t need = ktf_ivector_train_workspace_bytes(B, I, D, S);
+    if (need < 0) return (int)need;
+    KTF_REQUIRE(F >= 0 && F < ((int64_t)1 << 31), "%s: frame count %lld out of range", who, (long long)F);
+    KTF_REQUIRE(ldx >= D, "%s: ldx %lld < D %d", who, (long long)ldx, (int)D);
+    KTF_REQUIRE(n >= 1 && n <= KTF_IVECTOR_MAX_GSELECT, "%s: %d slots per frame outside 1 .. %d", who, (int)n, KTF_IVECTOR_MAX_GSELECT);
+    KTF_REQUIRE(posterior_scale >= 0.f, "%s: posterior_scale must be >= 0", who);
+    KTF_REQUIRE(offsets && sigma_inv_M && U && workspace, "%s: null argument", who);
+    KTF_REQUIRE(gamma && Y && R && ivector_sum && ivector_scatter && totals, "%s: null accumulator", who);
+    KTF_REQUIRE(F == 0 || (x && gauss && post), "%s: null frames / posteriors", who);
+    KTF_REQUIRE((int64_t)workspace_bytes >= need, "%s: workspace %zu bytes < %lld", who, workspace_bytes, (long long)need);
+    KTF_REQUIRE(((uintptr_t)workspace & 255) == 0, "%s: workspace not 256-byte aligned", who);
+    hipStream_t st = (hipStream_t)stream;
+    char* ws = (char*)workspace;
+    const IvLayout l = iv_layout(B, I, D, S);
+    const TrLayout t = tr_layout(B, I, D, S);
+    double* scat = (double*)(ws + t.scat);
+    double* wv = (double*)(ws + t.w);
+    double* tail = (double*)(ws + t.tail);
+    int rc = iv_run_stages(who, x, F, (int)D, ldx, offsets, (int)B, gauss, post, (int)n, posterior_scale, 1.f, 0.f, sigma_inv_M, U, (int)I,
+                           (int)S, prior_offset, wv, 8, ws, st);
+    if (rc != KTF_OK) return rc;
+    hipLaunchKernelGGL(ivcov_kernel, dim3(B), dim3(COV_THREADS), 0, st, (const double*)(ws + l.lin), offsets, F, (int)S, prior_offset,
+                       (double*)(ws + l.L), scat, wv, tail);
+    KTF_CHECK_LAUNCH(who);
+    const int64_t P = (int64_t)S * (S + 1) / 2, ID = (int64_t)I * D;
+    const double* gam = (const double*)(ws + l.gamma);
+    const double* Fst = (const double*)(ws + l.F);
+    if ((rc = atb(who, gam, I, scat, P, R, P, I, P, B, st)) != KTF_OK) return rc;                 // R_i += gamma_ui W_u
+    if ((rc = atb(who, Fst, ID, wv, S, Y, S, ID, S, B, st)) != KTF_OK) return rc;                 // Y_i += F_ui w_u^T
+    if ((rc = atb(who, gam, I, tail, 2, gamma, 1, I, 1, B, st)) != KTF_OK) return rc;             // gamma += gamma_u (counted utterances)
+    if ((rc = atb(who, tail, 2, wv, S, ivector_sum, S, 1, S, B, st)) != KTF_OK) return rc;
+    if ((rc = atb(who, tail, 2, scat, P, ivector_scatter, P, 1, P, B, st)) != KTF_OK) return rc;
+    return atb(who, tail, 2, tail, 2, totals, 2, 1, 2, B, st);                                    // (num_ivectors, sum of the scalars)
+}
+
+extern "C" int64_t ktf_ivector_acc2_workspace_bytes(int64_t F, int32_t I, int32_t n) {
+    const char* who = "ktf_ivector_acc2_workspace_bytes";
+    KTF_REQUIRE(I >= 1 && I <= KTF_IVECTOR_MAX_GAUSS, "%s: %d Gaussians outside 1 .. %d", who, (int)I, KTF_IVECTOR_MAX_GAUSS);
+    KTF_REQUIRE(n >= 1 && n <= KTF_IVECTOR_MAX_GSELECT, "%s: %d slots per frame outside 1 .. %d", who, (int)n, KTF_IVECTOR_MAX_GSELECT);
+    KTF_REQUIRE(F >= 0 && F * n < ((int64_t)1 << 31), "%s: F * n = %lld outside 0 .. 2^31 - 1", who, (long long)(F * n));
+    return sec_layout(F > 0 ? F : 1, I, n).bytes;
+}
+
+extern "C" int ktf_ivector_acc_second_order(const float* x, int64_t F, int32_t D, int64_t ldx, const int32_t* gauss, const float* post,
+                                            int32_t n, float posterior_scale, int32_t I, double* Ssec, void* workspace,
+                                            size_t workspace_bytes, void* stream) {
+    const char* who = "ktf_ivector_acc_second_order";
+    KTF_REQUIRE(F >= 0 && F < ((int64_t)1 << 31), "%s: frame count %lld out of range", who, (long long)F);
+    const int64_t need = ktf_ivector_acc2_workspace_bytes(F, I, n);
+    if (need < 0) return (int)need;
+    KTF_REQUIRE(D >= 1 && D <= KTF_IVECTOR_MAX_FEAT_DIM, "%s: feature dim %d outside 1 .. %d", who, (int)D, KTF_IVECTOR_MAX_FEAT_DIM);
+    KTF_REQUIRE(ldx >= D, "%s: ldx %lld < D %d", who, (long long)ldx, (int)D);
+    KTF_REQUIRE(posterior_scale >= 0.f, "%s: posterior_scale must be >= 0", who);
+    KTF_REQUIRE(Ssec && workspace, "%s: null argument", who);
+    KTF_REQUIRE(F == 0 || (x && gauss && post), "%s: null frames / posteriors", who);
+    KTF_REQUIRE((int64_t)workspace_bytes >= need, "%s: workspace %zu bytes < %lld", who, workspace_bytes, (long long)need);
+    KTF_REQUIRE(((uintptr_t)workspace & 255) == 0, "%s: workspace not 256-byte aligned", who);
+    if (F == 0) return KTF_OK;
+    hipStream_t st = (hipStream_t)stream;
+    char* ws = (char*)workspace;
+    const SecLayout l = sec_layout(F, I, n);
+    const int64_t np = F * n;
+    int* counts = (int*)(ws + l.counts);
+    int* total = (int*)(ws + l.total);
+    int* start = (int*)(ws + l.start);
+    int* pairs = (int*)(ws + l.pairs);
+    const size_t lds = (size_t)I * sizeof(int);
+    hipLaunchKernelGGL(sec_hist_kernel, dim3((unsigned)l.nch), dim3(256), lds, st, gauss, np, (int)I, counts);
+    KTF_CHECK_LAUNCH(who);
+    hipLaunchKernelGGL(sec_scan_kernel, dim3(ktf_cdiv(I, 256)), dim3(256), 0, st, counts, l.nch, (int)I, total);
+    KTF_CHECK_LAUNCH(who);
+    hipLaunchKernelGGL(sec_start_kernel, dim3(1), dim3(256), 0, st, (const int*)total, (int)I, start);
+    KTF_CHECK_LAUNCH(who);
+    hipLaunchKernelGGL(sec_scatter_kernel, dim3((unsigned)l.nch), dim3(64), lds, st, gauss, np, (int)I, (const int*)counts, (const int*)start,
+                       pairs);
+    KTF_CHECK_LAUNCH(who);
+    hipLaunchKernelGGL(sec_acc_kernel, dim3(I), dim3(256), 0, st, x, (int)D, ldx, post, (int)n, posterior_scale, (const int*)start,
+                       (const int*)pairs, Ssec);
+    KTF_CHECK_LAUNCH(who);
+    return KTF_OK;
+}

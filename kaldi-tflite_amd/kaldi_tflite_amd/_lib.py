@@ -162,6 +162,12 @@ PROTOTYPES = {
     "ktf_ivector_workspace_bytes": (_i64, [_i32, _i32, _i32, _i32]),
     "ktf_ivector_extract": (C.c_int, [_P, _i64, _i32, _i64, _P, _i32, _P, _P, _i32, _f32, _f32, _f32, _P, _P, _i32, _i32, C.c_double,
                                       _P, _i32, _P, C.c_size_t, _P]),
+    "ktf_ivector_train_workspace_bytes": (_i64, [_i32, _i32, _i32, _i32]),
+    "ktf_ivector_acc_stats": (C.c_int, [_P, _i64, _i32, _i64, _P, _i32, _P, _P, _i32, _f32, _P, _P, _i32, _i32, C.c_double, _P, _P, _P, _P,
+                                        _P, _P, _P, C.c_size_t, _P]),
+    "ktf_ivector_acc2_workspace_bytes": (_i64, [_i64, _i32, _i32]),
+    "ktf_ivector_acc_second_order": (C.c_int, [_P, _i64, _i32, _i64, _P, _P, _i32, _f32, _i32, _P, _P, C.c_size_t, _P]),
+    "ktf_atb_f64": (C.c_int, [_P, _i64, _P, _i64, _P, _i64, _i64, _i64, _i64, _P]),
     "ktf_fgmm_workspace_bytes": (_i64, [_i64, _i32, _i32, _i32]),
     "ktf_fgmm_post_f32": (C.c_int, [_P, _i64, _i32, _i64, _P, _i32, _P, _P, _P, _i32, _f32, _P, _P, _P, C.c_size_t, _P]),
     "ktf_add_deltas_f32": (C.c_int, [_P, _i64, _i64, _i32, _i64, _i64, _P, _P, _i32, _i32, _P, _P]),

@@ -529,3 +529,55 @@ def WriteKaldiPlda(path, mean, transform, psi, binary=True):
     with open(path, "wb") as f:
         f.write((b"\0B" if binary else b"") + b"<Plda> " + _array_bytes(mean, binary) + _array_bytes(transform, binary)
                 + _array_bytes(psi, binary) + b"</Plda> ")
+
+
+class IvecExtractorModel(KaldiIvecExtractorReader):
+    """An i-vector extractor held in memory (training.ivector_extractor_init / ivector_extractor_est), usable wherever a
+    KaldiIvecExtractorReader is: M (I, D, S), sigmaInv (I, D, D) full symmetric, priorOffset, wVec (I; default: the log of uniform
+    weights), w (default: empty, no ivector-dependent weights), all fp64; sigmaInvM and U are derived as the reader derives them."""
+
+    def __init__(self, M, sigmaInv, priorOffset, wVec=None, w=None):
+        M = np.ascontiguousarray(M, dtype=np.float64)
+        sig = np.ascontiguousarray(sigmaInv, dtype=np.float64)
+        if M.ndim != 3 or sig.shape != (M.shape[0], M.shape[1], M.shape[1]) or M.shape[0] < 1:
+            raise ValueError(f"inconsistent extractor shapes: M {M.shape}, sigmaInv {sig.shape}")
+        self.path, self.binary = None, True
+        self.numGauss = int(M.shape[0])
+        self.M, self.sigmaInv = list(M), list(sig)
+        self.priorOffset = float(priorOffset)
+        self.wVec = np.full(self.numGauss, -np.log(self.numGauss)) if wVec is None else np.asarray(wVec, np.float64)
+        self.w = np.zeros((0, 0), np.float64) if w is None else np.asarray(w, np.float64)
+        if self.wVec.shape != (self.numGauss,):
+            raise ValueError(f"wVec must hold {self.numGauss} values, got {self.wVec.shape}")
+        self.deriveVars()
+
+
+def _packed_bytes(a):
+    """One symmetric fp64 matrix as Kaldi's SpMatrix<double>: "DP ", 0x04 + int32 rows, the lower triangle row by row."""
+    a = np.asarray(a, np.float64)
+    n = a.shape[0]
+    if a.shape != (n, n):
+        raise ValueError(f"expected a square matrix, got {a.shape}")
+    return b"DP " + b"\x04" + _I32.pack(n) + np.ascontiguousarray(a[np.tril_indices(n)], dtype="<f8").tobytes()
+
+
+def WriteKaldiIvecExtractor(path, extractor, binary=True):
+    """Kaldi's IvectorExtractor::Write, binary mode: "\\0B<IvectorExtractor> <w> " DM "<w_vec> " DV "<M> " int32 I, I x DM,
+    "<SigmaInv> " I x DP (packed fp64 lower triangles) "<IvectorOffset> " double "</IvectorExtractor> ". `extractor`: a
+    KaldiIvecExtractorReader or IvecExtractorModel. Everything is written as fp64; text mode is not implemented."""
+    if not binary:
+        raise NotImplementedError("WriteKaldiIvecExtractor writes Kaldi's binary mode only")
+    e = extractor
+    I = int(e.numGauss)
+    if len(e.M) != I or len(e.sigmaInv) != I:
+        raise ValueError("inconsistent extractor: numGauss does not match M / sigmaInv")
+    w = np.asarray(e.w, np.float64)
+    w = w if w.ndim == 2 else np.zeros((0, 0), np.float64)
+    out = [b"\0B<IvectorExtractor> <w> ", _array_bytes(w, True), b"<w_vec> ", _array_bytes(np.asarray(e.wVec, np.float64).reshape(-1), True),
+           b"<M> \x04", _I32.pack(I)]
+    out += [_array_bytes(np.asarray(m, np.float64), True) for m in e.M]
+    out.append(b"<SigmaInv> ")
+    out += [_packed_bytes(s) for s in e.sigmaInv]
+    out += [b"<IvectorOffset> \x08", struct.pack("<d", float(e.priorOffset)), b"</IvectorExtractor> "]
+    with open(path, "wb") as f:
+        f.write(b"".join(out))

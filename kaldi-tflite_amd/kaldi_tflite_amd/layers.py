@@ -1584,6 +1584,52 @@ class IvectorExtractor(Layer):
                                                  self.priorOffset, dtype)
         return out
 
+    def _train_chunks(self, B):
+        per = ops.ivector_train_workspace_bytes(1, self.numGauss, self.featDim, self.ivecDim)
+        step = int(max(1, min(B, 65535, self.workspaceLimit // max(per, 1))))
+        return [(b, min(B, b + step)) for b in range(0, B, step)]
+
+    def _accumulate(self, stats, x, off, posts):
+        if self.acousticWeight != 1.0 or self.maxCount != 0.0:
+            raise ValueError("ivector-extractor-acc-stats has no acoustic_weight and no max_count: the layer must keep their defaults")
+        if tuple(stats.shape) != (self.numGauss, self.featDim, self.ivecDim):
+            raise ValueError(f"statistics of shape {tuple(stats.shape)} do not match the extractor "
+                             f"{(self.numGauss, self.featDim, self.ivecDim)}")
+        stats._alloc(x.device)
+        B = len(off) - 1
+        _, _, sim, U, _ = self._consts(x.device)
+        chunks = self._train_chunks(B)
+        with L.on_device(x.device):
+            for b0, b1 in chunks:
+                lo, hi = int(off[b0]), int(off[b1])
+                g, p = posts(lo, hi)
+                o = torch.as_tensor((off[b0:b1 + 1] - lo).astype(np.int32), device=x.device)
+                ops.ivector_acc_stats(x[lo:hi], o, g, p, self.posteriorScale, sim, U, self.priorOffset, stats.gamma, stats.Y, stats.R,
+                                      stats.ivector_sum, stats.ivector_scatter, stats.totals)
+                if stats.updateVariances:
+                    ops.ivector_acc_second_order(x[lo:hi], g, p, self.posteriorScale, stats.Ssec)
+        return len(chunks)
+
+    def accumulate(self, stats, feats, lengths=None, mask=None):
+        """Extension: ivector-extractor-acc-stats on the batch `__call__` would extract from, posterior stage included (with or
+        without full_ubm), added to `stats` (training.IvectorStats) in place. The utterances run in chunks whose workspace stays
+        under workspace_limit; for the same sequence of calls and the same limit every accumulator is bit-identical run to run.
+        ValueError if the layer's acoustic_weight != 1 or max_count != 0, or if stats was made for another extractor shape.
+        -> the number of chunks."""
+        x, off = self._frames(feats, lengths, mask)
+        return self._accumulate(stats, x, off, lambda lo, hi: self._post(x[lo:hi]))
+
+    def accumulate_from_posteriors(self, stats, feats, gauss, post, lengths=None, mask=None):
+        """`accumulate` on posteriors the caller supplies, laid out as `from_posteriors` takes them."""
+        x, off = self._frames(feats, lengths, mask)
+        if gauss.shape != post.shape or gauss.dim() != 2 or gauss.shape[0] != x.shape[0]:
+            raise ValueError(f"gauss / post must both be ({x.shape[0]}, n), got {tuple(gauss.shape)} / {tuple(post.shape)}")
+        if not 1 <= gauss.shape[1] <= L.IVECTOR_MAX_GSELECT:
+            raise ValueError(f"{gauss.shape[1]} slots per frame outside 1 .. {L.IVECTOR_MAX_GSELECT}")
+        g = gauss.to(device=x.device, dtype=torch.int32).contiguous()
+        p = post.to(device=x.device, dtype=torch.float32).contiguous()
+        return self._accumulate(stats, x, off, lambda lo, hi: (g[lo:hi], p[lo:hi]))
+
     def __call__(self, feats, lengths=None, mask=None, dtype=torch.float32):
         """feats (B, T, D) fp32 on a GPU; lengths: the first lengths[b] frames of utterance b; mask: (B, T) or (B, T, 1), nonzero =
         voiced (select-voiced-frames, e.g. VAD(return_indexes=False)); neither: every frame. -> (B, S) i-vectors (fp32, Kaldi's

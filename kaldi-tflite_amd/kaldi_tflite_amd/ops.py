@@ -940,6 +940,61 @@ def ivector_extract(x, offsets, gauss, post, posterior_scale, acoustic_weight, m
     return out
 
 
+def ivector_train_workspace_bytes(B, I, D, S):
+    n = int(L.load().ktf_ivector_train_workspace_bytes(int(B), int(I), int(D), int(S)))
+    if n < 0:
+        L.check(n, "ktf_ivector_train_workspace_bytes")
+    return n
+
+
+def ivector_acc_stats(x, offsets, gauss, post, posterior_scale, sigma_inv_M, U, prior_offset, gamma, Y, R, ivector_sum,
+                      ivector_scatter, totals):
+    """ivector-extractor-acc-stats for B = offsets.numel() - 1 utterances whose frames lie end to end in x (F, D), added in place to
+    the fp64 device accumulators gamma (I), Y (I * D, S), R (I, P), ivector_sum (S), ivector_scatter (P), totals (2) =
+    (num_ivectors, the sum of the utterances' marginal-likelihood scalars): ktf_ivector_acc_stats."""
+    lib = L.load()
+    F, D = x.shape
+    B = offsets.numel() - 1
+    I, S = U.shape[0], sigma_inv_M.shape[1]
+    nbytes = ivector_train_workspace_bytes(B, I, D, S)
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=x.device)
+    with L.on_device(x.device):
+        rc = lib.ktf_ivector_acc_stats(L.ptr(x), F, D, x.stride(0) if F else D, L.ptr(offsets), B, L.ptr(gauss), L.ptr(post), gauss.shape[1],
+                                       float(posterior_scale), L.ptr(sigma_inv_M), L.ptr(U), I, S, float(prior_offset), L.ptr(gamma),
+                                       L.ptr(Y), L.ptr(R), L.ptr(ivector_sum), L.ptr(ivector_scatter), L.ptr(totals), L.ptr(ws), nbytes,
+                                       L.stream_ptr())
+    L.check(rc, "ktf_ivector_acc_stats")
+
+
+def ivector_acc_second_order(x, gauss, post, posterior_scale, Ssec):
+    """Ssec (I, D, D) fp64 += sum_t p'_ti x_t x_t^T over the frames x (F, D) and their slots gauss / post (F, n), bit-identical run
+    to run: ktf_ivector_acc_second_order."""
+    lib = L.load()
+    F, D = x.shape
+    I, n = Ssec.shape[0], gauss.shape[1]
+    nbytes = int(lib.ktf_ivector_acc2_workspace_bytes(F, I, n))
+    if nbytes < 0:
+        L.check(nbytes, "ktf_ivector_acc2_workspace_bytes")
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=x.device)
+    with L.on_device(x.device):
+        rc = lib.ktf_ivector_acc_second_order(L.ptr(x), F, D, x.stride(0) if F else D, L.ptr(gauss), L.ptr(post), n, float(posterior_scale),
+                                              I, L.ptr(Ssec), L.ptr(ws), nbytes, L.stream_ptr())
+    L.check(rc, "ktf_ivector_acc_second_order")
+
+
+def atb_f64(A, B, C):
+    """C (M, N) += A^T B in place: A (K, M), B (K, N), C fp64 device matrices with unit inner strides (ktf_atb_f64, fp64 MFMA)."""
+    K, M = A.shape
+    N = B.shape[1]
+    if B.shape[0] != K or tuple(C.shape) != (M, N) or any(t.dtype != torch.float64 or (t.numel() and t.stride(1) != 1) for t in (A, B, C)):
+        raise ValueError("atb_f64: need fp64 A (K, M), B (K, N), C (M, N) with unit inner strides")
+    with L.on_device(C.device):
+        rc = L.load().ktf_atb_f64(L.ptr(A), A.stride(0) if K else M, L.ptr(B), B.stride(0) if K else N, L.ptr(C), C.stride(0), M, N, K,
+                                  L.stream_ptr())
+    L.check(rc, "ktf_atb_f64")
+    return C
+
+
 def fgmm_workspace_bytes(F, I, D, n):
     b = int(L.load().ktf_fgmm_workspace_bytes(int(F), int(I), int(D), int(n)))
     if b < 0:

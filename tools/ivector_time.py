@@ -6,7 +6,12 @@ utterances for scale. The model is random (built on the device: no files). Print
 preselection (ktf_ivector_post_f32 with min_post 0), the new stage (ktf_fgmm_post_f32) and the whole call, next to the diagonal
 posterior stage on the same frames.
 
-    python tools/ivector_time.py [--B 1024] [--T 1000] [--I 2048] [--D 60] [--S 400 600] [--reps 3] [--full-ubm]
+--train times extractor training on the same batch: one `accumulate`, synchronised, and its parts: the
+posterior stage, the stages shared with extraction (the `extract` figure), everything ktf_ivector_acc_stats launches (shared stages,
+covariance and scatter, the A^T B accumulations), the R job of ktf_atb_f64 alone on one chunk (TFLOP/s and its fraction of the 78.6 TF
+fp64 MFMA rate), the second-order statistics, and one ivector_extractor_est (host NumPy; --no-est skips it).
+
+    python tools/ivector_time.py [--B 1024] [--T 1000] [--I 2048] [--D 60] [--S 400 600] [--reps 3] [--full-ubm] [--train [--no-est]]
 """
 
 import argparse
@@ -79,6 +84,57 @@ def timed(fn, reps):
     return best, out
 
 
+def train_times(a, layer, ie, x, flat, off, g, p, t_call):
+    """The --train figures (milliseconds unless named otherwise)."""
+    dev = flat.device
+    I, D, S = layer.numGauss, layer.featDim, layer.ivecDim
+    P = S * (S + 1) // 2
+    _, _, sim, U, _ = layer._consts(dev)
+    st = ktf.training.IvectorStats(ie)
+    layer.accumulate(st, x[:2])                                                 # warm-up, allocates the accumulators
+    chunks = layer._train_chunks(a.B)
+    posts = lambda lo, hi: (g[lo:hi], p[lo:hi])                                 # noqa: E731
+
+    def acc_stats():
+        for b0, b1 in chunks:
+            lo, hi = int(off[b0]), int(off[b1])
+            o = torch.as_tensor((off[b0:b1 + 1] - lo).astype(np.int32), device=dev)
+            ops.ivector_acc_stats(flat[lo:hi], o, g[lo:hi], p[lo:hi], layer.posteriorScale, sim, U, layer.priorOffset, st.gamma, st.Y, st.R,
+                                  st.ivector_sum, st.ivector_scatter, st.totals)
+
+    def second():
+        for b0, b1 in chunks:
+            lo, hi = int(off[b0]), int(off[b1])
+            ops.ivector_acc_second_order(flat[lo:hi], g[lo:hi], p[lo:hi], layer.posteriorScale, st.Ssec)
+    t_stats, _ = timed(acc_stats, a.reps)
+    t_sec, _ = timed(second, a.reps)
+    t_from, _ = timed(lambda: layer._accumulate(st, flat, off, posts), a.reps)
+    t_acc, _ = timed(lambda: layer.accumulate(st, x), a.reps)
+    bc = chunks[0][1] - chunks[0][0]
+    gen = torch.Generator(device=dev).manual_seed(5)
+    A = torch.rand((bc, I), generator=gen, device=dev, dtype=torch.float64)
+    Bm = torch.rand((bc, P), generator=gen, device=dev, dtype=torch.float64)
+    t_atb, _ = timed(lambda: ops.atb_f64(A, Bm, st.R), a.reps)
+    tf = 2.0 * I * P * bc / t_atb / 1e12
+    out = {"train_chunks": len(chunks), "chunk_utts": bc, "accumulate_ms": round(t_acc * 1e3, 3),
+           "accumulate_from_posteriors_ms": round(t_from * 1e3, 3), "acc_stats_ms": round(t_stats * 1e3, 3),
+           "second_order_ms": round(t_sec * 1e3, 3), "atb_R_job_ms": round(t_atb * 1e3, 3), "atb_R_tflops": round(tf, 2),
+           "atb_R_fraction_of_78.6": round(tf / 78.6, 3), "accumulate_over_call": round(t_acc / t_call, 2)}
+    del A, Bm
+    if not a.no_est:
+        st2 = ktf.training.IvectorStats(ie)
+        layer.accumulate(st2, x)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        h = st2.host()
+        t_copy = time.perf_counter() - t0
+        new = ktf.training.ivector_extractor_est(ie, st2, gaussian_min_count=0.0)
+        out.update(est_s=round(new.estInfo["seconds"], 3), est_backend=new.estInfo["backend"], est_copy_to_host_s=round(t_copy, 3),
+                   objf=st2.objf())
+        del h, st2
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--B", type=int, default=1024)
@@ -89,6 +145,8 @@ def main():
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--host-utts", type=int, default=2)
     ap.add_argument("--full-ubm", action="store_true")
+    ap.add_argument("--train", action="store_true")
+    ap.add_argument("--no-est", action="store_true")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     torch.cuda.set_device(dev)
@@ -129,6 +187,8 @@ def main():
             gamma, F = R.stats(xs[b], gg, pp, a.I)
             R.extract_packed(gamma, F, ie.sigmaInvM, ie.U, ie.priorOffset)
         t_host = (time.perf_counter() - t0) / h
+        if a.train:
+            extra.update(train_times(a, layer, ie, x, flat, off, g, p, t_all))
         print(json.dumps({
             "build_id": L.load().ktf_build_id().decode(), "device": torch.cuda.get_device_name(dev),
             "B": a.B, "T": a.T, "I": a.I, "D": a.D, "S": S, "chunks": len(layer._chunks(a.B)),
