@@ -706,6 +706,12 @@ int64_t ktf_fgmm_workspace_bytes(int64_t F, int32_t I, int32_t D, int32_t n);
 int ktf_fgmm_post_f32(const float* x, int64_t F, int32_t D, int64_t ldx, const int32_t* gselect, int32_t n,
                       const float* means_invcovars, const float* inv_covars, const float* gconst, int32_t I, float min_post,
                       int32_t* gauss, float* post, void* workspace, size_t workspace_bytes, void* stream);
+/* ktf_fgmm_post_f32 with one more output: loglike (F) device fp32 or null, the frame's log-likelihood max + log(sum exp(l - max))
+ * over the listed set, taken BEFORE the pruning (0 for a frame that counts as an empty list). gauss / post are bit-identical to
+ * ktf_fgmm_post_f32's, with or without loglike; ktf_fgmm_post_f32 forwards here with null. */
+int ktf_fgmm_post_ll_f32(const float* x, int64_t F, int32_t D, int64_t ldx, const int32_t* gselect, int32_t n,
+                         const float* means_invcovars, const float* inv_covars, const float* gconst, int32_t I, float min_post,
+                         int32_t* gauss, float* post, float* loglike, void* workspace, size_t workspace_bytes, void* stream);
 /* add-deltas (Kaldi's DeltaFeatures): x (B, T, D) fp32, element (b, t, d) at x[b * stride_b + t * stride_t + d] -> out (B, T,
  * D * (order + 1)) contiguous. coeffs: device fp32 (order + 1, 2 * order * window + 1), row i the order-i filter centred at column
  * order * window and zero beyond +- i * window (the caller computes them in fp32 as DeltaFeatures does). Block i of frame t is
@@ -714,6 +720,44 @@ int ktf_fgmm_post_f32(const float* x, int64_t F, int32_t D, int64_t ldx, const i
 #define KTF_ADD_DELTAS_MAX_CONTEXT 32
 int ktf_add_deltas_f32(const float* x, int64_t B, int64_t T, int32_t D, int64_t stride_b, int64_t stride_t, const int32_t* lengths,
                        const float* coeffs, int32_t order, int32_t window, float* out, void* stream);
+
+/* ------------------------------------------------------------------ UBM training statistics
+ * The E-steps and accumulators of Kaldi's sid/train_diag_ubm.sh (gmm-global-init-from-feats, gmm-global-acc-stats --gselect) and
+ * sid/train_full_ubm.sh (fgmm-global-acc-stats --gselect); the updates run on the host (kaldi_tflite_amd/training.py). Frames x
+ * (F, D) fp32, row stride ldx; the limits of the i-vector entries: D <= KTF_IVECTOR_MAX_FEAT_DIM, I <= KTF_IVECTOR_MAX_GAUSS,
+ * n <= KTF_IVECTOR_MAX_GSELECT, F * n < 2^31.
+ *
+ * DiagGmm::LogLikelihoodsPreselect, then the softmax of gmm-global-acc-stats --gselect: gselect (F, n) device int32 lists the
+ * Gaussians of a frame, entries outside [0, I) are skipped. For each listed g, in fp32 and ascending d,
+ *   l = gconst_g; l = fma(x_d, means_invvars_gd, l); l = fma(-0.5 * fl(x_d * x_d), inv_vars_gd, l)
+ * post (F, n) = exp(l - max) / sum in the list's own slot order (no pruning, no sorting; skipped slots 0); loglike (F) = max +
+ * log(sum). A frame with nothing listed, or whose listed l are all -inf, gets zeros and loglike 0; *valid (device int32, may be
+ * null) is increased by the number of the other frames. A frame's bits depend on its own row and list alone. */
+int ktf_gmm_post_preselect_f32(const float* x, int64_t F, int32_t D, int64_t ldx, const int32_t* gselect, int32_t n,
+                               const float* means_invvars, const float* inv_vars, const float* gconst, int32_t I, float* post,
+                               float* loglike, int32_t* valid, void* stream);
+/* The E-step of gmm-global-init-from-feats (no gselect): the log-likelihoods of all I Gaussians as ktf_ivector_post_f32 computes
+ * them (W (2D, I) and gconst as there; the same device code, the same bits), softmax over all I in fp32:
+ *   P (F, I) fp64 = fp32(exp(l - max) / sum);  Xaug (F, 2D + 1) fp64 = [1, x, x^2], the squares exact;  loglike (F) fp32 = max + log(sum).
+ * The statistics are then ktf_atb_f64(A = P, B = Xaug) into (I, 2D + 1) = [occ, mean_acc, var_acc]. workspace: 256-byte aligned,
+ * at least ktf_gmm_post_dense_workspace_bytes(F, I) bytes (F * I fp32; a negative KTF_* code on bad arguments). */
+int64_t ktf_gmm_post_dense_workspace_bytes(int64_t F, int32_t I);
+int ktf_gmm_post_dense_f32(const float* x, int64_t F, int32_t D, int64_t ldx, const float* W, const float* gconst, int32_t I, double* P,
+                           double* Xaug, float* loglike, void* workspace, size_t workspace_bytes, void* stream);
+/* AccumDiagGmm / AccumFullGmm::AccumulateFromPosteriors with double accumulators, on (frame, slot) pairs: gauss / post (F, n) device
+ * int32 / fp32; a slot with an index outside [0, I) or a weight of 0 is skipped. Added in place to fp64 device accumulators:
+ *   occ (I) += sum p;  mean_acc (I, D) += sum p x;  second_acc = var_acc (I, D) += sum p x^2 (full = 0)
+ *                                                   or cov_acc (I, D, D) += sum p x x^T (full != 0), symmetric bit for bit.
+ * The pairs are bucketed by Gaussian with the stable counting sort of ktf_ivector_acc_second_order; a bucket is cut into items of
+ * KTF_GMM_ACC_ITEM_ROWS rows by a rule that depends on its count alone; an item is summed in ascending pair order (diagonal form:
+ * fp64 VALU; full form: [1, x]^T diag(p) [1, x] on v_mfma_f64_16x16x4_f64, the lower triangle computed and mirrored); the items of
+ * a Gaussian are added in ascending item order and that sum is added to the accumulator. No floating-point atomics: the same call
+ * sequence gives the same bits. workspace: 256-byte aligned, at least ktf_gmm_acc_workspace_bytes(F, I, D, n, full) bytes (a
+ * negative KTF_* code on bad arguments). */
+#define KTF_GMM_ACC_ITEM_ROWS 1024
+int64_t ktf_gmm_acc_workspace_bytes(int64_t F, int32_t I, int32_t D, int32_t n, int32_t full);
+int ktf_gmm_acc_f64(const float* x, int64_t F, int32_t D, int64_t ldx, const int32_t* gauss, const float* post, int32_t n, int32_t I,
+                    int32_t full, double* occ, double* mean_acc, double* second_acc, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------ PLDA back-end training statistics
  * The parts of Kaldi's `ivector-compute-lda`, `ivector-compute-plda` (PldaStats, PldaEstimator) and `est-pca --read-vectors=true`

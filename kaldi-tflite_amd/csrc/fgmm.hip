@@ -11,7 +11,8 @@
 //                      into LDS (transposed) and runs Y^T = inv_covars_g . X^T on v_mfma_f32_32x32x2_f32 (exact fp32, k ascending):
 //                      the frame is on the lane, Y's dimensions in the accumulators, so the row dot sum_j x_j (mi_j - y_j / 2) is
 //                      taken in registers in an order that depends on D alone; gconst added; written to ll[pair].
-//   fg_softmax_kernel  one wave per frame: softmax over the listed slots, prune below min_post, renormalise, sort.
+//   fg_softmax_kernel  one wave per frame: softmax over the listed slots (and, for ktf_fgmm_post_ll_f32, the frame's log-likelihood
+//                      before pruning), prune below min_post, renormalise, sort.
 //   adddeltas_kernel   one thread per output element, unfused multiply and add (fp contract off) in tap order.
 #include "common.h"
 
@@ -214,7 +215,8 @@ __device__ __forceinline__ bool fg_before(float va, int ga, int sa, float vb, in
 }
 
 __global__ void __launch_bounds__(FG_THREADS) fg_softmax_kernel(const int* __restrict__ gsel, const float* __restrict__ ll, int64_t F, int n, int I,
-                                                                 float min_post, int* __restrict__ gauss, float* __restrict__ post) {
+                                                                 float min_post, int* __restrict__ gauss, float* __restrict__ post,
+                                                                 float* __restrict__ loglike) {
     const int lane = threadIdx.x & 63;
     const int64_t t = (int64_t)blockIdx.x * FG_WAVES + (threadIdx.x >> 6);
     if (t >= F) return;
@@ -240,7 +242,9 @@ __global__ void __launch_bounds__(FG_THREADS) fg_softmax_kernel(const int* __res
     // a frame whose listed log-likelihoods are all -inf (zero-weight components) has no arg-max: it counts as an empty list
     const bool valid = g >= 0 && bv > -INFINITY;
     float p = valid ? expf(l - bv) : 0.f;
-    p = p / wave_sum(p);                         // no valid slot: 0 / 0, never kept (valid is false)
+    const float tot = wave_sum(p);
+    p = p / tot;                                 // no valid slot: 0 / 0, never kept (valid is false)
+    if (loglike && lane == 0) loglike[t] = bv > -INFINITY ? bv + logf(tot) : 0.f;   // before pruning; an empty list: 0
     if (min_post != 0.f) {
         if (p < min_post) p = 0.f;
         const float s2 = wave_sum(valid ? p : 0.f);
@@ -317,10 +321,9 @@ extern "C" int64_t ktf_fgmm_workspace_bytes(int64_t F, int32_t I, int32_t D, int
     return fg_layout(F, I, n).total;
 }
 
-extern "C" int ktf_fgmm_post_f32(const float* x, int64_t F, int32_t D, int64_t ldx, const int32_t* gselect, int32_t n,
-                                 const float* means_invcovars, const float* inv_covars, const float* gconst, int32_t I, float min_post,
-                                 int32_t* gauss, float* post, void* workspace, size_t workspace_bytes, void* stream) {
-    const char* who = "ktf_fgmm_post_f32";
+static int fg_post(const char* who, const float* x, int64_t F, int32_t D, int64_t ldx, const int32_t* gselect, int32_t n,
+                   const float* means_invcovars, const float* inv_covars, const float* gconst, int32_t I, float min_post, int32_t* gauss,
+                   float* post, float* loglike, void* workspace, size_t workspace_bytes, void* stream) {
     const int rc = fg_check_shape(who, F, I, D, n);
     if (rc != KTF_OK) return rc;
     KTF_REQUIRE(ldx >= D, "%s: ldx %lld < D %d", who, (long long)ldx, (int)D);
@@ -358,7 +361,7 @@ extern "C" int ktf_fgmm_post_f32(const float* x, int64_t F, int32_t D, int64_t l
     }
     KTF_CHECK_LAUNCH(who);
     hipLaunchKernelGGL(fg_softmax_kernel, dim3((unsigned)((F + FG_WAVES - 1) / FG_WAVES)), dim3(FG_THREADS), 0, st, gselect, (const float*)ll, F,
-                       (int)n, (int)I, min_post, gauss, post);
+                       (int)n, (int)I, min_post, gauss, post, loglike);
     KTF_CHECK_LAUNCH(who);
     return KTF_OK;
 }
@@ -382,4 +385,18 @@ extern "C" int ktf_add_deltas_f32(const float* x, int64_t B, int64_t T, int32_t 
                        lengths, coeffs, (int)order, (int)window, total, out);
     KTF_CHECK_LAUNCH(who);
     return KTF_OK;
+}
+
+extern "C" int ktf_fgmm_post_f32(const float* x, int64_t F, int32_t D, int64_t ldx, const int32_t* gselect, int32_t n,
+                                 const float* means_invcovars, const float* inv_covars, const float* gconst, int32_t I, float min_post,
+                                 int32_t* gauss, float* post, void* workspace, size_t workspace_bytes, void* stream) {
+    return fg_post("ktf_fgmm_post_f32", x, F, D, ldx, gselect, n, means_invcovars, inv_covars, gconst, I, min_post, gauss, post, nullptr,
+                   workspace, workspace_bytes, stream);
+}
+
+extern "C" int ktf_fgmm_post_ll_f32(const float* x, int64_t F, int32_t D, int64_t ldx, const int32_t* gselect, int32_t n,
+                                    const float* means_invcovars, const float* inv_covars, const float* gconst, int32_t I, float min_post,
+                                    int32_t* gauss, float* post, float* loglike, void* workspace, size_t workspace_bytes, void* stream) {
+    return fg_post("ktf_fgmm_post_ll_f32", x, F, D, ldx, gselect, n, means_invcovars, inv_covars, gconst, I, min_post, gauss, post, loglike,
+                   workspace, workspace_bytes, stream);
 }

@@ -14,11 +14,9 @@
 //                     substitution of linear + priorOffset e0, ivector(0) -= priorOffset.
 // Every stage is per utterance with a fixed reduction order, so an utterance's bits do not depend on its batch or position.
 #include "ivector_stages.h"
+#include "gmm_loglike.h"
 
 namespace {
-
-constexpr int IVP_FT = 32;          // frames per workgroup of the posterior kernel
-constexpr int IVP_GT = 256;         // Gaussians per tile (= threads)
 
 inline size_t ivpost_lds_bytes(int D, int n) { return (size_t)4 * (2 * D * IVP_FT + IVP_FT * (IVP_GT + 1) + 2 * IVP_FT * n + IVP_FT); }
 
@@ -39,33 +37,14 @@ __global__ void __launch_bounds__(IVP_GT) ivpost_kernel(const float* __restrict_
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int64_t f0 = (int64_t)blockIdx.x * IVP_FT;
     const int K = 2 * D;
-    for (int e = tid; e < IVP_FT * D; e += IVP_GT) {
-        const int f = e / D, d = e - f * D;
-        const float v = f0 + f < F ? x[(f0 + f) * ldx + d] : 0.f;
-        xs[d][f] = v;
-        xs[D + d][f] = v * v;
-    }
+    ivp_load_frames(xs, x, f0, F, D, ldx, tid);
     if (tid < IVP_FT) lcnt[tid] = 0;
     __syncthreads();
     for (int g0 = 0; g0 < I; g0 += IVP_GT) {
         const int g = g0 + tid;
         if (g < I) {
             float acc[IVP_FT];
-            const float gc = gconst[g];
-#pragma unroll
-            for (int f = 0; f < IVP_FT; ++f) acc[f] = gc;
-            for (int k = 0; k < K; ++k) {
-                const float w = W[(int64_t)k * I + g];
-                const float4* xr = reinterpret_cast<const float4*>(&xs[k][0]);
-#pragma unroll
-                for (int q = 0; q < IVP_FT / 4; ++q) {
-                    const float4 v = xr[q];
-                    acc[4 * q + 0] = fmaf(v.x, w, acc[4 * q + 0]);
-                    acc[4 * q + 1] = fmaf(v.y, w, acc[4 * q + 1]);
-                    acc[4 * q + 2] = fmaf(v.z, w, acc[4 * q + 2]);
-                    acc[4 * q + 3] = fmaf(v.w, w, acc[4 * q + 3]);
-                }
-            }
+            ivp_loglikes(acc, xs, W, gconst[g], I, g, K);
 #pragma unroll
             for (int f = 0; f < IVP_FT; ++f) ll[f][tid] = acc[f];
         }

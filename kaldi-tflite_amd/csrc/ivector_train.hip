@@ -10,11 +10,13 @@
 //   atb_kernel       C += A^T B in fp64 on v_mfma_f64_16x16x4_f64: A (K x M) and B (K x N) row-major, K = the utterances of the
 //                    chunk, ascending inside every output element; no atomics, no split of K. One kernel for R (A = gamma,
 //                    B = W), Y (A = F, B = w), gamma, the prior's sum and scatter and the two scalar totals (A = the flags).
-//   sec_*_kernel     second-order statistics Ssec_i += sum_t p'_ti x_t x_t^T: the (frame, slot) pairs are bucketed by Gaussian with
+//   sec_*_kernel     second-order statistics Ssec_i += sum_t p'_ti x_t x_t^T: the (frame, slot) pairs are bucketed by Gaussian (the
+//                    bucketing kernels live in gmm_bucket.h, shared with gmm_train.hip) with
 //                    a STABLE counting sort (integer histograms per chunk of pairs, exclusive scans, then one wave per chunk that
 //                    ranks equal Gaussians by lane order), so a bucket lists its pairs in ascending pair id and its fp64 sum, taken
 //                    row after row, has the same bits on every run.
 #include "ivector_stages.h"
+#include "gmm_bucket.h"
 
 namespace {
 
@@ -24,7 +26,6 @@ constexpr int COV_THREADS = 256;
 constexpr int ATB_MT = 2;           // 16-row MFMA tiles per wave
 constexpr int ATB_NT = 4;           // 16-column MFMA tiles per wave
 constexpr int ATB_WAVES = 4;        // waves per workgroup, stacked along M: a workgroup owns 128 x 64 of C
-constexpr int SEC_CH = 8192;        // pairs per bucketing chunk (one wave scatters a chunk in pair order)
 constexpr int SEC_RB = 16;          // bucket rows staged in LDS per step
 
 struct TrLayout {
@@ -260,112 +261,7 @@ int atb(const char* who, const double* A, int64_t lda, const double* Bm, int64_t
     return KTF_OK;
 }
 
-// ---------------------------------------------------------------- second-order statistics
-struct SecLayout {
-    int64_t counts, total, start, pairs, bytes;
-    int64_t nch;
-};
-
-SecLayout sec_layout(int64_t F, int64_t I, int64_t n) {
-    SecLayout l;
-    const int64_t np = F * n;
-    l.nch = (np + SEC_CH - 1) / SEC_CH;
-    int64_t at = 0;
-    l.counts = at; at += al256(l.nch * I * 4);
-    l.total = at;  at += al256(I * 4);
-    l.start = at;  at += al256((I + 1) * 4);
-    l.pairs = at;  at += al256(np * 4);
-    l.bytes = at;
-    return l;
-}
-
-// counts[chunk][g] = the chunk's pairs of Gaussian g (integer counts: the LDS atomics cannot change the result)
-__global__ void __launch_bounds__(256) sec_hist_kernel(const int* __restrict__ gauss, int64_t np, int I, int* __restrict__ counts) {
-    extern __shared__ int sec_lds[];
-    const int tid = threadIdx.x;
-    for (int g = tid; g < I; g += 256) sec_lds[g] = 0;
-    __syncthreads();
-    const int64_t e0 = (int64_t)blockIdx.x * SEC_CH;
-    for (int64_t e = e0 + tid; e < e0 + SEC_CH && e < np; e += 256) {
-        const int g = gauss[e];
-        if (g >= 0 && g < I) atomicAdd(&sec_lds[g], 1);
-    }
-    __syncthreads();
-    for (int g = tid; g < I; g += 256) counts[(int64_t)blockIdx.x * I + g] = sec_lds[g];
-}
-
-// counts[chunk][g] -> the pairs of g in earlier chunks; total[g]
-__global__ void sec_scan_kernel(int* __restrict__ counts, int64_t nch, int I, int* __restrict__ total) {
-    const int g = blockIdx.x * blockDim.x + threadIdx.x;
-    if (g >= I) return;
-    int run = 0;
-    for (int64_t c = 0; c < nch; ++c) {
-        const int v = counts[c * I + g];
-        counts[c * I + g] = run;
-        run += v;
-    }
-    total[g] = run;
-}
-
-// start[g] = sum of total[< g], start[I] = all pairs kept (one workgroup)
-__global__ void __launch_bounds__(256) sec_start_kernel(const int* __restrict__ total, int I, int* __restrict__ start) {
-    __shared__ int seg[256];
-    const int tid = threadIdx.x, per = (I + 255) / 256;
-    const int g0 = tid * per, g1 = g0 + per < I ? g0 + per : I;
-    int s = 0;
-    for (int g = g0; g < g1; ++g) s += total[g];
-    seg[tid] = s;
-    __syncthreads();
-    if (tid == 0) {
-        int run = 0;
-        for (int t = 0; t < 256; ++t) {
-            const int v = seg[t];
-            seg[t] = run;
-            run += v;
-        }
-        start[I] = run;
-    }
-    __syncthreads();
-    int run = seg[tid];
-    for (int g = g0; g < g1; ++g) {
-        start[g] = run;
-        run += total[g];
-    }
-}
-
-// one wave per chunk, 64 pairs per step in pair order: a pair's slot is its bucket's cursor + the number of lower lanes with the
-// same Gaussian, and the highest such lane moves the cursor on. Every slot index is < start[I] <= np by the counts above.
-__global__ void __launch_bounds__(64) sec_scatter_kernel(const int* __restrict__ gauss, int64_t np, int I, const int* __restrict__ counts,
-                                                          const int* __restrict__ start, int* __restrict__ pairs) {
-    extern __shared__ int sec_lds[];
-    const int lane = threadIdx.x;
-    for (int g = lane; g < I; g += 64) sec_lds[g] = start[g] + counts[(int64_t)blockIdx.x * I + g];
-    __syncthreads();
-    const int64_t e0 = (int64_t)blockIdx.x * SEC_CH;
-    for (int64_t eb = e0; eb < e0 + SEC_CH && eb < np; eb += 64) {
-        const int64_t e = eb + lane;
-        int g = e < np ? gauss[e] : -1;
-        if (g >= I) g = -1;
-        int rank = 0;
-        bool later = false;
-        for (int j = 0; j < 64; ++j) {
-            const int gj = __shfl(g, j);
-            if (gj == g) {
-                rank += j < lane;
-                later |= j > lane;
-            }
-        }
-        int pos = 0;
-        if (g >= 0) {
-            pos = sec_lds[g] + rank;
-            pairs[pos] = (int)e;
-        }
-        __syncthreads();
-        if (g >= 0 && !later) sec_lds[g] = pos + 1;
-        __syncthreads();
-    }
-}
-
+// ---------------------------------------------------------------- second-order statistics (the bucketing: gmm_bucket.h)
 // Ssec[g] (D x D) += sum over the bucket's rows, in bucket order, of p' x x^T: one workgroup per Gaussian, thread (ty, tx) owns
 // elements (ty + 16 a, tx + 16 c). x_i x_j is exact in fp64 (fp32 inputs), so the result is symmetric bit for bit.
 __global__ void __launch_bounds__(256) sec_acc_kernel(const float* __restrict__ x, int D, int64_t ldx, const float* __restrict__ post, int n,
@@ -506,22 +402,11 @@ extern "C" int ktf_ivector_acc_second_order(const float* x, int64_t F, int32_t D
     char* ws = (char*)workspace;
     const SecLayout l = sec_layout(F, I, n);
     const int64_t np = F * n;
-    int* counts = (int*)(ws + l.counts);
-    int* total = (int*)(ws + l.total);
-    int* start = (int*)(ws + l.start);
-    int* pairs = (int*)(ws + l.pairs);
-    const size_t lds = (size_t)I * sizeof(int);
-    hipLaunchKernelGGL(sec_hist_kernel, dim3((unsigned)l.nch), dim3(256), lds, st, gauss, np, (int)I, counts);
-    KTF_CHECK_LAUNCH(who);
-    hipLaunchKernelGGL(sec_scan_kernel, dim3(ktf_cdiv(I, 256)), dim3(256), 0, st, counts, l.nch, (int)I, total);
-    KTF_CHECK_LAUNCH(who);
-    hipLaunchKernelGGL(sec_start_kernel, dim3(1), dim3(256), 0, st, (const int*)total, (int)I, start);
-    KTF_CHECK_LAUNCH(who);
-    hipLaunchKernelGGL(sec_scatter_kernel, dim3((unsigned)l.nch), dim3(64), lds, st, gauss, np, (int)I, (const int*)counts, (const int*)start,
-                       pairs);
-    KTF_CHECK_LAUNCH(who);
-    hipLaunchKernelGGL(sec_acc_kernel, dim3(I), dim3(256), 0, st, x, (int)D, ldx, post, (int)n, posterior_scale, (const int*)start,
-                       (const int*)pairs, Ssec);
+    const int* start = (const int*)(ws + l.start);
+    const int* pairs = (const int*)(ws + l.pairs);
+    const int rc = sec_bucket(who, gauss, np, (int)I, l, ws, st);
+    if (rc != KTF_OK) return rc;
+    hipLaunchKernelGGL(sec_acc_kernel, dim3(I), dim3(256), 0, st, x, (int)D, ldx, post, (int)n, posterior_scale, start, pairs, Ssec);
     KTF_CHECK_LAUNCH(who);
     return KTF_OK;
 }

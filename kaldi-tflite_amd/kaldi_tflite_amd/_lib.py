@@ -170,6 +170,12 @@ PROTOTYPES = {
     "ktf_atb_f64": (C.c_int, [_P, _i64, _P, _i64, _P, _i64, _i64, _i64, _i64, _P]),
     "ktf_fgmm_workspace_bytes": (_i64, [_i64, _i32, _i32, _i32]),
     "ktf_fgmm_post_f32": (C.c_int, [_P, _i64, _i32, _i64, _P, _i32, _P, _P, _P, _i32, _f32, _P, _P, _P, C.c_size_t, _P]),
+    "ktf_fgmm_post_ll_f32": (C.c_int, [_P, _i64, _i32, _i64, _P, _i32, _P, _P, _P, _i32, _f32, _P, _P, _P, _P, C.c_size_t, _P]),
+    "ktf_gmm_post_preselect_f32": (C.c_int, [_P, _i64, _i32, _i64, _P, _i32, _P, _P, _P, _i32, _P, _P, _P, _P]),
+    "ktf_gmm_post_dense_workspace_bytes": (_i64, [_i64, _i32]),
+    "ktf_gmm_post_dense_f32": (C.c_int, [_P, _i64, _i32, _i64, _P, _P, _i32, _P, _P, _P, _P, C.c_size_t, _P]),
+    "ktf_gmm_acc_workspace_bytes": (_i64, [_i64, _i32, _i32, _i32, _i32]),
+    "ktf_gmm_acc_f64": (C.c_int, [_P, _i64, _i32, _i64, _P, _P, _i32, _i32, _i32, _P, _P, _P, _P, C.c_size_t, _P]),
     "ktf_add_deltas_f32": (C.c_int, [_P, _i64, _i64, _i32, _i64, _i64, _P, _P, _i32, _i32, _P, _P]),
     "ktf_train_class_means": (C.c_int, [_P, _i64, _i32, _P, _i64, _P, _i64, _P, _P, _P]),
     "ktf_train_workspace_bytes": (_i64, [_i64, _i32]),
@@ -185,6 +191,7 @@ PLDA_DENSE_MAX_SWEEPS = 30
 AHC_MAX_N = 32767                   # ktf_ahc_*: rows per recording
 AHC_LDS_SLOTS = 5120                # ... up to which the merge loop's state sits in LDS
 IVECTOR_MAX_FEAT_DIM, IVECTOR_MAX_GAUSS, IVECTOR_MAX_GSELECT, IVECTOR_MAX_DIM = 128, 8192, 64, 1024   # ktf_ivector_*
+GMM_ACC_ITEM_ROWS = 1024            # ktf_gmm_acc_f64: rows of a bucket per item
 ADD_DELTAS_MAX_CONTEXT = 32         # ktf_add_deltas_f32: order * window
 TRAIN_MAX_DIM = 1024                # ktf_train_*, ktf_plda_em_project
 

@@ -581,3 +581,72 @@ def WriteKaldiIvecExtractor(path, extractor, binary=True):
     out += [b"<IvectorOffset> \x08", struct.pack("<d", float(e.priorOffset)), b"</IvectorExtractor> "]
     with open(path, "wb") as f:
         f.write(b"".join(out))
+
+
+class DiagGmmModel(KaldiDiagGmmReader):
+    """A diagonal GMM held in memory (training.init_diag_ubm / diag_gmm_est), usable wherever a KaldiDiagGmmReader is: weights (I),
+    means_invvars (I, D), inv_vars (I, D), rounded once to fp32 as Kaldi stores them; gconsts by the reader's computeGconsts."""
+
+    def __init__(self, weights, means_invvars, inv_vars):
+        w, mi, iv = (np.ascontiguousarray(a, dtype=np.float32) for a in (weights, means_invvars, inv_vars))
+        if mi.ndim != 2 or iv.shape != mi.shape or w.shape != (mi.shape[0],) or mi.shape[0] < 1 or mi.shape[1] < 1:
+            raise ValueError(f"inconsistent DiagGMM shapes: weights {w.shape}, means_invvars {mi.shape}, inv_vars {iv.shape}")
+        self.path, self.binary, self.storedGconsts = None, True, None
+        self.weights, self.means_invvars, self.inv_vars = w, mi, iv
+        self.numGauss, self.featDim = int(mi.shape[0]), int(mi.shape[1])
+        self.gconsts = self.computeGconsts()
+
+
+class FullGmmModel(KaldiFullGmmReader):
+    """A full-covariance GMM held in memory (training.diag_to_full / full_gmm_est), usable wherever a KaldiFullGmmReader is: weights
+    (I), means_invcovars (I, D), inv_covars (I, D, D), rounded once to fp32; the lower triangle of every inverse covariance is
+    mirrored (Kaldi stores that triangle alone), so inv_covars is symmetric bit for bit. gconsts by the reader's computeGconsts,
+    which raises ValueError if an inverse covariance is not positive definite."""
+
+    def __init__(self, weights, means_invcovars, inv_covars):
+        w, mic = (np.ascontiguousarray(a, dtype=np.float32) for a in (weights, means_invcovars))
+        ic = np.array(inv_covars, dtype=np.float32)
+        if mic.ndim != 2 or ic.shape != mic.shape + mic.shape[1:] or w.shape != (mic.shape[0],) or mic.shape[0] < 1 or mic.shape[1] < 1:
+            raise ValueError(f"inconsistent FullGMM shapes: weights {w.shape}, means_invcovars {mic.shape}, inv_covars {ic.shape}")
+        r, c = np.tril_indices(mic.shape[1])
+        ic[:, c, r] = ic[:, r, c]
+        self.path, self.binary, self.storedGconsts = None, True, None
+        self.weights, self.means_invcovars, self.inv_covars = w, mic, ic
+        self.numGauss, self.featDim = int(mic.shape[0]), int(mic.shape[1])
+        self.gconsts = self.computeGconsts()
+
+
+def WriteKaldiDiagGmm(path, gmm, binary=True):
+    """Kaldi's DiagGmm::Write, binary mode: "\\0B<DiagGMM> <GCONSTS> " FV "<WEIGHTS> " FV "<MEANS_INVVARS> " FM "<INV_VARS> " FM
+    "</DiagGMM> ", all fp32. `gmm`: a KaldiDiagGmmReader or DiagGmmModel; the gconsts written are gmm.gconsts. Text mode is not
+    implemented."""
+    if not binary:
+        raise NotImplementedError("WriteKaldiDiagGmm writes Kaldi's binary mode only")
+    f32 = lambda a: np.asarray(a, np.float32)  # noqa: E731
+    I, D = f32(gmm.means_invvars).shape
+    if f32(gmm.inv_vars).shape != (I, D) or f32(gmm.weights).shape != (I,) or f32(gmm.gconsts).shape != (I,):
+        raise ValueError("inconsistent DiagGMM shapes")
+    with open(path, "wb") as f:
+        f.write(b"\0B<DiagGMM> <GCONSTS> " + _array_bytes(f32(gmm.gconsts), True) + b"<WEIGHTS> " + _array_bytes(f32(gmm.weights), True)
+                + b"<MEANS_INVVARS> " + _array_bytes(f32(gmm.means_invvars), True) + b"<INV_VARS> " + _array_bytes(f32(gmm.inv_vars), True)
+                + b"</DiagGMM> ")
+
+
+def WriteKaldiFullGmm(path, gmm, binary=True):
+    """Kaldi's FullGmm::Write, binary mode: "\\0B<FullGMM> <GCONSTS> " FV "<WEIGHTS> " FV "<MEANS_INVCOVARS> " FM "<INV_COVARS> " then
+    I packed fp32 lower triangles ("FP ", 0x04 + int32 rows, the triangle row by row) "</FullGMM> ". `gmm`: a KaldiFullGmmReader or
+    FullGmmModel. Text mode is not implemented."""
+    if not binary:
+        raise NotImplementedError("WriteKaldiFullGmm writes Kaldi's binary mode only")
+    f32 = lambda a: np.asarray(a, np.float32)  # noqa: E731
+    I, D = f32(gmm.means_invcovars).shape
+    ic = f32(gmm.inv_covars)
+    if ic.shape != (I, D, D) or f32(gmm.weights).shape != (I,) or f32(gmm.gconsts).shape != (I,):
+        raise ValueError("inconsistent FullGMM shapes")
+    r, c = np.tril_indices(D)
+    out = [b"\0B<FullGMM> <GCONSTS> ", _array_bytes(f32(gmm.gconsts), True), b"<WEIGHTS> ", _array_bytes(f32(gmm.weights), True),
+           b"<MEANS_INVCOVARS> ", _array_bytes(f32(gmm.means_invcovars), True), b"<INV_COVARS> "]
+    out += [b"FP \x04" + _I32.pack(D) + np.ascontiguousarray(ic[i][r, c], dtype="<f4").tobytes() for i in range(I)]
+    out.append(b"</FullGMM> ")
+    with open(path, "wb") as f:
+        f.write(b"".join(out))

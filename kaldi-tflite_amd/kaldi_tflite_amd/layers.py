@@ -1410,6 +1410,34 @@ class PLDA(Layer):
 
 
 # =============================================================================== i-vectors
+def select_frames(feats, D, lengths, mask):
+    """(B, T, D) device fp32 -> (frames (F, D) in utterance order, offsets (B + 1) host int64): the first lengths[b] frames of
+    utterance b, or the frames with a nonzero mask (B, T) / (B, T, 1), or every frame."""
+    if not isinstance(feats, torch.Tensor) or not feats.is_cuda:
+        raise ValueError("feats must be a (B, T, D) tensor on a GPU")
+    if feats.dim() != 3 or feats.shape[2] != D:
+        raise ValueError(f"feats must be (B, T, {D}), got {tuple(feats.shape)}")
+    if feats.dtype != torch.float32:
+        raise ValueError(f"feats must be float32, got {feats.dtype}")
+    B, T, D = feats.shape
+    if lengths is not None and mask is not None:
+        raise ValueError("pass lengths or mask, not both")
+    if mask is not None:
+        m = mask.reshape(mask.shape[0], -1) if isinstance(mask, torch.Tensor) else torch.as_tensor(np.asarray(mask))
+        if m.dim() != 2 or tuple(m.shape) != (B, T):
+            raise ValueError(f"mask must be (B, T) or (B, T, 1) = ({B}, {T}), got {tuple(mask.shape)}")
+        m = m.to(feats.device) != 0
+    elif lengths is not None:
+        n = np.asarray(lengths.cpu() if isinstance(lengths, torch.Tensor) else lengths, dtype=np.int64).reshape(-1)
+        if n.shape[0] != B or (n < 0).any() or (n > T).any():
+            raise ValueError(f"lengths must hold {B} values in 0 .. {T}")
+        m = torch.arange(T, device=feats.device)[None, :] < torch.as_tensor(n, device=feats.device)[:, None]
+    else:
+        return feats.reshape(B * T, D) if feats.is_contiguous() else feats.contiguous().reshape(B * T, D), np.arange(B + 1) * T
+    counts = m.sum(1).cpu().numpy().astype(np.int64)
+    return feats[m].contiguous(), np.concatenate([[0], np.cumsum(counts)])
+
+
 class IvectorExtractor(Layer):
     """Extension (the reference reads `final.ie` and extracts nothing): Kaldi's sid/extract_ivectors.sh core on the GPU,
 
@@ -1520,29 +1548,7 @@ class IvectorExtractor(Layer):
 
     def _frames(self, feats, lengths, mask):
         """(B, T, D) device fp32 -> (frames (F, D) in utterance order, offsets (B + 1) host int64)."""
-        if not isinstance(feats, torch.Tensor) or not feats.is_cuda:
-            raise ValueError("feats must be a (B, T, D) tensor on a GPU")
-        if feats.dim() != 3 or feats.shape[2] != self.featDim:
-            raise ValueError(f"feats must be (B, T, {self.featDim}), got {tuple(feats.shape)}")
-        if feats.dtype != torch.float32:
-            raise ValueError(f"feats must be float32, got {feats.dtype}")
-        B, T, D = feats.shape
-        if lengths is not None and mask is not None:
-            raise ValueError("pass lengths or mask, not both")
-        if mask is not None:
-            m = mask.reshape(mask.shape[0], -1) if isinstance(mask, torch.Tensor) else torch.as_tensor(np.asarray(mask))
-            if m.dim() != 2 or tuple(m.shape) != (B, T):
-                raise ValueError(f"mask must be (B, T) or (B, T, 1) = ({B}, {T}), got {tuple(mask.shape)}")
-            m = m.to(feats.device) != 0
-        elif lengths is not None:
-            n = np.asarray(lengths.cpu() if isinstance(lengths, torch.Tensor) else lengths, dtype=np.int64).reshape(-1)
-            if n.shape[0] != B or (n < 0).any() or (n > T).any():
-                raise ValueError(f"lengths must hold {B} values in 0 .. {T}")
-            m = torch.arange(T, device=feats.device)[None, :] < torch.as_tensor(n, device=feats.device)[:, None]
-        else:
-            return feats.reshape(B * T, D) if feats.is_contiguous() else feats.contiguous().reshape(B * T, D), np.arange(B + 1) * T
-        counts = m.sum(1).cpu().numpy().astype(np.int64)
-        return feats[m].contiguous(), np.concatenate([[0], np.cumsum(counts)])
+        return select_frames(feats, self.featDim, lengths, mask)
 
     def _chunks(self, B):
         per = ops.ivector_workspace_bytes(1, self.numGauss, self.featDim, self.ivecDim)

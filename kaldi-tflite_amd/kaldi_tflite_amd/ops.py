@@ -1021,6 +1021,92 @@ def fgmm_post(x, gselect, means_invcovars, inv_covars, gconst, min_post):
     return gauss, post
 
 
+def fgmm_post_ll(x, gselect, means_invcovars, inv_covars, gconst, min_post, want_loglike=True):
+    """fgmm_post with the frames' log-likelihoods (before pruning) -> (gauss, post, loglike (F) fp32 or None): ktf_fgmm_post_ll_f32."""
+    lib = L.load()
+    F, D = x.shape
+    n = gselect.shape[1]
+    I = gconst.shape[0]
+    gauss = torch.empty((F, n), dtype=torch.int32, device=x.device)
+    post = torch.empty((F, n), dtype=torch.float32, device=x.device)
+    ll = torch.empty((F,), dtype=torch.float32, device=x.device) if want_loglike else None
+    nbytes = fgmm_workspace_bytes(F, I, D, n)
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=x.device)
+    with L.on_device(x.device):
+        rc = lib.ktf_fgmm_post_ll_f32(L.ptr(x), F, D, x.stride(0) if F else D, L.ptr(gselect), n, L.ptr(means_invcovars), L.ptr(inv_covars),
+                                      L.ptr(gconst), I, float(min_post), L.ptr(gauss), L.ptr(post), L.ptr(ll), L.ptr(ws), nbytes,
+                                      L.stream_ptr())
+    L.check(rc, "ktf_fgmm_post_ll_f32")
+    return gauss, post, ll
+
+
+# ----------------------------------------------------------------------------- UBM training statistics (ktf_gmm_*)
+def gmm_post_preselect(x, gselect, means_invvars, inv_vars, gconst, valid=None):
+    """gmm-global-acc-stats --gselect's E-step on frames x (F, D) fp32 and lists gselect (F, n) int32: -> (post (F, n) fp32 in the
+    list's slot order, loglike (F) fp32); `valid` (1,) int32 on the device is increased by the frames with a non-empty list."""
+    F, D = x.shape
+    n = gselect.shape[1]
+    post = torch.empty((F, n), dtype=torch.float32, device=x.device)
+    ll = torch.empty((F,), dtype=torch.float32, device=x.device)
+    with L.on_device(x.device):
+        rc = L.load().ktf_gmm_post_preselect_f32(L.ptr(x), F, D, x.stride(0) if F else D, L.ptr(gselect), n, L.ptr(means_invvars),
+                                                 L.ptr(inv_vars), L.ptr(gconst), gconst.shape[0], L.ptr(post), L.ptr(ll), L.ptr(valid),
+                                                 L.stream_ptr())
+    L.check(rc, "ktf_gmm_post_preselect_f32")
+    return post, ll
+
+
+def gmm_post_dense_workspace_bytes(F, I):
+    b = int(L.load().ktf_gmm_post_dense_workspace_bytes(int(F), int(I)))
+    if b < 0:
+        L.check(b, "ktf_gmm_post_dense_workspace_bytes")
+    return b
+
+
+def gmm_post_dense(x, W, gconst):
+    """The dense E-step of gmm-global-init-from-feats on frames x (F, D) fp32: W (2D, I), gconst (I) as ivector_post takes them ->
+    (P (F, I) fp64, Xaug (F, 2D + 1) fp64 = [1, x, x^2], loglike (F) fp32): ktf_gmm_post_dense_f32."""
+    F, D = x.shape
+    I = gconst.shape[0]
+    P = torch.empty((F, I), dtype=torch.float64, device=x.device)
+    Xaug = torch.empty((F, 2 * D + 1), dtype=torch.float64, device=x.device)
+    ll = torch.empty((F,), dtype=torch.float32, device=x.device)
+    nbytes = gmm_post_dense_workspace_bytes(F, I)
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=x.device)
+    with L.on_device(x.device):
+        rc = L.load().ktf_gmm_post_dense_f32(L.ptr(x), F, D, x.stride(0) if F else D, L.ptr(W), L.ptr(gconst), I, L.ptr(P), L.ptr(Xaug),
+                                             L.ptr(ll), L.ptr(ws), nbytes, L.stream_ptr())
+    L.check(rc, "ktf_gmm_post_dense_f32")
+    return P, Xaug, ll
+
+
+def gmm_acc_workspace_bytes(F, I, D, n, full):
+    b = int(L.load().ktf_gmm_acc_workspace_bytes(int(F), int(I), int(D), int(n), int(bool(full))))
+    if b < 0:
+        L.check(b, "ktf_gmm_acc_workspace_bytes")
+    return b
+
+
+def gmm_acc(x, gauss, post, occ, mean_acc, second_acc):
+    """GMM EM statistics on the pairs gauss / post (F, n) of frames x (F, D) fp32, added in place to the fp64 device accumulators occ
+    (I), mean_acc (I, D) and second_acc: var_acc (I, D) = the diagonal form, cov_acc (I, D, D) = the full form. ktf_gmm_acc_f64."""
+    F, D = x.shape
+    I, n = occ.shape[0], gauss.shape[1]
+    full = second_acc.dim() == 3
+    if tuple(gauss.shape) != (F, n) or tuple(post.shape) != (F, n) or tuple(mean_acc.shape) != (I, D) or \
+            tuple(second_acc.shape) != ((I, D, D) if full else (I, D)) or \
+            any(t.dtype != torch.float64 or not t.is_contiguous() for t in (occ, mean_acc, second_acc)) or \
+            gauss.dtype != torch.int32 or post.dtype != torch.float32 or not gauss.is_contiguous() or not post.is_contiguous():
+        raise ValueError("gmm_acc: need gauss int32 / post fp32 (F, n) and contiguous fp64 occ (I), mean_acc (I, D), "
+                         "second_acc (I, D) or (I, D, D)")
+    nbytes = gmm_acc_workspace_bytes(F, I, D, n, full)
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=x.device)
+    with L.on_device(x.device):
+        rc = L.load().ktf_gmm_acc_f64(L.ptr(x), F, D, x.stride(0) if F else D, L.ptr(gauss), L.ptr(post), n, I, int(full), L.ptr(occ),
+                                      L.ptr(mean_acc), L.ptr(second_acc), L.ptr(ws), nbytes, L.stream_ptr())
+    L.check(rc, "ktf_gmm_acc_f64")
+
+
 def add_deltas(x, lengths, coeffs, order, window):
     """add-deltas on x (B, T, D) fp32 with a unit inner stride; lengths (B,) int32 on the device or None; coeffs (order + 1,
     2 * order * window + 1) fp32 on the device -> (B, T, D * (order + 1)) fp32, ktf_add_deltas_f32."""

@@ -7,7 +7,10 @@ cost grows with N or S run on the GPU (csrc/plda_train.hip, fp64); the D x D fac
 are host NumPy arrays (compute_plda: a ktf.layers.PLDA), ready for the ktf.io writers, XvectorExtractor.from_parts and PLDA.
 
 Eigenvector signs: Kaldi's are arbitrary. Here every eigenvector's largest-magnitude component is positive (on a tie the lowest index
-decides). A row's sign leaves PLDA scores and LDA'd, length-normalised scores unchanged."""
+decides). A row's sign leaves PLDA scores and LDA'd, length-normalised scores unchanged.
+
+Further down: i-vector extractor training and UBM training, Kaldi's sid/train_diag_ubm.sh and
+sid/train_full_ubm.sh: E-steps and fp64 EM statistics on the GPU (csrc/gmm_train.hip), updates on the host."""
 
 import numpy as np
 import torch
@@ -361,3 +364,439 @@ def train_ivector_extractor(layer_kwargs, full_ubm, batches, num_iters, ivector_
         objfs.append(stats.objf())
         model = ivector_extractor_est(model, stats, **est_kwargs)
     return model, objfs
+
+
+# ----------------------------------------------------------------------------- UBM training
+def _diag_gmm(g):
+    from . import io as kio
+    return g if isinstance(g, kio.KaldiDiagGmmReader) else kio.KaldiDiagGmmReader(g, binary=True)
+
+
+def _full_gmm(g):
+    from . import io as kio
+    return g if isinstance(g, kio.KaldiFullGmmReader) else kio.KaldiFullGmmReader(g, binary=True)
+
+
+def _check_gmm_shape(I, D):
+    if not (1 <= I <= L.IVECTOR_MAX_GAUSS and 1 <= D <= L.IVECTOR_MAX_FEAT_DIM):
+        raise ValueError(f"GMM shape (I={I}, D={D}) outside I <= {L.IVECTOR_MAX_GAUSS}, D <= {L.IVECTOR_MAX_FEAT_DIM}")
+
+
+def _gmm_frames(feats, D, lengths, mask):
+    """feats (B, T, D), or (F, D) = one utterance -> the selected frames (F, D) end to end, as IvectorExtractor.posteriors lays them."""
+    from .layers import select_frames
+    L.require_gpu()
+    if isinstance(feats, torch.Tensor) and feats.dim() == 2:
+        feats = feats[None]
+    return select_frames(feats, D, lengths, mask)[0]
+
+
+def _device_consts(gmm, device, make):
+    """The model's device arrays, uploaded once per model object and device."""
+    cache = gmm.__dict__.setdefault("_deviceConsts", {})
+    key = str(torch.device(device))
+    if key not in cache:
+        cache[key] = tuple(torch.as_tensor(np.ascontiguousarray(a), device=device) for a in make())
+    return cache[key]
+
+
+def _diag_consts(d, device):
+    """W (2D, I) = [means_invvars^T; -inv_vars^T / 2] and gconst as ktf_ivector_post_f32 takes them, means_invvars, inv_vars."""
+    f = np.float32
+    return _device_consts(d, device, lambda: (np.concatenate([d.means_invvars.astype(f).T, (f(-0.5) * d.inv_vars.astype(f)).T]),
+                                              d.gconsts.astype(f), d.means_invvars.astype(f), d.inv_vars.astype(f)))
+
+
+def _full_consts(g, device):
+    f = np.float32
+    return _device_consts(g, device, lambda: (g.means_invcovars.astype(f), g.inv_covars.astype(f), g.gconsts.astype(f)))
+
+
+def _max_frames(nbytes, limit, n):
+    """The most frames F (F * n < 2^31, at least one) for which nbytes(F) <= limit."""
+    lo, hi = 1, ((1 << 31) - 1) // max(int(n), 1)
+    if nbytes(hi) <= limit:
+        return hi
+    while hi - lo > 1:
+        mid = (lo + hi) // 2
+        if nbytes(mid) <= limit:
+            lo = mid
+        else:
+            hi = mid
+    return lo
+
+
+def select_gaussians(dubm, feats, n, lengths=None, mask=None):
+    """gmm-gselect --n=n: the n Gaussians of the diagonal GMM `dubm` (a path to final.dubm, an io.KaldiDiagGmmReader or
+    io.DiagGmmModel) with the largest log-likelihood per frame (ties: the lower index; ktf_ivector_post_f32 with min_post = 0) ->
+    gselect (F, n) int32 on the device, -1 beyond min(n, I). Frames are laid end to end as IvectorExtractor.posteriors lays them."""
+    d = _diag_gmm(dubm)
+    _check_gmm_shape(d.numGauss, d.featDim)
+    if not 1 <= int(n) <= L.IVECTOR_MAX_GSELECT:
+        raise ValueError(f"n {n} outside 1 .. {L.IVECTOR_MAX_GSELECT}")
+    x = _gmm_frames(feats, d.featDim, lengths, mask)
+    W, gc, _, _ = _diag_consts(d, x.device)
+    with L.launch_scope(x.device):
+        return ops.ivector_post(x, W, gc, int(n), 0.0)[0]
+
+
+class _GmmStats:
+    """fp64 device accumulators of a GMM's EM statistics (allocated on the device of the first batch): occ (I), mean_acc (I, D) and
+    the second-order term; loglike_sum = the sum of the frames' log-likelihoods under the model the statistics are taken with,
+    frames = the frames counted (those with a non-empty Gaussian list)."""
+    full = False
+
+    def __init__(self, gmm):
+        g = (_full_gmm if self.full else _diag_gmm)(gmm)
+        _check_gmm_shape(g.numGauss, g.featDim)
+        self.shape = (int(g.numGauss), int(g.featDim))
+        self.device = None
+        self.loglike_sum, self.frames = 0.0, 0
+
+    def _second(self):
+        return self.cov_acc if self.full else self.var_acc
+
+    def _alloc(self, device):
+        if self.device is not None:
+            if torch.device(device) != self.device:
+                raise ValueError(f"the statistics live on {self.device}, the batch on {device}")
+            return
+        I, D = self.shape
+        self.device = torch.device(device)
+        z = lambda *sh: torch.zeros(sh, dtype=torch.float64, device=self.device)  # noqa: E731
+        self.occ, self.mean_acc = z(I), z(I, D)
+        if self.full:
+            self.cov_acc = z(I, D, D)
+        else:
+            self.var_acc = z(I, D)
+
+    def merge(self, other):
+        """gmm-global-sum-accs / fgmm-global-sum-accs: add another object's statistics (taken with the same model) to this one."""
+        if type(other) is not type(self) or other.shape != self.shape:
+            raise ValueError(f"cannot merge statistics of shape {getattr(other, 'shape', None)} into {self.shape}")
+        if other.device is not None:
+            self._alloc(other.device)
+            self.occ.add_(other.occ)
+            self.mean_acc.add_(other.mean_acc)
+            self._second().add_(other._second())
+        self.loglike_sum += other.loglike_sum
+        self.frames += other.frames
+        return self
+
+    def host(self):
+        """(occ (I), mean_acc (I, D), the second-order accumulator) as NumPy fp64 copies."""
+        I, D = self.shape
+        if self.device is None:
+            return np.zeros(I), np.zeros((I, D)), np.zeros((I, D, D) if self.full else (I, D))
+        return self.occ.cpu().numpy(), self.mean_acc.cpu().numpy(), self._second().cpu().numpy()
+
+    def objf(self):
+        """The mean frame log-likelihood of the accumulated data under the model the statistics were taken with."""
+        if self.frames < 1:
+            raise ValueError("objf: no frames accumulated")
+        return self.loglike_sum / self.frames
+
+
+class DiagGmmStats(_GmmStats):
+    """Kaldi's AccumDiagGmm (gmm-global-acc-stats): occ (I), mean_acc (I, D), var_acc (I, D) = sum p x^2."""
+    full = False
+
+
+class FullGmmStats(_GmmStats):
+    """Kaldi's AccumFullGmm (fgmm-global-acc-stats): occ (I), mean_acc (I, D), cov_acc (I, D, D) = sum p x x^T."""
+    full = True
+
+
+def _check_acc(stats, g, x, gselect, kind):
+    if not isinstance(stats, kind) or stats.shape != (g.numGauss, g.featDim):
+        raise ValueError(f"statistics of shape {getattr(stats, 'shape', None)} do not match the model {(g.numGauss, g.featDim)}")
+    if gselect is None:
+        return None
+    if not isinstance(gselect, torch.Tensor) or gselect.dim() != 2 or gselect.shape[0] != x.shape[0] or \
+            not 1 <= gselect.shape[1] <= L.IVECTOR_MAX_GSELECT:
+        raise ValueError(f"gselect must be ({x.shape[0]}, n) with 1 <= n <= {L.IVECTOR_MAX_GSELECT}, got "
+                         f"{tuple(getattr(gselect, 'shape', ()))}")
+    return gselect.to(device=x.device, dtype=torch.int32).contiguous()
+
+
+def acc_diag_gmm(stats, gmm, feats, gselect=None, lengths=None, mask=None, workspace_limit=1 << 30):
+    """gmm-global-acc-stats on one batch, added to `stats` (DiagGmmStats) in place. With gselect (F, n) int32 (select_gaussians; an
+    index outside [0, I) is skipped) the posteriors are taken over each frame's list (ktf_gmm_post_preselect_f32) and the
+    statistics over the pairs (ktf_gmm_acc_f64). With gselect=None every Gaussian takes part (the E-step of
+    gmm-global-init-from-feats): ktf_gmm_post_dense_f32, then ktf_atb_f64 into (I, 2D + 1). The frames run in chunks whose workspace
+    stays under workspace_limit bytes, added in order. -> the number of chunks."""
+    d = _diag_gmm(gmm)
+    _check_gmm_shape(d.numGauss, d.featDim)
+    I, D = d.numGauss, d.featDim
+    x = _gmm_frames(feats, D, lengths, mask)
+    gsel = _check_acc(stats, d, x, gselect, DiagGmmStats)
+    F = x.shape[0]
+    if F == 0:
+        return 0
+    stats._alloc(x.device)
+    W, gc, mi, iv = _diag_consts(d, x.device)
+    chunks = 0
+    with L.launch_scope(x.device):
+        if gsel is None:
+            per = I * 4 + I * 8 + (2 * D + 1) * 8                     # workspace, P and Xaug per frame
+            step = int(max(1, min(F, int(workspace_limit) // per)))
+            tmp = torch.zeros((I, 2 * D + 1), dtype=torch.float64, device=x.device)
+            ll_sum = 0.0
+            for lo in range(0, F, step):
+                P, Xaug, ll = ops.gmm_post_dense(x[lo:lo + step], W, gc)
+                ops.atb_f64(P, Xaug, tmp)
+                ll_sum += float(ll.double().sum())
+                chunks += 1
+            stats.occ.add_(tmp[:, 0])
+            stats.mean_acc.add_(tmp[:, 1:D + 1])
+            stats.var_acc.add_(tmp[:, D + 1:])
+            stats.loglike_sum += ll_sum
+            stats.frames += F
+        else:
+            n = gsel.shape[1]
+            step = min(F, _max_frames(lambda f: ops.gmm_acc_workspace_bytes(f, I, D, n, False), int(workspace_limit), n))
+            valid = torch.zeros((1,), dtype=torch.int32, device=x.device)
+            ll_sum = 0.0
+            for lo in range(0, F, step):
+                xs, gs = x[lo:lo + step], gsel[lo:lo + step]
+                post, ll = ops.gmm_post_preselect(xs, gs, mi, iv, gc, valid)
+                ops.gmm_acc(xs, gs, post, stats.occ, stats.mean_acc, stats.var_acc)
+                ll_sum += float(ll.double().sum())
+                chunks += 1
+            stats.loglike_sum += ll_sum
+            stats.frames += int(valid.item())
+    return chunks
+
+
+def acc_full_gmm(stats, gmm, feats, gselect, lengths=None, mask=None, workspace_limit=1 << 30):
+    """fgmm-global-acc-stats --gselect on one batch, added to `stats` (FullGmmStats) in place: the posteriors of each frame's list
+    under the full GMM with their log-likelihood (ktf_fgmm_post_ll_f32, no pruning), then ktf_gmm_acc_f64's full form. Chunked as
+    acc_diag_gmm. -> the number of chunks."""
+    g = _full_gmm(gmm)
+    _check_gmm_shape(g.numGauss, g.featDim)
+    I, D = g.numGauss, g.featDim
+    x = _gmm_frames(feats, D, lengths, mask)
+    if gselect is None:
+        raise ValueError("acc_full_gmm needs gselect (select_gaussians)")
+    gsel = _check_acc(stats, g, x, gselect, FullGmmStats)
+    F = x.shape[0]
+    if F == 0:
+        return 0
+    stats._alloc(x.device)
+    mic, ic, gc = _full_consts(g, x.device)
+    n = gsel.shape[1]
+    step = min(F, _max_frames(lambda f: ops.fgmm_workspace_bytes(f, I, D, n) + ops.gmm_acc_workspace_bytes(f, I, D, n, True),
+                              int(workspace_limit), n))
+    chunks, ll_sum, frames = 0, 0.0, 0
+    with L.launch_scope(x.device):
+        for lo in range(0, F, step):
+            xs = x[lo:lo + step]
+            gauss, post, ll = ops.fgmm_post_ll(xs, gsel[lo:lo + step], mic, ic, gc, 0.0)
+            ops.gmm_acc(xs, gauss, post, stats.occ, stats.mean_acc, stats.cov_acc)
+            ll_sum += float(ll.double().sum())
+            frames += int((gauss[:, 0] >= 0).sum())
+            chunks += 1
+    stats.loglike_sum += ll_sum
+    stats.frames += frames
+    return chunks
+
+
+def _diag_params(d):
+    """(means, variances) in fp64 from the stored fp32 fields."""
+    var = 1.0 / d.inv_vars.astype(np.float64)
+    return d.means_invvars.astype(np.float64) * var, var
+
+
+def _diag_model(weights, mean, var):
+    from . import io as kio
+    return kio.DiagGmmModel(weights, mean / var, 1.0 / var)
+
+
+def _est_gate(occ, min_gaussian_weight, min_gaussian_occupancy):
+    tot = occ.sum()
+    if not tot > 0:
+        raise ValueError("no statistics accumulated")
+    prob = occ / tot
+    return prob, (occ > float(min_gaussian_occupancy)) & (prob > float(min_gaussian_weight))
+
+
+def diag_gmm_est(gmm, stats, min_gaussian_weight=1e-5, min_gaussian_occupancy=10.0, min_variance=0.001, remove_low_count_gaussians=True):
+    """gmm-global-est (MleDiagGmmUpdate, all of weights, means and variances) -> io.DiagGmmModel. prob_i = occ_i / sum occ; a Gaussian
+    with occ_i > min_gaussian_occupancy and prob_i > min_gaussian_weight gets mean = mean_acc / occ, var = max(var_acc / occ -
+    mean^2, min_variance), weight prob_i; any other is removed or, with remove_low_count_gaussians=False, keeps its mean and
+    variance and takes weight prob_i. Weights are renormalised. ValueError if every Gaussian would be removed. The model's
+    `estInfo`: {"removed", "floored" (variance elements floored), "kept" (the indices of the Gaussians kept)}."""
+    d = _diag_gmm(gmm)
+    if not isinstance(stats, DiagGmmStats) or stats.shape != (d.numGauss, d.featDim):
+        raise ValueError(f"statistics of shape {getattr(stats, 'shape', None)} do not match the model {(d.numGauss, d.featDim)}")
+    occ, macc, vacc = stats.host()
+    prob, ok = _est_gate(occ, min_gaussian_weight, min_gaussian_occupancy)
+    mean, var = _diag_params(d)
+    o = occ[ok][:, None]
+    m = macc[ok] / o
+    v = vacc[ok] / o - m * m
+    floored = int((v < float(min_variance)).sum())
+    mean[ok], var[ok] = m, np.maximum(v, float(min_variance))
+    keep = ok if remove_low_count_gaussians else np.ones_like(ok)
+    if not keep.any():
+        raise ValueError("gmm-global-est: every Gaussian would be removed (too few frames)")
+    w = prob[keep]
+    out = _diag_model(w / w.sum(), mean[keep], var[keep])
+    out.estInfo = {"removed": int((~keep).sum()), "floored": floored, "kept": np.nonzero(keep)[0]}
+    return out
+
+
+def full_gmm_est(gmm, stats, min_gaussian_weight=1e-5, min_gaussian_occupancy=100.0, variance_floor=0.001, max_condition=1e5,
+                 remove_low_count_gaussians=True):
+    """fgmm-global-est (MleFullGmmUpdate) -> io.FullGmmModel. The gate of diag_gmm_est; cov = cov_acc / occ - mean mean^T,
+    symmetrised, = V diag(lam) V^T with lam floored at max(variance_floor, lam_max / max_condition); inv_covars = V diag(1 / lam)
+    V^T, means_invcovars = inv_covars mean. `estInfo`: {"removed", "floored" (Gaussians with a floored eigenvalue), "kept"}."""
+    from . import io as kio
+    g = _full_gmm(gmm)
+    if not isinstance(stats, FullGmmStats) or stats.shape != (g.numGauss, g.featDim):
+        raise ValueError(f"statistics of shape {getattr(stats, 'shape', None)} do not match the model {(g.numGauss, g.featDim)}")
+    occ, macc, cacc = stats.host()
+    prob, ok = _est_gate(occ, min_gaussian_weight, min_gaussian_occupancy)
+    ic = g.inv_covars.astype(np.float64)
+    mic = g.means_invcovars.astype(np.float64)
+    floored = 0
+    if ok.any():
+        o = occ[ok]
+        m = macc[ok] / o[:, None]
+        cov = cacc[ok] / o[:, None, None] - m[:, :, None] * m[:, None, :]
+        lam, V = np.linalg.eigh(0.5 * (cov + np.swapaxes(cov, 1, 2)))
+        floor = np.maximum(float(variance_floor), lam.max(1) / float(max_condition))
+        floored = int((lam < floor[:, None]).any(1).sum())
+        lam = np.maximum(lam, floor[:, None])
+        inv = np.matmul(V / lam[:, None, :], np.swapaxes(V, 1, 2))
+        ic[ok] = 0.5 * (inv + np.swapaxes(inv, 1, 2))
+        mic[ok] = np.einsum("ide,ie->id", ic[ok], m)
+    keep = ok if remove_low_count_gaussians else np.ones_like(ok)
+    if not keep.any():
+        raise ValueError("fgmm-global-est: every Gaussian would be removed (too few frames)")
+    w = prob[keep]
+    out = kio.FullGmmModel(w / w.sum(), mic[keep], ic[keep])
+    out.estInfo = {"removed": int((~keep).sum()), "floored": floored, "kept": np.nonzero(keep)[0]}
+    return out
+
+
+def split_largest(weights, mean, var, target, normals):
+    """Kaldi's DiagGmm::Split on fp64 arrays: until there are `target` Gaussians, the one of largest weight (ties: the lower index)
+    halves its weight and is copied; the copy's mean is + 0.1 sqrt(var) * r, the original's - 0.1 sqrt(var) * r, r = next(normals)
+    (D standard normal values). -> (weights, mean, var)."""
+    w, m, v = list(weights), list(mean), list(var)
+    while len(w) < target:
+        i = int(np.argmax(w))
+        r = np.asarray(next(normals), dtype=np.float64)
+        w[i] *= 0.5
+        step = 0.1 * np.sqrt(v[i]) * r
+        w.append(w[i])
+        m.append(m[i] + step)
+        v.append(v[i].copy())
+        m[i] = m[i] - step
+    return np.asarray(w), np.asarray(m), np.asarray(v)
+
+
+def init_diag_ubm(feats, num_gauss, num_gauss_init=None, num_iters=20, num_frames=500000, lengths=None, mask=None, seed=0,
+                  workspace_limit=1 << 30, **est):
+    """gmm-global-init-from-feats --num-gauss --num-gauss-init --num-iters --num-frames -> (io.DiagGmmModel, [objf of iteration 0,
+    1, ...]). Every random draw comes from rng = np.random.default_rng(seed) on the host, in this order: (1) if there are more than
+    num_frames frames, rng.choice(F, num_frames, replace=False), sorted ascending; (2) rng.choice(F', num_gauss_init, replace=False),
+    the frames that become the initial means; (3) one rng.standard_normal(D) per split, in split order. The initial model has the
+    global variance (floored at 1e-10) and uniform weights. Then num_iters dense EM iterations (acc_diag_gmm without gselect,
+    diag_gmm_est(**est)); after each the model is split (split_largest) up to cur = min(num_gauss, cur + (num_gauss -
+    num_gauss_init) // max(1, num_iters // 2)), cur starting at num_gauss_init. num_gauss_init defaults to num_gauss // 2 (at least 1).
+    Kaldi's own generator is not reproduced."""
+    num_gauss, num_iters = int(num_gauss), int(num_iters)
+    ngi = max(1, num_gauss // 2) if num_gauss_init is None else int(num_gauss_init)
+    if not 1 <= ngi <= num_gauss <= L.IVECTOR_MAX_GAUSS or num_iters < 1 or int(num_frames) < 1:
+        raise ValueError(f"need 1 <= num_gauss_init ({ngi}) <= num_gauss ({num_gauss}) <= {L.IVECTOR_MAX_GAUSS}, num_iters >= 1 and "
+                         "num_frames >= 1")
+    D = feats.shape[-1] if isinstance(feats, torch.Tensor) else 0
+    if not 1 <= D <= L.IVECTOR_MAX_FEAT_DIM:
+        raise ValueError(f"feature dim {D} outside 1 .. {L.IVECTOR_MAX_FEAT_DIM}")
+    x = _gmm_frames(feats, D, lengths, mask)
+    rng = np.random.default_rng(seed)
+    if x.shape[0] > int(num_frames):
+        idx = np.sort(rng.choice(x.shape[0], int(num_frames), replace=False))
+        x = x[torch.as_tensor(idx, device=x.device)].contiguous()
+    F = x.shape[0]
+    if F < ngi:
+        raise ValueError(f"{F} frames cannot seed {ngi} Gaussians")
+    first = rng.choice(F, ngi, replace=False)
+    xd = x.double()
+    gmean = xd.mean(0)
+    gvar = ((xd * xd).mean(0) - gmean * gmean).clamp_min(1e-10).cpu().numpy()
+    mean = x[torch.as_tensor(first, device=x.device)].double().cpu().numpy()
+    model = _diag_model(np.full(ngi, 1.0 / ngi), mean, np.tile(gvar, (ngi, 1)))
+    normals = (rng.standard_normal(D) for _ in iter(int, 1))            # one draw per split, as long as splits are asked for
+    inc = (num_gauss - ngi) // max(1, num_iters // 2)
+    cur, objfs = ngi, []
+    for _ in range(num_iters):
+        stats = DiagGmmStats(model)
+        acc_diag_gmm(stats, model, x, workspace_limit=workspace_limit)
+        objfs.append(stats.objf())
+        model = diag_gmm_est(model, stats, **est)
+        cur = min(num_gauss, cur + inc)
+        if cur > model.numGauss:
+            m, v = _diag_params(model)
+            model = _diag_model(*split_largest(model.weights.astype(np.float64), m, v, cur, normals))
+    return model, objfs
+
+
+def diag_to_full(dubm):
+    """gmm-global-to-fgmm: the same weights and means, inv_covars = diag(inv_vars) -> io.FullGmmModel."""
+    from . import io as kio
+    d = _diag_gmm(dubm)
+    I, D = d.numGauss, d.featDim
+    ic = np.zeros((I, D, D), np.float32)
+    ic[:, np.arange(D), np.arange(D)] = d.inv_vars.astype(np.float32)
+    return kio.FullGmmModel(d.weights, d.means_invvars, ic)
+
+
+def _remap_gselect(gsel, kept, I):
+    """The cached lists after a removal: old index -> new index, a removed Gaussian -> -1."""
+    table = np.full(I + 1, -1, np.int32)                     # entry I serves the indices outside [0, I)
+    table[kept] = np.arange(len(kept), dtype=np.int32)
+    t = torch.as_tensor(table, device=gsel.device)
+    g = gsel.long()
+    return t[torch.where((g >= 0) & (g < I), g, torch.full_like(g, I))]
+
+
+def _train_ubm(model, sel_model, batches, gselect_n, num_iters, gselect, stats_cls, acc, est, est_kwargs):
+    batches = [tuple(b) if isinstance(b, (tuple, list)) else (b,) for b in batches]
+    if gselect is None:
+        gselect = [select_gaussians(sel_model, b[0], gselect_n, *b[1:]) for b in batches]
+    elif len(gselect) != len(batches):
+        raise ValueError(f"gselect must hold one (F, n) tensor per batch ({len(batches)}), got {len(gselect)}")
+    gselect = list(gselect)
+    remove_last = bool(est_kwargs.pop("remove_low_count_gaussians", True))
+    objfs = []
+    for it in range(int(num_iters)):
+        stats = stats_cls(model)
+        for b, gs in zip(batches, gselect):
+            acc(stats, model, b[0], gs, *b[1:])
+        objfs.append(stats.objf())
+        I = model.numGauss
+        model = est(model, stats, remove_low_count_gaussians=remove_last and it == int(num_iters) - 1, **est_kwargs)
+        if model.estInfo["removed"]:
+            gselect = [_remap_gselect(gs.to(torch.int32), model.estInfo["kept"], I) for gs in gselect]
+    return model, objfs
+
+
+def train_diag_ubm(dubm, batches, gselect_n=30, num_iters=4, gselect=None, **est):
+    """sid/train_diag_ubm.sh after the initialisation: gmm-gselect once from the incoming model, then num_iters times
+    gmm-global-acc-stats --gselect over `batches` (a list of argument tuples (feats[, lengths[, mask]])) and gmm-global-est(**est),
+    low-count Gaussians removed on the last iteration only (the cached lists are remapped, removed entries become -1). `gselect`:
+    one (F, n) tensor per batch in place of the computed lists. -> (io.DiagGmmModel, [objf of each iteration])."""
+    d = _diag_gmm(dubm)
+    return _train_ubm(d, d, batches, gselect_n, num_iters, gselect, DiagGmmStats, acc_diag_gmm, diag_gmm_est, dict(est))
+
+
+def train_full_ubm(fubm, batches, gselect_n=20, num_iters=4, gselect=None, **est):
+    """sid/train_full_ubm.sh: gmm-gselect once from fubm.toDiag() (fgmm-global-to-gmm), then num_iters times fgmm-global-acc-stats
+    --gselect and fgmm-global-est(**est), low-count Gaussians removed on the last iteration only. `fubm`: a path to final.ubm, an
+    io.KaldiFullGmmReader or io.FullGmmModel (diag_to_full). -> (io.FullGmmModel, [objf of each iteration])."""
+    g = _full_gmm(fubm)
+    return _train_ubm(g, None if gselect is not None else g.toDiag(), batches, gselect_n, num_iters, gselect, FullGmmStats, acc_full_gmm,
+                      full_gmm_est, dict(est))
