@@ -43,6 +43,7 @@ void ktf_set_error(const char* fmt, ...);
     } while (0)
 
 static inline int ktf_cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
+static inline int64_t al256(int64_t b) { return (b + 255) & ~(int64_t)255; }       // workspace arrays start 256-byte aligned
 
 #ifdef __HIPCC__
 typedef __attribute__((ext_vector_type(4))) float f32x4;
@@ -59,6 +60,13 @@ __device__ __forceinline__ double wave_sum_d(double v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;
+}
+
+// LDS written by a wave becomes visible to the same wave's other lanes (no workgroup barrier: the wave works alone)
+__device__ __forceinline__ void wave_lds_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
 // round-to-nearest-even f32 -> bf16 bits (plain cast keeps NaN a NaN; v_cvt_pk_bf16_f32 at -O3)

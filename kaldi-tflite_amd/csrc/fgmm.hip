@@ -1,12 +1,9 @@
 // Full-covariance UBM posteriors on preselected Gaussians (Kaldi's `fgmm-global-gselect-to-post`) and `add-deltas`.
 //
 // A (frame, slot) pair names a D x D matrix, so the pairs are turned round: bucketed by Gaussian, then every bucket is a GEMM.
-//   fg_count_kernel    pairs cut into chunks of FG_CH; per chunk a histogram over the Gaussians in LDS -> table (chunks x I).
-//   fg_colscan_kernel  per Gaussian the exclusive prefix of its table column (chunk order), the total -> cnt.
-//   fg_scan_kernel     exclusive scans over the Gaussians: bucket starts and, with buckets cut into items of FG_ROWS rows so that a
-//                      popular Gaussian is spread over workgroups, item starts.
-//   fg_scatter_kernel  per chunk: pair id -> its bucket, at the chunk's base + an LDS counter (the order inside a chunk's share of a
-//                      bucket is whatever the LDS atomics give; every pair's value is computed alone, so no bit depends on it).
+//   gmm_bucket.hip     the counting sort of the pairs by Gaussian, with the unordered scatter (every pair's value is computed alone,
+//                      so no bit depends on the order inside a bucket), and the cut of every bucket into items of FG_ROWS rows, so
+//                      that a popular Gaussian is spread over workgroups.
 //   fg_quad_kernel     one workgroup per item: inv_covars_g and means_invcovars_g in LDS; each wave gathers 32 rows of x at a time
 //                      into LDS (transposed) and runs Y^T = inv_covars_g . X^T on v_mfma_f32_32x32x2_f32 (exact fp32, k ascending):
 //                      the frame is on the lane, Y's dimensions in the accumulators, so the row dot sum_j x_j (mi_j - y_j / 2) is
@@ -14,36 +11,26 @@
 //   fg_softmax_kernel  one wave per frame: softmax over the listed slots (and, for ktf_fgmm_post_ll_f32, the frame's log-likelihood
 //                      before pruning), prune below min_post, renormalise, sort.
 //   adddeltas_kernel   one thread per output element, unfused multiply and add (fp contract off) in tap order.
-#include "common.h"
+#include "gmm_bucket.h"
 
 namespace {
 
-constexpr int FG_CH = 32768;        // pairs per bucketing workgroup
 constexpr int FG_THREADS = 256;
 constexpr int FG_WAVES = FG_THREADS / 64;
 constexpr int FG_ROWS = 512;        // rows of a bucket per quadratic-form workgroup
 constexpr int FG_XLD = 33;          // row stride of the transposed x tile (32 frames + 1: conflict-free transposed writes)
-constexpr int FG_SCAN = 1024;       // threads of the scan kernel: KTF_IVECTOR_MAX_GAUSS / 8
-
-__host__ __device__ inline int64_t fal256(int64_t b) { return (b + 255) & ~(int64_t)255; }
 
 struct FgLayout {
-    int64_t table, cnt, bstart, wstart, pairs, ll, total;
-    int nc;
+    SecLayout sec;
+    int64_t istart, ll, total;
 };
 
 FgLayout fg_layout(int64_t F, int64_t I, int64_t n) {
     FgLayout l;
-    const int64_t P = F * n;
-    l.nc = (int)((P + FG_CH - 1) / FG_CH);
-    if (l.nc < 1) l.nc = 1;
-    int64_t at = 0;
-    l.table = at;  at += fal256((int64_t)l.nc * I * 4);
-    l.cnt = at;    at += fal256(I * 4);
-    l.bstart = at; at += fal256((I + 1) * 4);
-    l.wstart = at; at += fal256((I + 1) * 4);
-    l.pairs = at;  at += fal256(P * 4);
-    l.ll = at;     at += fal256(P * 4);
+    l.sec = sec_layout(F, I, n, false);
+    int64_t at = l.sec.bytes;
+    l.istart = at; at += al256((I + 1) * 4);
+    l.ll = at;     at += al256(F * n * 4);
     l.total = at;
     return l;
 }
@@ -52,92 +39,10 @@ inline int fg_dk(int D) { return (D + 1) & ~1; }
 inline int fg_dp(int D) { return (D + 31) & ~31; }
 inline size_t fg_quad_lds(int D) { return (size_t)4 * (fg_dk(D) * fg_dp(D) + fg_dp(D) + FG_WAVES * fg_dp(D) * FG_XLD); }
 
-__global__ void __launch_bounds__(FG_THREADS) fg_count_kernel(const int* __restrict__ gsel, int64_t P, int I, int* __restrict__ table) {
-    extern __shared__ int fg_hist[];
-    const int tid = threadIdx.x;
-    for (int g = tid; g < I; g += FG_THREADS) fg_hist[g] = 0;
-    __syncthreads();
-    const int64_t e0 = (int64_t)blockIdx.x * FG_CH, e1 = e0 + FG_CH < P ? e0 + FG_CH : P;
-    for (int64_t e = e0 + tid; e < e1; e += FG_THREADS) {
-        const int g = gsel[e];
-        if (g >= 0 && g < I) atomicAdd(&fg_hist[g], 1);
-    }
-    __syncthreads();
-    for (int g = tid; g < I; g += FG_THREADS) table[(int64_t)blockIdx.x * I + g] = fg_hist[g];
-}
-
-__global__ void __launch_bounds__(FG_THREADS) fg_colscan_kernel(int* __restrict__ table, int nc, int I, int* __restrict__ cnt) {
-    const int g = blockIdx.x * FG_THREADS + threadIdx.x;
-    if (g >= I) return;
-    int run = 0;
-    for (int c = 0; c < nc; ++c) {
-        const int v = table[(int64_t)c * I + g];
-        table[(int64_t)c * I + g] = run;
-        run += v;
-    }
-    cnt[g] = run;
-}
-
-// bstart[g] = sum_{h < g} cnt[h], wstart[g] = sum_{h < g} ceil(cnt[h] / FG_ROWS); entry I holds the totals
-__global__ void __launch_bounds__(FG_SCAN) fg_scan_kernel(const int* __restrict__ cnt, int I, int* __restrict__ bstart, int* __restrict__ wstart) {
-    __shared__ int sb[2][FG_SCAN];
-    __shared__ int sw[2][FG_SCAN];
-    const int tid = threadIdx.x;
-    const int per = (I + FG_SCAN - 1) / FG_SCAN;
-    const int g0 = tid * per, g1 = g0 + per < I ? g0 + per : I;
-    int b = 0, w = 0;
-    for (int g = g0; g < g1; ++g) {
-        b += cnt[g];
-        w += (cnt[g] + FG_ROWS - 1) / FG_ROWS;
-    }
-    sb[0][tid] = b;
-    sw[0][tid] = w;
-    __syncthreads();
-    int cur = 0;
-    for (int o = 1; o < FG_SCAN; o <<= 1) {
-        const int vb = sb[cur][tid] + (tid >= o ? sb[cur][tid - o] : 0);
-        const int vw = sw[cur][tid] + (tid >= o ? sw[cur][tid - o] : 0);
-        sb[cur ^ 1][tid] = vb;
-        sw[cur ^ 1][tid] = vw;
-        cur ^= 1;
-        __syncthreads();
-    }
-    int rb = sb[cur][tid] - b, rw = sw[cur][tid] - w;       // exclusive
-    for (int g = g0; g < g1; ++g) {
-        bstart[g] = rb;
-        wstart[g] = rw;
-        rb += cnt[g];
-        rw += (cnt[g] + FG_ROWS - 1) / FG_ROWS;
-    }
-    if (tid == FG_SCAN - 1) {
-        bstart[I] = sb[cur][tid];
-        wstart[I] = sw[cur][tid];
-    }
-}
-
-__global__ void __launch_bounds__(FG_THREADS) fg_scatter_kernel(const int* __restrict__ gsel, int64_t P, int I, const int* __restrict__ table,
-                                                                 const int* __restrict__ bstart, int* __restrict__ pairs) {
-    extern __shared__ int fg_cur[];
-    const int tid = threadIdx.x;
-    for (int g = tid; g < I; g += FG_THREADS) fg_cur[g] = bstart[g] + table[(int64_t)blockIdx.x * I + g];
-    __syncthreads();
-    const int64_t e0 = (int64_t)blockIdx.x * FG_CH, e1 = e0 + FG_CH < P ? e0 + FG_CH : P;
-    for (int64_t e = e0 + tid; e < e1; e += FG_THREADS) {
-        const int g = gsel[e];
-        if (g >= 0 && g < I) pairs[atomicAdd(&fg_cur[g], 1)] = (int)e;      // < P by construction of the counts
-    }
-}
-
-__device__ __forceinline__ void wave_lds_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 // NJ = Dp / 32 blocks of 32 output dimensions. S = inv_covars (I, D, D) row-major, symmetric (read as S[k][j]).
 template <int NJ>
 __global__ void __launch_bounds__(FG_THREADS) fg_quad_kernel(const float* __restrict__ x, int D, int64_t ldx, int n, const int* __restrict__ pairs,
-                                                              const int* __restrict__ bstart, const int* __restrict__ wstart, int I,
+                                                              const int* __restrict__ start, const int* __restrict__ istart, int I,
                                                               const float* __restrict__ mic, const float* __restrict__ S,
                                                               const float* __restrict__ gconst, float* __restrict__ ll) {
     constexpr int Dp = NJ * 32;
@@ -147,17 +52,9 @@ __global__ void __launch_bounds__(FG_THREADS) fg_quad_kernel(const float* __rest
     float* ms = Ss + Dk * Dp;                    // (Dp): means_invcovars_g, zero beyond D
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, r = lane & 31, h = lane >> 5;
     float* Xs = ms + Dp + wv * Dp * FG_XLD;      // this wave's (Dp, 32) tile of x^T, row stride FG_XLD
-    const int w = blockIdx.x;
-    if (w >= wstart[I]) return;
-    int lo = 0, hi = I;                          // wstart[lo] <= w < wstart[hi]
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (wstart[mid] <= w) lo = mid;
-        else hi = mid;
-    }
-    const int g = lo;
-    const int r0 = bstart[g] + (w - wstart[g]) * FG_ROWS;
-    const int r1 = r0 + FG_ROWS < bstart[g + 1] ? r0 + FG_ROWS : bstart[g + 1];
+    const BucketItem it = bucket_item(blockIdx.x, start, istart, I, FG_ROWS);
+    if (it.g < 0) return;
+    const int g = it.g, r0 = it.r0, r1 = it.r1;
     const float* Sg = S + (int64_t)g * D * D;
     for (int e = tid; e < Dk * Dp; e += FG_THREADS) {
         const int k = e / Dp, j = e - k * Dp;
@@ -299,24 +196,16 @@ __global__ void __launch_bounds__(256) adddeltas_kernel(const float* __restrict_
 }
 
 template <int NJ>
-void fg_launch_quad(int items, size_t lds, hipStream_t st, const float* x, int D, int64_t ldx, int n, const int* pairs, const int* bstart,
-                    const int* wstart, int I, const float* mic, const float* S, const float* gconst, float* ll) {
+void fg_launch_quad(int items, size_t lds, hipStream_t st, const float* x, int D, int64_t ldx, int n, const int* pairs, const int* start,
+                    const int* istart, int I, const float* mic, const float* S, const float* gconst, float* ll) {
     KTF_LDS_ONCE(fg_quad_lds(NJ * 32), fg_quad_kernel<NJ>);
-    hipLaunchKernelGGL(fg_quad_kernel<NJ>, dim3(items), dim3(FG_THREADS), lds, st, x, D, ldx, n, pairs, bstart, wstart, I, mic, S, gconst, ll);
-}
-
-int fg_check_shape(const char* who, int64_t F, int32_t I, int32_t D, int32_t n) {
-    KTF_REQUIRE(D >= 1 && D <= KTF_IVECTOR_MAX_FEAT_DIM, "%s: feature dim %d outside 1 .. %d", who, (int)D, KTF_IVECTOR_MAX_FEAT_DIM);
-    KTF_REQUIRE(I >= 1 && I <= KTF_IVECTOR_MAX_GAUSS, "%s: %d Gaussians outside 1 .. %d", who, (int)I, KTF_IVECTOR_MAX_GAUSS);
-    KTF_REQUIRE(n >= 1 && n <= KTF_IVECTOR_MAX_GSELECT, "%s: %d slots per frame outside 1 .. %d", who, (int)n, KTF_IVECTOR_MAX_GSELECT);
-    KTF_REQUIRE(F >= 0 && F * n < ((int64_t)1 << 31), "%s: frame count %lld out of range (F * n < 2^31)", who, (long long)F);
-    return KTF_OK;
+    hipLaunchKernelGGL(fg_quad_kernel<NJ>, dim3(items), dim3(FG_THREADS), lds, st, x, D, ldx, n, pairs, start, istart, I, mic, S, gconst, ll);
 }
 
 }  // namespace
 
 extern "C" int64_t ktf_fgmm_workspace_bytes(int64_t F, int32_t I, int32_t D, int32_t n) {
-    const int rc = fg_check_shape("ktf_fgmm_workspace_bytes", F, I, D, n);
+    const int rc = bucket_check_shape("ktf_fgmm_workspace_bytes", F, I, D, n);
     if (rc != KTF_OK) return rc;
     return fg_layout(F, I, n).total;
 }
@@ -324,7 +213,7 @@ extern "C" int64_t ktf_fgmm_workspace_bytes(int64_t F, int32_t I, int32_t D, int
 static int fg_post(const char* who, const float* x, int64_t F, int32_t D, int64_t ldx, const int32_t* gselect, int32_t n,
                    const float* means_invcovars, const float* inv_covars, const float* gconst, int32_t I, float min_post, int32_t* gauss,
                    float* post, float* loglike, void* workspace, size_t workspace_bytes, void* stream) {
-    const int rc = fg_check_shape(who, F, I, D, n);
+    int rc = bucket_check_shape(who, F, I, D, n);
     if (rc != KTF_OK) return rc;
     KTF_REQUIRE(ldx >= D, "%s: ldx %lld < D %d", who, (long long)ldx, (int)D);
     KTF_REQUIRE(min_post >= 0.f && min_post < 1.f, "%s: min_post %g outside [0, 1)", who, (double)min_post);
@@ -334,30 +223,21 @@ static int fg_post(const char* who, const float* x, int64_t F, int32_t D, int64_
     KTF_REQUIRE((int64_t)workspace_bytes >= l.total, "%s: workspace %zu bytes < %lld", who, workspace_bytes, (long long)l.total);
     KTF_REQUIRE(((uintptr_t)workspace & 255) == 0, "%s: workspace not 256-byte aligned", who);
     char* ws = (char*)workspace;
-    int* table = (int*)(ws + l.table);
-    int* cnt = (int*)(ws + l.cnt);
-    int* bstart = (int*)(ws + l.bstart);
-    int* wstart = (int*)(ws + l.wstart);
-    int* pairs = (int*)(ws + l.pairs);
+    const int* start = (const int*)(ws + l.sec.start);
+    const int* pairs = (const int*)(ws + l.sec.pairs);
+    int* istart = (int*)(ws + l.istart);
     float* ll = (float*)(ws + l.ll);
     hipStream_t st = (hipStream_t)stream;
     const int64_t P = F * n;
-    hipLaunchKernelGGL(fg_count_kernel, dim3(l.nc), dim3(FG_THREADS), (size_t)I * 4, st, gselect, P, (int)I, table);
-    KTF_CHECK_LAUNCH(who);
-    hipLaunchKernelGGL(fg_colscan_kernel, dim3(ktf_cdiv(I, FG_THREADS)), dim3(FG_THREADS), 0, st, table, l.nc, (int)I, cnt);
-    KTF_CHECK_LAUNCH(who);
-    hipLaunchKernelGGL(fg_scan_kernel, dim3(1), dim3(FG_SCAN), 0, st, (const int*)cnt, (int)I, bstart, wstart);
-    KTF_CHECK_LAUNCH(who);
-    hipLaunchKernelGGL(fg_scatter_kernel, dim3(l.nc), dim3(FG_THREADS), (size_t)I * 4, st, gselect, P, (int)I, (const int*)table,
-                       (const int*)bstart, pairs);
-    KTF_CHECK_LAUNCH(who);
-    const int items = (int)((P + FG_ROWS - 1) / FG_ROWS) + I;       // an upper bound of wstart[I]; the rest exit at once
+    if ((rc = sec_bucket(who, gselect, P, (int)I, l.sec, ws, st)) != KTF_OK) return rc;
+    if ((rc = bucket_items(who, start, (int)I, FG_ROWS, istart, nullptr, st)) != KTF_OK) return rc;
+    const int items = (int)((P + FG_ROWS - 1) / FG_ROWS) + I;       // an upper bound of istart[I]; the rest exit at once
     const size_t lds = fg_quad_lds(D);
     switch (fg_dp(D) / 32) {
-        case 1: fg_launch_quad<1>(items, lds, st, x, D, ldx, n, pairs, bstart, wstart, I, means_invcovars, inv_covars, gconst, ll); break;
-        case 2: fg_launch_quad<2>(items, lds, st, x, D, ldx, n, pairs, bstart, wstart, I, means_invcovars, inv_covars, gconst, ll); break;
-        case 3: fg_launch_quad<3>(items, lds, st, x, D, ldx, n, pairs, bstart, wstart, I, means_invcovars, inv_covars, gconst, ll); break;
-        default: fg_launch_quad<4>(items, lds, st, x, D, ldx, n, pairs, bstart, wstart, I, means_invcovars, inv_covars, gconst, ll); break;
+        case 1: fg_launch_quad<1>(items, lds, st, x, D, ldx, n, pairs, start, istart, I, means_invcovars, inv_covars, gconst, ll); break;
+        case 2: fg_launch_quad<2>(items, lds, st, x, D, ldx, n, pairs, start, istart, I, means_invcovars, inv_covars, gconst, ll); break;
+        case 3: fg_launch_quad<3>(items, lds, st, x, D, ldx, n, pairs, start, istart, I, means_invcovars, inv_covars, gconst, ll); break;
+        default: fg_launch_quad<4>(items, lds, st, x, D, ldx, n, pairs, start, istart, I, means_invcovars, inv_covars, gconst, ll); break;
     }
     KTF_CHECK_LAUNCH(who);
     hipLaunchKernelGGL(fg_softmax_kernel, dim3((unsigned)((F + FG_WAVES - 1) / FG_WAVES)), dim3(FG_THREADS), 0, st, gselect, (const float*)ll, F,

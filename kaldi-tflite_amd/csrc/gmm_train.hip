@@ -5,8 +5,8 @@
 //                     over the list in slot order, the frame's log-likelihood, the count of frames with a non-empty list.
 //   gdense_ll_kernel  the log-likelihoods of ALL Gaussians on the tile of gmm_loglike.h (the bits of ktf_ivector_post_f32), written
 //   gdense_sm_kernel  to the workspace (F, I); then one wave per frame: softmax over all I, P (fp64), Xaug = [1, x, x^2] (fp64).
-//   gacc_items_kernel the buckets of gmm_bucket.h cut into items of KTF_GMM_ACC_ITEM_ROWS rows: item starts and, for the Gaussians
-//                     with more than one item, the starts of their partial results.
+//   gmm_bucket.hip    the pairs bucketed by Gaussian, the buckets cut into items of KTF_GMM_ACC_ITEM_ROWS rows: item starts and,
+//                     for the Gaussians with more than one item, the starts of their partial results.
 //   gacc_diag_kernel  one workgroup per item, VALU fp64: wave w takes the item's rows r = w (mod 4) in order, lane l the columns
 //                     l and l + 64; the four waves' sums are added in wave order.
 //   gacc_full_kernel  one workgroup per item: Z^T diag(p) Z with z = [1, x] on v_mfma_f64_16x16x4_f64. GACC_RB rows at a time are
@@ -39,14 +39,14 @@ struct GaccLayout {
 
 GaccLayout gacc_layout(int64_t F, int64_t I, int64_t D, int64_t n, int full) {
     GaccLayout l;
-    l.sec = sec_layout(F > 0 ? F : 1, I, n);
+    l.sec = sec_layout(F > 0 ? F : 1, I, n, true);
     const int64_t np = F * n;
     l.max_items = np / KTF_GMM_ACC_ITEM_ROWS + I;          // sum of ceil(count / rows) over the Gaussians
     l.max_parts = 2 * (np / KTF_GMM_ACC_ITEM_ROWS) + 1;    // a Gaussian with count > rows has ceil(count / rows) < 2 count / rows items
     int64_t at = l.sec.bytes;
-    l.istart = at; at += sec_al256((I + 1) * 4);
-    l.pstart = at; at += sec_al256((I + 1) * 4);
-    l.part = at;   at += sec_al256(l.max_parts * gacc_stride((int)D, full) * 8);
+    l.istart = at; at += al256((I + 1) * 4);
+    l.pstart = at; at += al256((I + 1) * 4);
+    l.part = at;   at += al256(l.max_parts * gacc_stride((int)D, full) * 8);
     l.total = at;
     return l;
 }
@@ -61,9 +61,7 @@ __global__ void __launch_bounds__(64 * GPRE_WAVES) gpre_kernel(const float* __re
     const int64_t t = (int64_t)blockIdx.x * GPRE_WAVES + wv;
     if (t >= F) return;                                      // (no workgroup barrier below: a wave works alone)
     for (int d = lane; d < D; d += 64) xs[wv][d] = x[t * ldx + d];
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_lds_sync();
     int g = -1;
     if (lane < n) {
         g = gsel[t * n + lane];
@@ -145,71 +143,6 @@ __global__ void __launch_bounds__(64 * GPRE_WAVES) gdense_sm_kernel(const float*
 }
 
 // ---------------------------------------------------------------- (d) statistics on (frame, slot) pairs
-// istart[g] = sum_{h < g} ceil(cnt_h / rows), pstart[g] = the same over the Gaussians with more than one item; entry I: the totals
-__global__ void __launch_bounds__(256) gacc_items_kernel(const int* __restrict__ start, int I, int* __restrict__ istart, int* __restrict__ pstart) {
-    __shared__ int si[256];
-    __shared__ int sp[256];
-    const int tid = threadIdx.x, per = (I + 255) / 256;
-    const int g0 = tid * per < I ? tid * per : I, g1 = g0 + per < I ? g0 + per : I;
-    int a = 0, b = 0;
-    for (int g = g0; g < g1; ++g) {
-        const int it = (start[g + 1] - start[g] + KTF_GMM_ACC_ITEM_ROWS - 1) / KTF_GMM_ACC_ITEM_ROWS;
-        a += it;
-        b += it > 1 ? it : 0;
-    }
-    si[tid] = a;
-    sp[tid] = b;
-    __syncthreads();
-    if (tid == 0) {
-        int ra = 0, rb = 0;
-        for (int t = 0; t < 256; ++t) {
-            const int va = si[t], vb = sp[t];
-            si[t] = ra;
-            sp[t] = rb;
-            ra += va;
-            rb += vb;
-        }
-        istart[I] = ra;
-        pstart[I] = rb;
-    }
-    __syncthreads();
-    a = si[tid];
-    b = sp[tid];
-    for (int g = g0; g < g1; ++g) {
-        const int it = (start[g + 1] - start[g] + KTF_GMM_ACC_ITEM_ROWS - 1) / KTF_GMM_ACC_ITEM_ROWS;
-        istart[g] = a;
-        pstart[g] = b;
-        a += it;
-        b += it > 1 ? it : 0;
-    }
-}
-
-struct GaccItem {
-    int g, r0, r1, part;            // Gaussian, bucket rows [r0, r1), the partial slot or -1 (a single item: add to the accumulator)
-};
-
-// item w -> its Gaussian and rows; g = -1 beyond the last item
-__device__ __forceinline__ GaccItem gacc_item(int w, const int* __restrict__ start, const int* __restrict__ istart,
-                                              const int* __restrict__ pstart, int I) {
-    GaccItem it;
-    it.g = -1;
-    it.r0 = it.r1 = 0;
-    it.part = -1;
-    if (w >= istart[I]) return it;
-    int lo = 0, hi = I;                          // istart[lo] <= w < istart[hi]
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (istart[mid] <= w) lo = mid;
-        else hi = mid;
-    }
-    const int k = w - istart[lo];
-    it.g = lo;
-    it.r0 = start[lo] + k * KTF_GMM_ACC_ITEM_ROWS;
-    it.r1 = it.r0 + KTF_GMM_ACC_ITEM_ROWS < start[lo + 1] ? it.r0 + KTF_GMM_ACC_ITEM_ROWS : start[lo + 1];
-    if (istart[lo + 1] - istart[lo] > 1) it.part = pstart[lo] + k;
-    return it;
-}
-
 // element (i, j), j <= i, of sum p z z^T -> the accumulators (z = [1, x]); the mirror gets the same value
 __device__ __forceinline__ void gacc_emit_full(int i, int j, double v, int g, int D, double* __restrict__ occ, double* __restrict__ mean,
                                                double* __restrict__ cov) {
@@ -235,8 +168,9 @@ __global__ void __launch_bounds__(GACC_THREADS) gacc_diag_kernel(const float* __
                                                                  double* __restrict__ occ, double* __restrict__ mean, double* __restrict__ var,
                                                                  double* __restrict__ part) {
     __shared__ double red[GACC_WAVES][2 * KTF_IVECTOR_MAX_FEAT_DIM + 1];
-    const GaccItem it = gacc_item(blockIdx.x, start, istart, pstart, I);
+    const BucketItem it = bucket_item(blockIdx.x, start, istart, I, KTF_GMM_ACC_ITEM_ROWS);
     if (it.g < 0) return;
+    const int slot = it.items > 1 ? pstart[it.g] + it.k : -1;        // of its partial result; a single item adds to the accumulator
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     double o = 0.0, m[2] = {0.0, 0.0}, s[2] = {0.0, 0.0};
     for (int r = it.r0 + wv; r < it.r1; r += GACC_WAVES) {
@@ -268,7 +202,7 @@ __global__ void __launch_bounds__(GACC_THREADS) gacc_diag_kernel(const float* __
         double v = red[0][c];
 #pragma unroll
         for (int w = 1; w < GACC_WAVES; ++w) v += red[w][c];
-        if (it.part >= 0) part[(int64_t)it.part * C + c] = v;
+        if (slot >= 0) part[(int64_t)slot * C + c] = v;
         else gacc_emit_diag(c, v, it.g, D, occ, mean, var);
     }
 }
@@ -285,8 +219,9 @@ __global__ void __launch_bounds__(GACC_THREADS) gacc_full_kernel(const float* __
     constexpr int TPW = (NTILES + GACC_WAVES - 1) / GACC_WAVES;
     __shared__ double zs[GACC_RB][ZP];
     __shared__ double ps[GACC_RB];
-    const GaccItem it = gacc_item(blockIdx.x, start, istart, pstart, I);
+    const BucketItem it = bucket_item(blockIdx.x, start, istart, I, KTF_GMM_ACC_ITEM_ROWS);
     if (it.g < 0) return;
+    const int slot = it.items > 1 ? pstart[it.g] + it.k : -1;        // of its partial result; a single item adds to the accumulator
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, lc = lane & 15, lk = lane >> 4;
     const int Dz = D + 1;
     int ti[TPW], tj[TPW];
@@ -336,7 +271,7 @@ __global__ void __launch_bounds__(GACC_THREADS) gacc_full_kernel(const float* __
         for (int r = 0; r < 4; ++r) {
             const int i = 16 * ti[s] + lk + 4 * r, j = 16 * tj[s] + lc;
             if (i < Dz && j <= i) {
-                if (it.part >= 0) part[((int64_t)it.part * Dz + i) * Dz + j] = acc[s][r];
+                if (slot >= 0) part[((int64_t)slot * Dz + i) * Dz + j] = acc[s][r];
                 else gacc_emit_full(i, j, acc[s][r], it.g, D, occ, mean, cov);
             }
         }
@@ -370,22 +305,13 @@ void gacc_launch_full(int items, hipStream_t st, const float* x, int D, int64_t 
                        mean, cov, part);
 }
 
-int gmm_check_shape(const char* who, int64_t F, int32_t I, int32_t D, int32_t n) {
-    KTF_REQUIRE(D >= 1 && D <= KTF_IVECTOR_MAX_FEAT_DIM, "%s: feature dim %d outside 1 .. %d", who, (int)D, KTF_IVECTOR_MAX_FEAT_DIM);
-    KTF_REQUIRE(I >= 1 && I <= KTF_IVECTOR_MAX_GAUSS, "%s: %d Gaussians outside 1 .. %d", who, (int)I, KTF_IVECTOR_MAX_GAUSS);
-    KTF_REQUIRE(n >= 1 && n <= KTF_IVECTOR_MAX_GSELECT, "%s: %d slots per frame outside 1 .. %d", who, (int)n, KTF_IVECTOR_MAX_GSELECT);
-    KTF_REQUIRE(F >= 0 && F < ((int64_t)1 << 31) && F * n < ((int64_t)1 << 31), "%s: frame count %lld out of range (F * n < 2^31)", who,
-                (long long)F);
-    return KTF_OK;
-}
-
 }  // namespace
 
 extern "C" int ktf_gmm_post_preselect_f32(const float* x, int64_t F, int32_t D, int64_t ldx, const int32_t* gselect, int32_t n,
                                           const float* means_invvars, const float* inv_vars, const float* gconst, int32_t I, float* post,
                                           float* loglike, int32_t* valid, void* stream) {
     const char* who = "ktf_gmm_post_preselect_f32";
-    const int rc = gmm_check_shape(who, F, I, D, n);
+    const int rc = bucket_check_shape(who, F, I, D, n);
     if (rc != KTF_OK) return rc;
     KTF_REQUIRE(ldx >= D, "%s: ldx %lld < D %d", who, (long long)ldx, (int)D);
     if (F == 0) return KTF_OK;
@@ -400,7 +326,7 @@ extern "C" int64_t ktf_gmm_post_dense_workspace_bytes(int64_t F, int32_t I) {
     const char* who = "ktf_gmm_post_dense_workspace_bytes";
     KTF_REQUIRE(I >= 1 && I <= KTF_IVECTOR_MAX_GAUSS, "%s: %d Gaussians outside 1 .. %d", who, (int)I, KTF_IVECTOR_MAX_GAUSS);
     KTF_REQUIRE(F >= 0 && F < ((int64_t)1 << 31), "%s: frame count %lld out of range", who, (long long)F);
-    return sec_al256((F > 0 ? F : 1) * I * 4);
+    return al256((F > 0 ? F : 1) * I * 4);
 }
 
 extern "C" int ktf_gmm_post_dense_f32(const float* x, int64_t F, int32_t D, int64_t ldx, const float* W, const float* gconst, int32_t I,
@@ -427,7 +353,7 @@ extern "C" int ktf_gmm_post_dense_f32(const float* x, int64_t F, int32_t D, int6
 }
 
 extern "C" int64_t ktf_gmm_acc_workspace_bytes(int64_t F, int32_t I, int32_t D, int32_t n, int32_t full) {
-    const int rc = gmm_check_shape("ktf_gmm_acc_workspace_bytes", F, I, D, n);
+    const int rc = bucket_check_shape("ktf_gmm_acc_workspace_bytes", F, I, D, n);
     if (rc != KTF_OK) return rc;
     return gacc_layout(F, I, D, n, full != 0).total;
 }
@@ -436,7 +362,7 @@ extern "C" int ktf_gmm_acc_f64(const float* x, int64_t F, int32_t D, int64_t ldx
                                int32_t full, double* occ, double* mean_acc, double* second_acc, void* workspace, size_t workspace_bytes,
                                void* stream) {
     const char* who = "ktf_gmm_acc_f64";
-    int rc = gmm_check_shape(who, F, I, D, n);
+    int rc = bucket_check_shape(who, F, I, D, n);
     if (rc != KTF_OK) return rc;
     KTF_REQUIRE(ldx >= D, "%s: ldx %lld < D %d", who, (long long)ldx, (int)D);
     KTF_REQUIRE(occ && mean_acc && second_acc && workspace, "%s: null argument", who);
@@ -453,8 +379,7 @@ extern "C" int ktf_gmm_acc_f64(const float* x, int64_t F, int32_t D, int64_t ldx
     int* pstart = (int*)(ws + l.pstart);
     double* part = (double*)(ws + l.part);
     if ((rc = sec_bucket(who, gauss, F * n, (int)I, l.sec, ws, st)) != KTF_OK) return rc;
-    hipLaunchKernelGGL(gacc_items_kernel, dim3(1), dim3(256), 0, st, start, (int)I, istart, pstart);
-    KTF_CHECK_LAUNCH(who);
+    if ((rc = bucket_items(who, start, (int)I, KTF_GMM_ACC_ITEM_ROWS, istart, pstart, st)) != KTF_OK) return rc;
     const int items = (int)l.max_items;
 #define KTF_GACC_FULL(NT)                                                                                                              \
     case NT:                                                                                                                           \

@@ -14,7 +14,6 @@ constexpr int64_t GKC = 2048;       // GEMM K chunk: a function of K alone
 constexpr int NB = 32;              // Cholesky panel width
 constexpr int SOLVE_THREADS = 256;
 
-__host__ __device__ inline int64_t al256(int64_t b) { return (b + 255) & ~(int64_t)255; }
 
 // frames [t0, t1) of utterance b, clamped to the F rows the caller declared (an inconsistent table reads nothing out of range)
 __device__ __forceinline__ void utt_rows(const int* off, int b, int64_t F, int64_t* t0, int64_t* t1) {

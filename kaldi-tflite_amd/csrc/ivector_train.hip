@@ -10,11 +10,9 @@
 //   atb_kernel       C += A^T B in fp64 on v_mfma_f64_16x16x4_f64: A (K x M) and B (K x N) row-major, K = the utterances of the
 //                    chunk, ascending inside every output element; no atomics, no split of K. One kernel for R (A = gamma,
 //                    B = W), Y (A = F, B = w), gamma, the prior's sum and scatter and the two scalar totals (A = the flags).
-//   sec_*_kernel     second-order statistics Ssec_i += sum_t p'_ti x_t x_t^T: the (frame, slot) pairs are bucketed by Gaussian (the
-//                    bucketing kernels live in gmm_bucket.h, shared with gmm_train.hip) with
-//                    a STABLE counting sort (integer histograms per chunk of pairs, exclusive scans, then one wave per chunk that
-//                    ranks equal Gaussians by lane order), so a bucket lists its pairs in ascending pair id and its fp64 sum, taken
-//                    row after row, has the same bits on every run.
+//   sec_acc_kernel   second-order statistics Ssec_i += sum_t p'_ti x_t x_t^T: the (frame, slot) pairs are bucketed by Gaussian with the
+//                    STABLE counting sort of gmm_bucket.hip, so a bucket lists its pairs in ascending pair id and its fp64 sum,
+//                    taken row after row, has the same bits on every run.
 #include "ivector_stages.h"
 #include "gmm_bucket.h"
 
@@ -261,7 +259,7 @@ int atb(const char* who, const double* A, int64_t lda, const double* Bm, int64_t
     return KTF_OK;
 }
 
-// ---------------------------------------------------------------- second-order statistics (the bucketing: gmm_bucket.h)
+// ---------------------------------------------------------------- second-order statistics (the bucketing: gmm_bucket.hip)
 // Ssec[g] (D x D) += sum over the bucket's rows, in bucket order, of p' x x^T: one workgroup per Gaussian, thread (ty, tx) owns
 // elements (ty + 16 a, tx + 16 c). x_i x_j is exact in fp64 (fp32 inputs), so the result is symmetric bit for bit.
 __global__ void __launch_bounds__(256) sec_acc_kernel(const float* __restrict__ x, int D, int64_t ldx, const float* __restrict__ post, int n,
@@ -376,18 +374,15 @@ extern "C" int ktf_ivector_acc_stats(const float* x, int64_t F, int32_t D, int64
 }
 
 extern "C" int64_t ktf_ivector_acc2_workspace_bytes(int64_t F, int32_t I, int32_t n) {
-    const char* who = "ktf_ivector_acc2_workspace_bytes";
-    KTF_REQUIRE(I >= 1 && I <= KTF_IVECTOR_MAX_GAUSS, "%s: %d Gaussians outside 1 .. %d", who, (int)I, KTF_IVECTOR_MAX_GAUSS);
-    KTF_REQUIRE(n >= 1 && n <= KTF_IVECTOR_MAX_GSELECT, "%s: %d slots per frame outside 1 .. %d", who, (int)n, KTF_IVECTOR_MAX_GSELECT);
-    KTF_REQUIRE(F >= 0 && F * n < ((int64_t)1 << 31), "%s: F * n = %lld outside 0 .. 2^31 - 1", who, (long long)(F * n));
-    return sec_layout(F > 0 ? F : 1, I, n).bytes;
+    const int rc = bucket_check_pairs("ktf_ivector_acc2_workspace_bytes", F, I, n);
+    if (rc != KTF_OK) return rc;
+    return sec_layout(F > 0 ? F : 1, I, n, true).bytes;
 }
 
 extern "C" int ktf_ivector_acc_second_order(const float* x, int64_t F, int32_t D, int64_t ldx, const int32_t* gauss, const float* post,
                                             int32_t n, float posterior_scale, int32_t I, double* Ssec, void* workspace,
                                             size_t workspace_bytes, void* stream) {
     const char* who = "ktf_ivector_acc_second_order";
-    KTF_REQUIRE(F >= 0 && F < ((int64_t)1 << 31), "%s: frame count %lld out of range", who, (long long)F);
     const int64_t need = ktf_ivector_acc2_workspace_bytes(F, I, n);
     if (need < 0) return (int)need;
     KTF_REQUIRE(D >= 1 && D <= KTF_IVECTOR_MAX_FEAT_DIM, "%s: feature dim %d outside 1 .. %d", who, (int)D, KTF_IVECTOR_MAX_FEAT_DIM);
@@ -400,7 +395,7 @@ extern "C" int ktf_ivector_acc_second_order(const float* x, int64_t F, int32_t D
     if (F == 0) return KTF_OK;
     hipStream_t st = (hipStream_t)stream;
     char* ws = (char*)workspace;
-    const SecLayout l = sec_layout(F, I, n);
+    const SecLayout l = sec_layout(F, I, n, true);
     const int64_t np = F * n;
     const int* start = (const int*)(ws + l.start);
     const int* pairs = (const int*)(ws + l.pairs);

@@ -1,6 +1,6 @@
 """Full-covariance UBM posteriors on the MI355X (ktf_fgmm_post_f32, ktf.layers.IvectorExtractor(full_ubm=...)) against the fp64 NumPy
 restatement (tests/_fgmm_ref.py) on well-posed frames, the toDiag() path, the whole call, bit stability across runs, batch
-composition and chunking, skewed buckets, and the unchanged diagonal path."""
+composition and chunking, skewed buckets, the position of a frame in the call, and the unchanged diagonal path."""
 
 import numpy as np
 import pytest
@@ -184,6 +184,32 @@ def test_one_popular_gaussian_and_empty_ones(tmp_path):
     assert np.array_equal(g[ok], wg[ok])
     assert np.abs(p[ok] - wp[ok]).max() <= 2e-5
     check_layout(g, p, I)
+
+
+def test_bits_independent_of_frame_position():
+    """A frame's posteriors and log-likelihood do not depend on where the frame sits in the call, so not on the order of the pairs
+    inside a bucket either: the same frames permuted give the same rows, permuted. 90 % of the frames come from component 2, whose
+    bucket spans three 512-row work items; Gaussian 5 is never listed; a few list entries are -1 or outside [0, I)."""
+    rng = np.random.default_rng(26)
+    I, D, n, F = 6, 33, 3, 1500
+    stored, (mean, cov) = G.random_full_ubm(rng, I, D)
+    gc = G.gconsts(*stored).astype(np.float32)
+    comp = np.where(rng.uniform(size=F) < 0.9, 2, rng.integers(0, I - 1, F))
+    x = G.draw_frames(rng, mean, cov, F, comp=comp)
+    sel = np.stack([rng.choice(I - 1, n, replace=False) for _ in range(F)]).astype(np.int32)
+    sel[(comp == 2) & ~(sel == 2).any(1), 0] = 2
+    sel[rng.choice(F, 12, replace=False), rng.integers(0, n, 12)] = np.tile(np.array([-1, I, I + 3, -7], np.int32), 3)
+    sel[17] = -1
+    counts = np.bincount(sel[(sel >= 0) & (sel < I)], minlength=I)
+    assert 2 * 512 < counts[2] <= 3 * 512 and counts[5] == 0
+    perm = rng.permutation(F)
+    d = lambda a: torch.as_tensor(np.ascontiguousarray(a), device=DEV)  # noqa: E731
+    model = (d(stored[1]), d(stored[2]), d(gc), 0.025)
+    g, p, ll = ops.fgmm_post_ll(d(x), d(sel), *model)
+    g2, p2, ll2 = ops.fgmm_post_ll(d(x[perm]), d(sel[perm]), *model)
+    at = torch.as_tensor(perm, device=DEV)
+    assert (g >= 0).any(1).sum().item() == F - 1 and torch.isfinite(ll).all()
+    assert torch.equal(g2, g[at]) and torch.equal(p2, p[at]) and torch.equal(ll2, ll[at])
 
 
 def test_without_full_ubm_nothing_changes(tmp_path):
