@@ -794,6 +794,73 @@ int ktf_train_gram_f64(const double* y, int64_t N, int32_t D, const int32_t* idx
 int ktf_plda_em_project(const double* mu, int64_t S, int32_t D, const double* mbar, const double* P, const double* lam,
                         const int32_t* counts, double* a, double* b, void* stream);
 
+/* ------------------------------------------------------------------ VB-HMM resegmentation
+ * The variational-Bayes HMM of Kaldi's diarization/VB_resegmentation.sh (VB_diarization.py, min_dur = 1) for the N recordings of a
+ * call: I Gaussians, D features, R i-vector dimensions, K <= KTF_VB_MAX_SPEAKERS speakers. Frames lie end to end in x (F, D) fp32,
+ * row stride ldx: recording r owns frames [offsets[r], offsets[r + 1]) and blocks [boffsets[r], boffsets[r + 1]) of the TB rows of
+ * q / lls (both tables: N + 1 device int32); block b of a recording covers its frames [b d, min((b + 1) d, T_r)), d = downsample.
+ * Every fp64 sum runs in a fixed order that depends on the recording alone: its results have the same bits alone and in a batch.
+ *
+ * Posteriors: l as ktf_ivector_post_f32 computes it (W, gconst as there; the same device code) times ll_scale in fp32;
+ * loglike (F) = G = max + log sum exp(l - max) over all I; p = fp32(exp(l - G) * stat_scale). A frame keeps the Gaussians with
+ * p >= sparsity_thr, largest first, ties to the lower index, at most n, not renormalised: gauss / post (F, n), unused slots (-1, 0).
+ * *truncated (device int32) is increased by the number of frames with more than n candidates. workspace: 256-byte aligned, at
+ * least ktf_vb_post_workspace_bytes(F, I) bytes (F * I fp32). */
+#define KTF_VB_MAX_SPEAKERS 16
+#define KTF_VB_FB_CHUNK 128
+int64_t ktf_vb_post_workspace_bytes(int64_t F, int32_t I);
+int ktf_vb_post_f32(const float* x, int64_t F, int32_t D, int64_t ldx, const float* W, const float* gconst, int32_t I, int32_t n,
+                    float ll_scale, float stat_scale, float sparsity_thr, int32_t* gauss, float* post, float* loglike,
+                    int32_t* truncated, void* workspace, size_t workspace_bytes, void* stream);
+/* The (frame, slot) pairs of gauss (F, n) bucketed by Gaussian with the stable counting sort of ktf_ivector_acc_second_order:
+ * start (I + 1) and pairs (F * n) device int32; pairs[start[c] .. start[c + 1]) lists the pair ids t * n + slot of Gaussian c in
+ * ascending order (slots with an index outside [0, I) are left out). Once per call of the resegmentation. */
+int64_t ktf_vb_bucket_workspace_bytes(int64_t F, int32_t I, int32_t n);
+int ktf_vb_bucket(const int32_t* gauss, int64_t F, int32_t n, int32_t I, int32_t* start, int32_t* pairs, void* workspace,
+                  size_t workspace_bytes, void* stream);
+/* Soft statistics of speaker s of recording r (row r K + s): Nst (N K, I) = sum_t q_ts p_tc, Fst (N K, I D) = sum_t q_ts p_tc
+ * (x_t - m_c), over the pairs of c in ascending pair order; q (TB, K) fp64, a frame uses the row of its block; means (I, D) fp64.
+ * Every element is written. No floating-point atomics. */
+int ktf_vb_speaker_stats(const float* x, int64_t F, int32_t D, int64_t ldx, const int32_t* offsets, const int32_t* boffsets, int32_t N,
+                         int64_t TB, int32_t downsample, const float* post, int32_t n, const int32_t* start, const int32_t* pairs,
+                         int32_t I, const double* means, const double* q, int32_t K, double* Nst, double* Fst, void* stream);
+/* Speaker posteriors of the B = N K rows: lin = Bm^T vec(F) (Bm (I D, R): row (c, d) = iE_cd M_c[d, :]), Q = I + sum_c N_c U_c =
+ * L L^T (U (I, P), P = R(R+1)/2, packed lower triangles: the layouts of ktf_ivector_extract), C = Q^-1, a (B, R) = C lin,
+ * Wp (B, P) = C + a a^T packed, kl (B) = (R - tr W) / 2 - sum_j log L_jj, h (B, I D) = Bm a, g (B, I) = tr(U_c W) / 2 (on packed
+ * triangles the off-diagonal entries count twice). The two products with B rows run on v_mfma_f64_16x16x4_f64. workspace: 256-byte
+ * aligned, at least ktf_vb_update_workspace_bytes(B, I, D, R) bytes. */
+int64_t ktf_vb_update_workspace_bytes(int32_t B, int32_t I, int32_t D, int32_t R);
+int ktf_vb_speaker_update(const double* Nst, const double* Fst, int32_t B, int32_t I, int32_t D, int32_t R, const double* Bm,
+                          const double* U, double* a, double* Wp, double* kl, double* h, double* g, void* workspace,
+                          size_t workspace_bytes, void* stream);
+/* lls (TB, K) fp64: row b = sum over the block's frames in order, then their slots in order, of p_tc ((x_t - m_c) . h_sc - g_sc). */
+int ktf_vb_block_loglike(const float* x, int64_t F, int32_t D, int64_t ldx, const int32_t* offsets, const int32_t* boffsets, int32_t N,
+                         int64_t TB, int32_t downsample, const int32_t* gauss, const float* post, int32_t n, int32_t I,
+                         const double* means, const double* h, const double* g, int32_t K, double* lls, void* stream);
+/* Forward-backward of the HMM with initial probabilities sp (N, K) and transitions i -> j = loop_prob [i = j] + (1 - loop_prob)
+ * sp_j over each recording's blocks, emissions exp(lls): a chunked scan in scaled fp64, KTF_VB_FB_CHUNK blocks per chunk (a
+ * function of nothing else). q (TB, K) = the state posteriors; tll (N) = log p(blocks) (0 for a recording without blocks); sp_out
+ * (N, K) proportional to q_0j + sum_{b >= 1} Pr(block b entered j through the non-loop term), normalised (sp itself for a recording
+ * without blocks). workspace: 256-byte aligned, at least ktf_vb_fb_workspace_bytes(TB, N) bytes. */
+int64_t ktf_vb_fb_workspace_bytes(int64_t TB, int32_t N);
+int ktf_vb_forward_backward(const double* lls, const int32_t* boffsets, int32_t N, int64_t TB, int32_t K, const double* sp,
+                            double loop_prob, double* q, double* sp_out, double* tll, void* workspace, size_t workspace_bytes,
+                            void* stream);
+/* The same forward-backward in its serial form, for measurement only (tools/bench_vb.py times the chunked scan against it; nothing
+ * in the package calls it): one wave per recording walks all its blocks, lane i = speaker i, the scaled forward vectors kept in the
+ * workspace. Same arguments and results (to rounding; the sums run in another order); workspace: 256-byte aligned, at least
+ * ktf_vb_fb_serial_workspace_bytes(TB, N) bytes. */
+int64_t ktf_vb_fb_serial_workspace_bytes(int64_t TB, int32_t N);
+int ktf_vb_forward_backward_serial(const double* lls, const int32_t* boffsets, int32_t N, int64_t TB, int32_t K, const double* sp,
+                                   double loop_prob, double* q, double* sp_out, double* tll, void* workspace, size_t workspace_bytes,
+                                   void* stream);
+/* The bound. ktf_vb_loglike_sums: gsum (N) fp64 = sum_t G_t over each recording's frames of loglike (F) fp32, thread-strided from
+ * the recording's first frame and then a fixed tree (once per call). ktf_vb_bound: bound (N) = stat_scale gsum + tll + sum_s kl
+ * (kl (N K), s ascending). Neither depends on where a recording lies in the packed arrays. */
+int ktf_vb_loglike_sums(const float* loglike, const int32_t* offsets, int32_t N, int64_t F, double* gsum, void* stream);
+int ktf_vb_bound(const double* gsum, const double* tll, const double* kl, int32_t N, int32_t K, double stat_scale, double* bound,
+                 void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -184,6 +184,20 @@ PROTOTYPES = {
     "ktf_train_gram_f32": (C.c_int, [_P, _i64, _i32, _P, _i64, _P, _P, _P, _P, C.c_size_t, _P]),
     "ktf_train_gram_f64": (C.c_int, [_P, _i64, _i32, _P, _i64, _P, _P, _P, _P, C.c_size_t, _P]),
     "ktf_plda_em_project": (C.c_int, [_P, _i64, _i32, _P, _P, _P, _P, _P, _P, _P]),
+    "ktf_vb_post_workspace_bytes": (_i64, [_i64, _i32]),
+    "ktf_vb_post_f32": (C.c_int, [_P, _i64, _i32, _i64, _P, _P, _i32, _i32, _f32, _f32, _f32, _P, _P, _P, _P, _P, C.c_size_t, _P]),
+    "ktf_vb_bucket_workspace_bytes": (_i64, [_i64, _i32, _i32]),
+    "ktf_vb_bucket": (C.c_int, [_P, _i64, _i32, _i32, _P, _P, _P, C.c_size_t, _P]),
+    "ktf_vb_speaker_stats": (C.c_int, [_P, _i64, _i32, _i64, _P, _P, _i32, _i64, _i32, _P, _i32, _P, _P, _i32, _P, _P, _i32, _P, _P, _P]),
+    "ktf_vb_update_workspace_bytes": (_i64, [_i32, _i32, _i32, _i32]),
+    "ktf_vb_speaker_update": (C.c_int, [_P, _P, _i32, _i32, _i32, _i32, _P, _P, _P, _P, _P, _P, _P, _P, C.c_size_t, _P]),
+    "ktf_vb_block_loglike": (C.c_int, [_P, _i64, _i32, _i64, _P, _P, _i32, _i64, _i32, _P, _P, _i32, _i32, _P, _P, _P, _i32, _P, _P]),
+    "ktf_vb_fb_workspace_bytes": (_i64, [_i64, _i32]),
+    "ktf_vb_forward_backward": (C.c_int, [_P, _P, _i32, _i64, _i32, _P, C.c_double, _P, _P, _P, _P, C.c_size_t, _P]),
+    "ktf_vb_fb_serial_workspace_bytes": (_i64, [_i64, _i32]),
+    "ktf_vb_forward_backward_serial": (C.c_int, [_P, _P, _i32, _i64, _i32, _P, C.c_double, _P, _P, _P, _P, C.c_size_t, _P]),
+    "ktf_vb_loglike_sums": (C.c_int, [_P, _P, _i32, _i64, _P, _P]),
+    "ktf_vb_bound": (C.c_int, [_P, _P, _P, _i32, _i32, C.c_double, _P, _P]),
 }
 PLDA_DENSE_NO_PCA = -1.0            # ktf_plda_dense_*: target_energy for "no PCA"
 PLDA_DENSE_MAX_DIM = 512
@@ -194,6 +208,7 @@ IVECTOR_MAX_FEAT_DIM, IVECTOR_MAX_GAUSS, IVECTOR_MAX_GSELECT, IVECTOR_MAX_DIM = 
 GMM_ACC_ITEM_ROWS = 1024            # ktf_gmm_acc_f64: rows of a bucket per item
 ADD_DELTAS_MAX_CONTEXT = 32         # ktf_add_deltas_f32: order * window
 TRAIN_MAX_DIM = 1024                # ktf_train_*, ktf_plda_em_project
+VB_MAX_SPEAKERS, VB_FB_CHUNK = 16, 128   # ktf_vb_*: speakers per recording, blocks per chunk of the forward-backward scan
 
 _lib = None
 

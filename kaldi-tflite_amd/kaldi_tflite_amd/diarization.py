@@ -193,3 +193,278 @@ def diarize(ext, plda, wavs, target_energy=0.1, threshold=None, num_speakers=Non
     labels = torch.cat(labels) if len(labels) > 1 else labels[0]
     counts[torch.as_tensor(live, device=dev)] = cnt
     return Diarization(res, labels, counts, rttm(res, labels, reco_ids))
+
+
+# =============================================================================== VB-HMM resegmentation
+def frame_labels(res, labels, num_frames, frame_shift=0.01):
+    """Per-frame initial labels for VBResegmenter from `res` (XvectorExtractor.extract_windows' result) and one label per window
+    (agglomerative_cluster's, 1 .. K): per recording the windows in start order under rttm_pieces' midpoint rule; frame t (its start,
+    t * frame_shift seconds) takes the label of the piece that holds it, minus 1 (the resegmenter counts speakers from 0), and -1
+    outside every piece. num_frames: R frame counts (or one int for all). -> a list of R host int32 arrays."""
+    R = len(res.lengths)
+    nf = [int(num_frames)] * R if isinstance(num_frames, (numbers.Integral, np.integer)) else [int(v) for v in num_frames]
+    if len(nf) != R or min(nf, default=0) < 0:
+        raise ValueError(f"num_frames must be an int or {R} non-negative ints, got {num_frames!r}")
+    if not _real(frame_shift) or not float(frame_shift) > 0:
+        raise ValueError(f"frame_shift must be > 0, got {frame_shift!r}")
+    win = res.windows.cpu().numpy().astype(np.int64).reshape(-1, 3)
+    lab = _labels_host(labels, win.shape[0])
+    scale = float(res.frame_shift) / float(frame_shift)         # window units -> frames of the caller
+    out = []
+    for r in range(R):
+        o = np.full(nf[r], -1, np.int32)
+        sel = np.nonzero(win[:, 0] == r)[0]
+        order = sel[np.argsort(win[sel, 1], kind="stable")]
+        for a, b, k in rttm_pieces(win[order, 1], win[order, 2], lab[order]):
+            lo, hi = int(np.ceil(a * scale - 1e-9)), int(np.ceil(b * scale - 1e-9))     # frames with a <= t < b
+            o[max(lo, 0):max(min(hi, nf[r]), 0)] = int(k) - 1
+        out.append(o)
+    return out
+
+
+def frame_rttm(labels, offsets, frame_index=None, frame_shift=0.01, reco_ids=None, channel=1):
+    """RTTM lines from per-frame labels (VBResult.labels): labels (F,) for the recordings' rows end to end, recording r owning rows
+    [offsets[r], offsets[r + 1]). frame_index (F,): the original frame of every row within its recording when a mask selected the
+    rows (default: row - offsets[r]). Runs of equal labels over consecutive frame indices merge into one line in rttm's format,
+    speaker = label + 1 (agglomerative_cluster's numbering); rows with a negative label give no line."""
+    lab = np.asarray(labels.cpu() if isinstance(labels, torch.Tensor) else labels).reshape(-1).astype(np.int64)
+    off = np.asarray(offsets.cpu() if isinstance(offsets, torch.Tensor) else offsets).reshape(-1).astype(np.int64)
+    if off.size < 1 or off[0] != 0 or (np.diff(off) < 0).any() or off[-1] != lab.size:
+        raise ValueError(f"offsets must ascend from 0 to {lab.size}, got {off.tolist()}")
+    R = off.size - 1
+    if frame_index is None:
+        idx = np.arange(lab.size, dtype=np.int64) - np.repeat(off[:-1], np.diff(off))
+    else:
+        idx = np.asarray(frame_index.cpu() if isinstance(frame_index, torch.Tensor) else frame_index).reshape(-1).astype(np.int64)
+        if idx.size != lab.size:
+            raise ValueError(f"{idx.size} frame indices for {lab.size} labels")
+    reco_ids = [f"reco{r}" for r in range(R)] if reco_ids is None else list(reco_ids)
+    if len(reco_ids) != R:
+        raise ValueError(f"{len(reco_ids)} reco_ids for {R} recordings")
+    shift = float(frame_shift)
+    lines = []
+    for r in range(R):
+        l, i = lab[off[r]:off[r + 1]], idx[off[r]:off[r + 1]]
+        if l.size == 0:
+            continue
+        cut = np.nonzero((l[1:] != l[:-1]) | (i[1:] != i[:-1] + 1))[0] + 1
+        for a, b in zip(np.concatenate([[0], cut]), np.concatenate([cut, [l.size]])):
+            if l[a] < 0:
+                continue
+            st, en = i[a], i[b - 1] + 1
+            lines.append(f"SPEAKER {reco_ids[r]} {channel} {st * shift:.3f} {(en - st) * shift:.3f} <NA> <NA> {int(l[a]) + 1} <NA> <NA>")
+    return lines
+
+
+class VBResult:
+    """VBResegmenter's result: q (sum T', K) fp64 block posteriors packed over the recordings, frame_q (F, K) the block rows
+    repeated per frame, labels (F,) int32 (arg-max, ties to the lower index), sp (N, K), bound (N, max_iters) NaN-padded, all on the
+    GPU; iters (N,) and offsets (N + 1) host int64 (recording r owns frames offsets[r] .. offsets[r + 1]); truncated_frames int."""
+
+    def __init__(self, q, frame_q, labels, sp, bound, iters, truncated_frames, offsets):
+        self.q, self.frame_q, self.labels, self.sp, self.bound = q, frame_q, labels, sp, bound
+        self.iters, self.truncated_frames, self.offsets = iters, truncated_frames, offsets
+
+
+class VBResegmenter:
+    """Extension: the VB-HMM resegmentation of Kaldi's diarization/VB_resegmentation.sh (VB_diarization.py, Diez / Burget) on the
+    GPU, at any frame rate and batched over recordings. `ie`: a path to `final.ie`, an io.KaldiIvecExtractorReader or the
+    io.IvecExtractorModel training returns; `dubm`: a path to `final.dubm`, an io.KaldiDiagGmmReader or an io.DiagGmmModel. As in
+    Kaldi's wrapper the means and diagonal precisions come from the diagonal UBM and only M comes from the extractor (its SigmaInv,
+    prior offset and <w> are not used). The defaults are those of VB_resegmentation.sh as remembered (the script is not pinned
+    here): max_speakers 10, max_iters 10, epsilon 1e-6, loop_prob 0.9, stat_scale 0.2, ll_scale 1.0, alpha_q_init 100.0, downsample
+    25, sparsity_thr 0.001, min_dur 1; num_slots (at most 64 kept Gaussians per frame) is this implementation's. min_dur != 1 raises
+    NotImplementedError. The rules are those of include/ktf_hip.h (ktf_vb_*) and INTEGRATION.md §2j."""
+
+    def __init__(self, ie, dubm, max_speakers=10, max_iters=10, epsilon=1e-6, loop_prob=0.9, stat_scale=0.2, ll_scale=1.0,
+                 alpha_q_init=100.0, downsample=25, sparsity_thr=0.001, num_slots=32, min_dur=1, workspace_limit=1 << 30):
+        from . import io as kio
+        if int(min_dur) != 1:
+            raise NotImplementedError("VBResegmenter implements min_dur = 1 only")
+        ie = ie if isinstance(ie, kio.KaldiIvecExtractorReader) else kio.KaldiIvecExtractorReader(ie, binary=True)
+        ubm = dubm if isinstance(dubm, kio.KaldiDiagGmmReader) else kio.KaldiDiagGmmReader(dubm, binary=True)
+        if ubm.numGauss != ie.numGauss or ubm.featDim != ie.featDim:
+            raise ValueError(f"UBM ({ubm.numGauss} Gaussians, dim {ubm.featDim}) does not match the extractor "
+                             f"({ie.numGauss} Gaussians, dim {ie.featDim})")
+        I, D, R = ie.numGauss, ie.featDim, ie.ivecDim
+        if not (1 <= I <= L.IVECTOR_MAX_GAUSS and 1 <= D <= L.IVECTOR_MAX_FEAT_DIM and 1 <= R <= L.IVECTOR_MAX_DIM):
+            raise ValueError(f"model shape (I={I}, D={D}, R={R}) outside I <= {L.IVECTOR_MAX_GAUSS}, D <= {L.IVECTOR_MAX_FEAT_DIM}, "
+                             f"R <= {L.IVECTOR_MAX_DIM}")
+        if not 1 <= int(max_speakers) <= L.VB_MAX_SPEAKERS:
+            raise ValueError(f"max_speakers {max_speakers} outside 1 .. {L.VB_MAX_SPEAKERS}")
+        if not 1 <= int(num_slots) <= L.IVECTOR_MAX_GSELECT:
+            raise ValueError(f"num_slots {num_slots} outside 1 .. {L.IVECTOR_MAX_GSELECT}")
+        if int(downsample) < 1:
+            raise ValueError(f"downsample {downsample} < 1")
+        if int(max_iters) < 1:
+            raise ValueError(f"max_iters {max_iters} < 1")
+        if not 0.0 <= float(loop_prob) <= 1.0:
+            raise ValueError(f"loop_prob {loop_prob} outside [0, 1]")
+        if not 0.0 <= float(sparsity_thr) < 1.0:
+            raise ValueError(f"sparsity_thr {sparsity_thr} outside [0, 1)")
+        if not (float(stat_scale) > 0 and float(ll_scale) > 0 and float(alpha_q_init) > 0):
+            raise ValueError("stat_scale, ll_scale and alpha_q_init must be > 0")
+        self.numGauss, self.featDim, self.ivecDim = I, D, R
+        self.maxSpeakers, self.maxIters, self.epsilon = int(max_speakers), int(max_iters), float(epsilon)
+        self.loopProb, self.statScale, self.llScale = float(loop_prob), float(stat_scale), float(ll_scale)
+        self.alphaQInit, self.downsample, self.sparsityThr = float(alpha_q_init), int(downsample), float(sparsity_thr)
+        self.numSlots, self.workspaceLimit = int(num_slots), int(workspace_limit)
+        iv = ubm.inv_vars.astype(np.float64)
+        self._W = np.ascontiguousarray(np.concatenate([ubm.means_invvars.astype(np.float32).T,
+                                                       (np.float32(-0.5) * ubm.inv_vars.astype(np.float32)).T]))
+        self._gconst = np.ascontiguousarray(ubm.gconsts, dtype=np.float32)
+        self._means = np.ascontiguousarray(ubm.means_invvars.astype(np.float64) / iv)
+        M = np.asarray(ie.M, dtype=np.float64)                                  # (I, D, R)
+        self._B = np.ascontiguousarray((iv[:, :, None] * M).reshape(I * D, R))
+        r, c = np.tril_indices(R)
+        self._U = np.zeros((I, R * (R + 1) // 2), dtype=np.float64)
+        for i0 in range(0, I, 64):
+            tmp = np.matmul(np.swapaxes(M[i0:i0 + 64], 1, 2), iv[i0:i0 + 64, :, None] * M[i0:i0 + 64])
+            self._U[i0:i0 + 64] = tmp[:, r, c]
+        self._dev_cache = {}
+
+    def _consts(self, device):
+        key = str(device)
+        if key not in self._dev_cache:
+            f = lambda a: torch.as_tensor(a, device=device)  # noqa: E731
+            self._dev_cache[key] = tuple(f(a) for a in (self._W, self._gconst, self._means, self._B, self._U))
+        return self._dev_cache[key]
+
+    def posteriors(self, x):
+        """Step 1 on packed frames x (F, D): -> (gauss, post, loglike, truncated (1,) device int32). The frames run in chunks whose
+        workspace stays under workspace_limit; a frame's bits depend on its own row alone."""
+        W, gc = self._consts(x.device)[:2]
+        F = x.shape[0]
+        trunc = torch.zeros((1,), dtype=torch.int32, device=x.device)
+        step = max(1, self.workspaceLimit // max(1, ops.vb_post_workspace_bytes(1, self.numGauss)))
+        if F <= step:
+            return ops.vb_post(x, W, gc, self.numSlots, self.llScale, self.statScale, self.sparsityThr, trunc) + (trunc,)
+        g = torch.empty((F, self.numSlots), dtype=torch.int32, device=x.device)
+        p = torch.empty((F, self.numSlots), dtype=torch.float32, device=x.device)
+        ll = torch.empty((F,), dtype=torch.float32, device=x.device)
+        for lo in range(0, F, step):
+            g[lo:lo + step], p[lo:lo + step], ll[lo:lo + step] = ops.vb_post(x[lo:lo + step], W, gc, self.numSlots, self.llScale,
+                                                                             self.statScale, self.sparsityThr, trunc)
+        return g, p, ll, trunc
+
+    def _frames(self, feats, lengths, mask):
+        from .layers import select_frames
+        return select_frames(feats, self.featDim, lengths, mask)
+
+    def __call__(self, feats, lengths=None, mask=None, init_labels=None, q0=None, sp0=None, seed=0):
+        """feats (N, T, D) fp32 on a GPU; lengths / mask as IvectorExtractor takes them. Initialisation: init_labels (F,) ints over
+        the selected frames (one-hot rows, a block takes the label of its first frame, a label outside [0, K) gives a uniform row),
+        or q0 packed (sum T', K), or neither: rows of np.random.default_rng(seed).gamma(alpha_q_init, size=(sum T', K)) normalised.
+        sp0 (K,) or (N, K), default uniform. -> VBResult."""
+        x, off = self._frames(feats, lengths, mask)
+        self._check_init(x, off, init_labels, q0, sp0)
+        with L.on_device(x.device):
+            g, p, ll, trunc = self.posteriors(x)
+            return self._run(x, off, g, p, ll, trunc, init_labels, q0, sp0, seed)
+
+    def from_posteriors(self, feats, gauss, post, loglike, lengths=None, mask=None, init_labels=None, q0=None, sp0=None, seed=0):
+        """`__call__` on posteriors the caller supplies: gauss / post (F, n) and loglike (F) aligned with the selected frames."""
+        x, off = self._frames(feats, lengths, mask)
+        F = x.shape[0]
+        if gauss.shape != post.shape or gauss.dim() != 2 or gauss.shape[0] != F or tuple(loglike.shape) != (F,):
+            raise ValueError(f"gauss / post must both be ({F}, n) and loglike ({F},), got {tuple(gauss.shape)} / {tuple(post.shape)} / "
+                             f"{tuple(loglike.shape)}")
+        if not 1 <= gauss.shape[1] <= L.IVECTOR_MAX_GSELECT:
+            raise ValueError(f"{gauss.shape[1]} slots per frame outside 1 .. {L.IVECTOR_MAX_GSELECT}")
+        if any(t.device != x.device for t in (gauss, post, loglike)):
+            raise ValueError("feats, gauss, post and loglike must be on one device")
+        self._check_init(x, off, init_labels, q0, sp0)
+        g = gauss.to(dtype=torch.int32).contiguous()
+        p = post.to(dtype=torch.float32).contiguous()
+        with L.on_device(x.device):
+            return self._run(x, off, g, p, loglike.to(torch.float32).contiguous(), torch.zeros((1,), dtype=torch.int32, device=x.device), init_labels, q0,
+                             sp0, seed)
+
+    def _blocks(self, off):
+        d = self.downsample
+        T = np.diff(off)
+        return np.concatenate([[0], np.cumsum((T + d - 1) // d)]).astype(np.int64)
+
+    def _check_init(self, x, off, init_labels, q0, sp0):
+        K, N, F = self.maxSpeakers, len(off) - 1, x.shape[0]
+        TB = int(self._blocks(off)[-1])
+        if init_labels is not None and q0 is not None:
+            raise ValueError("pass init_labels or q0, not both")
+        for t in (init_labels, q0, sp0):
+            if isinstance(t, torch.Tensor) and t.is_cuda and t.device != x.device:
+                raise ValueError("every input must be on the device of feats")
+        if init_labels is not None and int(np.prod(np.shape(init_labels))) != F:
+            raise ValueError(f"init_labels must hold {F} values, got shape {tuple(np.shape(init_labels))}")
+        if q0 is not None:
+            if tuple(q0.shape) != (TB, K):
+                raise ValueError(f"q0 must be ({TB}, {K}), got {tuple(q0.shape)}")
+            qh = np.asarray(q0.cpu() if isinstance(q0, torch.Tensor) else q0, dtype=np.float64)
+            if not np.isfinite(qh).all() or (qh < 0).any() or (qh > 1 + 1e-9).any():
+                raise ValueError("q0 must hold probabilities")
+        if sp0 is not None:
+            sh = np.asarray(sp0.cpu() if isinstance(sp0, torch.Tensor) else sp0, dtype=np.float64)
+            if sh.shape not in ((K,), (N, K)) or not np.isfinite(sh).all() or (sh < 0).any() or (sh > 1 + 1e-9).any() or \
+                    (np.abs(sh.sum(-1) - 1) > 1e-6).any():
+                raise ValueError(f"sp0 must be ({K},) or ({N}, {K}) probabilities that sum to 1")
+
+    def _init_q(self, off, boff, init_labels, q0, seed, device):
+        K, d = self.maxSpeakers, self.downsample
+        TB = int(boff[-1])
+        if q0 is not None:
+            return torch.as_tensor(np.asarray(q0.cpu() if isinstance(q0, torch.Tensor) else q0, dtype=np.float64), device=device).contiguous()
+        if init_labels is None:
+            q = np.random.default_rng(seed).gamma(self.alphaQInit, size=(TB, K))
+            return torch.as_tensor(q / q.sum(1, keepdims=True), device=device)
+        lab = np.asarray(init_labels.cpu() if isinstance(init_labels, torch.Tensor) else init_labels).reshape(-1).astype(np.int64)
+        first = np.concatenate([off[r] + d * np.arange(boff[r + 1] - boff[r]) for r in range(len(off) - 1)] + [np.zeros(0, np.int64)])
+        lb = lab[first.astype(np.int64)]
+        q = np.full((TB, K), 1.0 / K)
+        ok = (lb >= 0) & (lb < K)
+        q[ok] = 0.0
+        q[np.nonzero(ok)[0], lb[ok]] = 1.0
+        return torch.as_tensor(q, device=device)
+
+    def _run(self, x, off, g, p, ll, trunc, init_labels, q0, sp0, seed):
+        dev = x.device
+        K, N, d = self.maxSpeakers, len(off) - 1, self.downsample
+        off = np.asarray(off, dtype=np.int64)
+        boff = self._blocks(off)
+        TB, F = int(boff[-1]), x.shape[0]
+        _, _, means, Bm, U = self._consts(dev)
+        q = self._init_q(off, boff, init_labels, q0, seed, dev)
+        sh = np.full((N, K), 1.0 / K) if sp0 is None else np.asarray(sp0.cpu() if isinstance(sp0, torch.Tensor) else sp0, dtype=np.float64)
+        sp = torch.as_tensor(np.ascontiguousarray(np.broadcast_to(sh, (N, K))), device=dev)
+        bound = np.full((N, self.maxIters), np.nan)
+        iters = np.zeros(N, np.int64)
+        live = np.diff(off) > 0
+        if TB:
+            o32 = torch.as_tensor(off.astype(np.int32), device=dev)
+            b32 = torch.as_tensor(boff.astype(np.int32), device=dev)
+            start, pairs = ops.vb_bucket(g, self.numGauss)
+            rec_of_block = torch.as_tensor(np.repeat(np.arange(N), np.diff(boff)), device=dev)
+            gsum = ops.vb_loglike_sums(ll, o32)                 # sum_t G_t per recording, in an order of the recording's own
+            active = live.copy()
+            prev = np.full(N, np.nan)
+            for it in range(self.maxIters):
+                Nst, Fst = ops.vb_speaker_stats(x, o32, b32, d, p, start, pairs, means, q)
+                _, _, kl, h, gg = ops.vb_speaker_update(Nst, Fst, Bm, U)
+                lls = ops.vb_block_loglike(x, o32, b32, d, TB, g, p, means, h, gg, K)
+                qn, spn, tll = ops.vb_forward_backward(lls, b32, sp, self.loopProb)
+                Lr = ops.vb_bound(gsum, tll, kl, self.statScale).cpu().numpy()      # the iteration's one device -> host read
+                if active.all():
+                    q, sp = qn, spn
+                else:
+                    act = torch.as_tensor(active, device=dev)
+                    q = torch.where(act[rec_of_block][:, None], qn, q)
+                    sp = torch.where(act[:, None], spn, sp)
+                bound[active, it] = Lr[active]
+                iters[active] = it + 1
+                if it > 0:
+                    active = active & ~(Lr - prev < self.epsilon)
+                prev = np.where(active, Lr, prev)
+                if not active.any():
+                    break
+        block_of_frame = np.concatenate([boff[r] + np.arange(off[r + 1] - off[r]) // d for r in range(N)] + [np.zeros(0, np.int64)])
+        fq = q[torch.as_tensor(block_of_frame.astype(np.int64), device=dev)] if F else torch.zeros((0, K), dtype=torch.float64, device=dev)
+        labels = fq.argmax(1).to(torch.int32) if F else torch.zeros((0,), dtype=torch.int32, device=dev)
+        return VBResult(q, fq, labels, sp, torch.as_tensor(bound, device=dev), iters, int(trunc.item()), off)

@@ -1175,3 +1175,153 @@ def plda_em_project(mu, mbar, P, lam, counts):
                                           L.stream_ptr())
     L.check(rc, "ktf_plda_em_project")
     return a, b
+
+
+# ----------------------------------------------------------------------------- VB-HMM resegmentation (ktf_vb_*)
+def _vb_ws(fn, name, *args, device):
+    n = int(fn(*args))
+    if n < 0:
+        L.check(n, name)
+    return torch.empty((n,), dtype=torch.uint8, device=device), n
+
+
+def vb_post_workspace_bytes(F, I):
+    n = int(L.load().ktf_vb_post_workspace_bytes(int(F), int(I)))
+    if n < 0:
+        L.check(n, "ktf_vb_post_workspace_bytes")
+    return n
+
+
+def vb_post(x, W, gconst, num_slots, ll_scale, stat_scale, sparsity_thr, truncated):
+    """Thresholded posteriors over all Gaussians on frames x (F, D) fp32: W (2D, I), gconst (I) as ivector_post takes them ->
+    (gauss (F, n) int32, post (F, n) fp32, loglike (F) fp32); `truncated` (1,) int32 on the device is increased by the frames with
+    more than n candidates: ktf_vb_post_f32."""
+    lib = L.load()
+    F, D = x.shape
+    n, I = int(num_slots), gconst.shape[0]
+    gauss = torch.empty((F, n), dtype=torch.int32, device=x.device)
+    post = torch.empty((F, n), dtype=torch.float32, device=x.device)
+    ll = torch.empty((F,), dtype=torch.float32, device=x.device)
+    ws, nbytes = _vb_ws(lib.ktf_vb_post_workspace_bytes, "ktf_vb_post_workspace_bytes", F, I, device=x.device)
+    with L.on_device(x.device):
+        rc = lib.ktf_vb_post_f32(L.ptr(x), F, D, x.stride(0) if F else D, L.ptr(W), L.ptr(gconst), I, n, float(ll_scale), float(stat_scale),
+                                 float(sparsity_thr), L.ptr(gauss), L.ptr(post), L.ptr(ll), L.ptr(truncated), L.ptr(ws), nbytes,
+                                 L.stream_ptr())
+    L.check(rc, "ktf_vb_post_f32")
+    return gauss, post, ll
+
+
+def vb_bucket(gauss, I):
+    """The (frame, slot) pairs of gauss (F, n) int32 bucketed by Gaussian in ascending pair order -> (start (I + 1), pairs (F n))
+    int32: ktf_vb_bucket."""
+    lib = L.load()
+    F, n = gauss.shape
+    start = torch.empty((I + 1,), dtype=torch.int32, device=gauss.device)
+    pairs = torch.empty((F * n,), dtype=torch.int32, device=gauss.device)
+    ws, nbytes = _vb_ws(lib.ktf_vb_bucket_workspace_bytes, "ktf_vb_bucket_workspace_bytes", F, I, n, device=gauss.device)
+    with L.on_device(gauss.device):
+        rc = lib.ktf_vb_bucket(L.ptr(gauss), F, n, I, L.ptr(start), L.ptr(pairs), L.ptr(ws), nbytes, L.stream_ptr())
+    L.check(rc, "ktf_vb_bucket")
+    return start, pairs
+
+
+def vb_speaker_stats(x, offsets, boffsets, downsample, post, start, pairs, means, q):
+    """Soft statistics of the N = offsets.numel() - 1 recordings in x (F, D): q (TB, K) fp64, means (I, D) fp64 -> (Nst (N K, I),
+    Fst (N K, I D)) fp64: ktf_vb_speaker_stats."""
+    F, D = x.shape
+    N, (TB, K), I = offsets.numel() - 1, q.shape, means.shape[0]
+    Nst = torch.empty((N * K, I), dtype=torch.float64, device=x.device)
+    Fst = torch.empty((N * K, I * D), dtype=torch.float64, device=x.device)
+    with L.on_device(x.device):
+        rc = L.load().ktf_vb_speaker_stats(L.ptr(x), F, D, x.stride(0) if F else D, L.ptr(offsets), L.ptr(boffsets), N, TB, int(downsample),
+                                           L.ptr(post), post.shape[1], L.ptr(start), L.ptr(pairs), I, L.ptr(means), L.ptr(q), K, L.ptr(Nst),
+                                           L.ptr(Fst), L.stream_ptr())
+    L.check(rc, "ktf_vb_speaker_stats")
+    return Nst, Fst
+
+
+def vb_speaker_update(Nst, Fst, Bm, U):
+    """Nst (B, I), Fst (B, I D), Bm (I D, R), U (I, P) fp64 -> a (B, R), W (B, P) packed, kl (B), h (B, I D), g (B, I):
+    ktf_vb_speaker_update."""
+    lib = L.load()
+    B, I = Nst.shape
+    R = Bm.shape[1]
+    D = Bm.shape[0] // I
+    P = R * (R + 1) // 2
+    dev = Nst.device
+    f = lambda *s: torch.empty(s, dtype=torch.float64, device=dev)  # noqa: E731
+    a, Wp, kl, h, g = f(B, R), f(B, P), f(B), f(B, I * D), f(B, I)
+    ws, nbytes = _vb_ws(lib.ktf_vb_update_workspace_bytes, "ktf_vb_update_workspace_bytes", B, I, D, R, device=dev)
+    with L.on_device(dev):
+        rc = lib.ktf_vb_speaker_update(L.ptr(Nst), L.ptr(Fst), B, I, D, R, L.ptr(Bm), L.ptr(U), L.ptr(a), L.ptr(Wp), L.ptr(kl), L.ptr(h),
+                                       L.ptr(g), L.ptr(ws), nbytes, L.stream_ptr())
+    L.check(rc, "ktf_vb_speaker_update")
+    return a, Wp, kl, h, g
+
+
+def vb_block_loglike(x, offsets, boffsets, downsample, TB, gauss, post, means, h, g, K):
+    """lls (TB, K) fp64 of the blocks: ktf_vb_block_loglike."""
+    F, D = x.shape
+    N, I = offsets.numel() - 1, means.shape[0]
+    lls = torch.empty((TB, K), dtype=torch.float64, device=x.device)
+    with L.on_device(x.device):
+        rc = L.load().ktf_vb_block_loglike(L.ptr(x), F, D, x.stride(0) if F else D, L.ptr(offsets), L.ptr(boffsets), N, TB, int(downsample),
+                                           L.ptr(gauss), L.ptr(post), gauss.shape[1], I, L.ptr(means), L.ptr(h), L.ptr(g), int(K), L.ptr(lls),
+                                           L.stream_ptr())
+    L.check(rc, "ktf_vb_block_loglike")
+    return lls
+
+
+def vb_forward_backward(lls, boffsets, sp, loop_prob):
+    """lls (TB, K), sp (N, K) fp64, boffsets (N + 1) int32 -> (q (TB, K), sp_out (N, K), tll (N)) fp64: ktf_vb_forward_backward."""
+    lib = L.load()
+    TB, K = lls.shape
+    N = boffsets.numel() - 1
+    dev = lls.device
+    q = torch.empty((TB, K), dtype=torch.float64, device=dev)
+    sp_out = torch.empty((N, K), dtype=torch.float64, device=dev)
+    tll = torch.empty((N,), dtype=torch.float64, device=dev)
+    ws, nbytes = _vb_ws(lib.ktf_vb_fb_workspace_bytes, "ktf_vb_fb_workspace_bytes", TB, N, device=dev)
+    with L.on_device(dev):
+        rc = lib.ktf_vb_forward_backward(L.ptr(lls), L.ptr(boffsets), N, TB, K, L.ptr(sp), float(loop_prob), L.ptr(q), L.ptr(sp_out),
+                                         L.ptr(tll), L.ptr(ws), nbytes, L.stream_ptr())
+    L.check(rc, "ktf_vb_forward_backward")
+    return q, sp_out, tll
+
+
+def vb_forward_backward_serial(lls, boffsets, sp, loop_prob):
+    """The forward-backward in its serial form (one wave per recording walks every block), for tools/bench_vb.py to time the chunked
+    scan against; the package itself never calls it. Arguments and results as vb_forward_backward: ktf_vb_forward_backward_serial."""
+    lib = L.load()
+    TB, K = lls.shape
+    N = boffsets.numel() - 1
+    dev = lls.device
+    q = torch.empty((TB, K), dtype=torch.float64, device=dev)
+    sp_out = torch.empty((N, K), dtype=torch.float64, device=dev)
+    tll = torch.empty((N,), dtype=torch.float64, device=dev)
+    ws, nbytes = _vb_ws(lib.ktf_vb_fb_serial_workspace_bytes, "ktf_vb_fb_serial_workspace_bytes", TB, N, device=dev)
+    with L.on_device(dev):
+        rc = lib.ktf_vb_forward_backward_serial(L.ptr(lls), L.ptr(boffsets), N, TB, K, L.ptr(sp), float(loop_prob), L.ptr(q), L.ptr(sp_out),
+                                                L.ptr(tll), L.ptr(ws), nbytes, L.stream_ptr())
+    L.check(rc, "ktf_vb_forward_backward_serial")
+    return q, sp_out, tll
+
+
+def vb_loglike_sums(loglike, offsets):
+    """gsum (N) fp64 = each recording's sum of loglike (F) fp32 in a fixed order of its own: ktf_vb_loglike_sums."""
+    N = offsets.numel() - 1
+    gsum = torch.empty((N,), dtype=torch.float64, device=loglike.device)
+    with L.on_device(loglike.device):
+        rc = L.load().ktf_vb_loglike_sums(L.ptr(loglike), L.ptr(offsets), N, loglike.shape[0], L.ptr(gsum), L.stream_ptr())
+    L.check(rc, "ktf_vb_loglike_sums")
+    return gsum
+
+
+def vb_bound(gsum, tll, kl, stat_scale):
+    """bound (N) fp64 = stat_scale gsum + tll + the recording's K entries of kl (N K) added in order: ktf_vb_bound."""
+    N = gsum.shape[0]
+    bound = torch.empty((N,), dtype=torch.float64, device=gsum.device)
+    with L.on_device(gsum.device):
+        rc = L.load().ktf_vb_bound(L.ptr(gsum), L.ptr(tll), L.ptr(kl), N, kl.numel() // N, float(stat_scale), L.ptr(bound), L.stream_ptr())
+    L.check(rc, "ktf_vb_bound")
+    return bound
