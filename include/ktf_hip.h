@@ -209,11 +209,27 @@ int ktf_cmvn_f32(const float* x, int64_t B, int64_t T, int32_t D, int64_t ldx, c
                  const KtfCmvnCfg* cfg, float* out, int64_t ldo, int32_t* out_lens, float* work, void* stream);
 /* Fused hot path: VAD -> per-utterance compaction -> CMVN (xvector_extractor.py:162-166).
  * out_dtype KTF_F32 or KTF_BF16. idx_work = B*T int32 (on return: the kept frame numbers of each utterance),
- * work = B*T*2*D floats (touched only by recordings too long for the LDS: more than ~38,000 frames). Any T < 2^31 / ldo.
+ * work = B*T*2*D floats (touched only when the rows do not fit the LDS beside the frame map: ktf_vad_cmvn_plan). Any T < 2^31 / ldo.
  * Batches of fewer than 256 utterances spread each utterance over up to eight workgroups (same values, bit for bit). */
 int ktf_vad_cmvn(const float* feats, int64_t B, int64_t T, int32_t D, const KtfVadCfg* vad, const KtfCmvnCfg* cmvn,
                  void* out, int32_t out_dtype, int64_t ldo, int32_t* lens, int32_t* idx_work, float* work,
                  void* stream);
+
+/* Where ktf_vad_cmvn / ktf_cmvn_f32 keep their working data for a given input size: each launcher decides it per call from
+ * (B, T, D, ldo) alone, and these two calls report that decision. Host arithmetic only (no GPU call; they work without a GPU).
+ * A field of 0 means "not in LDS": the frame map then lives in idx_work, the rows in `work`, the window sums are summed
+ * directly and the vote reads the energy out of the feature rows. */
+typedef struct KtfVcPlan {
+    int64_t pos_ints;      /* LDS ints of the compacted-row -> frame map (ktf_vad_cmvn only)                       */
+    int64_t stage_floats;  /* LDS floats of the staged rows                                                         */
+    int64_t bs_floats;     /* LDS floats of the sums of 32-row blocks                                               */
+    int64_t col_floats;    /* LDS floats of the energy column (ktf_vad_cmvn only)                                   */
+    int64_t lds_bytes;     /* dynamic LDS of the launch: the four above plus the kernels' fixed scratch, in bytes   */
+    int32_t nsplit;        /* workgroups per utterance (> 1 only in the all-in-LDS form, batches below 256)         */
+    int32_t lds_form;      /* 1: the kernel instantiation that addresses the rows as LDS                            */
+} KtfVcPlan;
+int ktf_vad_cmvn_plan(int64_t B, int64_t T, int32_t D, int64_t ldo, KtfVcPlan* plan);
+int ktf_cmvn_plan(int64_t T, int32_t D, int64_t ldo, KtfVcPlan* plan);
 
 /* Per-utterance routing by voiced length (no reference counterpart: the reference runs one utterance at a time in fp32). lens (B) ->
  * lens_main[b] = lens[b] >= min_frames ? lens[b] : 0 and lens_short[b] = 0 < lens[b] < min_frames ? lens[b] : 0. host_flag (optional):

@@ -1,6 +1,6 @@
 // VAD -> per-utterance compaction -> sliding-window CMVN for gfx950.
 //
-// One 256-thread workgroup owns one utterance (utterances are independent, so a batch is
+// One 1024-thread workgroup (VC_THREADS) owns one utterance (utterances are independent, so a batch is
 // B workgroups; no inter-workgroup traffic). The energy VAD needs the utterance mean of C0
 // (block reduction), a (2*ctx+1)-tap vote with the reference's edge denominators, and a
 // block-wide exclusive scan (wave ballots + LDS) to compact the kept frame numbers.
@@ -150,10 +150,54 @@ extern "C" int ktf_vad_index(const float* feats, int64_t B, int64_t T, int32_t D
     return KTF_OK;
 }
 
-// floats of LDS used to stage one utterance (0 = stage in the global workspace): whole utterances up to 150 KiB
+// floats of LDS used to stage one utterance (0 = stage in the global workspace): whole utterances up to 148 KiB
 static int64_t vc_stage_floats(int64_t T, int32_t D) {
     const int64_t need = T * D;
     return (need * 4 <= 148 * 1024) ? need : 0;
+}
+
+// ---------------------------------------------------------------------------------------------- where the working data lives
+// The one place both launchers decide it (and ktf_cmvn_plan / ktf_vad_cmvn_plan report it): a chain of "does it still fit in
+// 158 KiB beside what is already placed" tests, in the order map -> rows -> block sums -> energy column.
+static const int64_t VC_LDS_FIT = 158 * 1024;
+
+static void vc_plan_finish(KtfVcPlan* p) {
+    p->lds_bytes = (VC_GM + p->pos_ints + p->bs_floats + p->col_floats + p->stage_floats) * (int64_t)sizeof(float);
+}
+
+// ktf_cmvn_f32: rows in LDS (cmvn_kernel<true>) or in `work`; block sums only when they fit beside the staged utterance
+static void cmvn_plan(int64_t T, int32_t D, int64_t ldo, KtfVcPlan* p) {
+    p->pos_ints = 0;
+    p->col_floats = 0;
+    p->stage_floats = vc_stage_floats(T, D);
+    p->bs_floats = 2 * ((T + CMVN_CHUNK - 1) / CMVN_CHUNK) * ldo;
+    if ((VC_GM + p->bs_floats + p->stage_floats) * 4 > VC_LDS_FIT) p->bs_floats = 0;
+    p->nsplit = 1;
+    p->lds_form = p->stage_floats ? 1 : 0;
+    vc_plan_finish(p);
+}
+
+// ktf_vad_cmvn. The frame -> compacted-row map lives in LDS while (T + VC_GM) * 4 B <= 158 KiB (utterances up to ~6.4 min at
+// 10 ms); beyond that it lives in idx_work (which then holds the map, not a copy of it). Small batches: up to eight workgroups
+// share an utterance (cmvn_block) while the map, the energy column and the rows are all staged in LDS (a split workgroup of the
+// global-workspace form would write rows its siblings write too); that is also the LDSF instantiation.
+static void vad_cmvn_plan(int64_t B, int64_t T, int32_t D, int64_t ldo, KtfVcPlan* p) {
+    int64_t pos_ints = (T + 3) & ~3ll;
+    if ((VC_GM + pos_ints) * 4 > VC_LDS_FIT) pos_ints = 0;
+    int64_t stage_floats = vc_stage_floats(T, D);
+    if ((VC_GM + pos_ints + stage_floats) * 4 > VC_LDS_FIT) stage_floats = 0;
+    int64_t bs_floats = 2 * ((T + CMVN_CHUNK - 1) / CMVN_CHUNK) * ldo;
+    if ((VC_GM + pos_ints + bs_floats + stage_floats) * 4 > VC_LDS_FIT) bs_floats = 0;
+    int64_t col_floats = (T + 3) & ~3ll;
+    if ((VC_GM + pos_ints + bs_floats + col_floats + stage_floats) * 4 > VC_LDS_FIT) col_floats = 0;
+    p->pos_ints = pos_ints;
+    p->stage_floats = stage_floats;
+    p->bs_floats = bs_floats;
+    p->col_floats = col_floats;
+    p->lds_form = (pos_ints && stage_floats && col_floats) ? 1 : 0;
+    p->nsplit = 1;
+    if (p->lds_form) p->nsplit = (int32_t)(B >= 256 ? 1 : (256 / B > 8 ? 8 : 256 / B));
+    vc_plan_finish(p);
 }
 
 static int check_cmvn(const char* who, const KtfCmvnCfg* c) {
@@ -172,10 +216,10 @@ extern "C" int ktf_cmvn_f32(const float* x, int64_t B, int64_t T, int32_t D, int
     KTF_REQUIRE(ldo <= VC_GM / 4, "ktf_cmvn_f32: ldo > %d", VC_GM / 4);
     KTF_REQUIRE(T < (1ll << 31) / (ldo > 0 ? ldo : 1), "ktf_cmvn_f32: T*ldo too large");
     if (B * T == 0) return KTF_OK;
-    int64_t stage_floats = vc_stage_floats(T, D);
-    int64_t bs_floats = 2 * ((T + CMVN_CHUNK - 1) / CMVN_CHUNK) * ldo;
-    if ((VC_GM + bs_floats + stage_floats) * 4 > 158 * 1024) bs_floats = 0;     // block sums only when they fit beside the staged utterance
-    const size_t lds = (VC_GM + (size_t)bs_floats + (size_t)stage_floats) * sizeof(float);
+    KtfVcPlan pl;
+    cmvn_plan(T, D, ldo, &pl);
+    const int64_t stage_floats = pl.stage_floats, bs_floats = pl.bs_floats;
+    const size_t lds = (size_t)pl.lds_bytes;
     if (stage_floats) {
         KTF_LDS_ONCE(160 * 1024, cmvn_kernel<true>);
         hipLaunchKernelGGL(cmvn_kernel<true>, dim3((unsigned)B), dim3(VC_THREADS), lds, (hipStream_t)stream, x, T, D, ldx, lens, *cfg,
@@ -206,23 +250,12 @@ extern "C" int ktf_vad_cmvn(const float* feats, int64_t B, int64_t T, int32_t D,
         return KTF_OK;
     }
     hipStream_t st = (hipStream_t)stream;
-    // the frame -> compacted-row map lives in LDS while (T + VC_GM) * 4 B <= 158 KiB (utterances up to ~6.5 min at 10 ms);
-    // beyond that it lives in idx_work (which then holds the map, not the kept frame numbers)
-    int64_t pos_ints = (T + 3) & ~3ll;
-    if ((VC_GM + pos_ints) * 4 > 158 * 1024) pos_ints = 0;
-    int64_t stage_floats = vc_stage_floats(T, D);
-    if ((VC_GM + pos_ints + stage_floats) * 4 > 158 * 1024) stage_floats = 0;
-    int64_t bs_floats = 2 * ((T + CMVN_CHUNK - 1) / CMVN_CHUNK) * ldo;
-    if ((VC_GM + pos_ints + bs_floats + stage_floats) * 4 > 158 * 1024) bs_floats = 0;
-    int64_t col_floats = (T + 3) & ~3ll;
-    if ((VC_GM + pos_ints + bs_floats + col_floats + stage_floats) * 4 > 158 * 1024) col_floats = 0;
-    const size_t lds = (VC_GM + (size_t)pos_ints + (size_t)bs_floats + (size_t)col_floats + (size_t)stage_floats) * sizeof(float);
-    // small batches: up to eight workgroups share an utterance (cmvn_block), while the utterance and its map are staged in LDS
-    // (a split workgroup of the global-workspace form would write rows its siblings write too)
-    unsigned nsplit = 1;
-    if (pos_ints && stage_floats && col_floats) nsplit = (unsigned)(B >= 256 ? 1 : (256 / B > 8 ? 8 : 256 / B));
-    const dim3 grid((unsigned)B, nsplit);
-    const bool ldsf = pos_ints && stage_floats && col_floats;       // map, energy column and rows all in LDS
+    KtfVcPlan pl;
+    vad_cmvn_plan(B, T, D, ldo, &pl);
+    const int64_t pos_ints = pl.pos_ints, stage_floats = pl.stage_floats, bs_floats = pl.bs_floats, col_floats = pl.col_floats;
+    const size_t lds = (size_t)pl.lds_bytes;
+    const dim3 grid((unsigned)B, (unsigned)pl.nsplit);
+    const bool ldsf = pl.lds_form != 0;       // map, energy column and rows all in LDS
 #define VC_LAUNCH(OutT, F)                                                                                             \
     {                                                                                                                  \
         KTF_LDS_ONCE(160 * 1024, (vad_cmvn_kernel<OutT, F>));                                                          \
@@ -236,6 +269,30 @@ extern "C" int ktf_vad_cmvn(const float* feats, int64_t B, int64_t T, int32_t D,
     }
 #undef VC_LAUNCH
     KTF_CHECK_LAUNCH("ktf_vad_cmvn");
+    return KTF_OK;
+}
+
+// The placements the two launchers above choose, for callers (and tests) that want to know which of them an input takes.
+// Host arithmetic only: no HIP call, so both work without a GPU.
+static int check_plan(const char* who, int64_t B, int64_t T, int32_t D, int64_t ldo, const KtfVcPlan* plan) {
+    KTF_REQUIRE(plan, "%s: null plan", who);
+    KTF_REQUIRE(B > 0 && T > 0 && D > 0, "%s: bad sizes", who);
+    KTF_REQUIRE(ldo >= D && ldo <= VC_GM / 4, "%s: ldo must be in [D, %d]", who, VC_GM / 4);
+    KTF_REQUIRE(T < (1ll << 31) / ldo, "%s: T*ldo too large", who);
+    return KTF_OK;
+}
+
+extern "C" int ktf_cmvn_plan(int64_t T, int32_t D, int64_t ldo, KtfVcPlan* plan) {
+    int rc = check_plan("ktf_cmvn_plan", 1, T, D, ldo, plan);
+    if (rc) return rc;
+    cmvn_plan(T, D, ldo, plan);
+    return KTF_OK;
+}
+
+extern "C" int ktf_vad_cmvn_plan(int64_t B, int64_t T, int32_t D, int64_t ldo, KtfVcPlan* plan) {
+    int rc = check_plan("ktf_vad_cmvn_plan", B, T, D, ldo, plan);
+    if (rc) return rc;
+    vad_cmvn_plan(B, T, D, ldo, plan);
     return KTF_OK;
 }
 

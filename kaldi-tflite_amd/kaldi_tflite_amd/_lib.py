@@ -74,6 +74,11 @@ class CmvnCfg(C.Structure):
     _fields_ = [("window", C.c_int32), ("norm_vars", C.c_int32), ("valid", C.c_int32), ("reserved", C.c_int32)]
 
 
+class VcPlan(C.Structure):
+    _fields_ = [("pos_ints", C.c_int64), ("stage_floats", C.c_int64), ("bs_floats", C.c_int64), ("col_floats", C.c_int64),
+                ("lds_bytes", C.c_int64), ("nsplit", C.c_int32), ("lds_form", C.c_int32)]
+
+
 class TdnnDesc(C.Structure):
     _fields_ = [("units", C.c_int32), ("din", C.c_int32), ("din_pad", C.c_int32), ("nctx", C.c_int32),
                 ("ctx", C.c_int32 * 16), ("subsampling", C.c_int32), ("valid", C.c_int32), ("act", C.c_int32),
@@ -98,6 +103,8 @@ PROTOTYPES = {
     "ktf_vad_index": (C.c_int, [_P, _i64, _i64, _i32, C.POINTER(VadCfg), _P, _P, _P]),
     "ktf_cmvn_f32": (C.c_int, [_P, _i64, _i64, _i32, _i64, _P, C.POINTER(CmvnCfg), _P, _i64, _P, _P, _P]),
     "ktf_vad_cmvn": (C.c_int, [_P, _i64, _i64, _i32, C.POINTER(VadCfg), C.POINTER(CmvnCfg), _P, _i32, _i64, _P, _P, _P, _P]),
+    "ktf_vad_cmvn_plan": (C.c_int, [_i64, _i64, _i32, _i64, C.POINTER(VcPlan)]),
+    "ktf_cmvn_plan": (C.c_int, [_i64, _i32, _i64, C.POINTER(VcPlan)]),
     "ktf_route_short": (C.c_int, [_P, _i64, _i32, _P, _P, _P, _i32, _P]),
     "ktf_tdnn_out_len": (_i64, [_i64, C.POINTER(TdnnDesc)]),
     "ktf_tdnn_out_lens": (C.c_int, [_P, _i64, C.POINTER(TdnnDesc), _P, _P]),

@@ -293,6 +293,21 @@ def vad_cmvn(feats, vad_cfg, cmvn_cfg, out, lens, idx_work, work):
     L.check(rc, "ktf_vad_cmvn")
 
 
+def vad_cmvn_plan(B, T, D, ldo):
+    """Where `vad_cmvn` keeps its working data for a (B, T, D) batch written at row stride ldo: a `VcPlan` (ktf_vad_cmvn_plan;
+    host arithmetic, no GPU needed)."""
+    plan = L.VcPlan()
+    L.check(L.load().ktf_vad_cmvn_plan(B, T, D, ldo, C.byref(plan)), "ktf_vad_cmvn_plan")
+    return plan
+
+
+def cmvn_plan(T, D, ldo=None):
+    """The same for `cmvn` on utterances of T frames (ktf_cmvn_plan)."""
+    plan = L.VcPlan()
+    L.check(L.load().ktf_cmvn_plan(T, D, D if ldo is None else ldo, C.byref(plan)), "ktf_cmvn_plan")
+    return plan
+
+
 def last_kernel():
     """Kernel family the calling thread's last ktf_tdnn* / ktf_tdnn_mx* call launched (include/ktf_hip.h)."""
     return (L.load().ktf_tdnn_last_kernel() or b"").decode()

@@ -84,6 +84,12 @@ int main(void) {
     EXPECT_EINVAL(ktf_stats_finalize(NULL, NULL, 1, 1, 4, 1, 1e-10f, f, 8, NULL));
     EXPECT_EINVAL(ktf_stats_finalize_slots(d, 1, 128, NULL, 1000, 1, 4, 1, 1e-10f, f, 8, NULL));       /* too few slots */
     EXPECT_EINVAL(ktf_route_short(NULL, 1, 400, l, l, NULL, 0, NULL));
+    KtfVcPlan vp;
+    EXPECT_EINVAL(ktf_vad_cmvn_plan(1, 100, 30, 32, NULL));
+    EXPECT_EINVAL(ktf_vad_cmvn_plan(1, 0, 30, 32, &vp));
+    EXPECT_EINVAL(ktf_cmvn_plan(100, 30, 29, &vp));                                                    /* ldo < D */
+    if (ktf_vad_cmvn_plan(5, 998, 30, 32, &vp) != KTF_OK || vp.nsplit != 8 || !vp.lds_form || vp.stage_floats != 998 * 30 ||
+        ktf_cmvn_plan(20481, 30, 30, &vp) != KTF_OK || vp.stage_floats || vp.bs_floats || vp.lds_bytes != 8192) { printf("FAIL: ktf_vad_cmvn_plan / ktf_cmvn_plan\n"); ++fails; }
     t.gemm = KTF_GEMM_BF16X3; t.x_dtype = KTF_BF16; t.w_dtype = KTF_BF16; t.y_dtype = KTF_F32; t.units = 256;
     EXPECT_EINVAL(ktf_tdnn_split_flat(f, f, 1, 1, 32, NULL, NULL, &t, f, f, NULL, NULL, NULL, f, NULL, 256, NULL));        /* no row map */
     t.valid = 1;

@@ -562,3 +562,52 @@ def test_sequential_with_a_valid_padded_windowed_pooling_builds_for_any_number_o
     assert m.get_layer("t1.affine").inputDim == 192
     assert m.get_layer("w").compute_output_shape((None, None, 96)) == (None, None, 192)
     assert m.get_layer("w").compute_output_shape((2, 40, 96)) == (2, m.get_layer("w").numOutputSteps(40), 192)
+
+
+# ----------------------------------------------------------------------------- VAD / CMVN: where the launchers keep their working data
+def test_vad_cmvn_placement_plans_are_pinned():
+    """`ktf_vad_cmvn` places four things per call -- the frame map, the staged rows, the 32-row block sums and the energy column -- and
+    `ktf_cmvn_f32` two, by a chain of "does it still fit" tests over (T, D, ldo); `ktf_vad_cmvn_plan` / `ktf_cmvn_plan` report what the
+    launchers decide. A scan of T = 1 .. 45,000 meets nine distinct fused plans and four stand-alone ones at every width, each within
+    the 160 KiB the kernels are opted in to (checked per T by the scan), more than one workgroup per utterance only where map, rows
+    and column are all in LDS, and -- for the shipped width -- at the boundaries INTEGRATION.md tabulates (tests/test_gpu_vad_cmvn_
+    placements.py runs the kernels on both sides of each of them)."""
+    import _vc_plans as P
+    from kaldi_tflite_amd import ops
+    for D, ldo in [(30, 32), (40, 64), (80, 96), (23, 32)]:
+        runs = P.fused_runs(D, ldo)
+        assert len(runs) == 9 and len({r[2] for r in runs}) == 9, (D, ldo, runs)
+        assert runs[0][0] == 1 and runs[-1][1] == P.T_SCAN
+    for D in (30, 40, 80):
+        runs = P.cmvn_runs(D, D)
+        assert len(runs) == 4 and len({r[2] for r in runs}) == 4, (D, runs)
+    #                                            map    rows   sums   column LDS form
+    assert P.fused_runs(30, 32) == ((1, 1128, (True, True, True, True, True)),
+                                    (1129, 1162, (True, True, True, False, False)),
+                                    (1163, 1200, (True, True, False, True, True)),
+                                    (1201, 1238, (True, True, False, False, False)),
+                                    (1239, 9600, (True, False, True, True, False)),
+                                    (9601, 12800, (True, False, True, False, False)),
+                                    (12801, 19200, (True, False, False, True, False)),
+                                    (19201, 38400, (True, False, False, False, False)),
+                                    (38401, P.T_SCAN, (False, False, False, False, False)))
+    assert [(r[0], r[2][1:3]) for r in P.cmvn_runs(30, 30)] == [(1, (True, True)), (1205, (True, False)), (1263, (False, True)),
+                                                                (20481, (False, False))]
+    assert all(r[2][4] == r[2][1] and not r[2][0] and not r[2][3] for r in P.cmvn_runs(30, 30))     # no map, no column; LDS form = rows in LDS
+    # workgroups per utterance: 256 / B up to eight, and only in the all-in-LDS form
+    for D, ldo in [(30, 32), (80, 96)]:
+        for first, last, k in P.fused_runs(D, ldo):
+            for T in (first, last):
+                for B, want in [(1, 8), (5, 8), (32, 8), (33, 7), (100, 2), (128, 2), (129, 1), (255, 1), (256, 1), (1000, 1)]:
+                    p = ops.vad_cmvn_plan(B, T, D, ldo)
+                    assert P.placement(p) == k, "the placement does not depend on the batch"
+                    assert p.nsplit == (want if (k[0] and k[1] and k[3]) else 1), (D, ldo, T, B, p.nsplit)
+                    assert bool(p.lds_form) == (k[0] and k[1] and k[3])
+                assert ops.cmvn_plan(T, D, ldo).nsplit == 1
+    lib = L.load()
+    plan = L.VcPlan()
+    assert lib.ktf_vad_cmvn_plan(1, 100, 30, 32, None) == -1 and "null plan" in L.last_error()
+    assert lib.ktf_vad_cmvn_plan(0, 100, 30, 32, C.byref(plan)) == -1 and "bad sizes" in L.last_error()
+    assert lib.ktf_vad_cmvn_plan(1, 100, 30, 29, C.byref(plan)) == -1 and "ldo" in L.last_error()
+    assert lib.ktf_cmvn_plan(100, 30, 513, C.byref(plan)) == -1 and "ldo" in L.last_error()
+    assert lib.ktf_cmvn_plan(0, 30, 30, C.byref(plan)) == -1 and "bad sizes" in L.last_error()
