@@ -29,6 +29,15 @@ void ktf_set_error(const char* fmt, ...);
         }                                                                         \
     } while (0)
 
+// a HIP runtime call (hipMemsetAsync, hipMemcpyAsync) that must succeed; `what` is its name, a string literal
+#define KTF_CHECK_HIP(expr, name, what)                   \
+    do {                                                  \
+        if ((expr) != hipSuccess) {                       \
+            ktf_set_error("%s: " what " failed", name);   \
+            return KTF_ELAUNCH;                           \
+        }                                                 \
+    } while (0)
+
 // Opt a kernel in to more than 64 KiB of dynamic LDS: once per call site (= kernel instantiation) and device, not per
 // launch (a per-launch hipFuncSetAttribute was ~10 host calls per batch-1 extraction).
 #define KTF_LDS_ONCE(bytes, ...)                                                                       \
@@ -44,6 +53,13 @@ void ktf_set_error(const char* fmt, ...);
 
 static inline int ktf_cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 static inline int64_t al256(int64_t b) { return (b + 255) & ~(int64_t)255; }       // workspace arrays start 256-byte aligned
+
+// the caller's workspace against the `need` bytes its entry point computed (need >= 0)
+static inline int ktf_check_workspace(const char* who, const void* ws, size_t bytes, int64_t need) {
+    KTF_REQUIRE((int64_t)bytes >= need, "%s: workspace %zu bytes < %lld", who, bytes, (long long)need);
+    KTF_REQUIRE(((uintptr_t)ws & 255) == 0, "%s: workspace not 256-byte aligned", who);
+    return KTF_OK;
+}
 
 #ifdef __HIPCC__
 typedef __attribute__((ext_vector_type(4))) float f32x4;

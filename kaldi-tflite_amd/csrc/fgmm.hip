@@ -220,8 +220,7 @@ static int fg_post(const char* who, const float* x, int64_t F, int32_t D, int64_
     if (F == 0) return KTF_OK;
     KTF_REQUIRE(x && gselect && means_invcovars && inv_covars && gconst && gauss && post && workspace, "%s: null argument", who);
     const FgLayout l = fg_layout(F, I, n);
-    KTF_REQUIRE((int64_t)workspace_bytes >= l.total, "%s: workspace %zu bytes < %lld", who, workspace_bytes, (long long)l.total);
-    KTF_REQUIRE(((uintptr_t)workspace & 255) == 0, "%s: workspace not 256-byte aligned", who);
+    if (ktf_check_workspace(who, workspace, workspace_bytes, l.total) != KTF_OK) return KTF_EINVAL;
     char* ws = (char*)workspace;
     const int* start = (const int*)(ws + l.sec.start);
     const int* pairs = (const int*)(ws + l.sec.pairs);

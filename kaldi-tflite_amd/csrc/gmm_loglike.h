@@ -1,6 +1,7 @@
-// The diagonal-GMM log-likelihood tile shared by ktf_ivector_post_f32 (ivector.hip) and ktf_gmm_post_dense_f32 (gmm_train.hip):
-// IVP_FT frames per workgroup as [x, x^2] transposed in LDS, one Gaussian per thread, l = gconst + sum_k [x, x^2]_k W_kg with one
-// fmaf per term in ascending k. Both kernels therefore give the same bits for the same frame and Gaussian.
+// The diagonal-GMM log-likelihood tile shared by the fused selection of ktf_ivector_post_f32 (ivector.hip) and the dense kernel of
+// gmm_loglike.hip (ktf_gmm_post_dense_f32 in gmm_train.hip, ktf_vb_post_f32 in vb_post.hip): IVP_FT frames per workgroup as [x, x^2]
+// transposed in LDS, one Gaussian per thread, l = gconst + sum_k [x, x^2]_k W_kg with one fmaf per term in ascending k. Both
+// kernels therefore give the same bits for the same frame and Gaussian.
 #pragma once
 #include "common.h"
 
@@ -8,6 +9,12 @@ namespace {
 
 constexpr int IVP_FT = 32;          // frames per workgroup of the posterior kernels
 constexpr int IVP_GT = 256;         // Gaussians per tile (= threads)
+
+// LDS bytes of the tile's frames: 2D rows of IVP_FT floats
+inline size_t ivp_tile_lds_bytes(int D) { return (size_t)4 * 2 * D * IVP_FT; }
+
+// (v, g) ranks before (w, h): the larger value first, the lower index on ties
+__device__ __forceinline__ bool ranks_before(float v, int g, float w, int h) { return v > w || (v == w && g < h); }
 
 // xs (2D rows of IVP_FT): [x, x^2] of frames f0 .. f0 + IVP_FT - 1 transposed (a float4 is 4 frames of one k); zeros beyond F
 __device__ __forceinline__ void ivp_load_frames(float (*xs)[IVP_FT], const float* __restrict__ x, int64_t f0, int64_t F, int D, int64_t ldx,
@@ -40,3 +47,7 @@ __device__ __forceinline__ void ivp_loglikes(float (&acc)[IVP_FT], const float (
 }
 
 }  // namespace
+
+// ll (F, I) = the log-likelihoods of ALL I Gaussians on the F frames of x (F >= 1): one launch, IVP_FT frames per workgroup
+int gmm_dense_loglike(const char* who, const float* x, int64_t F, int D, int64_t ldx, const float* W, const float* gconst, int I, float* ll,
+                      hipStream_t stream);

@@ -3,8 +3,9 @@
 //
 //   gpre_kernel       one wave per frame, one listed Gaussian per lane: the fp32 diagonal log-likelihood in ascending d, softmax
 //                     over the list in slot order, the frame's log-likelihood, the count of frames with a non-empty list.
-//   gdense_ll_kernel  the log-likelihoods of ALL Gaussians on the tile of gmm_loglike.h (the bits of ktf_ivector_post_f32), written
-//   gdense_sm_kernel  to the workspace (F, I); then one wave per frame: softmax over all I, P (fp64), Xaug = [1, x, x^2] (fp64).
+//   gdense_ll_kernel  (gmm_loglike.hip) the log-likelihoods of ALL Gaussians on the tile of gmm_loglike.h (the bits of
+//   gdense_sm_kernel  ktf_ivector_post_f32), written to the workspace (F, I); then one wave per frame: softmax over all I, P (fp64),
+//                     Xaug = [1, x, x^2] (fp64).
 //   gmm_bucket.hip    the pairs bucketed by Gaussian, the buckets cut into items of KTF_GMM_ACC_ITEM_ROWS rows: item starts and,
 //                     for the Gaussians with more than one item, the starts of their partial results.
 //   gacc_diag_kernel  one workgroup per item, VALU fp64: wave w takes the item's rows r = w (mod 4) in order, lane l the columns
@@ -17,10 +18,9 @@
 // An item of a Gaussian with a single item adds straight into the accumulator (the same sum). No floating-point atomics anywhere.
 #include "gmm_bucket.h"
 #include "gmm_loglike.h"
+#include "f64_mfma.h"
 
 namespace {
-
-typedef double f64x4 __attribute__((ext_vector_type(4)));
 
 constexpr int GACC_THREADS = 256;
 constexpr int GACC_WAVES = GACC_THREADS / 64;
@@ -93,25 +93,6 @@ __global__ void __launch_bounds__(64 * GPRE_WAVES) gpre_kernel(const float* __re
 }
 
 // ---------------------------------------------------------------- (b) dense posteriors
-inline size_t gdense_lds_bytes(int D) { return (size_t)4 * 2 * D * IVP_FT; }
-
-__global__ void __launch_bounds__(IVP_GT) gdense_ll_kernel(const float* __restrict__ x, int64_t F, int D, int64_t ldx, const float* __restrict__ W,
-                                                           const float* __restrict__ gconst, int I, float* __restrict__ ll) {
-    extern __shared__ __attribute__((aligned(16))) float gd_lds[];
-    float(*xs)[IVP_FT] = reinterpret_cast<float(*)[IVP_FT]>(gd_lds);
-    const int tid = threadIdx.x;
-    const int64_t f0 = (int64_t)blockIdx.x * IVP_FT;
-    ivp_load_frames(xs, x, f0, F, D, ldx, tid);
-    __syncthreads();
-    for (int g = tid; g < I; g += IVP_GT) {
-        float acc[IVP_FT];
-        ivp_loglikes(acc, xs, W, gconst[g], I, g, 2 * D);
-#pragma unroll
-        for (int f = 0; f < IVP_FT; ++f)
-            if (f0 + f < F) ll[(f0 + f) * I + g] = acc[f];
-    }
-}
-
 // one wave per frame; lane l owns the Gaussians l, l + 64, ...: its sum in that order, then the butterfly
 __global__ void __launch_bounds__(64 * GPRE_WAVES) gdense_sm_kernel(const float* __restrict__ x, int64_t F, int D, int64_t ldx,
                                                                     const float* __restrict__ ll, int I, double* __restrict__ P,
@@ -338,14 +319,11 @@ extern "C" int ktf_gmm_post_dense_f32(const float* x, int64_t F, int32_t D, int6
     KTF_REQUIRE(ldx >= D, "%s: ldx %lld < D %d", who, (long long)ldx, (int)D);
     if (F == 0) return KTF_OK;
     KTF_REQUIRE(x && W && gconst && P && Xaug && loglike && workspace, "%s: null argument", who);
-    KTF_REQUIRE((int64_t)workspace_bytes >= need, "%s: workspace %zu bytes < %lld", who, workspace_bytes, (long long)need);
-    KTF_REQUIRE(((uintptr_t)workspace & 255) == 0, "%s: workspace not 256-byte aligned", who);
+    if (ktf_check_workspace(who, workspace, workspace_bytes, need) != KTF_OK) return KTF_EINVAL;
     hipStream_t st = (hipStream_t)stream;
     float* ll = (float*)workspace;
-    KTF_LDS_ONCE(gdense_lds_bytes(KTF_IVECTOR_MAX_FEAT_DIM), gdense_ll_kernel);
-    hipLaunchKernelGGL(gdense_ll_kernel, dim3((unsigned)((F + IVP_FT - 1) / IVP_FT)), dim3(IVP_GT), gdense_lds_bytes(D), st, x, F, (int)D, ldx, W,
-                       gconst, (int)I, ll);
-    KTF_CHECK_LAUNCH(who);
+    const int rc = gmm_dense_loglike(who, x, F, (int)D, ldx, W, gconst, (int)I, ll, st);
+    if (rc != KTF_OK) return rc;
     hipLaunchKernelGGL(gdense_sm_kernel, dim3((unsigned)((F + GPRE_WAVES - 1) / GPRE_WAVES)), dim3(64 * GPRE_WAVES), 0, st, x, F, (int)D, ldx,
                        (const float*)ll, (int)I, P, Xaug, loglike);
     KTF_CHECK_LAUNCH(who);
@@ -368,8 +346,7 @@ extern "C" int ktf_gmm_acc_f64(const float* x, int64_t F, int32_t D, int64_t ldx
     KTF_REQUIRE(occ && mean_acc && second_acc && workspace, "%s: null argument", who);
     KTF_REQUIRE(F == 0 || (x && gauss && post), "%s: null frames / posteriors", who);
     const GaccLayout l = gacc_layout(F, I, D, n, full != 0);
-    KTF_REQUIRE((int64_t)workspace_bytes >= l.total, "%s: workspace %zu bytes < %lld", who, workspace_bytes, (long long)l.total);
-    KTF_REQUIRE(((uintptr_t)workspace & 255) == 0, "%s: workspace not 256-byte aligned", who);
+    if (ktf_check_workspace(who, workspace, workspace_bytes, l.total) != KTF_OK) return KTF_EINVAL;
     if (F == 0) return KTF_OK;
     hipStream_t st = (hipStream_t)stream;
     char* ws = (char*)workspace;

@@ -13,16 +13,13 @@
 //   ivsolve_kernel    (d) per utterance: Q + I unpacked, blocked Cholesky (32-column panels, in the workspace), forward and back
 //                     substitution of linear + priorOffset e0, ivector(0) -= priorOffset.
 // Every stage is per utterance with a fixed reduction order, so an utterance's bits do not depend on its batch or position.
+// (a) is in this file; (b) - (d) are compiled once in ivector_stages.hip, for the extractor training and the VB speaker update too.
 #include "ivector_stages.h"
 #include "gmm_loglike.h"
 
 namespace {
 
-inline size_t ivpost_lds_bytes(int D, int n) { return (size_t)4 * (2 * D * IVP_FT + IVP_FT * (IVP_GT + 1) + 2 * IVP_FT * n + IVP_FT); }
-
-
-// (v, g) ranks before (w, h): larger log-likelihood first, the lower index on ties
-__device__ __forceinline__ bool better(float v, int g, float w, int h) { return v > w || (v == w && g < h); }
+inline size_t ivpost_lds_bytes(int D, int n) { return ivp_tile_lds_bytes(D) + (size_t)4 * (IVP_FT * (IVP_GT + 1) + 2 * IVP_FT * n + IVP_FT); }
 
 __global__ void __launch_bounds__(IVP_GT) ivpost_kernel(const float* __restrict__ x, int64_t F, int D, int64_t ldx,
                                                          const float* __restrict__ W, const float* __restrict__ gconst, int I, int n,
@@ -60,14 +57,14 @@ __global__ void __launch_bounds__(IVP_GT) ivpost_kernel(const float* __restrict_
                 const float v = gg < I ? ll[f][c + lane] : 0.f;
                 const float tv = __shfl(val, n - 1);
                 const int ti = __shfl(idx, n - 1);
-                unsigned long long m = __ballot(gg < I && (cnt < n || better(v, gg, tv, ti)));
+                unsigned long long m = __ballot(gg < I && (cnt < n || ranks_before(v, gg, tv, ti)));
                 while (m) {
                     const int src = __ffsll((long long)m) - 1;
                     m &= m - 1;
                     const float cv = __shfl(v, src);
                     const int cg = g0 + c + src;
-                    if (cnt == n && !better(cv, cg, __shfl(val, n - 1), __shfl(idx, n - 1))) continue;
-                    const int pos = __popcll(__ballot(lane < cnt && better(val, idx, cv, cg)));
+                    if (cnt == n && !ranks_before(cv, cg, __shfl(val, n - 1), __shfl(idx, n - 1))) continue;
+                    const int pos = __popcll(__ballot(lane < cnt && ranks_before(val, idx, cv, cg)));
                     const float pv = __shfl(val, lane > 0 ? lane - 1 : 0);
                     const int pi = __shfl(idx, lane > 0 ? lane - 1 : 0);
                     if (lane == pos) {
@@ -157,8 +154,7 @@ extern "C" int ktf_ivector_extract(const float* x, int64_t F, int32_t D, int64_t
     KTF_REQUIRE(out_dtype_bytes == 4 || out_dtype_bytes == 8, "%s: out_dtype_bytes %d, need 4 or 8", who, (int)out_dtype_bytes);
     KTF_REQUIRE(offsets && sigma_inv_M && U && ivectors && workspace, "%s: null argument", who);
     KTF_REQUIRE(F == 0 || (x && gauss && post), "%s: null frames / posteriors", who);
-    KTF_REQUIRE((int64_t)workspace_bytes >= need, "%s: workspace %zu bytes < %lld", who, workspace_bytes, (long long)need);
-    KTF_REQUIRE(((uintptr_t)workspace & 255) == 0, "%s: workspace not 256-byte aligned", who);
+    if (ktf_check_workspace(who, workspace, workspace_bytes, need) != KTF_OK) return KTF_EINVAL;
     return iv_run_stages(who, x, F, (int)D, ldx, offsets, (int)B, gauss, post, (int)n, posterior_scale, acoustic_weight, max_count,
                          sigma_inv_M, U, (int)I, (int)S, prior_offset, ivectors, (int)out_dtype_bytes, (char*)workspace, (hipStream_t)stream);
 }

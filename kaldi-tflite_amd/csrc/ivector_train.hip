@@ -3,26 +3,22 @@
 // totals. Stages (b) - (d) of the extraction (ivector_stages.h) leave gamma, F, the linear term and the Cholesky factor L of
 // Q = I + sum_i gamma_i U_i in the workspace; from there
 //
-//   ivcov_kernel     per utterance (one workgroup): sum_j log L_jj, X = L^-1 in place (blocked, 32 x 32 tiles in LDS), z = X lin',
-//                    w = X^T z (the posterior mean, the prior offset kept), W = X^T X + w w^T as a packed lower triangle, and the
-//                    scalar lin'^T w / 2 - sum_j log L_jj - offset^2 / 2 of the marginal likelihood. An utterance with no frames
-//                    gets zeros and the flag 0.
-//   atb_kernel       C += A^T B in fp64 on v_mfma_f64_16x16x4_f64: A (K x M) and B (K x N) row-major, K = the utterances of the
-//                    chunk, ascending inside every output element; no atomics, no split of K. One kernel for R (A = gamma,
-//                    B = W), Y (A = F, B = w), gamma, the prior's sum and scatter and the two scalar totals (A = the flags).
+//   ivcov_kernel     (ivector_stages.hip) per utterance (one workgroup): sum_j log L_jj, X = L^-1 in place (blocked, 32 x 32 tiles
+//                    in LDS), z = X lin', w = X^T z (the posterior mean, the prior offset kept), W = X^T X + w w^T as a packed lower
+//                    triangle, and the scalar lin'^T w / 2 - sum_j log L_jj - offset^2 / 2 of the marginal likelihood. An utterance
+//                    with no frames gets zeros and the flag 0.
+//   f64_atb          (f64_mfma.hip) C += A^T B in fp64 on v_mfma_f64_16x16x4_f64: A (K x M) and B (K x N) row-major, K = the
+//                    utterances of the chunk, ascending inside every output element; no atomics, no split of K. One kernel for R
+//                    (A = gamma, B = W), Y (A = F, B = w), gamma, the prior's sum and scatter and the two scalar totals (A = the flags).
 //   sec_acc_kernel   second-order statistics Ssec_i += sum_t p'_ti x_t x_t^T: the (frame, slot) pairs are bucketed by Gaussian with the
 //                    STABLE counting sort of gmm_bucket.hip, so a bucket lists its pairs in ascending pair id and its fp64 sum,
 //                    taken row after row, has the same bits on every run.
-#include "ivector_cov.h"
+#include "ivector_stages.h"
+#include "f64_mfma.h"
 #include "gmm_bucket.h"
 
 namespace {
 
-typedef double f64x4 __attribute__((ext_vector_type(4)));
-
-constexpr int ATB_MT = 2;           // 16-row MFMA tiles per wave
-constexpr int ATB_NT = 4;           // 16-column MFMA tiles per wave
-constexpr int ATB_WAVES = 4;        // waves per workgroup, stacked along M: a workgroup owns 128 x 64 of C
 constexpr int SEC_RB = 16;          // bucket rows staged in LDS per step
 
 struct TrLayout {
@@ -39,64 +35,6 @@ TrLayout tr_layout(int64_t B, int64_t I, int64_t D, int64_t S) {
     t.tail = at; at += al256(B * 2 * 8);
     t.total = at;
     return t;
-}
-
-// C (M x N, ldc) += A^T B: A (K x M, lda), B (K x N, ldb), all fp64 row-major. v_mfma_f64_16x16x4_f64: lane l holds A^T[row l & 15]
-// [k = l >> 4] and B[k = l >> 4][col l & 15]; result reg r of lane l is C[row (l >> 4) + 4 r][col l & 15]. The accumulators start
-// from C, and k runs upwards four at a time, so every element is C + its terms in ascending k whatever M, N or the grid.
-__global__ void __launch_bounds__(64 * ATB_WAVES) atb_kernel(const double* __restrict__ A, int64_t lda, const double* __restrict__ Bm,
-                                                              int64_t ldb, double* __restrict__ Cm, int64_t ldc, int64_t M, int64_t N,
-                                                              int64_t K) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int lc = lane & 15, lk = lane >> 4;
-    const int64_t m0 = ((int64_t)blockIdx.y * ATB_WAVES + wave) * (16 * ATB_MT);
-    const int64_t n0 = (int64_t)blockIdx.x * (16 * ATB_NT);
-    if (m0 >= M) return;
-    f64x4 acc[ATB_MT][ATB_NT];
-#pragma unroll
-    for (int i = 0; i < ATB_MT; ++i)
-#pragma unroll
-        for (int j = 0; j < ATB_NT; ++j)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int64_t row = m0 + 16 * i + lk + 4 * r, col = n0 + 16 * j + lc;
-                acc[i][j][r] = (row < M && col < N) ? Cm[row * ldc + col] : 0.0;
-            }
-    for (int64_t k0 = 0; k0 < K; k0 += 4) {
-        const int64_t k = k0 + lk;
-        double a[ATB_MT], bv[ATB_NT];
-#pragma unroll
-        for (int i = 0; i < ATB_MT; ++i) {
-            const int64_t m = m0 + 16 * i + lc;
-            a[i] = (k < K && m < M) ? A[k * lda + m] : 0.0;
-        }
-#pragma unroll
-        for (int j = 0; j < ATB_NT; ++j) {
-            const int64_t c = n0 + 16 * j + lc;
-            bv[j] = (k < K && c < N) ? Bm[k * ldb + c] : 0.0;
-        }
-#pragma unroll
-        for (int i = 0; i < ATB_MT; ++i)
-#pragma unroll
-            for (int j = 0; j < ATB_NT; ++j) acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[i], bv[j], acc[i][j], 0, 0, 0);
-    }
-#pragma unroll
-    for (int i = 0; i < ATB_MT; ++i)
-#pragma unroll
-        for (int j = 0; j < ATB_NT; ++j)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int64_t row = m0 + 16 * i + lk + 4 * r, col = n0 + 16 * j + lc;
-                if (row < M && col < N) Cm[row * ldc + col] = acc[i][j][r];
-            }
-}
-
-int atb(const char* who, const double* A, int64_t lda, const double* Bm, int64_t ldb, double* Cm, int64_t ldc, int64_t M, int64_t N,
-        int64_t K, hipStream_t st) {
-    hipLaunchKernelGGL(atb_kernel, dim3(ktf_cdiv(N, 16 * ATB_NT), ktf_cdiv(M, 16 * ATB_MT * ATB_WAVES)), dim3(64 * ATB_WAVES), 0, st, A, lda,
-                       Bm, ldb, Cm, ldc, M, N, K);
-    KTF_CHECK_LAUNCH(who);
-    return KTF_OK;
 }
 
 // ---------------------------------------------------------------- second-order statistics (the bucketing: gmm_bucket.hip)
@@ -164,7 +102,7 @@ extern "C" int ktf_atb_f64(const double* A, int64_t lda, const double* B, int64_
                 (long long)ldc);
     KTF_REQUIRE(C && (K == 0 || (A && B)), "%s: null argument", who);
     if (K == 0) return KTF_OK;
-    return atb(who, A, lda, B, ldb, C, ldc, M, N, K, (hipStream_t)stream);
+    return f64_atb(who, A, lda, B, ldb, C, ldc, M, N, K, (hipStream_t)stream);
 }
 
 extern "C" int64_t ktf_ivector_train_workspace_bytes(int32_t B, int32_t I, int32_t D, int32_t S) {
@@ -187,8 +125,7 @@ extern "C" int ktf_ivector_acc_stats(const float* x, int64_t F, int32_t D, int64
     KTF_REQUIRE(offsets && sigma_inv_M && U && workspace, "%s: null argument", who);
     KTF_REQUIRE(gamma && Y && R && ivector_sum && ivector_scatter && totals, "%s: null accumulator", who);
     KTF_REQUIRE(F == 0 || (x && gauss && post), "%s: null frames / posteriors", who);
-    KTF_REQUIRE((int64_t)workspace_bytes >= need, "%s: workspace %zu bytes < %lld", who, workspace_bytes, (long long)need);
-    KTF_REQUIRE(((uintptr_t)workspace & 255) == 0, "%s: workspace not 256-byte aligned", who);
+    if (ktf_check_workspace(who, workspace, workspace_bytes, need) != KTF_OK) return KTF_EINVAL;
     hipStream_t st = (hipStream_t)stream;
     char* ws = (char*)workspace;
     const IvLayout l = iv_layout(B, I, D, S);
@@ -199,18 +136,17 @@ extern "C" int ktf_ivector_acc_stats(const float* x, int64_t F, int32_t D, int64
     int rc = iv_run_stages(who, x, F, (int)D, ldx, offsets, (int)B, gauss, post, (int)n, posterior_scale, 1.f, 0.f, sigma_inv_M, U, (int)I,
                            (int)S, prior_offset, wv, 8, ws, st);
     if (rc != KTF_OK) return rc;
-    hipLaunchKernelGGL(ivcov_kernel, dim3(B), dim3(COV_THREADS), 0, st, (const double*)(ws + l.lin), offsets, F, (int)S, prior_offset,
-                       (double*)(ws + l.L), scat, wv, tail);
-    KTF_CHECK_LAUNCH(who);
+    rc = iv_cov(who, (const double*)(ws + l.lin), offsets, (int)B, F, (int)S, prior_offset, (double*)(ws + l.L), scat, wv, tail, st);
+    if (rc != KTF_OK) return rc;
     const int64_t P = (int64_t)S * (S + 1) / 2, ID = (int64_t)I * D;
     const double* gam = (const double*)(ws + l.gamma);
     const double* Fst = (const double*)(ws + l.F);
-    if ((rc = atb(who, gam, I, scat, P, R, P, I, P, B, st)) != KTF_OK) return rc;                 // R_i += gamma_ui W_u
-    if ((rc = atb(who, Fst, ID, wv, S, Y, S, ID, S, B, st)) != KTF_OK) return rc;                 // Y_i += F_ui w_u^T
-    if ((rc = atb(who, gam, I, tail, 2, gamma, 1, I, 1, B, st)) != KTF_OK) return rc;             // gamma += gamma_u (counted utterances)
-    if ((rc = atb(who, tail, 2, wv, S, ivector_sum, S, 1, S, B, st)) != KTF_OK) return rc;
-    if ((rc = atb(who, tail, 2, scat, P, ivector_scatter, P, 1, P, B, st)) != KTF_OK) return rc;
-    return atb(who, tail, 2, tail, 2, totals, 2, 1, 2, B, st);                                    // (num_ivectors, sum of the scalars)
+    if ((rc = f64_atb(who, gam, I, scat, P, R, P, I, P, B, st)) != KTF_OK) return rc;             // R_i += gamma_ui W_u
+    if ((rc = f64_atb(who, Fst, ID, wv, S, Y, S, ID, S, B, st)) != KTF_OK) return rc;             // Y_i += F_ui w_u^T
+    if ((rc = f64_atb(who, gam, I, tail, 2, gamma, 1, I, 1, B, st)) != KTF_OK) return rc;         // gamma += gamma_u (counted utterances)
+    if ((rc = f64_atb(who, tail, 2, wv, S, ivector_sum, S, 1, S, B, st)) != KTF_OK) return rc;
+    if ((rc = f64_atb(who, tail, 2, scat, P, ivector_scatter, P, 1, P, B, st)) != KTF_OK) return rc;
+    return f64_atb(who, tail, 2, tail, 2, totals, 2, 1, 2, B, st);                                // (num_ivectors, sum of the scalars)
 }
 
 extern "C" int64_t ktf_ivector_acc2_workspace_bytes(int64_t F, int32_t I, int32_t n) {
@@ -230,8 +166,7 @@ extern "C" int ktf_ivector_acc_second_order(const float* x, int64_t F, int32_t D
     KTF_REQUIRE(posterior_scale >= 0.f, "%s: posterior_scale must be >= 0", who);
     KTF_REQUIRE(Ssec && workspace, "%s: null argument", who);
     KTF_REQUIRE(F == 0 || (x && gauss && post), "%s: null frames / posteriors", who);
-    KTF_REQUIRE((int64_t)workspace_bytes >= need, "%s: workspace %zu bytes < %lld", who, workspace_bytes, (long long)need);
-    KTF_REQUIRE(((uintptr_t)workspace & 255) == 0, "%s: workspace not 256-byte aligned", who);
+    if (ktf_check_workspace(who, workspace, workspace_bytes, need) != KTF_OK) return KTF_EINVAL;
     if (F == 0) return KTF_OK;
     hipStream_t st = (hipStream_t)stream;
     char* ws = (char*)workspace;

@@ -86,8 +86,8 @@ def test_posteriors_overflow_counter():
 
 # ------------------------------------------------------------------------------------------------ statistics, update, lls
 @functools.lru_cache(maxsize=None)
-def stage_case(R, K, ds):
-    I, D, n, lens = 6, 5, 3, [37, 0, 58]
+def stage_case(R, K, ds, I=6, D=5):
+    n, lens = 3, [37, 0, 58]
     rng = np.random.default_rng(R * 100 + K * 10 + ds)
     (w, mi, iv), M = V.random_model(rng, I, D, R)
     m, iE, B, UU = V.consts(mi, iv, M)
@@ -120,11 +120,8 @@ def run_stages(c, K, ds):
     return dict(N=Nst, F=Fst, a=a, W=Wp, kl=kl, h=h, g=gg, lls=lls)
 
 
-@pytest.mark.parametrize("ds", [1, 7])
-@pytest.mark.parametrize("K", [1, 3, 10])
-@pytest.mark.parametrize("R", [4, 33, 100])
-def test_stats_update_loglike(R, K, ds):
-    c = stage_case(R, K, ds)
+def check_stages(R, K, ds, **shape):
+    c = stage_case(R, K, ds, **shape)
     got = {k: v.cpu().numpy() for k, v in run_stages(c, K, ds).items()}
     again = {k: v.cpu().numpy() for k, v in run_stages(c, K, ds).items()}
     recs, I, D = c["recs"], c["I"], c["D"]
@@ -134,13 +131,26 @@ def test_stats_update_loglike(R, K, ds):
                 kl=np.concatenate([r["up"][2] for r in recs]), h=np.concatenate([r["up"][3].reshape(K, I * D) for r in recs]),
                 g=np.concatenate([r["up"][4] for r in recs]), lls=np.concatenate([r["lls"] for r in recs]))
     errs = {k: rel(got[k], want[k]) for k in want}
-    print(f"vb stages R={R} K={K} downsample={ds}: " + ", ".join(f"{k} {e:.2e}" for k, e in errs.items()) + " (bound 1e-8)")
+    print(f"vb stages I={I} D={D} R={R} K={K} downsample={ds}: " + ", ".join(f"{k} {e:.2e}" for k, e in errs.items()) + " (bound 1e-8)")
     for k in want:
         assert got[k].shape == want[k].shape, k
         assert errs[k] <= 1e-8, (k, errs[k])
         assert np.array_equal(got[k], again[k]), k
     # the recording without frames: zero statistics, the prior's update
     assert not got["N"][K:2 * K].any() and not got["F"][K:2 * K].any() and not got["a"][K:2 * K].any() and not got["kl"][K:2 * K].any()
+
+
+@pytest.mark.parametrize("ds", [1, 7])
+@pytest.mark.parametrize("K", [1, 3, 10])
+@pytest.mark.parametrize("R", [4, 33, 100])
+def test_stats_update_loglike(R, K, ds):
+    check_stages(R, K, ds)
+
+
+def test_stats_update_loglike_two_workgroups_along_n():
+    # h = a B^T has N = I D = 275 columns: two workgroups of the A B^T product along N, the second with one ragged wave and three
+    # that exit (the shapes above have N = 30: one workgroup, one wave); M = 9 speaker rows
+    check_stages(5, 3, 1, I=11, D=25)
 
 
 # ------------------------------------------------------------------------------------------------ forward-backward
