@@ -877,6 +877,38 @@ int ktf_vb_loglike_sums(const float* loglike, const int32_t* offsets, int32_t N,
 int ktf_vb_bound(const double* gsum, const double* tll, const double* kl, int32_t N, int32_t K, double stat_scale, double* bound,
                  void* stream);
 
+/* ------------------------------------------------------------------ VBx
+ * The VB-HMM of Landini / Diez / Burget ("Bayesian HMM clustering of x-vector sequences") over the window x-vectors of the N
+ * recordings of a call, in the PLDA-transformed space: within-class covariance I, between-class covariance diag(phi), D <=
+ * KTF_VBX_MAX_DIM dimensions (512, ktf_plda_dense_*'s limit: no stage keeps a 16 x D block in LDS, so no LDS budget binds it),
+ * K <= KTF_VB_MAX_SPEAKERS speakers, everything fp64. Windows lie end to end in time order: recording r owns rows [offsets[r],
+ * offsets[r + 1]) of the TB rows of x / rho / gamma / lls (offsets: N + 1 device int32, the convention of ktf_vb_*). One iteration is
+ * ktf_vbx_speaker_update, ktf_vbx_loglike, ktf_vb_forward_backward (gamma = q, pi = sp) and ktf_vb_bound with a zero gsum and
+ * Fb kl: ELBO = tll + Fb sum_k kl_k. A speaker with pi_k = 0 and a zero gamma column stays at zero and adds 0 to the bound, so a
+ * batch runs at one K and zero-pads the speakers a recording does not use.
+ * Every fp64 sum runs in a fixed order that depends on the recording alone: its results have the same bits alone, in a batch and
+ * at any offset. The orders: G_t: lane l of a wave takes d = l, l + 64, ..., then a butterfly over the 64 lanes. gamma^T rho and
+ * N_k: a recording's windows are cut into chunks of KTF_VBX_UPDATE_ROWS counted from its first window, one workgroup per chunk;
+ * within a chunk the windows ascend, four per v_mfma_f64_16x16x4_f64; the chunks' partial sums are then added in chunk order. c_k
+ * and kl_k: lane j of 16 takes d = j, j + 16, ..., then a butterfly over the 16. lls_tk: d ascending, four per MFMA.
+ *
+ * ktf_vbx_prepare: x (TB, D), phi (D) > 0 -> rho (TB, D) = x sqrt(phi), G (TB) = -(sum_d x_td^2 + D log 2 pi) / 2. */
+#define KTF_VBX_MAX_DIM 512
+#define KTF_VBX_UPDATE_ROWS 256
+int ktf_vbx_prepare(const double* x, int64_t TB, int32_t D, const double* phi, double* rho, double* G, void* stream);
+/* With N_k = sum_t gamma_tk over the recording's windows and f = fa_over_fb: invL (N, K, D) = 1 / (1 + f N_k phi_d), alpha
+ * (N, K, D) = f invL sum_t gamma_tk rho_td, c (N, K) = sum_d (invL + alpha^2) phi_d / 2, kl (N, K) = sum_d (log invL - invL -
+ * alpha^2 + 1) / 2; gamma (TB, K). A recording without windows gets c = kl = 0 and its rows of alpha and invL are not written.
+ * workspace: 256-byte aligned, at least ktf_vbx_update_workspace_bytes(TB, N, D) bytes. */
+int64_t ktf_vbx_update_workspace_bytes(int64_t TB, int32_t N, int32_t D);
+int ktf_vbx_speaker_update(const double* gamma, const double* rho, int64_t TB, int32_t D, int32_t K, const int32_t* offsets, int32_t N,
+                           const double* phi, double fa_over_fb, double* alpha, double* invL, double* c, double* kl, void* workspace,
+                           size_t workspace_bytes, void* stream);
+/* lls (TB, K): row t of recording r = Fa (sum_d rho_td alpha_rkd - c_rk + G_t), in tiles of 16 windows x 16 speakers on the same
+ * MFMA; rows of another recording and speakers past K contribute nothing to a tile. */
+int ktf_vbx_loglike(const double* rho, const double* G, int64_t TB, int32_t D, int32_t K, const int32_t* offsets, int32_t N,
+                    const double* alpha, const double* c, double Fa, double* lls, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

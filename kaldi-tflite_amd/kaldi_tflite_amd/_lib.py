@@ -205,6 +205,10 @@ PROTOTYPES = {
     "ktf_vb_forward_backward_serial": (C.c_int, [_P, _P, _i32, _i64, _i32, _P, C.c_double, _P, _P, _P, _P, C.c_size_t, _P]),
     "ktf_vb_loglike_sums": (C.c_int, [_P, _P, _i32, _i64, _P, _P]),
     "ktf_vb_bound": (C.c_int, [_P, _P, _P, _i32, _i32, C.c_double, _P, _P]),
+    "ktf_vbx_prepare": (C.c_int, [_P, _i64, _i32, _P, _P, _P, _P]),
+    "ktf_vbx_update_workspace_bytes": (_i64, [_i64, _i32, _i32]),
+    "ktf_vbx_speaker_update": (C.c_int, [_P, _P, _i64, _i32, _i32, _P, _i32, _P, C.c_double, _P, _P, _P, _P, _P, C.c_size_t, _P]),
+    "ktf_vbx_loglike": (C.c_int, [_P, _P, _i64, _i32, _i32, _P, _i32, _P, _P, C.c_double, _P, _P]),
 }
 PLDA_DENSE_NO_PCA = -1.0            # ktf_plda_dense_*: target_energy for "no PCA"
 PLDA_DENSE_MAX_DIM = 512
@@ -216,6 +220,7 @@ GMM_ACC_ITEM_ROWS = 1024            # ktf_gmm_acc_f64: rows of a bucket per item
 ADD_DELTAS_MAX_CONTEXT = 32         # ktf_add_deltas_f32: order * window
 TRAIN_MAX_DIM = 1024                # ktf_train_*, ktf_plda_em_project
 VB_MAX_SPEAKERS, VB_FB_CHUNK = 16, 128   # ktf_vb_*: speakers per recording, blocks per chunk of the forward-backward scan
+VBX_MAX_DIM, VBX_UPDATE_ROWS = 512, 256  # ktf_vbx_*: dimensions; windows per workgroup of the speaker update
 
 _lib = None
 

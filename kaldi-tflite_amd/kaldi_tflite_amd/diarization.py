@@ -1,6 +1,6 @@
 """Extension: x-vector diarization on the device. Kaldi's `agglomerative-cluster` (single pass) over the blocks `PLDA.score_dense`
 returns, batched over recordings; RTTM lines from window labels and the wav -> RTTM composition `diarize`
-(INTEGRATION.md §2d)."""
+(INTEGRATION.md §2d); the VB-HMM resegmentation of frames (§2j) and VBx, the VB-HMM over the window x-vectors (§2k)."""
 
 import numbers
 
@@ -163,17 +163,22 @@ def rttm(res, labels, reco_ids=None, channel=1):
 
 class Diarization:
     """diarize's result: windows (extract_windows' WindowXvectors), labels (S,) int32 and counts (R,) int32 (speakers per recording, 0
-    for a recording without windows) on the GPU, rttm (list of str)."""
+    for a recording without windows) on the GPU, rttm (list of str). With diarize(vbx=...) labels, counts and rttm are VBx's,
+    ahc_labels (S,) keeps the clustering's labels and vbx the VBxResult; otherwise both are None."""
 
-    def __init__(self, windows, labels, counts, rttm_lines):
+    def __init__(self, windows, labels, counts, rttm_lines, ahc_labels=None, vbx=None):
         self.windows, self.labels, self.counts, self.rttm = windows, labels, counts, rttm_lines
+        self.ahc_labels, self.vbx = ahc_labels, vbx
 
 
 def diarize(ext, plda, wavs, target_energy=0.1, threshold=None, num_speakers=None, max_spk_fraction=1.0, segments=None, window=1.5,
-            period=0.75, min_segment=0.5, reco_ids=None):
+            period=0.75, min_segment=0.5, reco_ids=None, vbx=None):
     """wav -> RTTM: ext.extract_windows -> plda.score_dense (the recordings with windows) -> agglomerative_cluster -> rttm.
     num_speakers: None (threshold mode), an int, or R ints (one per recording of wavs). Recordings without windows are left out of
-    scoring and clustering and produce no lines."""
+    scoring and clustering and produce no lines. vbx: a VBx to run on the window x-vectors from the clustering's labels (the windows
+    of a recording must be in time order, as extract_windows lists them); the result's labels, counts and rttm are then VBx's."""
+    if vbx is not None and not isinstance(vbx, VBx):
+        raise ValueError(f"vbx must be a VBx, got {type(vbx).__name__}")
     res = ext.extract_windows(wavs, window=window, period=period, min_segment=min_segment, segments=segments)
     R = len(res.lengths)
     live = [r for r in range(R) if res.lengths[r] > 0]
@@ -181,7 +186,7 @@ def diarize(ext, plda, wavs, target_energy=0.1, threshold=None, num_speakers=Non
     counts = torch.zeros((R,), dtype=torch.int32, device=dev)
     if not live:
         labels = torch.zeros((0,), dtype=torch.int32, device=dev)
-        return Diarization(res, labels, counts, [])
+        return Diarization(res, labels, counts, [], ahc_labels=None if vbx is None else labels)
     ns = num_speakers
     if ns is not None and not isinstance(ns, (numbers.Integral, np.integer)):
         arr = list(ns.tolist() if isinstance(ns, torch.Tensor) else ns)
@@ -192,6 +197,9 @@ def diarize(ext, plda, wavs, target_energy=0.1, threshold=None, num_speakers=Non
     labels, cnt = agglomerative_cluster(scores, threshold=threshold, num_speakers=ns, max_spk_fraction=max_spk_fraction)
     labels = torch.cat(labels) if len(labels) > 1 else labels[0]
     counts[torch.as_tensor(live, device=dev)] = cnt
+    if vbx is not None:
+        out = vbx(res.xvectors, res.lengths, init_labels=labels)
+        return Diarization(res, out.labels, out.counts, rttm(res, out.labels, reco_ids), ahc_labels=labels, vbx=out)
     return Diarization(res, labels, counts, rttm(res, labels, reco_ids))
 
 
@@ -468,3 +476,235 @@ class VBResegmenter:
         fq = q[torch.as_tensor(block_of_frame.astype(np.int64), device=dev)] if F else torch.zeros((0, K), dtype=torch.float64, device=dev)
         labels = fq.argmax(1).to(torch.int32) if F else torch.zeros((0,), dtype=torch.int32, device=dev)
         return VBResult(q, fq, labels, sp, torch.as_tensor(bound, device=dev), iters, int(trunc.item()), off)
+
+
+# =============================================================================== VBx
+def _host(a, dtype=None):
+    return np.asarray(a.cpu() if isinstance(a, torch.Tensor) else a, dtype=dtype)
+
+
+def vbx_init(init_labels, offsets, K, smoothing):
+    """VBx's start from one integer label per window (host logic, no kernel): with the distinct labels of recording r in ascending
+    order as columns 0 .. K_r - 1, gamma0 = softmax(smoothing * onehot) over those columns and 0 on the rest, pi0 = 1 / K_r on them.
+    When K_r > K only the K clusters with the most windows are kept (ties to the lower label; columns still in ascending label
+    order) and a window of a dropped cluster gets a row uniform over the kept columns. -> gamma0 (S, K), pi0 (N, K) fp64 arrays."""
+    off = np.asarray(offsets, dtype=np.int64)
+    lab = _host(init_labels).reshape(-1)
+    if lab.size and lab.dtype.kind not in "iu":
+        raise ValueError(f"init_labels must be integers, got {lab.dtype}")
+    if lab.size != off[-1]:
+        raise ValueError(f"init_labels must hold {int(off[-1])} values, got {lab.size}")
+    N = len(off) - 1
+    gamma, pi = np.zeros((lab.size, K)), np.zeros((N, K))
+    hot = np.exp(float(smoothing))
+    for r in range(N):
+        l = lab[off[r]:off[r + 1]].astype(np.int64)
+        if l.size == 0:
+            pi[r] = 1.0 / K                      # never read: the recording has no window
+            continue
+        ids, cnt = np.unique(l, return_counts=True)
+        if ids.size > K:
+            ids = np.sort(ids[np.lexsort((ids, -cnt))[:K]])
+        Kr = ids.size
+        col = np.searchsorted(ids, l)
+        kept = (col < Kr) & (ids[np.minimum(col, Kr - 1)] == l)
+        g = np.full((l.size, Kr), 1.0 / (hot + Kr - 1))
+        g[np.nonzero(kept)[0], col[kept]] = hot / (hot + Kr - 1)
+        g[~kept] = 1.0 / Kr
+        gamma[off[r]:off[r + 1], :Kr] = g
+        pi[r, :Kr] = 1.0 / Kr
+    return gamma, pi
+
+
+def vbx_labels(gamma, offsets):
+    """labels (S,) int32 = arg-max of each row of gamma (S, K), ties to the lower index, renumbered per recording to 1 .. K'_r in
+    ascending column order, and counts (N,) int32 = K'_r (0 for a recording without windows); torch, on gamma's device."""
+    off = np.asarray(offsets, dtype=np.int64)
+    N, (S, K) = len(off) - 1, gamma.shape
+    dev = gamma.device
+    if S == 0:
+        return torch.zeros((0,), dtype=torch.int32, device=dev), torch.zeros((N,), dtype=torch.int32, device=dev)
+    top = gamma.max(1, keepdim=True).values
+    arg = (gamma == top).to(torch.int32).argmax(1)               # the first column that reaches the row's maximum
+    rec = torch.as_tensor(np.repeat(np.arange(N), np.diff(off)), device=dev)
+    used = torch.zeros((N, K), dtype=torch.int32, device=dev)
+    used[rec, arg] = 1
+    rank = torch.cumsum(used, 1)
+    return rank[rec, arg].to(torch.int32), used.sum(1).to(torch.int32)
+
+
+class VBxResult:
+    """VBx's result: gamma (S, K) fp64 window posteriors, pi (N, K), elbo (N, max_iters) NaN-padded, labels (S,) int32 (arg-max of
+    gamma, ties to the lower index, renumbered per recording to 1 .. K'_r in ascending column order) and counts (N,) int32 = K'_r (0
+    for a recording without windows), all on the GPU; iters (N,) and offsets (N + 1) host int64 (recording r owns windows
+    offsets[r] .. offsets[r + 1])."""
+
+    def __init__(self, gamma, pi, elbo, iters, offsets, labels, counts):
+        self.gamma, self.pi, self.elbo, self.iters, self.offsets, self.labels, self.counts = gamma, pi, elbo, iters, offsets, labels, counts
+
+
+class VBx:
+    """Extension: VBx (Landini, Diez, Burget, "Bayesian HMM clustering of x-vector sequences") on the GPU, batched over recordings:
+    the VB-HMM of VBResegmenter over the window x-vectors themselves, the speaker model being a PLDA with within-class covariance I
+    and between-class covariance diag(phi) in the transformed space. phi (D,) > 0; transform (D, Din) and offset (D,) take the input
+    vectors there (y = transform x + offset, D <= Din; None: the vectors are used as they are). The usual start is AHC's labels
+    (`diarize(..., vbx=...)`). The defaults are the BUT recipe's as remembered (the recipe is not pinned here): max_speakers 10,
+    max_iters 40, epsilon 1e-6, loop_prob 0.99, Fa 0.3, Fb 17.0, init_smoothing 5.0. The rules are those of include/ktf_hip.h
+    (ktf_vbx_*) and INTEGRATION.md §2k."""
+
+    def __init__(self, phi, transform=None, offset=None, max_speakers=10, max_iters=40, epsilon=1e-6, loop_prob=0.99, Fa=0.3, Fb=17.0,
+                 init_smoothing=5.0):
+        phi = np.ascontiguousarray(_host(phi), dtype=np.float64)
+        if phi.ndim != 1 or not 1 <= phi.size <= L.VBX_MAX_DIM:
+            raise ValueError(f"phi must be a vector of 1 .. {L.VBX_MAX_DIM} values, got shape {phi.shape}")
+        if not np.isfinite(phi).all() or (phi <= 0).any():
+            raise ValueError("phi must be positive and finite")
+        D = phi.size
+        if transform is None:
+            if offset is not None:
+                raise ValueError("offset needs a transform")
+            self._A = self._b = None
+            Din = D
+        else:
+            A = np.asarray(_host(transform), dtype=np.float64)
+            if A.ndim != 2 or A.shape[0] != D or not D <= A.shape[1] <= L.PLDA_DENSE_MAX_DIM or not np.isfinite(A).all():
+                raise ValueError(f"transform must be a finite ({D}, Din) matrix with {D} <= Din <= {L.PLDA_DENSE_MAX_DIM}, got shape {A.shape}")
+            Din = A.shape[1]
+            b = np.zeros(D) if offset is None else np.asarray(_host(offset), dtype=np.float64)
+            if b.shape != (D,) or not np.isfinite(b).all():
+                raise ValueError(f"offset must be a finite ({D},) vector, got shape {b.shape}")
+            self._A = np.zeros((Din, Din))       # ktf_plda_f64 takes a square matrix: rows past D are zero and dropped afterwards
+            self._A[:D] = A
+            self._b = np.concatenate([b, np.zeros(Din - D)])
+        if isinstance(max_speakers, bool) or not isinstance(max_speakers, (numbers.Integral, np.integer)) or \
+                not 1 <= int(max_speakers) <= L.VB_MAX_SPEAKERS:
+            raise ValueError(f"max_speakers {max_speakers!r} outside 1 .. {L.VB_MAX_SPEAKERS}")
+        if isinstance(max_iters, bool) or not isinstance(max_iters, (numbers.Integral, np.integer)) or int(max_iters) < 1:
+            raise ValueError(f"max_iters {max_iters!r} < 1")
+        if not _real(loop_prob) or not 0.0 <= float(loop_prob) <= 1.0:
+            raise ValueError(f"loop_prob {loop_prob!r} outside [0, 1]")
+        if not (_real(Fa) and _real(Fb) and 0 < float(Fa) < np.inf and 0 < float(Fb) < np.inf):
+            raise ValueError(f"Fa and Fb must be > 0 and finite, got {Fa!r}, {Fb!r}")
+        if not _real(epsilon) or np.isnan(float(epsilon)):
+            raise ValueError(f"epsilon must be a number, got {epsilon!r}")
+        if not _real(init_smoothing) or not 0.0 <= float(init_smoothing) <= 700.0:
+            raise ValueError(f"init_smoothing {init_smoothing!r} outside [0, 700]")
+        self.phi, self.dim, self.inputDim = phi, D, Din
+        self.maxSpeakers, self.maxIters, self.epsilon = int(max_speakers), int(max_iters), float(epsilon)
+        self.loopProb, self.Fa, self.Fb, self.initSmoothing = float(loop_prob), float(Fa), float(Fb), float(init_smoothing)
+        self._dev_cache = {}
+
+    @classmethod
+    def from_plda(cls, plda, lda_dim=None, **kw):
+        """The speaker model of a layers.PLDA: its transformMat and offset as the plain affine transform (no length normalisation,
+        whatever the layer's flags say) and its psi as phi. lda_dim keeps the first lda_dim rows, the largest between-class
+        variances when psi descends as Kaldi writes it; a psi that does not descend is refused when lda_dim truncates."""
+        A = np.asarray(plda.transformMat, dtype=np.float64)
+        b = np.asarray(plda.offset, dtype=np.float64)
+        psi = np.asarray(plda.psi, dtype=np.float64)
+        dim = psi.size
+        if lda_dim is None:
+            lda_dim = dim
+        if isinstance(lda_dim, bool) or not isinstance(lda_dim, (numbers.Integral, np.integer)) or not 1 <= int(lda_dim) <= dim:
+            raise ValueError(f"lda_dim {lda_dim!r} outside 1 .. {dim}")
+        lda_dim = int(lda_dim)
+        if lda_dim < dim and (np.diff(psi) > 0).any():
+            raise ValueError("psi does not descend: the first lda_dim rows would not be the largest between-class variances")
+        return cls(psi[:lda_dim], A[:lda_dim], b[:lda_dim], **kw)
+
+    def _consts(self, device):
+        key = str(device)
+        if key not in self._dev_cache:
+            f = lambda a: None if a is None else torch.as_tensor(np.ascontiguousarray(a), device=device)  # noqa: E731
+            self._dev_cache[key] = (f(self.phi), f(self._A), f(self._b))
+        return self._dev_cache[key]
+
+    def transform(self, x):
+        """x (S, Din) fp32 / fp64 on a GPU -> y (S, D) fp64 = transform x + offset (ktf_plda_f64 without length normalisation)."""
+        _, A, b = self._consts(x.device)
+        y = x.to(torch.float64).contiguous()
+        if A is None or y.shape[0] == 0:
+            return y[:, :self.dim].contiguous()
+        y = ops.plda(y, A, b, b, False, False, want_scores=False)[1]
+        return y if self.dim == self.inputDim else y[:, :self.dim].contiguous()
+
+    def _start(self, off, init_labels, gamma0, pi0, seed):
+        """-> gamma0 (S, K), pi0 (N, K) host fp64, checked."""
+        K, N, S = self.maxSpeakers, len(off) - 1, int(off[-1])
+        if init_labels is not None and gamma0 is not None:
+            raise ValueError("pass init_labels or gamma0, not both")
+        if init_labels is not None:
+            if pi0 is not None:
+                raise ValueError("init_labels set pi0 themselves")
+            return vbx_init(init_labels, off, K, self.initSmoothing)
+        if gamma0 is not None:
+            g = np.array(_host(gamma0), dtype=np.float64)
+            if g.shape != (S, K):
+                raise ValueError(f"gamma0 must be ({S}, {K}), got {g.shape}")
+            if not np.isfinite(g).all() or (g < 0).any() or (g > 1 + 1e-9).any():
+                raise ValueError("gamma0 must hold probabilities")
+        else:
+            g = np.random.default_rng(seed).gamma(1.0, size=(S, K))
+            g /= g.sum(1, keepdims=True)
+        if pi0 is None:
+            p = np.full((N, K), 1.0 / K)
+        else:
+            p = np.array(_host(pi0), dtype=np.float64)
+            if p.shape not in ((K,), (N, K)) or not np.isfinite(p).all() or (p < 0).any() or (np.abs(p.sum(-1) - 1) > 1e-6).any():
+                raise ValueError(f"pi0 must be ({K},) or ({N}, {K}) probabilities that sum to 1")
+            p = np.array(np.broadcast_to(p, (N, K)))
+        return g, p
+
+    def __call__(self, x, lengths, init_labels=None, gamma0=None, pi0=None, seed=0):
+        """x (S, Din) fp32 / fp64 on a GPU, the windows of all recordings end to end in time order; lengths: the N window counts.
+        Start: init_labels (S,) ints (vbx_init's rule with K = max_speakers), or gamma0 packed (S, K) with pi0 (K,) or (N, K)
+        (default uniform), or neither: rows of np.random.default_rng(seed).gamma(1.0, (S, K)) normalised and a uniform pi0. Every
+        recording runs until its ELBO gains less than epsilon (that iteration's gamma and pi are kept) or max_iters; one device ->
+        host read per iteration. -> VBxResult."""
+        if not isinstance(x, torch.Tensor) or x.dim() != 2 or not x.is_cuda or x.dtype not in (torch.float32, torch.float64):
+            raise ValueError("x must be a (S, Din) float32 or float64 tensor on a GPU")
+        if x.shape[1] != self.inputDim:
+            raise ValueError(f"x has {x.shape[1]} columns, the model takes {self.inputDim}")
+        lens = [int(v) for v in (lengths.tolist() if isinstance(lengths, (torch.Tensor, np.ndarray)) else lengths)]
+        if not 1 <= len(lens) <= 65535 or min(lens) < 0 or sum(lens) != x.shape[0]:
+            raise ValueError(f"lengths must be 1 .. 65535 non-negative counts that sum to {x.shape[0]}, got {lens}")
+        off = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+        g0, p0 = self._start(off, init_labels, gamma0, pi0, seed)
+        with L.on_device(x.device):
+            return self._run(x, off, g0, p0)
+
+    def _run(self, x, off, g0, p0):
+        dev = x.device
+        K, N, S = self.maxSpeakers, len(off) - 1, int(off[-1])
+        phi = self._consts(dev)[0]
+        gamma = torch.as_tensor(g0, device=dev)
+        pi = torch.as_tensor(p0, device=dev)
+        elbo = np.full((N, self.maxIters), np.nan)
+        iters = np.zeros(N, np.int64)
+        if S:
+            o32 = torch.as_tensor(off.astype(np.int32), device=dev)
+            rho, G = ops.vbx_prepare(self.transform(x), phi)
+            rec_of_row = torch.as_tensor(np.repeat(np.arange(N), np.diff(off)), device=dev)
+            zero = torch.zeros((N,), dtype=torch.float64, device=dev)
+            active = np.diff(off) > 0
+            prev = np.full(N, np.nan)
+            for it in range(self.maxIters):
+                alpha, _, c, kl = ops.vbx_speaker_update(gamma, rho, phi, self.Fa / self.Fb, o32)
+                lls = ops.vbx_loglike(rho, G, alpha, c, self.Fa, o32)
+                gn, pn, tll = ops.vb_forward_backward(lls, o32, pi, self.loopProb)
+                Lr = ops.vb_bound(zero, tll, kl * self.Fb, 0.0).cpu().numpy()       # the iteration's one device -> host read
+                if active.all():
+                    gamma, pi = gn, pn
+                else:
+                    act = torch.as_tensor(active, device=dev)
+                    gamma = torch.where(act[rec_of_row][:, None], gn, gamma)
+                    pi = torch.where(act[:, None], pn, pi)
+                elbo[active, it] = Lr[active]
+                iters[active] = it + 1
+                if it > 0:
+                    active = active & ~(Lr - prev < self.epsilon)
+                prev = np.where(active, Lr, prev)
+                if not active.any():
+                    break
+        labels, counts = vbx_labels(gamma, off)
+        return VBxResult(gamma, pi, torch.as_tensor(elbo, device=dev), iters, off, labels, counts)

@@ -1340,3 +1340,45 @@ def vb_bound(gsum, tll, kl, stat_scale):
         rc = L.load().ktf_vb_bound(L.ptr(gsum), L.ptr(tll), L.ptr(kl), N, kl.numel() // N, float(stat_scale), L.ptr(bound), L.stream_ptr())
     L.check(rc, "ktf_vb_bound")
     return bound
+
+
+# ----------------------------------------------------------------------------- VBx (ktf_vbx_*)
+def vbx_prepare(x, phi):
+    """x (TB, D), phi (D) fp64 -> (rho (TB, D) = x sqrt(phi), G (TB) = -(sum_d x^2 + D log 2 pi) / 2): ktf_vbx_prepare."""
+    TB, D = x.shape
+    rho = torch.empty((TB, D), dtype=torch.float64, device=x.device)
+    G = torch.empty((TB,), dtype=torch.float64, device=x.device)
+    with L.on_device(x.device):
+        rc = L.load().ktf_vbx_prepare(L.ptr(x), TB, D, L.ptr(phi), L.ptr(rho), L.ptr(G), L.stream_ptr())
+    L.check(rc, "ktf_vbx_prepare")
+    return rho, G
+
+
+def vbx_speaker_update(gamma, rho, phi, fa_over_fb, offsets):
+    """gamma (TB, K), rho (TB, D), phi (D) fp64, offsets (N + 1) int32 -> (alpha (N, K, D), invL (N, K, D), c (N, K), kl (N, K)); the
+    rows of alpha and invL of a recording without windows are zero: ktf_vbx_speaker_update."""
+    lib = L.load()
+    (TB, K), D, N = gamma.shape, rho.shape[1], offsets.numel() - 1
+    dev = gamma.device
+    alpha = torch.zeros((N, K, D), dtype=torch.float64, device=dev)
+    invL = torch.zeros((N, K, D), dtype=torch.float64, device=dev)
+    c = torch.empty((N, K), dtype=torch.float64, device=dev)
+    kl = torch.empty((N, K), dtype=torch.float64, device=dev)
+    ws, nbytes = _vb_ws(lib.ktf_vbx_update_workspace_bytes, "ktf_vbx_update_workspace_bytes", TB, N, D, device=dev)
+    with L.on_device(dev):
+        rc = lib.ktf_vbx_speaker_update(L.ptr(gamma), L.ptr(rho), TB, D, K, L.ptr(offsets), N, L.ptr(phi), float(fa_over_fb), L.ptr(alpha),
+                                        L.ptr(invL), L.ptr(c), L.ptr(kl), L.ptr(ws), nbytes, L.stream_ptr())
+    L.check(rc, "ktf_vbx_speaker_update")
+    return alpha, invL, c, kl
+
+
+def vbx_loglike(rho, G, alpha, c, Fa, offsets):
+    """lls (TB, K) fp64 = Fa (rho alpha^T - c + G) per recording: ktf_vbx_loglike."""
+    TB, D = rho.shape
+    N, K = c.shape
+    lls = torch.empty((TB, K), dtype=torch.float64, device=rho.device)
+    with L.on_device(rho.device):
+        rc = L.load().ktf_vbx_loglike(L.ptr(rho), L.ptr(G), TB, D, K, L.ptr(offsets), N, L.ptr(alpha), L.ptr(c), float(Fa), L.ptr(lls),
+                                      L.stream_ptr())
+    L.check(rc, "ktf_vbx_loglike")
+    return lls
