@@ -547,6 +547,30 @@ int ktf_plda_trials_f64(const double* test_tr, int64_t N, const double* enroll_t
 int ktf_plda_trials_f32(const float* test_tr, int64_t N, const float* enroll_tr, int64_t M, int32_t dim, const float* psi,
                         const float* enroll_num_examples, const int32_t* trials, int64_t T, float* scores, void* workspace,
                         size_t workspace_bytes, void* stream);
+/* Score normalisation against a cohort (S-norm; adaptive S-norm with top_n, Matejka et al. 2017): mean[r] and std[r] of the top_n
+ * largest entries of row r of x (R, C), row stride ld >= C elements; mean and std (R) fp64 on the device whatever the dtype of x.
+ * The selected multiset is the top_n largest values, with as many copies of the top_n-th largest as make the count top_n (unique
+ * whatever the ties); top_n >= C (INT32_MAX: "all") selects the whole row. mean = sum / top_n; std = sqrt(sum (x - mean)^2 / top_n),
+ * the population form, centred in a second pass; an all-tied selection has std exactly 0. One workgroup per row, radix select on
+ * order-preserving integer keys, no floating-point atomics: a row's result depends on its values in order, C, top_n and the dtype
+ * only (not on R, the row's index, ld or the run). Rows are assumed free of NaN (with one, the row's result is unspecified; nothing
+ * outside the arrays is touched). R == 0 launches nothing; C < 1 and top_n < 1 are refused. */
+int ktf_topn_stats_f64(const double* x, int64_t R, int64_t C, int64_t ld, int32_t top_n, double* mean, double* std, void* stream);
+int ktf_topn_stats_f32(const float* x, int64_t R, int64_t C, int64_t ld, int32_t top_n, double* mean, double* std, void* stream);
+/* ktf_topn_stats_* of the PLDA scores of R transformed vectors against a cohort of C transformed vectors, the (R, C) block formed in
+ * `workspace` (at least ktf_plda_cohort_workspace_bytes(R, C, dim, sizeof dtype) = R * C * sizeof dtype bytes, 256-byte aligned; a
+ * negative KTF_* code on bad arguments) and ranked on the same stream: no host reads, no allocations; the caller bounds the memory
+ * by the number of rows it passes per call. role 0 (test side, T-norm): row r is a test vector, the cohort vectors are the classes,
+ * counts (C) their examples: x[r][c] = ktf_plda_score_n_*(rows, cohort, counts)[r][c]. role 1 (enroll side, Z-norm): row r is a
+ * class, counts (R) the rows' examples, the cohort vectors are the tests: x[r][c] = ktf_plda_score_n_*(cohort, rows, counts)[c][r].
+ * counts NULL: every count 1 (ktf_plda_score_*). Every ranked score has the bits those entry points give its pair. */
+int64_t ktf_plda_cohort_workspace_bytes(int64_t R, int64_t C, int32_t dim, int32_t dtype_bytes);
+int ktf_plda_cohort_stats_f64(const double* rows_tr, int64_t R, const double* cohort_tr, int64_t C, int32_t dim, const double* psi,
+                              const double* counts, int32_t role, int32_t top_n, double* mean, double* std, void* workspace,
+                              size_t workspace_bytes, void* stream);
+int ktf_plda_cohort_stats_f32(const float* rows_tr, int64_t R, const float* cohort_tr, int64_t C, int32_t dim, const float* psi,
+                              const float* counts, int32_t role, int32_t top_n, double* mean, double* std, void* workspace,
+                              size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------ dense PLDA scoring with conversation-dependent PCA
  * Kaldi `ivector-plda-scoring-dense` (the scoring stage of x-vector diarization); the reference ships its golden table

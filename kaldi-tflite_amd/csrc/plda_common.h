@@ -98,11 +98,14 @@ __device__ __forceinline__ R wave_sum_as_256(int dim, int lane, F f) {
 // stages them per class row (plda_n_*; one wave per class row for the log sum, wave_sum_as_256) next to k_j * y_j, and a pair reads
 // its class's weight instead of the shared one. The no-class term keeps var2 = 1 + psi. With every count 1 the scores are those of
 // the count-free tile, bit for bit.
+// SWAP_STORE (score_norm.hip, the enroll side of a cohort): the block is stored with the class as the row, scores[j * B + i], so
+// that a class's B scores lie side by side. The tile is turned round in the LDS the test rows occupied and written out along i;
+// every score is the same expression as in the plain store.
 #define PLDA_TILE 64
 #define PLDA_DC 64
 #define PLDA_LDS_BYTES(R) (sizeof(R) * (2 * PLDA_TILE * (PLDA_DC + 1) + 2 * PLDA_DC + 8))        // 67,648 B in fp64
 #define PLDA_N_LDS_BYTES(R) (PLDA_LDS_BYTES(R) + sizeof(R) * (PLDA_TILE * (PLDA_DC + 1) + PLDA_TILE))   // 101,440 B in fp64
-template <typename R, bool PER_CLASS = false>
+template <typename R, bool PER_CLASS = false, bool SWAP_STORE = false>
 __device__ __forceinline__ void plda_score_tile(const R* __restrict__ y, int64_t B, const R* __restrict__ yc, int64_t Bc,
                                                 int dim, const R* __restrict__ psi, R* __restrict__ scores, int64_t i0,
                                                 int64_t j0, unsigned char* smraw, const R* __restrict__ cnt = nullptr) {
@@ -208,7 +211,23 @@ __device__ __forceinline__ void plda_score_tile(const R* __restrict__ y, int64_t
         for (int v = 0; v < 4; ++v) {
             const int64_t j = j0 + tj + 16 * v;
             const R ld1 = PER_CLASS ? l1c[tj + 16 * v] : logdet1;
-            if (i < B && j < Bc) scores[i * Bc + j] = (R)(-0.5) * (ld1 + a[u][v]) - (R)(-0.5) * (logdet2 + c[u]);
+            if constexpr (!SWAP_STORE) {
+                if (i < B && j < Bc) scores[i * Bc + j] = (R)(-0.5) * (ld1 + a[u][v]) - (R)(-0.5) * (logdet2 + c[u]);
+            } else {
+                a[u][v] = (R)(-0.5) * (ld1 + a[u][v]) - (R)(-0.5) * (logdet2 + c[u]);
+            }
+        }
+    }
+    if constexpr (SWAP_STORE) {
+        __syncthreads();                                           // (the last chunk's test rows have been consumed)
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+#pragma unroll
+            for (int v = 0; v < 4; ++v) yi[(tj + 16 * v) * LD + ti + 16 * u] = a[u][v];
+        __syncthreads();
+        for (int e = threadIdx.x; e < PLDA_TILE * PLDA_TILE; e += 256) {
+            const int jj = e / PLDA_TILE, ii = e - jj * PLDA_TILE;
+            if (i0 + ii < B && j0 + jj < Bc) scores[(j0 + jj) * B + i0 + ii] = yi[jj * LD + ii];
         }
     }
 }

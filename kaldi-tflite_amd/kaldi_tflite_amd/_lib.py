@@ -152,6 +152,11 @@ PROTOTYPES = {
     "ktf_plda_trials_workspace_bytes": (_i64, [_i64, _i64, _i32, _i32]),
     "ktf_plda_trials_f64": (C.c_int, [_P, _i64, _P, _i64, _i32, _P, _P, _P, _i64, _P, _P, C.c_size_t, _P]),
     "ktf_plda_trials_f32": (C.c_int, [_P, _i64, _P, _i64, _i32, _P, _P, _P, _i64, _P, _P, C.c_size_t, _P]),
+    "ktf_topn_stats_f64": (C.c_int, [_P, _i64, _i64, _i64, _i32, _P, _P, _P]),
+    "ktf_topn_stats_f32": (C.c_int, [_P, _i64, _i64, _i64, _i32, _P, _P, _P]),
+    "ktf_plda_cohort_workspace_bytes": (_i64, [_i64, _i64, _i32, _i32]),
+    "ktf_plda_cohort_stats_f64": (C.c_int, [_P, _i64, _P, _i64, _i32, _P, _P, _i32, _i32, _P, _P, _P, C.c_size_t, _P]),
+    "ktf_plda_cohort_stats_f32": (C.c_int, [_P, _i64, _P, _i64, _i32, _P, _P, _i32, _i32, _P, _P, _P, C.c_size_t, _P]),
     "ktf_plda_dense_workspace_bytes": (_i64, [_P, _i32, _i32, C.c_double]),
     "ktf_plda_dense_f64": (C.c_int, [_P, _i64, _i32, _P, _P, _i32, C.c_double, _P, _P, _P, _P, _P, _P, _i32, _i32, _P, _P, _P,
                                      C.c_size_t, _P, _P]),

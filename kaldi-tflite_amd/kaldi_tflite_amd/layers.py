@@ -1309,6 +1309,57 @@ class PLDA(Layer):
         n = self._counts(1.0 if enroll_num_examples is None else enroll_num_examples, M, t.device, "enroll_num_examples")
         return ops.plda_trials(t, e, self._dev[2], n, pairs)
 
+    def cohort_stats(self, vectors_tr, cohort_tr, top_n=None, role="test", num_examples=None, workspace_limit=1 << 30):
+        """Extension: the statistics of score normalisation against a cohort (S-norm; adaptive S-norm with top_n, Matejka et al.
+        2017) on TRANSFORMED vectors -> (mean, std), each (R,) float64 on the device: the mean and the centred population standard
+        deviation of the top_n largest of row r's C cohort scores (None or >= C: all of them, plain S-norm; ties at the threshold
+        fill the selection up to top_n, so it does not depend on how ties are broken).
+        role "test" (T-norm side): row r is a test vector scored against every cohort vector as a class; num_examples are the
+        cohort's counts (transform the cohort with them): row r is score(vectors_tr, cohort_tr, num_examples)[r].
+        role "enroll" (Z-norm side): row r is a class with count num_examples[r], every cohort vector (transformed without counts)
+        is scored against it as a test: row r is score(cohort_tr, vectors_tr, num_examples)[:, r].
+        Every ranked score has score's bits for its pair. num_examples is checked as transform's. The (R, C) scores are never held
+        at once: rows go through one workspace of at most workspace_limit bytes, chunk * C * itemsize <= workspace_limit with at
+        least one row per chunk (above 64 rows a multiple of 64, the score tile); the result does not depend on the chunking."""
+        if role not in ("test", "enroll"):
+            raise ValueError(f"role must be 'test' or 'enroll', got {role!r}")
+        if top_n is not None:
+            if isinstance(top_n, bool) or not isinstance(top_n, (int, np.integer)) or int(top_n) < 2:
+                raise ValueError(f"top_n must be None or an integer >= 2, got {top_n!r}")
+        if isinstance(workspace_limit, bool) or not isinstance(workspace_limit, (int, np.integer)) or int(workspace_limit) < 1:
+            raise ValueError(f"workspace_limit must be a positive number of bytes, got {workspace_limit!r}")
+        for t, what in ((vectors_tr, "vectors_tr"), (cohort_tr, "cohort_tr")):
+            if not isinstance(t, torch.Tensor) or not t.is_cuda:
+                raise ValueError(f"{what} must be a device tensor of transformed vectors")
+            if t.dim() != 2 or t.shape[1] != self.dim:
+                raise ValueError(f"{what} must be (rows, {self.dim}), got {tuple(t.shape)}")
+        if cohort_tr.device != vectors_tr.device:
+            raise ValueError(f"vectors on {vectors_tr.device}, the cohort on {cohort_tr.device}")
+        if cohort_tr.shape[0] < 1:
+            raise ValueError("the cohort is empty")
+        v, c = vectors_tr.to(self.paramDtype).contiguous(), cohort_tr.to(self.paramDtype).contiguous()
+        if self._dev is None or self._dev[0].device != v.device:
+            self._prepare(c)
+        R, Cn = v.shape[0], c.shape[0]
+        n = None
+        if num_examples is not None:
+            n = self._counts(num_examples, Cn if role == "test" else R, v.device, "num_examples")
+        mean = torch.empty((R,), dtype=torch.float64, device=v.device)
+        std = torch.empty((R,), dtype=torch.float64, device=v.device)
+        if R == 0:
+            return mean, std
+        chunk = min(max(1, int(workspace_limit) // (Cn * v.element_size())), 64 * 65535)
+        if chunk < R and chunk > 64:
+            chunk -= chunk % 64                                             # whole 64-row score tiles (a ragged tile only at the end)
+        chunk = min(chunk, R)
+        ws = torch.empty((ops.plda_cohort_workspace_bytes(chunk, Cn, self.dim, v.element_size()),), dtype=torch.uint8, device=v.device)
+        with L.launch_scope(v.device):
+            for r0 in range(0, R, chunk):
+                r1 = min(R, r0 + chunk)
+                ops.plda_cohort_stats(v[r0:r1], c, self._dev[2], n if n is None or role == "test" else n[r0:r1],
+                                      1 if role == "enroll" else 0, top_n, mean[r0:r1], std[r0:r1], ws)
+        return mean, std
+
     @staticmethod
     def _trial_pairs(trials_enroll, trials_test, M, N, device):
         """(T, 2) device int32 rows (class j, test i), every index checked in range."""

@@ -472,6 +472,53 @@ def plda_trials(test_tr, enroll_tr, psi, enroll_num_examples, pairs, workspace=N
     return scores
 
 
+# ----------------------------------------------------------------------------- score normalisation (ktf_topn_stats_*, ktf_plda_cohort_*)
+TOPN_ALL = (1 << 31) - 1            # the C-level top_n for "the whole row"
+
+
+def topn_stats(x, top_n):
+    """(mean, std) of the top_n largest entries of each row of x (R, C) fp32 / fp64 on the device (rows may be strided: a column
+    slice of a wider matrix is read in place) -> two (R,) fp64 tensors. top_n None or >= C: the whole row."""
+    lib = L.load()
+    if x.dim() != 2 or x.dtype not in (torch.float32, torch.float64):
+        raise ValueError(f"topn_stats: x must be a (R, C) fp32 or fp64 tensor, got {x.dtype} {tuple(x.shape)}")
+    R, Cn = x.shape
+    if R > 1 and not (x.stride(1) == 1 and x.stride(0) >= Cn) or R <= 1 and not x.is_contiguous():
+        x = x.contiguous()
+    ld = x.stride(0) if R > 1 else Cn
+    mean = torch.empty((R,), dtype=torch.float64, device=x.device)
+    std = torch.empty((R,), dtype=torch.float64, device=x.device)
+    fn = lib.ktf_topn_stats_f64 if x.dtype == torch.float64 else lib.ktf_topn_stats_f32
+    with L.on_device(x.device):
+        rc = fn(L.ptr(x), R, Cn, ld, TOPN_ALL if top_n is None else min(int(top_n), TOPN_ALL), L.ptr(mean), L.ptr(std), L.stream_ptr())
+    L.check(rc, "ktf_topn_stats")
+    return mean, std
+
+
+def plda_cohort_workspace_bytes(R, Cn, dim, dtype_bytes):
+    """Bytes of workspace ktf_plda_cohort_stats_* needs for R rows against Cn cohort vectors."""
+    n = int(L.load().ktf_plda_cohort_workspace_bytes(R, Cn, dim, dtype_bytes))
+    if n < 0:
+        L.check(n, "ktf_plda_cohort_workspace_bytes")
+    return n
+
+
+def plda_cohort_stats(rows_tr, cohort_tr, psi, counts, role, top_n, mean, std, workspace):
+    """topn_stats of the PLDA scores of rows_tr (R, dim) against cohort_tr (C, dim) into mean / std (R,) fp64. role 0: the rows are
+    tests, counts (C) or None belong to the cohort; role 1: the rows are classes with counts (R) or None. workspace: a uint8
+    device tensor of at least plda_cohort_workspace_bytes."""
+    lib = L.load()
+    R, dim = rows_tr.shape
+    Cn = cohort_tr.shape[0]
+    fn = lib.ktf_plda_cohort_stats_f64 if rows_tr.dtype == torch.float64 else lib.ktf_plda_cohort_stats_f32
+    with L.on_device(rows_tr.device):
+        rc = fn(L.ptr(rows_tr), R, L.ptr(cohort_tr), Cn, dim, L.ptr(psi), L.ptr(counts) if counts is not None else None, int(role),
+                TOPN_ALL if top_n is None else min(int(top_n), TOPN_ALL), L.ptr(mean), L.ptr(std), L.ptr(workspace), workspace.numel(),
+                L.stream_ptr())
+    L.check(rc, "ktf_plda_cohort_stats")
+    return mean, std
+
+
 def plda_dense_workspace_bytes(lengths, dim, target_energy):
     """Bytes of scratch ktf_plda_dense_* needs (lengths: host ints; target_energy None = no PCA)."""
     lib = L.load()

@@ -1,7 +1,9 @@
 """Extension: speaker verification the way Kaldi's recipes (sitw, sre16 v2, voxceleb) score it:
 ivector-mean over spk2utt on the raw x-vectors, ivector-subtract-global-mean / transform-vec / ivector-normalize-length
 (XvectorExtractor.postprocess), then ivector-plda-scoring --num-utts over a trial list (PLDA.transform with the counts,
-PLDA.score_trials). Host parsers for spk2utt and trials files, and the two figures every recipe ends with (eer, min_dcf)."""
+PLDA.score_trials), optionally followed by score normalisation against a cohort (S-norm / adaptive S-norm: PLDA.cohort_stats,
+as_norm, score_normalized). Host parsers for spk2utt and trials files, and the two figures every recipe ends
+with (eer, min_dcf)."""
 
 import numpy as np
 import torch
@@ -96,14 +98,119 @@ def _devices(*objs):
     return devs
 
 
-def score(ext, plda, enroll_wavs, spk2utt, test_wavs, trials):
+def _stats(stats, what, device):
+    """(mean, std) of as_norm as two 1-D float64 tensors of one length on `device`."""
+    if not (isinstance(stats, (tuple, list)) and len(stats) == 2):
+        raise ValueError(f"{what} must be a pair (mean, std)")
+    out = []
+    for a in stats:
+        t = a if isinstance(a, torch.Tensor) else torch.as_tensor(np.asarray(a, dtype=np.float64))
+        if t.device != device:
+            raise ValueError(f"{what} on {t.device}, the scores on {device}")
+        if t.dim() != 1 or not t.dtype.is_floating_point:
+            raise ValueError(f"{what} must hold 1-D floating-point tensors, got {t.dtype} {tuple(t.shape)}")
+        out.append(t.to(torch.float64))
+    if out[0].shape != out[1].shape:
+        raise ValueError(f"{what}: {out[0].shape[0]} means, {out[1].shape[0]} standard deviations")
+    return out
+
+
+def _indices(a, what, device):
+    """Trial indices as a 1-D int64 tensor on `device` (the checks of PLDA._trial_pairs; the range is checked by the caller)."""
+    if isinstance(a, torch.Tensor):
+        if a.device != device:
+            raise ValueError(f"{what} on {a.device}, the scores on {device}")
+        if a.dim() != 1 or a.dtype.is_floating_point or a.dtype == torch.bool or a.is_complex():
+            raise ValueError(f"{what} must be a 1-D integer tensor, got {a.dtype} {tuple(a.shape)}")
+        return a.to(torch.int64)
+    a = np.asarray(a)
+    if a.size == 0:
+        a = a.reshape(0).astype(np.int64)
+    if a.ndim != 1 or a.dtype.kind not in "iu":
+        raise ValueError(f"{what} must be a 1-D sequence of integers, got {a.dtype} {a.shape}")
+    return torch.as_tensor(a.astype(np.int64)).to(device)
+
+
+def as_norm(scores, trials_enroll, trials_test, enroll_stats=None, test_stats=None):
+    """Symmetric score normalisation of trial scores with cohort statistics (PLDA.cohort_stats): for trial t of model
+    e = trials_enroll[t] and test i = trials_test[t],
+        0.5 * ((s_t - mu_e) / sigma_e + (s_t - mu_i) / sigma_i)
+    with enroll_stats = (mu, sigma) per model (role "enroll") and test_stats = (mu, sigma) per test (role "test"). Only
+    enroll_stats: Z-norm, (s - mu_e) / sigma_e; only test_stats: T-norm, (s - mu_i) / sigma_i (neither is halved); giving neither
+    raises. scores (T,) in any float dtype -> (T,) float64, computed by torch indexing on the device the inputs are on (host
+    tensors included). Indices are host sequences or integer tensors on that device, checked in range (for a device tensor with
+    one reduction and one read). A sigma of 0 (an all-tied selection: a cohort of one vector, or equal scores) is not special-cased:
+    the division gives IEEE inf, or nan where the score equals the mean."""
+    if enroll_stats is None and test_stats is None:
+        raise ValueError("as_norm needs enroll_stats (Z-norm), test_stats (T-norm) or both (S-norm)")
+    s = scores if isinstance(scores, torch.Tensor) else torch.as_tensor(np.asarray(scores, dtype=np.float64))
+    if s.dim() != 1 or not s.dtype.is_floating_point:
+        raise ValueError(f"scores must be a 1-D floating-point tensor, got {s.dtype} {tuple(s.shape)}")
+    s = s.to(torch.float64)
+    je = _indices(trials_enroll, "trials_enroll", s.device)
+    it = _indices(trials_test, "trials_test", s.device)
+    if je.shape[0] != s.shape[0] or it.shape[0] != s.shape[0]:
+        raise ValueError(f"{s.shape[0]} scores, {je.shape[0]} enrollment indices, {it.shape[0]} test indices")
+    terms = []
+    for stats, idx, what in ((enroll_stats, je, "enroll_stats"), (test_stats, it, "test_stats")):
+        if stats is None:
+            continue
+        mu, sigma = _stats(stats, what, s.device)
+        if idx.shape[0] and bool(((idx < 0) | (idx >= mu.shape[0])).any()):
+            raise ValueError(f"a trial index is outside the {mu.shape[0]} entries of {what}")
+        terms.append((s - mu[idx]) / sigma[idx])
+    return terms[0] if len(terms) == 1 else 0.5 * (terms[0] + terms[1])
+
+
+def score_normalized(plda, enroll_tr, test_tr, trials, cohort, top_n=None, enroll_num_examples=None, cohort_num_examples=None,
+                     sides="both", workspace_limit=1 << 30):
+    """Trial scores with S-norm (top_n None) or adaptive S-norm (the top_n best cohort scores per side) -> (normalised (T,)
+    float64, raw (T,) in the PLDA's dtype: plda.score_trials' scores). enroll_tr / test_tr: TRANSFORMED models (with
+    enroll_num_examples, as for score_trials) and tests; trials: a pair (model indices, test indices); cohort: (C, dim)
+    post-processed cohort vectors as ext(...) or ext.postprocess(means) return them, NOT yet transformed by the PLDA: the enroll
+    side scores them as tests (plain transform), the test side as classes of cohort_num_examples examples each (None: 1; transform
+    with the counts). Statistics are computed only for the models and tests that occur in `trials` (PLDA.cohort_stats, at most
+    workspace_limit bytes of scores at a time). sides: "both" (S-norm), "enroll" (Z-norm) or "test" (T-norm)."""
+    if sides not in ("both", "enroll", "test"):
+        raise ValueError(f"sides must be 'both', 'enroll' or 'test', got {sides!r}")
+    if not (isinstance(trials, (list, tuple)) and len(trials) == 2):
+        raise ValueError("trials must be a pair (model indices, test indices)")
+    if not isinstance(cohort, torch.Tensor) or not cohort.is_cuda:
+        raise ValueError("cohort must be a (C, dim) device tensor of post-processed vectors")
+    coh = cohort.reshape(-1, cohort.shape[-1])
+    if coh.shape[1] != plda.dim or coh.shape[0] < 1:
+        raise ValueError(f"cohort must be (C >= 1, {plda.dim}), got {tuple(cohort.shape)}")
+    t, e = plda._scoring_inputs(test_tr, enroll_tr)
+    if coh.device != t.device:
+        raise ValueError(f"the cohort on {coh.device}, the vectors on {t.device}")
+    pairs = plda._trial_pairs(trials[0], trials[1], e.shape[0], t.shape[0], t.device).to(torch.int64)
+    enroll_stats = test_stats = None
+    je, it = pairs[:, 0], pairs[:, 1]
+    if sides in ("both", "enroll"):
+        models, je = torch.unique(pairs[:, 0], return_inverse=True)
+        n = None
+        if enroll_num_examples is not None:
+            n = plda._counts(enroll_num_examples, e.shape[0], t.device, "enroll_num_examples")[models]
+        enroll_stats = plda.cohort_stats(e[models], plda.transform(coh), top_n=top_n, role="enroll", num_examples=n,
+                                         workspace_limit=workspace_limit)
+    if sides in ("both", "test"):
+        tests, it = torch.unique(pairs[:, 1], return_inverse=True)
+        test_stats = plda.cohort_stats(t[tests], plda.transform(coh, num_examples=cohort_num_examples), top_n=top_n, role="test",
+                                       num_examples=cohort_num_examples, workspace_limit=workspace_limit)
+    raw = plda.score_trials(t, e, trials[0], trials[1], enroll_num_examples=enroll_num_examples)
+    return as_norm(raw, je, it, enroll_stats=enroll_stats, test_stats=test_stats), raw
+
+
+def score(ext, plda, enroll_wavs, spk2utt, test_wavs, trials, cohort=None, top_n=None, cohort_num_examples=None):
     """Kaldi's verification scoring chain, wav to trial scores. Enrollment: ext.embeddings(enroll_wavs) -> speaker_means(spk2utt)
     -> ext.postprocess -> plda.transform(num_examples=num_utts). Test: ext(test_wavs) -> plda.transform. Then
     plda.score_trials with the counts. trials: a pair (model indices into the speakers of spk2utt, test indices into the rows of
-    test_wavs) -> (T,) scores in the PLDA's dtype. Inputs spread over several devices are refused before anything is launched."""
+    test_wavs) -> (T,) scores in the PLDA's dtype. Inputs spread over several devices are refused before anything is launched.
+    cohort (C, dim) post-processed cohort vectors: the scores are normalised against it (score_normalized with top_n and
+    cohort_num_examples; S-norm on both sides) -> (T,) float64. Without a cohort nothing changes."""
     if not (isinstance(trials, (list, tuple)) and len(trials) == 2):
         raise ValueError("trials must be a pair (model indices, test indices)")
-    devs = _devices(enroll_wavs, test_wavs, trials, spk2utt if isinstance(spk2utt, tuple) else ())
+    devs = _devices(enroll_wavs, test_wavs, trials, cohort, spk2utt if isinstance(spk2utt, tuple) else ())
     if len(devs) > 1:
         raise ValueError(f"the inputs must all be on one GPU (or on the host), got {sorted(str(d) for d in devs)}")
     raw = ext.embeddings(enroll_wavs)
@@ -111,6 +218,9 @@ def score(ext, plda, enroll_wavs, spk2utt, test_wavs, trials):
     enroll_tr = plda.transform(ext.postprocess(means), num_examples=num_utts)
     tv = ext(test_wavs)
     test_tr = plda.transform(tv.reshape(-1, tv.shape[-1]))
+    if cohort is not None:
+        return score_normalized(plda, enroll_tr, test_tr, trials, cohort, top_n=top_n, enroll_num_examples=num_utts,
+                                cohort_num_examples=cohort_num_examples)[0]
     return plda.score_trials(test_tr, enroll_tr, trials[0], trials[1], enroll_num_examples=num_utts)
 
 
