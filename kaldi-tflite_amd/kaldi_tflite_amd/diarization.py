@@ -9,6 +9,7 @@ import torch
 
 from . import _lib as L
 from . import ops
+from ._host import chunks, host, is_int, is_real, per_device
 from .models import _Workspace
 
 _ws = _Workspace()
@@ -46,10 +47,6 @@ def _packed(blocks):
     return torch.as_strided(b0, (o,), (1,), b0.storage_offset())
 
 
-def _real(v):
-    return isinstance(v, numbers.Real) and not isinstance(v, (bool, np.bool_))
-
-
 def agglomerative_cluster(scores, threshold=None, num_speakers=None, max_spk_fraction=1.0, read_costs=False):
     """Kaldi's `agglomerative-cluster` (AgglomerativeClusterer, single pass) on the device.
 
@@ -65,20 +62,20 @@ def agglomerative_cluster(scores, threshold=None, num_speakers=None, max_spk_fra
     R = len(blocks)
     if not isinstance(read_costs, (bool, np.bool_)):
         raise ValueError(f"read_costs must be a bool, got {read_costs!r}")
-    if not _real(max_spk_fraction) or not 0.0 < float(max_spk_fraction) <= 1.0:
+    if not is_real(max_spk_fraction) or not 0.0 < float(max_spk_fraction) <= 1.0:
         raise ValueError(f"max_spk_fraction must be in (0, 1], got {max_spk_fraction!r}")
     if num_speakers is None:
         if float(max_spk_fraction) != 1.0:
             raise ValueError("max_spk_fraction applies with num_speakers only (Kaldi's threshold mode has no size limit)")
         if threshold is None:
             threshold = 0.0
-        if not _real(threshold) or np.isnan(float(threshold)):
+        if not is_real(threshold) or np.isnan(float(threshold)):
             raise ValueError(f"threshold must be a number, got {threshold!r}")
         min_clusters = None
     else:
         if threshold is not None:
             raise ValueError("give threshold or num_speakers, not both")
-        if isinstance(num_speakers, (numbers.Integral, np.integer)) and not isinstance(num_speakers, (bool, np.bool_)):
+        if is_int(num_speakers):
             ns = [int(num_speakers)] * R
         else:
             arr = np.asarray(num_speakers.tolist() if isinstance(num_speakers, torch.Tensor) else num_speakers)
@@ -108,7 +105,7 @@ def agglomerative_cluster(scores, threshold=None, num_speakers=None, max_spk_fra
 def _labels_host(labels, S):
     """labels: one (S,) tensor / array, or a list of per-recording ones laid end to end -> (S,) host int64."""
     parts = list(labels) if isinstance(labels, (list, tuple)) else [labels]
-    arrs = [np.asarray(p.cpu() if isinstance(p, torch.Tensor) else p).reshape(-1) for p in parts]
+    arrs = [host(p).reshape(-1) for p in parts]
     out = np.concatenate(arrs) if arrs else np.zeros(0, np.int64)
     if out.size != S:
         raise ValueError(f"{out.size} labels for {S} windows")
@@ -213,7 +210,7 @@ def frame_labels(res, labels, num_frames, frame_shift=0.01):
     nf = [int(num_frames)] * R if isinstance(num_frames, (numbers.Integral, np.integer)) else [int(v) for v in num_frames]
     if len(nf) != R or min(nf, default=0) < 0:
         raise ValueError(f"num_frames must be an int or {R} non-negative ints, got {num_frames!r}")
-    if not _real(frame_shift) or not float(frame_shift) > 0:
+    if not is_real(frame_shift) or not float(frame_shift) > 0:
         raise ValueError(f"frame_shift must be > 0, got {frame_shift!r}")
     win = res.windows.cpu().numpy().astype(np.int64).reshape(-1, 3)
     lab = _labels_host(labels, win.shape[0])
@@ -235,15 +232,15 @@ def frame_rttm(labels, offsets, frame_index=None, frame_shift=0.01, reco_ids=Non
     [offsets[r], offsets[r + 1]). frame_index (F,): the original frame of every row within its recording when a mask selected the
     rows (default: row - offsets[r]). Runs of equal labels over consecutive frame indices merge into one line in rttm's format,
     speaker = label + 1 (agglomerative_cluster's numbering); rows with a negative label give no line."""
-    lab = np.asarray(labels.cpu() if isinstance(labels, torch.Tensor) else labels).reshape(-1).astype(np.int64)
-    off = np.asarray(offsets.cpu() if isinstance(offsets, torch.Tensor) else offsets).reshape(-1).astype(np.int64)
+    lab = host(labels).reshape(-1).astype(np.int64)
+    off = host(offsets).reshape(-1).astype(np.int64)
     if off.size < 1 or off[0] != 0 or (np.diff(off) < 0).any() or off[-1] != lab.size:
         raise ValueError(f"offsets must ascend from 0 to {lab.size}, got {off.tolist()}")
     R = off.size - 1
     if frame_index is None:
         idx = np.arange(lab.size, dtype=np.int64) - np.repeat(off[:-1], np.diff(off))
     else:
-        idx = np.asarray(frame_index.cpu() if isinstance(frame_index, torch.Tensor) else frame_index).reshape(-1).astype(np.int64)
+        idx = host(frame_index).reshape(-1).astype(np.int64)
         if idx.size != lab.size:
             raise ValueError(f"{idx.size} frame indices for {lab.size} labels")
     reco_ids = [f"reco{r}" for r in range(R)] if reco_ids is None else list(reco_ids)
@@ -262,6 +259,40 @@ def frame_rttm(labels, offsets, frame_index=None, frame_shift=0.01, reco_ids=Non
             st, en = i[a], i[b - 1] + 1
             lines.append(f"SPEAKER {reco_ids[r]} {channel} {st * shift:.3f} {(en - st) * shift:.3f} <NA> <NA> {int(l[a]) + 1} <NA> <NA>")
     return lines
+
+
+def _vb_iterate(step, q, sp, row_offsets, max_iters, epsilon):
+    """The VB-HMM outer loop of VBResegmenter and VBx. q (rows, K) and sp (N, K) on the device are the start; recording r owns the
+    rows row_offsets[r] .. row_offsets[r + 1] (host ints) and runs while it has any. step(q, sp) -> (q_new, sp_new, bound (N,) on
+    the device) is one iteration for all recordings; a recording is frozen after the iteration whose bound gains less than epsilon
+    (that iteration's q and sp are kept) or after max_iters. One device -> host read per iteration; `step` is never called when no
+    recording has rows. -> (q, sp, bound (N, max_iters) NaN-padded, iters (N,) int64), the last two on the host."""
+    counts = np.diff(row_offsets)
+    N = counts.size
+    bound = np.full((N, max_iters), np.nan)
+    iters = np.zeros(N, np.int64)
+    active = counts > 0
+    prev = np.full(N, np.nan)
+    if not active.any():
+        return q, sp, bound, iters
+    rec_of_row = torch.as_tensor(np.repeat(np.arange(N), counts), device=q.device)
+    for it in range(max_iters):
+        qn, spn, Ld = step(q, sp)
+        Lr = Ld.cpu().numpy()                                   # the iteration's one device -> host read
+        if active.all():
+            q, sp = qn, spn
+        else:
+            act = torch.as_tensor(active, device=q.device)
+            q = torch.where(act[rec_of_row][:, None], qn, q)
+            sp = torch.where(act[:, None], spn, sp)
+        bound[active, it] = Lr[active]
+        iters[active] = it + 1
+        if it > 0:
+            active = active & ~(Lr - prev < epsilon)
+        prev = np.where(active, Lr, prev)
+        if not active.any():
+            break
+    return q, sp, bound, iters
 
 
 class VBResult:
@@ -329,14 +360,10 @@ class VBResegmenter:
         for i0 in range(0, I, 64):
             tmp = np.matmul(np.swapaxes(M[i0:i0 + 64], 1, 2), iv[i0:i0 + 64, :, None] * M[i0:i0 + 64])
             self._U[i0:i0 + 64] = tmp[:, r, c]
-        self._dev_cache = {}
 
     def _consts(self, device):
-        key = str(device)
-        if key not in self._dev_cache:
-            f = lambda a: torch.as_tensor(a, device=device)  # noqa: E731
-            self._dev_cache[key] = tuple(f(a) for a in (self._W, self._gconst, self._means, self._B, self._U))
-        return self._dev_cache[key]
+        return per_device(self, device, lambda: tuple(torch.as_tensor(a, device=device)
+                                                      for a in (self._W, self._gconst, self._means, self._B, self._U)))
 
     def posteriors(self, x):
         """Step 1 on packed frames x (F, D): -> (gauss, post, loglike, truncated (1,) device int32). The frames run in chunks whose
@@ -350,9 +377,9 @@ class VBResegmenter:
         g = torch.empty((F, self.numSlots), dtype=torch.int32, device=x.device)
         p = torch.empty((F, self.numSlots), dtype=torch.float32, device=x.device)
         ll = torch.empty((F,), dtype=torch.float32, device=x.device)
-        for lo in range(0, F, step):
-            g[lo:lo + step], p[lo:lo + step], ll[lo:lo + step] = ops.vb_post(x[lo:lo + step], W, gc, self.numSlots, self.llScale,
-                                                                             self.statScale, self.sparsityThr, trunc)
+        for lo, hi in chunks(F, step):
+            g[lo:hi], p[lo:hi], ll[lo:hi] = ops.vb_post(x[lo:hi], W, gc, self.numSlots, self.llScale, self.statScale, self.sparsityThr,
+                                                        trunc)
         return g, p, ll, trunc
 
     def _frames(self, feats, lengths, mask):
@@ -406,11 +433,11 @@ class VBResegmenter:
         if q0 is not None:
             if tuple(q0.shape) != (TB, K):
                 raise ValueError(f"q0 must be ({TB}, {K}), got {tuple(q0.shape)}")
-            qh = np.asarray(q0.cpu() if isinstance(q0, torch.Tensor) else q0, dtype=np.float64)
+            qh = host(q0, np.float64)
             if not np.isfinite(qh).all() or (qh < 0).any() or (qh > 1 + 1e-9).any():
                 raise ValueError("q0 must hold probabilities")
         if sp0 is not None:
-            sh = np.asarray(sp0.cpu() if isinstance(sp0, torch.Tensor) else sp0, dtype=np.float64)
+            sh = host(sp0, np.float64)
             if sh.shape not in ((K,), (N, K)) or not np.isfinite(sh).all() or (sh < 0).any() or (sh > 1 + 1e-9).any() or \
                     (np.abs(sh.sum(-1) - 1) > 1e-6).any():
                 raise ValueError(f"sp0 must be ({K},) or ({N}, {K}) probabilities that sum to 1")
@@ -419,11 +446,11 @@ class VBResegmenter:
         K, d = self.maxSpeakers, self.downsample
         TB = int(boff[-1])
         if q0 is not None:
-            return torch.as_tensor(np.asarray(q0.cpu() if isinstance(q0, torch.Tensor) else q0, dtype=np.float64), device=device).contiguous()
+            return torch.as_tensor(host(q0, np.float64), device=device).contiguous()
         if init_labels is None:
             q = np.random.default_rng(seed).gamma(self.alphaQInit, size=(TB, K))
             return torch.as_tensor(q / q.sum(1, keepdims=True), device=device)
-        lab = np.asarray(init_labels.cpu() if isinstance(init_labels, torch.Tensor) else init_labels).reshape(-1).astype(np.int64)
+        lab = host(init_labels).reshape(-1).astype(np.int64)
         first = np.concatenate([off[r] + d * np.arange(boff[r + 1] - boff[r]) for r in range(len(off) - 1)] + [np.zeros(0, np.int64)])
         lb = lab[first.astype(np.int64)]
         q = np.full((TB, K), 1.0 / K)
@@ -440,38 +467,22 @@ class VBResegmenter:
         TB, F = int(boff[-1]), x.shape[0]
         _, _, means, Bm, U = self._consts(dev)
         q = self._init_q(off, boff, init_labels, q0, seed, dev)
-        sh = np.full((N, K), 1.0 / K) if sp0 is None else np.asarray(sp0.cpu() if isinstance(sp0, torch.Tensor) else sp0, dtype=np.float64)
+        sh = np.full((N, K), 1.0 / K) if sp0 is None else host(sp0, np.float64)
         sp = torch.as_tensor(np.ascontiguousarray(np.broadcast_to(sh, (N, K))), device=dev)
-        bound = np.full((N, self.maxIters), np.nan)
-        iters = np.zeros(N, np.int64)
-        live = np.diff(off) > 0
+        step = None
         if TB:
             o32 = torch.as_tensor(off.astype(np.int32), device=dev)
             b32 = torch.as_tensor(boff.astype(np.int32), device=dev)
             start, pairs = ops.vb_bucket(g, self.numGauss)
-            rec_of_block = torch.as_tensor(np.repeat(np.arange(N), np.diff(boff)), device=dev)
             gsum = ops.vb_loglike_sums(ll, o32)                 # sum_t G_t per recording, in an order of the recording's own
-            active = live.copy()
-            prev = np.full(N, np.nan)
-            for it in range(self.maxIters):
+
+            def step(q, sp):
                 Nst, Fst = ops.vb_speaker_stats(x, o32, b32, d, p, start, pairs, means, q)
                 _, _, kl, h, gg = ops.vb_speaker_update(Nst, Fst, Bm, U)
                 lls = ops.vb_block_loglike(x, o32, b32, d, TB, g, p, means, h, gg, K)
                 qn, spn, tll = ops.vb_forward_backward(lls, b32, sp, self.loopProb)
-                Lr = ops.vb_bound(gsum, tll, kl, self.statScale).cpu().numpy()      # the iteration's one device -> host read
-                if active.all():
-                    q, sp = qn, spn
-                else:
-                    act = torch.as_tensor(active, device=dev)
-                    q = torch.where(act[rec_of_block][:, None], qn, q)
-                    sp = torch.where(act[:, None], spn, sp)
-                bound[active, it] = Lr[active]
-                iters[active] = it + 1
-                if it > 0:
-                    active = active & ~(Lr - prev < self.epsilon)
-                prev = np.where(active, Lr, prev)
-                if not active.any():
-                    break
+                return qn, spn, ops.vb_bound(gsum, tll, kl, self.statScale)
+        q, sp, bound, iters = _vb_iterate(step, q, sp, boff, self.maxIters, self.epsilon)
         block_of_frame = np.concatenate([boff[r] + np.arange(off[r + 1] - off[r]) // d for r in range(N)] + [np.zeros(0, np.int64)])
         fq = q[torch.as_tensor(block_of_frame.astype(np.int64), device=dev)] if F else torch.zeros((0, K), dtype=torch.float64, device=dev)
         labels = fq.argmax(1).to(torch.int32) if F else torch.zeros((0,), dtype=torch.int32, device=dev)
@@ -479,17 +490,13 @@ class VBResegmenter:
 
 
 # =============================================================================== VBx
-def _host(a, dtype=None):
-    return np.asarray(a.cpu() if isinstance(a, torch.Tensor) else a, dtype=dtype)
-
-
 def vbx_init(init_labels, offsets, K, smoothing):
     """VBx's start from one integer label per window (host logic, no kernel): with the distinct labels of recording r in ascending
     order as columns 0 .. K_r - 1, gamma0 = softmax(smoothing * onehot) over those columns and 0 on the rest, pi0 = 1 / K_r on them.
     When K_r > K only the K clusters with the most windows are kept (ties to the lower label; columns still in ascending label
     order) and a window of a dropped cluster gets a row uniform over the kept columns. -> gamma0 (S, K), pi0 (N, K) fp64 arrays."""
     off = np.asarray(offsets, dtype=np.int64)
-    lab = _host(init_labels).reshape(-1)
+    lab = host(init_labels).reshape(-1)
     if lab.size and lab.dtype.kind not in "iu":
         raise ValueError(f"init_labels must be integers, got {lab.dtype}")
     if lab.size != off[-1]:
@@ -554,7 +561,7 @@ class VBx:
 
     def __init__(self, phi, transform=None, offset=None, max_speakers=10, max_iters=40, epsilon=1e-6, loop_prob=0.99, Fa=0.3, Fb=17.0,
                  init_smoothing=5.0):
-        phi = np.ascontiguousarray(_host(phi), dtype=np.float64)
+        phi = np.ascontiguousarray(host(phi), dtype=np.float64)
         if phi.ndim != 1 or not 1 <= phi.size <= L.VBX_MAX_DIM:
             raise ValueError(f"phi must be a vector of 1 .. {L.VBX_MAX_DIM} values, got shape {phi.shape}")
         if not np.isfinite(phi).all() or (phi <= 0).any():
@@ -566,33 +573,31 @@ class VBx:
             self._A = self._b = None
             Din = D
         else:
-            A = np.asarray(_host(transform), dtype=np.float64)
+            A = np.asarray(host(transform), dtype=np.float64)
             if A.ndim != 2 or A.shape[0] != D or not D <= A.shape[1] <= L.PLDA_DENSE_MAX_DIM or not np.isfinite(A).all():
                 raise ValueError(f"transform must be a finite ({D}, Din) matrix with {D} <= Din <= {L.PLDA_DENSE_MAX_DIM}, got shape {A.shape}")
             Din = A.shape[1]
-            b = np.zeros(D) if offset is None else np.asarray(_host(offset), dtype=np.float64)
+            b = np.zeros(D) if offset is None else np.asarray(host(offset), dtype=np.float64)
             if b.shape != (D,) or not np.isfinite(b).all():
                 raise ValueError(f"offset must be a finite ({D},) vector, got shape {b.shape}")
             self._A = np.zeros((Din, Din))       # ktf_plda_f64 takes a square matrix: rows past D are zero and dropped afterwards
             self._A[:D] = A
             self._b = np.concatenate([b, np.zeros(Din - D)])
-        if isinstance(max_speakers, bool) or not isinstance(max_speakers, (numbers.Integral, np.integer)) or \
-                not 1 <= int(max_speakers) <= L.VB_MAX_SPEAKERS:
+        if not is_int(max_speakers) or not 1 <= int(max_speakers) <= L.VB_MAX_SPEAKERS:
             raise ValueError(f"max_speakers {max_speakers!r} outside 1 .. {L.VB_MAX_SPEAKERS}")
-        if isinstance(max_iters, bool) or not isinstance(max_iters, (numbers.Integral, np.integer)) or int(max_iters) < 1:
+        if not is_int(max_iters) or int(max_iters) < 1:
             raise ValueError(f"max_iters {max_iters!r} < 1")
-        if not _real(loop_prob) or not 0.0 <= float(loop_prob) <= 1.0:
+        if not is_real(loop_prob) or not 0.0 <= float(loop_prob) <= 1.0:
             raise ValueError(f"loop_prob {loop_prob!r} outside [0, 1]")
-        if not (_real(Fa) and _real(Fb) and 0 < float(Fa) < np.inf and 0 < float(Fb) < np.inf):
+        if not (is_real(Fa) and is_real(Fb) and 0 < float(Fa) < np.inf and 0 < float(Fb) < np.inf):
             raise ValueError(f"Fa and Fb must be > 0 and finite, got {Fa!r}, {Fb!r}")
-        if not _real(epsilon) or np.isnan(float(epsilon)):
+        if not is_real(epsilon) or np.isnan(float(epsilon)):
             raise ValueError(f"epsilon must be a number, got {epsilon!r}")
-        if not _real(init_smoothing) or not 0.0 <= float(init_smoothing) <= 700.0:
+        if not is_real(init_smoothing) or not 0.0 <= float(init_smoothing) <= 700.0:
             raise ValueError(f"init_smoothing {init_smoothing!r} outside [0, 700]")
         self.phi, self.dim, self.inputDim = phi, D, Din
         self.maxSpeakers, self.maxIters, self.epsilon = int(max_speakers), int(max_iters), float(epsilon)
         self.loopProb, self.Fa, self.Fb, self.initSmoothing = float(loop_prob), float(Fa), float(Fb), float(init_smoothing)
-        self._dev_cache = {}
 
     @classmethod
     def from_plda(cls, plda, lda_dim=None, **kw):
@@ -605,7 +610,7 @@ class VBx:
         dim = psi.size
         if lda_dim is None:
             lda_dim = dim
-        if isinstance(lda_dim, bool) or not isinstance(lda_dim, (numbers.Integral, np.integer)) or not 1 <= int(lda_dim) <= dim:
+        if not is_int(lda_dim) or not 1 <= int(lda_dim) <= dim:
             raise ValueError(f"lda_dim {lda_dim!r} outside 1 .. {dim}")
         lda_dim = int(lda_dim)
         if lda_dim < dim and (np.diff(psi) > 0).any():
@@ -613,11 +618,8 @@ class VBx:
         return cls(psi[:lda_dim], A[:lda_dim], b[:lda_dim], **kw)
 
     def _consts(self, device):
-        key = str(device)
-        if key not in self._dev_cache:
-            f = lambda a: None if a is None else torch.as_tensor(np.ascontiguousarray(a), device=device)  # noqa: E731
-            self._dev_cache[key] = (f(self.phi), f(self._A), f(self._b))
-        return self._dev_cache[key]
+        f = lambda a: None if a is None else torch.as_tensor(np.ascontiguousarray(a), device=device)  # noqa: E731
+        return per_device(self, device, lambda: (f(self.phi), f(self._A), f(self._b)))
 
     def transform(self, x):
         """x (S, Din) fp32 / fp64 on a GPU -> y (S, D) fp64 = transform x + offset (ktf_plda_f64 without length normalisation)."""
@@ -638,7 +640,7 @@ class VBx:
                 raise ValueError("init_labels set pi0 themselves")
             return vbx_init(init_labels, off, K, self.initSmoothing)
         if gamma0 is not None:
-            g = np.array(_host(gamma0), dtype=np.float64)
+            g = np.array(host(gamma0), dtype=np.float64)
             if g.shape != (S, K):
                 raise ValueError(f"gamma0 must be ({S}, {K}), got {g.shape}")
             if not np.isfinite(g).all() or (g < 0).any() or (g > 1 + 1e-9).any():
@@ -649,7 +651,7 @@ class VBx:
         if pi0 is None:
             p = np.full((N, K), 1.0 / K)
         else:
-            p = np.array(_host(pi0), dtype=np.float64)
+            p = np.array(host(pi0), dtype=np.float64)
             if p.shape not in ((K,), (N, K)) or not np.isfinite(p).all() or (p < 0).any() or (np.abs(p.sum(-1) - 1) > 1e-6).any():
                 raise ValueError(f"pi0 must be ({K},) or ({N}, {K}) probabilities that sum to 1")
             p = np.array(np.broadcast_to(p, (N, K)))
@@ -675,36 +677,21 @@ class VBx:
 
     def _run(self, x, off, g0, p0):
         dev = x.device
-        K, N, S = self.maxSpeakers, len(off) - 1, int(off[-1])
+        N, S = len(off) - 1, int(off[-1])
         phi = self._consts(dev)[0]
         gamma = torch.as_tensor(g0, device=dev)
         pi = torch.as_tensor(p0, device=dev)
-        elbo = np.full((N, self.maxIters), np.nan)
-        iters = np.zeros(N, np.int64)
+        step = None
         if S:
             o32 = torch.as_tensor(off.astype(np.int32), device=dev)
             rho, G = ops.vbx_prepare(self.transform(x), phi)
-            rec_of_row = torch.as_tensor(np.repeat(np.arange(N), np.diff(off)), device=dev)
             zero = torch.zeros((N,), dtype=torch.float64, device=dev)
-            active = np.diff(off) > 0
-            prev = np.full(N, np.nan)
-            for it in range(self.maxIters):
+
+            def step(gamma, pi):
                 alpha, _, c, kl = ops.vbx_speaker_update(gamma, rho, phi, self.Fa / self.Fb, o32)
                 lls = ops.vbx_loglike(rho, G, alpha, c, self.Fa, o32)
                 gn, pn, tll = ops.vb_forward_backward(lls, o32, pi, self.loopProb)
-                Lr = ops.vb_bound(zero, tll, kl * self.Fb, 0.0).cpu().numpy()       # the iteration's one device -> host read
-                if active.all():
-                    gamma, pi = gn, pn
-                else:
-                    act = torch.as_tensor(active, device=dev)
-                    gamma = torch.where(act[rec_of_row][:, None], gn, gamma)
-                    pi = torch.where(act[:, None], pn, pi)
-                elbo[active, it] = Lr[active]
-                iters[active] = it + 1
-                if it > 0:
-                    active = active & ~(Lr - prev < self.epsilon)
-                prev = np.where(active, Lr, prev)
-                if not active.any():
-                    break
+                return gn, pn, ops.vb_bound(zero, tll, kl * self.Fb, 0.0)
+        gamma, pi, elbo, iters = _vb_iterate(step, gamma, pi, off, self.maxIters, self.epsilon)
         labels, counts = vbx_labels(gamma, off)
         return VBxResult(gamma, pi, torch.as_tensor(elbo, device=dev), iters, off, labels, counts)

@@ -16,6 +16,7 @@ import torch
 
 from . import _lib as L
 from . import ops
+from ._host import chunks, host, is_int, max_under, per_device
 
 _name_counters = collections.defaultdict(int)
 
@@ -41,16 +42,6 @@ def _to_device(x):
     a = np.asarray(x)
     dt = np.float64 if a.dtype == np.float64 else np.float32
     return torch.as_tensor(np.ascontiguousarray(a, dtype=dt), device=dev)
-
-
-def _per_device(layer, device, make):
-    """One device-resident constant set per (layer, device): a layer called on a second GPU must not hand kernels
-    pointers into the first one's memory."""
-    cache = layer.__dict__.setdefault("_dev_cache", {})
-    key = str(device)
-    if key not in cache:
-        cache[key] = make()
-    return cache[key]
 
 
 class Layer:
@@ -214,7 +205,7 @@ class Framing(Layer):
         B = int(np.prod(lead)) if len(lead) else 1
         T = self.numFrames(n)
         cfg = self._cfg()
-        tables = _per_device(self, x.device, lambda: ops.FrontendTables(self.frameWidth, device=x.device))
+        tables = per_device(self, x.device, lambda: ops.FrontendTables(self.frameWidth, device=x.device))
         if x.dim() == 2 and not x.is_contiguous():
             cfg.row_stride = x.stride(0)
         else:
@@ -279,7 +270,7 @@ class Windowing(Layer):
             raise ValueError(f"layer was built for frames of {self._M} samples, got {M}")
         lead = x.shape[:-1]
         rows = int(np.prod(lead))
-        tables = _per_device(self, x.device, lambda: ops.FrontendTables(M, window=self.windowFunc, device=x.device))
+        tables = per_device(self, x.device, lambda: ops.FrontendTables(M, window=self.windowFunc, device=x.device))
         r = ops.frontend(x.reshape(1, rows, M), L.IN_FRAMES, self._cfg(M), tables, L.OUT_WINDOWED, rows, 1, rows,
                          seed=next(self._seed), want_energy=self.returnEnergy)
         if self.returnEnergy:
@@ -345,7 +336,7 @@ class FilterBank(Layer):
             raise ValueError(f"layer was built for frames of {self._M} samples, got {M}")
         lead = x.shape[:-1]
         rows = int(np.prod(lead))
-        tables = _per_device(self, x.device, lambda: ops.FrontendTables(M, mel_bank=self.melBank, device=x.device))
+        tables = per_device(self, x.device, lambda: ops.FrontendTables(M, mel_bank=self.melBank, device=x.device))
         cfg = L.FrontendCfg(frame_size=M, frame_shift=M, nfft=max(64, self.fftLength), num_mels=self.numBins, num_ceps=1,
                             use_power=int(self.usePower), use_log=int(self.useLogFBank), eps=self.eps)
         out = ops.frontend(x.reshape(1, rows, M), L.IN_WINDOWED, cfg, tables, L.OUT_FBANK, rows, 1, rows)
@@ -388,7 +379,7 @@ class DCT(Layer):
 
     def call(self, inputs):
         x = inputs.to(torch.float32).contiguous()
-        dct_dev = _per_device(self, x.device, lambda: ops.to_device_f32(self.dct, x.device))
+        dct_dev = per_device(self, x.device, lambda: ops.to_device_f32(self.dct, x.device))
         lead = x.shape[:-1]
         out = ops.dct(x.reshape(-1, x.shape[-1]), dct_dev, None, self.length)
         return out.reshape(*lead, self.length)
@@ -638,11 +629,11 @@ class AddDeltas(Layer):
             x = x.contiguous()
         n = None
         if lengths is not None:
-            h = np.asarray(lengths.cpu() if isinstance(lengths, torch.Tensor) else lengths, dtype=np.int64).reshape(-1)
+            h = host(lengths, np.int64).reshape(-1)
             if h.shape[0] != B or (h < 0).any() or (h > T).any():
                 raise ValueError(f"lengths must hold {B} values in 0 .. {T}")
             n = torch.as_tensor(h.astype(np.int32), device=x.device)
-        coeffs = _per_device(self, x.device, lambda: torch.as_tensor(self._coeffs, device=x.device))
+        coeffs = per_device(self, x.device, lambda: torch.as_tensor(self._coeffs, device=x.device))
         out = ops.add_deltas(x, n, coeffs, self.order, self.window)
         return out[0] if squeeze else out
 
@@ -1324,9 +1315,9 @@ class PLDA(Layer):
         if role not in ("test", "enroll"):
             raise ValueError(f"role must be 'test' or 'enroll', got {role!r}")
         if top_n is not None:
-            if isinstance(top_n, bool) or not isinstance(top_n, (int, np.integer)) or int(top_n) < 2:
+            if not is_int(top_n) or int(top_n) < 2:
                 raise ValueError(f"top_n must be None or an integer >= 2, got {top_n!r}")
-        if isinstance(workspace_limit, bool) or not isinstance(workspace_limit, (int, np.integer)) or int(workspace_limit) < 1:
+        if not is_int(workspace_limit) or int(workspace_limit) < 1:
             raise ValueError(f"workspace_limit must be a positive number of bytes, got {workspace_limit!r}")
         for t, what in ((vectors_tr, "vectors_tr"), (cohort_tr, "cohort_tr")):
             if not isinstance(t, torch.Tensor) or not t.is_cuda:
@@ -1354,8 +1345,7 @@ class PLDA(Layer):
         chunk = min(chunk, R)
         ws = torch.empty((ops.plda_cohort_workspace_bytes(chunk, Cn, self.dim, v.element_size()),), dtype=torch.uint8, device=v.device)
         with L.launch_scope(v.device):
-            for r0 in range(0, R, chunk):
-                r1 = min(R, r0 + chunk)
+            for r0, r1 in chunks(R, chunk):
                 ops.plda_cohort_stats(v[r0:r1], c, self._dev[2], n if n is None or role == "test" else n[r0:r1],
                                       1 if role == "enroll" else 0, top_n, mean[r0:r1], std[r0:r1], ws)
         return mean, std
@@ -1479,7 +1469,7 @@ def select_frames(feats, D, lengths, mask):
             raise ValueError(f"mask must be (B, T) or (B, T, 1) = ({B}, {T}), got {tuple(mask.shape)}")
         m = m.to(feats.device) != 0
     elif lengths is not None:
-        n = np.asarray(lengths.cpu() if isinstance(lengths, torch.Tensor) else lengths, dtype=np.int64).reshape(-1)
+        n = host(lengths, np.int64).reshape(-1)
         if n.shape[0] != B or (n < 0).any() or (n > T).any():
             raise ValueError(f"lengths must hold {B} values in 0 .. {T}")
         m = torch.arange(T, device=feats.device)[None, :] < torch.as_tensor(n, device=feats.device)[:, None]
@@ -1565,20 +1555,11 @@ class IvectorExtractor(Layer):
             f = lambda a: torch.as_tensor(a, device=device)  # noqa: E731
             full = None if self._full is None else tuple(f(a) for a in self._full)
             return f(self._W), f(self._gconst), f(self._sigmaInvM), f(self._U), full
-        return _per_device(self, device, make)
+        return per_device(self, device, make)
 
     def _frame_step(self):
         I, D, n = self.numGauss, self.featDim, self.numGselect
-        lo, hi = 1, ((1 << 31) - 1) // n
-        if ops.fgmm_workspace_bytes(hi, I, D, n) <= self.workspaceLimit:
-            return hi
-        while hi - lo > 1:
-            mid = (lo + hi) // 2
-            if ops.fgmm_workspace_bytes(mid, I, D, n) <= self.workspaceLimit:
-                lo = mid
-            else:
-                hi = mid
-        return lo
+        return max_under(lambda f: ops.fgmm_workspace_bytes(f, I, D, n), self.workspaceLimit, ((1 << 31) - 1) // n)
 
     def _post(self, x):
         """Posteriors of the frames x (F, D): gmm-global-get-post, or with a full UBM gmm-gselect | fgmm-global-gselect-to-post."""
@@ -1592,9 +1573,9 @@ class IvectorExtractor(Layer):
             return ops.fgmm_post(x, sel, mic, icov, fgc, self.minPost)
         g = torch.empty((F, self.numGselect), dtype=torch.int32, device=x.device)
         p = torch.empty((F, self.numGselect), dtype=torch.float32, device=x.device)
-        for lo in range(0, F, step):
-            sel, _ = ops.ivector_post(x[lo:lo + step], W, gc, self.numGselect, 0.0)
-            g[lo:lo + step], p[lo:lo + step] = ops.fgmm_post(x[lo:lo + step], sel, mic, icov, fgc, self.minPost)
+        for lo, hi in chunks(F, step):
+            sel, _ = ops.ivector_post(x[lo:hi], W, gc, self.numGselect, 0.0)
+            g[lo:hi], p[lo:hi] = ops.fgmm_post(x[lo:hi], sel, mic, icov, fgc, self.minPost)
         return g, p
 
     def _frames(self, feats, lengths, mask):
@@ -1603,8 +1584,7 @@ class IvectorExtractor(Layer):
 
     def _chunks(self, B):
         per = ops.ivector_workspace_bytes(1, self.numGauss, self.featDim, self.ivecDim)
-        step = int(max(1, min(B, 65535, self.workspaceLimit // max(per, 1))))
-        return [(b, min(B, b + step)) for b in range(0, B, step)]
+        return chunks(B, int(max(1, min(B, 65535, self.workspaceLimit // max(per, 1)))))
 
     def posteriors(self, feats, lengths=None, mask=None):
         """The posterior stage alone (gmm-global-get-post, or the full-UBM pair) -> (gauss (F, num_gselect) int32, post (F, num_gselect) fp32, offsets (B + 1) int64): the selected
@@ -1643,8 +1623,7 @@ class IvectorExtractor(Layer):
 
     def _train_chunks(self, B):
         per = ops.ivector_train_workspace_bytes(1, self.numGauss, self.featDim, self.ivecDim)
-        step = int(max(1, min(B, 65535, self.workspaceLimit // max(per, 1))))
-        return [(b, min(B, b + step)) for b in range(0, B, step)]
+        return chunks(B, int(max(1, min(B, 65535, self.workspaceLimit // max(per, 1)))))
 
     def _accumulate(self, stats, x, off, posts):
         if self.acousticWeight != 1.0 or self.maxCount != 0.0:

@@ -18,6 +18,7 @@ import torch
 
 from . import _lib as L
 from . import ops
+from ._host import is_real
 from .io import KaldiNnet3Reader, ReadKaldiArray
 from .layers import TDNN, BatchNorm, CMVN, Framing, MFCC, ReLU, StatsPooling, VAD, _GEMM, WEIGHTS_EPOCH, _f32_rows
 from .mx import Planes
@@ -705,14 +706,10 @@ def window_count(L, W, P, M):
     return 1 + max(0, -(-(L - W - M) // P))
 
 
-def _is_real(v):
-    return isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, (bool, np.bool_))
-
-
 def window_frames(shift, window, period, min_segment):
     """(W, P, M) in frames; ValueError unless window > 0, 0 < period <= window, min_segment >= 0 (and W, P >= 1 after rounding)."""
     for name, v in (("window", window), ("period", period), ("min_segment", min_segment)):
-        if not _is_real(v) or not math.isfinite(float(v)):
+        if not is_real(v) or not math.isfinite(float(v)):
             raise ValueError(f"{name} must be a finite number of seconds, got {v!r}")
     if not float(window) > 0:
         raise ValueError(f"window must be > 0, got {window}")
@@ -735,7 +732,7 @@ def caller_segments(segments, frames, shift):
     for r, (segs, T) in enumerate(zip(segments, frames)):
         rows, prev = [], 0
         for pair in segs:
-            if len(pair) != 2 or not all(_is_real(v) and math.isfinite(float(v)) for v in pair):
+            if len(pair) != 2 or not all(is_real(v) and math.isfinite(float(v)) for v in pair):
                 raise ValueError(f"recording {r}: a segment must be a (start_s, end_s) pair of numbers, got {pair!r}")
             if float(pair[1]) < float(pair[0]):
                 raise ValueError(f"recording {r}: segment {pair!r} ends before it starts")

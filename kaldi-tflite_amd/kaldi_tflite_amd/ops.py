@@ -395,16 +395,49 @@ def tdnn_stats(x, lens, desc, w, w_lo, bias, scale, shift, sums, zero=True):
     return sums
 
 
+# ----------------------------------------------------------------------------- the back-end wrappers' way into the library
+# (the extraction-path wrappers above and split_bf16 .. plda below spell their calls out: they run ~10 times per batch-1 extraction)
+def _call(name, device, *args):
+    """The library's `name`(*args, stream) with `device` current; a failure raises through L.check."""
+    fn = getattr(L.load(), name)
+    with L.on_device(device):
+        rc = fn(*args, L.stream_ptr())
+    L.check(rc, name)
+
+
+def _typed(stem, t):
+    """The `_f64` / `_f32` symbol of `stem` for tensor t."""
+    return stem + ("_f64" if t.dtype == torch.float64 else "_f32")
+
+
+def _size(name, *args):
+    """A `*_workspace_bytes` symbol's answer; a negative one raises through L.check."""
+    n = int(getattr(L.load(), name)(*args))
+    if n < 0:
+        L.check(n, name)
+    return n
+
+
+def _workspace(name, *args, device):
+    """A fresh uint8 workspace on `device` of the size `name`(*args) asks for."""
+    return torch.empty((_size(name, *args),), dtype=torch.uint8, device=device)
+
+
+def _ld(x):
+    """Row stride of a 2-D x; its width when it has no rows."""
+    return x.stride(0) if x.shape[0] else x.shape[1]
+
+
+def _new(like, *shape, dtype=None):
+    return torch.empty(shape, dtype=dtype or like.dtype, device=like.device)
+
+
 def plda_score(test_tr, enroll_tr, psi):
     """scores (N, M) of transformed test vectors against transformed enrollment vectors."""
-    lib = L.load()
     N, dim = test_tr.shape
     M = enroll_tr.shape[0]
-    scores = torch.empty((N, M), dtype=test_tr.dtype, device=test_tr.device)
-    fn = lib.ktf_plda_score_f64 if test_tr.dtype == torch.float64 else lib.ktf_plda_score_f32
-    with L.on_device(test_tr.device):
-        rc = fn(L.ptr(test_tr), N, L.ptr(enroll_tr), M, dim, L.ptr(psi), L.ptr(scores), L.stream_ptr())
-    L.check(rc, "ktf_plda_score")
+    scores = _new(test_tr, N, M)
+    _call(_typed("ktf_plda_score", test_tr), test_tr.device, L.ptr(test_tr), N, L.ptr(enroll_tr), M, dim, L.ptr(psi), L.ptr(scores))
     return scores
 
 
@@ -414,61 +447,45 @@ def spk_mean(raw, offsets, utts, S, means=None, num_utts=None):
     num_utts (S,) int32)."""
     U, D = raw.shape
     if means is None:
-        means = torch.empty((S, D), dtype=torch.float32, device=raw.device)
+        means = _new(raw, S, D, dtype=torch.float32)
     if num_utts is None:
-        num_utts = torch.empty((S,), dtype=torch.int32, device=raw.device)
-    with L.on_device(raw.device):
-        rc = L.load().ktf_spk_mean_f32(L.ptr(raw), U, D, L.ptr(offsets), S, L.ptr(utts), utts.numel(), L.ptr(means), L.ptr(num_utts),
-                                       L.stream_ptr())
-    L.check(rc, "ktf_spk_mean_f32")
+        num_utts = _new(raw, S, dtype=torch.int32)
+    _call("ktf_spk_mean_f32", raw.device, L.ptr(raw), U, D, L.ptr(offsets), S, L.ptr(utts), utts.numel(), L.ptr(means), L.ptr(num_utts))
     return means, num_utts
 
 
 def plda_transform_n(x, A, offset, psi, num_examples, normalize_length, simple_length_norm):
     """transformVector(x, num_examples): x (B, dim), num_examples (B,) on the device in x's dtype -> (B, dim)."""
-    lib = L.load()
     B, dim = x.shape
     tr = torch.empty_like(x)
-    fn = lib.ktf_plda_transform_n_f64 if x.dtype == torch.float64 else lib.ktf_plda_transform_n_f32
-    with L.on_device(x.device):
-        rc = fn(L.ptr(x), B, dim, L.ptr(A), L.ptr(offset), L.ptr(psi), L.ptr(num_examples), int(normalize_length),
-                int(simple_length_norm), L.ptr(tr), L.stream_ptr())
-    L.check(rc, "ktf_plda_transform_n")
+    _call(_typed("ktf_plda_transform_n", x), x.device, L.ptr(x), B, dim, L.ptr(A), L.ptr(offset), L.ptr(psi), L.ptr(num_examples),
+          int(normalize_length), int(simple_length_norm), L.ptr(tr))
     return tr
 
 
 def plda_score_n(test_tr, enroll_tr, psi, enroll_num_examples):
     """scores (N, M) with class j averaging enroll_num_examples[j] examples (device, the dtype of the vectors)."""
-    lib = L.load()
     N, dim = test_tr.shape
     M = enroll_tr.shape[0]
-    scores = torch.empty((N, M), dtype=test_tr.dtype, device=test_tr.device)
-    fn = lib.ktf_plda_score_n_f64 if test_tr.dtype == torch.float64 else lib.ktf_plda_score_n_f32
-    with L.on_device(test_tr.device):
-        rc = fn(L.ptr(test_tr), N, L.ptr(enroll_tr), M, dim, L.ptr(psi), L.ptr(enroll_num_examples), L.ptr(scores), L.stream_ptr())
-    L.check(rc, "ktf_plda_score_n")
+    scores = _new(test_tr, N, M)
+    _call(_typed("ktf_plda_score_n", test_tr), test_tr.device, L.ptr(test_tr), N, L.ptr(enroll_tr), M, dim, L.ptr(psi),
+          L.ptr(enroll_num_examples), L.ptr(scores))
     return scores
 
 
 def plda_trials(test_tr, enroll_tr, psi, enroll_num_examples, pairs, workspace=None):
     """scores (T,) of the trial list pairs (T, 2) device int32 rows (class j, test i). workspace(nbytes) -> a uint8 device tensor
     (None: a fresh one)."""
-    lib = L.load()
     N, dim = test_tr.shape
     M = enroll_tr.shape[0]
     T = pairs.shape[0]
-    scores = torch.empty((T,), dtype=test_tr.dtype, device=test_tr.device)
+    scores = _new(test_tr, T)
     if T == 0:
         return scores
-    nbytes = int(lib.ktf_plda_trials_workspace_bytes(N, M, dim, test_tr.element_size()))
-    if nbytes < 0:
-        L.check(nbytes, "ktf_plda_trials_workspace_bytes")
+    nbytes = _size("ktf_plda_trials_workspace_bytes", N, M, dim, test_tr.element_size())
     ws = workspace(nbytes) if workspace is not None else torch.empty((nbytes,), dtype=torch.uint8, device=test_tr.device)
-    fn = lib.ktf_plda_trials_f64 if test_tr.dtype == torch.float64 else lib.ktf_plda_trials_f32
-    with L.on_device(test_tr.device):
-        rc = fn(L.ptr(test_tr), N, L.ptr(enroll_tr), M, dim, L.ptr(psi), L.ptr(enroll_num_examples), L.ptr(pairs), T, L.ptr(scores),
-                L.ptr(ws), ws.numel(), L.stream_ptr())
-    L.check(rc, "ktf_plda_trials")
+    _call(_typed("ktf_plda_trials", test_tr), test_tr.device, L.ptr(test_tr), N, L.ptr(enroll_tr), M, dim, L.ptr(psi),
+          L.ptr(enroll_num_examples), L.ptr(pairs), T, L.ptr(scores), L.ptr(ws), ws.numel())
     return scores
 
 
@@ -476,58 +493,59 @@ def plda_trials(test_tr, enroll_tr, psi, enroll_num_examples, pairs, workspace=N
 TOPN_ALL = (1 << 31) - 1            # the C-level top_n for "the whole row"
 
 
+def _top_n(top_n):
+    return TOPN_ALL if top_n is None else min(int(top_n), TOPN_ALL)
+
+
 def topn_stats(x, top_n):
     """(mean, std) of the top_n largest entries of each row of x (R, C) fp32 / fp64 on the device (rows may be strided: a column
     slice of a wider matrix is read in place) -> two (R,) fp64 tensors. top_n None or >= C: the whole row."""
-    lib = L.load()
     if x.dim() != 2 or x.dtype not in (torch.float32, torch.float64):
         raise ValueError(f"topn_stats: x must be a (R, C) fp32 or fp64 tensor, got {x.dtype} {tuple(x.shape)}")
     R, Cn = x.shape
     if R > 1 and not (x.stride(1) == 1 and x.stride(0) >= Cn) or R <= 1 and not x.is_contiguous():
         x = x.contiguous()
     ld = x.stride(0) if R > 1 else Cn
-    mean = torch.empty((R,), dtype=torch.float64, device=x.device)
-    std = torch.empty((R,), dtype=torch.float64, device=x.device)
-    fn = lib.ktf_topn_stats_f64 if x.dtype == torch.float64 else lib.ktf_topn_stats_f32
-    with L.on_device(x.device):
-        rc = fn(L.ptr(x), R, Cn, ld, TOPN_ALL if top_n is None else min(int(top_n), TOPN_ALL), L.ptr(mean), L.ptr(std), L.stream_ptr())
-    L.check(rc, "ktf_topn_stats")
+    mean = _new(x, R, dtype=torch.float64)
+    std = _new(x, R, dtype=torch.float64)
+    _call(_typed("ktf_topn_stats", x), x.device, L.ptr(x), R, Cn, ld, _top_n(top_n), L.ptr(mean), L.ptr(std))
     return mean, std
 
 
 def plda_cohort_workspace_bytes(R, Cn, dim, dtype_bytes):
     """Bytes of workspace ktf_plda_cohort_stats_* needs for R rows against Cn cohort vectors."""
-    n = int(L.load().ktf_plda_cohort_workspace_bytes(R, Cn, dim, dtype_bytes))
-    if n < 0:
-        L.check(n, "ktf_plda_cohort_workspace_bytes")
-    return n
+    return _size("ktf_plda_cohort_workspace_bytes", R, Cn, dim, dtype_bytes)
 
 
 def plda_cohort_stats(rows_tr, cohort_tr, psi, counts, role, top_n, mean, std, workspace):
     """topn_stats of the PLDA scores of rows_tr (R, dim) against cohort_tr (C, dim) into mean / std (R,) fp64. role 0: the rows are
     tests, counts (C) or None belong to the cohort; role 1: the rows are classes with counts (R) or None. workspace: a uint8
     device tensor of at least plda_cohort_workspace_bytes."""
-    lib = L.load()
     R, dim = rows_tr.shape
     Cn = cohort_tr.shape[0]
-    fn = lib.ktf_plda_cohort_stats_f64 if rows_tr.dtype == torch.float64 else lib.ktf_plda_cohort_stats_f32
-    with L.on_device(rows_tr.device):
-        rc = fn(L.ptr(rows_tr), R, L.ptr(cohort_tr), Cn, dim, L.ptr(psi), L.ptr(counts) if counts is not None else None, int(role),
-                TOPN_ALL if top_n is None else min(int(top_n), TOPN_ALL), L.ptr(mean), L.ptr(std), L.ptr(workspace), workspace.numel(),
-                L.stream_ptr())
-    L.check(rc, "ktf_plda_cohort_stats")
+    _call(_typed("ktf_plda_cohort_stats", rows_tr), rows_tr.device, L.ptr(rows_tr), R, L.ptr(cohort_tr), Cn, dim, L.ptr(psi), L.ptr(counts),
+          int(role), _top_n(top_n), L.ptr(mean), L.ptr(std), L.ptr(workspace), workspace.numel())
     return mean, std
+
+
+def _host_i32(a):
+    return np.ascontiguousarray(a, dtype=np.int32)
+
+
+def _host_ptr(a):
+    return a.ctypes.data_as(C.c_void_p)
+
+
+def _fresh(device):
+    """The `scratch(role, shape, dtype)` of a caller that gave none: a fresh allocation each call."""
+    return lambda role, shape, dtype: torch.empty(shape, dtype=dtype, device=device)
 
 
 def plda_dense_workspace_bytes(lengths, dim, target_energy):
     """Bytes of scratch ktf_plda_dense_* needs (lengths: host ints; target_energy None = no PCA)."""
-    lib = L.load()
-    lens = np.ascontiguousarray(lengths, dtype=np.int32)
+    lens = _host_i32(lengths)
     t = L.PLDA_DENSE_NO_PCA if target_energy is None else float(target_energy)
-    n = lib.ktf_plda_dense_workspace_bytes(lens.ctypes.data_as(C.c_void_p), len(lens), int(dim), t)
-    if n < 0:
-        L.check(int(n), "ktf_plda_dense_workspace_bytes")
-    return int(n)
+    return _size("ktf_plda_dense_workspace_bytes", _host_ptr(lens), len(lens), int(dim), t)
 
 
 def plda_dense(x, lengths, target_energy, A, offset, psi, mean64, Tinv64, psi64, normalize_length, simple_length_norm,
@@ -535,59 +553,47 @@ def plda_dense(x, lengths, target_energy, A, offset, psi, mean64, Tinv64, psi64,
     """Dense per-recording scoring (ktf_plda_dense_*). x (S, dim) on the device, lengths host ints (R), target_energy None = no PCA.
     -> (scores: the R blocks n_r x n_r packed in one 1-D tensor, dims (R,) int32, status (1,) int32 -- the device word the caller
     reads once). `scratch(role, shape, dtype)` hands out workspace tensors (a fresh allocation each call without it)."""
-    lib = L.load()
     S, dim = x.shape
-    lens = np.ascontiguousarray(lengths, dtype=np.int32)
+    lens = _host_i32(lengths)
     R = len(lens)
     t = L.PLDA_DENSE_NO_PCA if target_energy is None else float(target_energy)
     nbytes = plda_dense_workspace_bytes(lens, dim, target_energy)
-    get = scratch or (lambda role, shape, dtype: torch.empty(shape, dtype=dtype, device=x.device))
+    get = scratch or _fresh(x.device)
     ws = get("plda_dense_ws", (nbytes,), torch.uint8)
     status = get("plda_dense_status", (1,), torch.int32)
     lens_dev = get("plda_dense_lengths", (R,), torch.int32)
     lens_dev.copy_(torch.from_numpy(lens))
-    scores = torch.empty((int(np.sum(lens.astype(np.int64) ** 2)),), dtype=x.dtype, device=x.device)
-    dims = torch.empty((R,), dtype=torch.int32, device=x.device)
-    fn = lib.ktf_plda_dense_f64 if x.dtype == torch.float64 else lib.ktf_plda_dense_f32
-    with L.on_device(x.device):
-        rc = fn(L.ptr(x), S, dim, lens.ctypes.data_as(C.c_void_p), L.ptr(lens_dev), R, t, L.ptr(A), L.ptr(offset), L.ptr(psi),
-                L.ptr(mean64), L.ptr(Tinv64), L.ptr(psi64), int(normalize_length), int(simple_length_norm), L.ptr(scores),
-                L.ptr(dims), L.ptr(ws), ws.numel(), L.ptr(status), L.stream_ptr())
-    L.check(rc, "ktf_plda_dense")
+    scores = _new(x, int(np.sum(lens.astype(np.int64) ** 2)))
+    dims = _new(x, R, dtype=torch.int32)
+    _call(_typed("ktf_plda_dense", x), x.device, L.ptr(x), S, dim, _host_ptr(lens), L.ptr(lens_dev), R, t, L.ptr(A), L.ptr(offset),
+          L.ptr(psi), L.ptr(mean64), L.ptr(Tinv64), L.ptr(psi64), int(normalize_length), int(simple_length_norm), L.ptr(scores),
+          L.ptr(dims), L.ptr(ws), ws.numel(), L.ptr(status))
     return scores, dims, status
 
 
 def ahc_workspace_bytes(lengths, dtype_bytes):
     """Bytes of scratch ktf_ahc_* needs (lengths: host ints)."""
-    lib = L.load()
-    lens = np.ascontiguousarray(lengths, dtype=np.int32)
-    n = lib.ktf_ahc_workspace_bytes(lens.ctypes.data_as(C.c_void_p), len(lens), int(dtype_bytes))
-    if n < 0:
-        L.check(int(n), "ktf_ahc_workspace_bytes")
-    return int(n)
+    lens = _host_i32(lengths)
+    return _size("ktf_ahc_workspace_bytes", _host_ptr(lens), len(lens), int(dtype_bytes))
 
 
 def ahc(scores, lengths, threshold, min_clusters, max_spk_fraction, read_costs, scratch=None):
     """Agglomerative clustering (ktf_ahc_*) of R packed blocks: scores 1-D, the blocks lengths[r]^2 one after another (as
     plda_dense returns them), lengths host ints, min_clusters None (1) or host ints (R). -> (labels (S,) int32, counts (R,) int32).
     `scratch(role, shape, dtype)` hands out workspace tensors (a fresh allocation each call without it)."""
-    lib = L.load()
-    lens = np.ascontiguousarray(lengths, dtype=np.int32)
+    lens = _host_i32(lengths)
     R = len(lens)
     nbytes = ahc_workspace_bytes(lens, scores.element_size())
-    get = scratch or (lambda role, shape, dtype: torch.empty(shape, dtype=dtype, device=scores.device))
+    get = scratch or _fresh(scores.device)
     ws = get("ahc_ws", (nbytes,), torch.uint8)
     meta = get("ahc_lengths", (2 * R,), torch.int32)          # lengths, then min_clusters
     host = np.concatenate([lens, np.ones(R, np.int32) if min_clusters is None else np.asarray(min_clusters, np.int32)])
     meta.copy_(torch.from_numpy(host))
-    labels = torch.empty((int(lens.astype(np.int64).sum()),), dtype=torch.int32, device=scores.device)
-    counts = torch.empty((R,), dtype=torch.int32, device=scores.device)
-    fn = lib.ktf_ahc_f64 if scores.dtype == torch.float64 else lib.ktf_ahc_f32
-    with L.on_device(scores.device):
-        rc = fn(L.ptr(scores), lens.ctypes.data_as(C.c_void_p), L.ptr(meta), R, int(bool(read_costs)), float(threshold),
-                L.ptr(meta[R:]) if min_clusters is not None else None, float(max_spk_fraction), L.ptr(labels), L.ptr(counts),
-                L.ptr(ws), ws.numel(), L.stream_ptr())
-    L.check(rc, "ktf_ahc")
+    labels = _new(scores, int(lens.astype(np.int64).sum()), dtype=torch.int32)
+    counts = _new(scores, R, dtype=torch.int32)
+    _call(_typed("ktf_ahc", scores), scores.device, L.ptr(scores), _host_ptr(lens), L.ptr(meta), R, int(bool(read_costs)), float(threshold),
+          L.ptr(meta[R:]) if min_clusters is not None else None, float(max_spk_fraction), L.ptr(labels), L.ptr(counts), L.ptr(ws),
+          ws.numel())
     return labels, counts
 
 
@@ -906,107 +912,78 @@ def plda(x, A, offset, psi, normalize_length, simple_length_norm, want_scores=Tr
 
 
 # ----------------------------------------------------------------------------- sliding-window diarization front end (ktf_diar_*)
-def _host_i32(a):
-    return np.ascontiguousarray(a, dtype=np.int32)
-
-
 def diar_segments(mfcc, frames, offsets, vad_cfg, seg_work, counts):
     """Energy-VAD speech segments of R recordings laid end to end in mfcc (F, D) (ktf_diar_segments). frames: host ints (R),
     offsets: device int32 (R + 1). Writes seg_work (2F int32) and counts[:R]."""
     fr = _host_i32(frames)
-    with L.on_device(mfcc.device):
-        rc = L.load().ktf_diar_segments(L.ptr(mfcc), mfcc.shape[-1], fr.ctypes.data_as(C.c_void_p), L.ptr(offsets), len(fr),
-                                        C.byref(vad_cfg), L.ptr(seg_work), L.ptr(counts), L.stream_ptr())
-    L.check(rc, "ktf_diar_segments")
+    _call("ktf_diar_segments", mfcc.device, L.ptr(mfcc), mfcc.shape[-1], _host_ptr(fr), L.ptr(offsets), len(fr), C.byref(vad_cfg),
+          L.ptr(seg_work), L.ptr(counts))
 
 
 def diar_windows(seg_work, frames, offsets, W, P, M, win_work, counts):
     """Windows of every segment in seg_work (ktf_diar_windows): writes win_work (2F int32) and counts[R:]."""
     fr = _host_i32(frames)
-    with L.on_device(seg_work.device):
-        rc = L.load().ktf_diar_windows(L.ptr(seg_work), fr.ctypes.data_as(C.c_void_p), L.ptr(offsets), len(fr), int(W), int(P), int(M),
-                                       L.ptr(win_work), L.ptr(counts), L.stream_ptr())
-    L.check(rc, "ktf_diar_windows")
+    _call("ktf_diar_windows", seg_work.device, L.ptr(seg_work), _host_ptr(fr), L.ptr(offsets), len(fr), int(W), int(P), int(M),
+          L.ptr(win_work), L.ptr(counts))
 
 
 def diar_compact(seg_work, win_work, counts, frames, offsets, G, S):
     """-> (segments (G, 3), windows (S, 3)) int32 device tables (ktf_diar_compact)."""
     fr = _host_i32(frames)
-    dev = seg_work.device
-    segs = torch.empty((G, 3), dtype=torch.int32, device=dev)
-    wins = torch.empty((S, 3), dtype=torch.int32, device=dev)
-    with L.on_device(dev):
-        rc = L.load().ktf_diar_compact(L.ptr(seg_work), L.ptr(win_work), L.ptr(counts), fr.ctypes.data_as(C.c_void_p), L.ptr(offsets), len(fr),
-                                       int(G), int(S), L.ptr(segs), L.ptr(wins), L.stream_ptr())
-    L.check(rc, "ktf_diar_compact")
+    segs = _new(seg_work, G, 3, dtype=torch.int32)
+    wins = _new(seg_work, S, 3, dtype=torch.int32)
+    _call("ktf_diar_compact", seg_work.device, L.ptr(seg_work), L.ptr(win_work), L.ptr(counts), _host_ptr(fr), L.ptr(offsets), len(fr),
+          int(G), int(S), L.ptr(segs), L.ptr(wins))
     return segs, wins
 
 
 def diar_segment_cmn(mfcc, frames, offsets, segments, cmvn_cfg, out, work):
     """CMN of every segment's rows of mfcc (F, D) into out (F, D) at the same rows (ktf_diar_segment_cmn)."""
     fr = _host_i32(frames)
-    with L.on_device(mfcc.device):
-        rc = L.load().ktf_diar_segment_cmn(L.ptr(mfcc), mfcc.shape[-1], fr.ctypes.data_as(C.c_void_p), L.ptr(offsets), len(fr), L.ptr(segments),
-                                           segments.shape[0], C.byref(cmvn_cfg), L.ptr(out), L.ptr(work), L.stream_ptr())
-    L.check(rc, "ktf_diar_segment_cmn")
+    _call("ktf_diar_segment_cmn", mfcc.device, L.ptr(mfcc), mfcc.shape[-1], _host_ptr(fr), L.ptr(offsets), len(fr), L.ptr(segments),
+          segments.shape[0], C.byref(cmvn_cfg), L.ptr(out), L.ptr(work))
 
 
 def diar_gather(cmn, D, frames, offsets, windows, w0, n, out, lens):
     """Windows [w0, w0 + n) of the table -> out (n, Tw, ldo) float32 / bfloat16 and lens (n,) (ktf_diar_gather)."""
     fr = _host_i32(frames)
-    with L.on_device(cmn.device):
-        rc = L.load().ktf_diar_gather(L.ptr(cmn), int(D), fr.ctypes.data_as(C.c_void_p), L.ptr(offsets), len(fr), L.ptr(windows), windows.shape[0],
-                                      int(w0), int(n), out.shape[1], L.ptr(out), L.ktf_dtype(out.dtype), out.stride(1), L.ptr(lens), L.stream_ptr())
-    L.check(rc, "ktf_diar_gather")
+    _call("ktf_diar_gather", cmn.device, L.ptr(cmn), int(D), _host_ptr(fr), L.ptr(offsets), len(fr), L.ptr(windows), windows.shape[0],
+          int(w0), int(n), out.shape[1], L.ptr(out), L.ktf_dtype(out.dtype), out.stride(1), L.ptr(lens))
 
 
 def ivector_post(x, W, gconst, num_gselect, min_post):
     """gmm-global-get-post on frames x (F, D) fp32 (row stride x.stride(0)): W (2D, I), gconst (I) fp32 on the same device ->
     (gauss (F, n) int32, post (F, n) fp32), ktf_ivector_post_f32."""
-    lib = L.load()
     F, D = x.shape
     n = int(num_gselect)
-    gauss = torch.empty((F, n), dtype=torch.int32, device=x.device)
-    post = torch.empty((F, n), dtype=torch.float32, device=x.device)
-    with L.on_device(x.device):
-        rc = lib.ktf_ivector_post_f32(L.ptr(x), F, D, x.stride(0) if F else D, L.ptr(W), L.ptr(gconst), gconst.shape[0], n,
-                                      float(min_post), L.ptr(gauss), L.ptr(post), L.stream_ptr())
-    L.check(rc, "ktf_ivector_post_f32")
+    gauss = _new(x, F, n, dtype=torch.int32)
+    post = _new(x, F, n, dtype=torch.float32)
+    _call("ktf_ivector_post_f32", x.device, L.ptr(x), F, D, _ld(x), L.ptr(W), L.ptr(gconst), gconst.shape[0], n, float(min_post),
+          L.ptr(gauss), L.ptr(post))
     return gauss, post
 
 
 def ivector_workspace_bytes(B, I, D, S):
-    n = int(L.load().ktf_ivector_workspace_bytes(int(B), int(I), int(D), int(S)))
-    if n < 0:
-        L.check(n, "ktf_ivector_workspace_bytes")
-    return n
+    return _size("ktf_ivector_workspace_bytes", int(B), int(I), int(D), int(S))
 
 
 def ivector_extract(x, offsets, gauss, post, posterior_scale, acoustic_weight, max_count, sigma_inv_M, U, prior_offset,
                     dtype=torch.float32):
     """Stats, linear / quadratic terms and the solve (ktf_ivector_extract) for B = offsets.numel() - 1 utterances whose frames lie
     end to end in x (F, D). -> (B, S) i-vectors of `dtype` (float32 or float64)."""
-    lib = L.load()
     F, D = x.shape
     B = offsets.numel() - 1
     I, S = U.shape[0], sigma_inv_M.shape[1]
-    out = torch.empty((B, S), dtype=dtype, device=x.device)
-    nbytes = ivector_workspace_bytes(B, I, D, S)
-    ws = torch.empty((nbytes,), dtype=torch.uint8, device=x.device)
-    with L.on_device(x.device):
-        rc = lib.ktf_ivector_extract(L.ptr(x), F, D, x.stride(0) if F else D, L.ptr(offsets), B, L.ptr(gauss), L.ptr(post),
-                                     gauss.shape[1], float(posterior_scale), float(acoustic_weight), float(max_count), L.ptr(sigma_inv_M),
-                                     L.ptr(U), I, S, float(prior_offset), L.ptr(out), out.element_size(), L.ptr(ws), nbytes,
-                                     L.stream_ptr())
-    L.check(rc, "ktf_ivector_extract")
+    out = _new(x, B, S, dtype=dtype)
+    ws = _workspace("ktf_ivector_workspace_bytes", B, I, D, S, device=x.device)
+    _call("ktf_ivector_extract", x.device, L.ptr(x), F, D, _ld(x), L.ptr(offsets), B, L.ptr(gauss), L.ptr(post), gauss.shape[1],
+          float(posterior_scale), float(acoustic_weight), float(max_count), L.ptr(sigma_inv_M), L.ptr(U), I, S, float(prior_offset),
+          L.ptr(out), out.element_size(), L.ptr(ws), ws.numel())
     return out
 
 
 def ivector_train_workspace_bytes(B, I, D, S):
-    n = int(L.load().ktf_ivector_train_workspace_bytes(int(B), int(I), int(D), int(S)))
-    if n < 0:
-        L.check(n, "ktf_ivector_train_workspace_bytes")
-    return n
+    return _size("ktf_ivector_train_workspace_bytes", int(B), int(I), int(D), int(S))
 
 
 def ivector_acc_stats(x, offsets, gauss, post, posterior_scale, sigma_inv_M, U, prior_offset, gamma, Y, R, ivector_sum,
@@ -1014,34 +991,23 @@ def ivector_acc_stats(x, offsets, gauss, post, posterior_scale, sigma_inv_M, U, 
     """ivector-extractor-acc-stats for B = offsets.numel() - 1 utterances whose frames lie end to end in x (F, D), added in place to
     the fp64 device accumulators gamma (I), Y (I * D, S), R (I, P), ivector_sum (S), ivector_scatter (P), totals (2) =
     (num_ivectors, the sum of the utterances' marginal-likelihood scalars): ktf_ivector_acc_stats."""
-    lib = L.load()
     F, D = x.shape
     B = offsets.numel() - 1
     I, S = U.shape[0], sigma_inv_M.shape[1]
-    nbytes = ivector_train_workspace_bytes(B, I, D, S)
-    ws = torch.empty((nbytes,), dtype=torch.uint8, device=x.device)
-    with L.on_device(x.device):
-        rc = lib.ktf_ivector_acc_stats(L.ptr(x), F, D, x.stride(0) if F else D, L.ptr(offsets), B, L.ptr(gauss), L.ptr(post), gauss.shape[1],
-                                       float(posterior_scale), L.ptr(sigma_inv_M), L.ptr(U), I, S, float(prior_offset), L.ptr(gamma),
-                                       L.ptr(Y), L.ptr(R), L.ptr(ivector_sum), L.ptr(ivector_scatter), L.ptr(totals), L.ptr(ws), nbytes,
-                                       L.stream_ptr())
-    L.check(rc, "ktf_ivector_acc_stats")
+    ws = _workspace("ktf_ivector_train_workspace_bytes", B, I, D, S, device=x.device)
+    _call("ktf_ivector_acc_stats", x.device, L.ptr(x), F, D, _ld(x), L.ptr(offsets), B, L.ptr(gauss), L.ptr(post), gauss.shape[1],
+          float(posterior_scale), L.ptr(sigma_inv_M), L.ptr(U), I, S, float(prior_offset), L.ptr(gamma), L.ptr(Y), L.ptr(R),
+          L.ptr(ivector_sum), L.ptr(ivector_scatter), L.ptr(totals), L.ptr(ws), ws.numel())
 
 
 def ivector_acc_second_order(x, gauss, post, posterior_scale, Ssec):
     """Ssec (I, D, D) fp64 += sum_t p'_ti x_t x_t^T over the frames x (F, D) and their slots gauss / post (F, n), bit-identical run
     to run: ktf_ivector_acc_second_order."""
-    lib = L.load()
     F, D = x.shape
     I, n = Ssec.shape[0], gauss.shape[1]
-    nbytes = int(lib.ktf_ivector_acc2_workspace_bytes(F, I, n))
-    if nbytes < 0:
-        L.check(nbytes, "ktf_ivector_acc2_workspace_bytes")
-    ws = torch.empty((nbytes,), dtype=torch.uint8, device=x.device)
-    with L.on_device(x.device):
-        rc = lib.ktf_ivector_acc_second_order(L.ptr(x), F, D, x.stride(0) if F else D, L.ptr(gauss), L.ptr(post), n, float(posterior_scale),
-                                              I, L.ptr(Ssec), L.ptr(ws), nbytes, L.stream_ptr())
-    L.check(rc, "ktf_ivector_acc_second_order")
+    ws = _workspace("ktf_ivector_acc2_workspace_bytes", F, I, n, device=x.device)
+    _call("ktf_ivector_acc_second_order", x.device, L.ptr(x), F, D, _ld(x), L.ptr(gauss), L.ptr(post), n, float(posterior_scale), I,
+          L.ptr(Ssec), L.ptr(ws), ws.numel())
 
 
 def atb_f64(A, B, C):
@@ -1050,55 +1016,40 @@ def atb_f64(A, B, C):
     N = B.shape[1]
     if B.shape[0] != K or tuple(C.shape) != (M, N) or any(t.dtype != torch.float64 or (t.numel() and t.stride(1) != 1) for t in (A, B, C)):
         raise ValueError("atb_f64: need fp64 A (K, M), B (K, N), C (M, N) with unit inner strides")
-    with L.on_device(C.device):
-        rc = L.load().ktf_atb_f64(L.ptr(A), A.stride(0) if K else M, L.ptr(B), B.stride(0) if K else N, L.ptr(C), C.stride(0), M, N, K,
-                                  L.stream_ptr())
-    L.check(rc, "ktf_atb_f64")
+    _call("ktf_atb_f64", C.device, L.ptr(A), _ld(A), L.ptr(B), _ld(B), L.ptr(C), C.stride(0), M, N, K)
     return C
 
 
 def fgmm_workspace_bytes(F, I, D, n):
-    b = int(L.load().ktf_fgmm_workspace_bytes(int(F), int(I), int(D), int(n)))
-    if b < 0:
-        L.check(b, "ktf_fgmm_workspace_bytes")
-    return b
+    return _size("ktf_fgmm_workspace_bytes", int(F), int(I), int(D), int(n))
 
 
 def fgmm_post(x, gselect, means_invcovars, inv_covars, gconst, min_post):
     """fgmm-global-gselect-to-post on frames x (F, D) fp32 (row stride x.stride(0)) and the lists gselect (F, n) int32 (entries
     outside [0, I) skipped): means_invcovars (I, D), inv_covars (I, D, D) full symmetric, gconst (I), fp32 on the same device ->
     (gauss (F, n) int32, post (F, n) fp32), ktf_fgmm_post_f32."""
-    lib = L.load()
     F, D = x.shape
     n = gselect.shape[1]
     I = gconst.shape[0]
-    gauss = torch.empty((F, n), dtype=torch.int32, device=x.device)
-    post = torch.empty((F, n), dtype=torch.float32, device=x.device)
-    nbytes = fgmm_workspace_bytes(F, I, D, n)
-    ws = torch.empty((nbytes,), dtype=torch.uint8, device=x.device)
-    with L.on_device(x.device):
-        rc = lib.ktf_fgmm_post_f32(L.ptr(x), F, D, x.stride(0) if F else D, L.ptr(gselect), n, L.ptr(means_invcovars), L.ptr(inv_covars),
-                                   L.ptr(gconst), I, float(min_post), L.ptr(gauss), L.ptr(post), L.ptr(ws), nbytes, L.stream_ptr())
-    L.check(rc, "ktf_fgmm_post_f32")
+    gauss = _new(x, F, n, dtype=torch.int32)
+    post = _new(x, F, n, dtype=torch.float32)
+    ws = _workspace("ktf_fgmm_workspace_bytes", F, I, D, n, device=x.device)
+    _call("ktf_fgmm_post_f32", x.device, L.ptr(x), F, D, _ld(x), L.ptr(gselect), n, L.ptr(means_invcovars), L.ptr(inv_covars),
+          L.ptr(gconst), I, float(min_post), L.ptr(gauss), L.ptr(post), L.ptr(ws), ws.numel())
     return gauss, post
 
 
 def fgmm_post_ll(x, gselect, means_invcovars, inv_covars, gconst, min_post, want_loglike=True):
     """fgmm_post with the frames' log-likelihoods (before pruning) -> (gauss, post, loglike (F) fp32 or None): ktf_fgmm_post_ll_f32."""
-    lib = L.load()
     F, D = x.shape
     n = gselect.shape[1]
     I = gconst.shape[0]
-    gauss = torch.empty((F, n), dtype=torch.int32, device=x.device)
-    post = torch.empty((F, n), dtype=torch.float32, device=x.device)
-    ll = torch.empty((F,), dtype=torch.float32, device=x.device) if want_loglike else None
-    nbytes = fgmm_workspace_bytes(F, I, D, n)
-    ws = torch.empty((nbytes,), dtype=torch.uint8, device=x.device)
-    with L.on_device(x.device):
-        rc = lib.ktf_fgmm_post_ll_f32(L.ptr(x), F, D, x.stride(0) if F else D, L.ptr(gselect), n, L.ptr(means_invcovars), L.ptr(inv_covars),
-                                      L.ptr(gconst), I, float(min_post), L.ptr(gauss), L.ptr(post), L.ptr(ll), L.ptr(ws), nbytes,
-                                      L.stream_ptr())
-    L.check(rc, "ktf_fgmm_post_ll_f32")
+    gauss = _new(x, F, n, dtype=torch.int32)
+    post = _new(x, F, n, dtype=torch.float32)
+    ll = _new(x, F, dtype=torch.float32) if want_loglike else None
+    ws = _workspace("ktf_fgmm_workspace_bytes", F, I, D, n, device=x.device)
+    _call("ktf_fgmm_post_ll_f32", x.device, L.ptr(x), F, D, _ld(x), L.ptr(gselect), n, L.ptr(means_invcovars), L.ptr(inv_covars),
+          L.ptr(gconst), I, float(min_post), L.ptr(gauss), L.ptr(post), L.ptr(ll), L.ptr(ws), ws.numel())
     return gauss, post, ll
 
 
@@ -1108,21 +1059,15 @@ def gmm_post_preselect(x, gselect, means_invvars, inv_vars, gconst, valid=None):
     list's slot order, loglike (F) fp32); `valid` (1,) int32 on the device is increased by the frames with a non-empty list."""
     F, D = x.shape
     n = gselect.shape[1]
-    post = torch.empty((F, n), dtype=torch.float32, device=x.device)
-    ll = torch.empty((F,), dtype=torch.float32, device=x.device)
-    with L.on_device(x.device):
-        rc = L.load().ktf_gmm_post_preselect_f32(L.ptr(x), F, D, x.stride(0) if F else D, L.ptr(gselect), n, L.ptr(means_invvars),
-                                                 L.ptr(inv_vars), L.ptr(gconst), gconst.shape[0], L.ptr(post), L.ptr(ll), L.ptr(valid),
-                                                 L.stream_ptr())
-    L.check(rc, "ktf_gmm_post_preselect_f32")
+    post = _new(x, F, n, dtype=torch.float32)
+    ll = _new(x, F, dtype=torch.float32)
+    _call("ktf_gmm_post_preselect_f32", x.device, L.ptr(x), F, D, _ld(x), L.ptr(gselect), n, L.ptr(means_invvars), L.ptr(inv_vars),
+          L.ptr(gconst), gconst.shape[0], L.ptr(post), L.ptr(ll), L.ptr(valid))
     return post, ll
 
 
 def gmm_post_dense_workspace_bytes(F, I):
-    b = int(L.load().ktf_gmm_post_dense_workspace_bytes(int(F), int(I)))
-    if b < 0:
-        L.check(b, "ktf_gmm_post_dense_workspace_bytes")
-    return b
+    return _size("ktf_gmm_post_dense_workspace_bytes", int(F), int(I))
 
 
 def gmm_post_dense(x, W, gconst):
@@ -1130,23 +1075,17 @@ def gmm_post_dense(x, W, gconst):
     (P (F, I) fp64, Xaug (F, 2D + 1) fp64 = [1, x, x^2], loglike (F) fp32): ktf_gmm_post_dense_f32."""
     F, D = x.shape
     I = gconst.shape[0]
-    P = torch.empty((F, I), dtype=torch.float64, device=x.device)
-    Xaug = torch.empty((F, 2 * D + 1), dtype=torch.float64, device=x.device)
-    ll = torch.empty((F,), dtype=torch.float32, device=x.device)
-    nbytes = gmm_post_dense_workspace_bytes(F, I)
-    ws = torch.empty((nbytes,), dtype=torch.uint8, device=x.device)
-    with L.on_device(x.device):
-        rc = L.load().ktf_gmm_post_dense_f32(L.ptr(x), F, D, x.stride(0) if F else D, L.ptr(W), L.ptr(gconst), I, L.ptr(P), L.ptr(Xaug),
-                                             L.ptr(ll), L.ptr(ws), nbytes, L.stream_ptr())
-    L.check(rc, "ktf_gmm_post_dense_f32")
+    P = _new(x, F, I, dtype=torch.float64)
+    Xaug = _new(x, F, 2 * D + 1, dtype=torch.float64)
+    ll = _new(x, F, dtype=torch.float32)
+    ws = _workspace("ktf_gmm_post_dense_workspace_bytes", F, I, device=x.device)
+    _call("ktf_gmm_post_dense_f32", x.device, L.ptr(x), F, D, _ld(x), L.ptr(W), L.ptr(gconst), I, L.ptr(P), L.ptr(Xaug), L.ptr(ll),
+          L.ptr(ws), ws.numel())
     return P, Xaug, ll
 
 
 def gmm_acc_workspace_bytes(F, I, D, n, full):
-    b = int(L.load().ktf_gmm_acc_workspace_bytes(int(F), int(I), int(D), int(n), int(bool(full))))
-    if b < 0:
-        L.check(b, "ktf_gmm_acc_workspace_bytes")
-    return b
+    return _size("ktf_gmm_acc_workspace_bytes", int(F), int(I), int(D), int(n), int(bool(full)))
 
 
 def gmm_acc(x, gauss, post, occ, mean_acc, second_acc):
@@ -1161,56 +1100,41 @@ def gmm_acc(x, gauss, post, occ, mean_acc, second_acc):
             gauss.dtype != torch.int32 or post.dtype != torch.float32 or not gauss.is_contiguous() or not post.is_contiguous():
         raise ValueError("gmm_acc: need gauss int32 / post fp32 (F, n) and contiguous fp64 occ (I), mean_acc (I, D), "
                          "second_acc (I, D) or (I, D, D)")
-    nbytes = gmm_acc_workspace_bytes(F, I, D, n, full)
-    ws = torch.empty((nbytes,), dtype=torch.uint8, device=x.device)
-    with L.on_device(x.device):
-        rc = L.load().ktf_gmm_acc_f64(L.ptr(x), F, D, x.stride(0) if F else D, L.ptr(gauss), L.ptr(post), n, I, int(full), L.ptr(occ),
-                                      L.ptr(mean_acc), L.ptr(second_acc), L.ptr(ws), nbytes, L.stream_ptr())
-    L.check(rc, "ktf_gmm_acc_f64")
+    ws = _workspace("ktf_gmm_acc_workspace_bytes", F, I, D, n, int(full), device=x.device)
+    _call("ktf_gmm_acc_f64", x.device, L.ptr(x), F, D, _ld(x), L.ptr(gauss), L.ptr(post), n, I, int(full), L.ptr(occ), L.ptr(mean_acc),
+          L.ptr(second_acc), L.ptr(ws), ws.numel())
 
 
 def add_deltas(x, lengths, coeffs, order, window):
     """add-deltas on x (B, T, D) fp32 with a unit inner stride; lengths (B,) int32 on the device or None; coeffs (order + 1,
     2 * order * window + 1) fp32 on the device -> (B, T, D * (order + 1)) fp32, ktf_add_deltas_f32."""
     B, T, D = x.shape
-    out = torch.empty((B, T, D * (order + 1)), dtype=torch.float32, device=x.device)
-    with L.on_device(x.device):
-        rc = L.load().ktf_add_deltas_f32(L.ptr(x), B, T, D, x.stride(0) if B > 1 else T * max(x.stride(1), D),
-                                         x.stride(1) if T > 1 else D, L.ptr(lengths), L.ptr(coeffs), int(order), int(window), L.ptr(out),
-                                         L.stream_ptr())
-    L.check(rc, "ktf_add_deltas_f32")
+    out = _new(x, B, T, D * (order + 1), dtype=torch.float32)
+    _call("ktf_add_deltas_f32", x.device, L.ptr(x), B, T, D, x.stride(0) if B > 1 else T * max(x.stride(1), D),
+          x.stride(1) if T > 1 else D, L.ptr(lengths), L.ptr(coeffs), int(order), int(window), L.ptr(out))
     return out
 
 
 # ----------------------------------------------------------------------------- back-end training (ktf_train_*, ktf_plda_em_project)
 def train_workspace(rows, D, device):
     """A uint8 device buffer for ktf_train_mean_* / ktf_train_gram_* over up to `rows` rows of dimension D."""
-    n = int(L.load().ktf_train_workspace_bytes(int(rows), int(D)))
-    if n < 0:
-        L.check(n, "ktf_train_workspace_bytes")
-    return torch.empty((n,), dtype=torch.uint8, device=device)
+    return _workspace("ktf_train_workspace_bytes", int(rows), int(D), device=device)
 
 
 def train_class_means(x, offsets, utts, S):
     """x (N, D) fp32, the CSR map offsets (S + 1) / utts on the device (int32) -> (means (S, D) fp64, counts (S,) int32)."""
     N, D = x.shape
-    means = torch.empty((S, D), dtype=torch.float64, device=x.device)
-    counts = torch.empty((S,), dtype=torch.int32, device=x.device)
-    with L.on_device(x.device):
-        rc = L.load().ktf_train_class_means(L.ptr(x), N, D, L.ptr(offsets), S, L.ptr(utts), utts.numel(), L.ptr(means), L.ptr(counts),
-                                            L.stream_ptr())
-    L.check(rc, "ktf_train_class_means")
+    means = _new(x, S, D, dtype=torch.float64)
+    counts = _new(x, S, dtype=torch.int32)
+    _call("ktf_train_class_means", x.device, L.ptr(x), N, D, L.ptr(offsets), S, L.ptr(utts), utts.numel(), L.ptr(means), L.ptr(counts))
     return means, counts
 
 
 def train_mean(y, ws):
     """Column means (D,) fp64 of y (rows, D) fp32 or fp64."""
     rows, D = y.shape
-    out = torch.empty((D,), dtype=torch.float64, device=y.device)
-    fn = L.load().ktf_train_mean_f64 if y.dtype == torch.float64 else L.load().ktf_train_mean_f32
-    with L.on_device(y.device):
-        rc = fn(L.ptr(y), rows, D, L.ptr(out), L.ptr(ws), ws.numel(), L.stream_ptr())
-    L.check(rc, "ktf_train_mean")
+    out = _new(y, D, dtype=torch.float64)
+    _call(_typed("ktf_train_mean", y), y.device, L.ptr(y), rows, D, L.ptr(out), L.ptr(ws), ws.numel())
     return out
 
 
@@ -1219,11 +1143,9 @@ def train_gram(y, ws, idx=None, center=None, weights=None):
     (one per listed row) device fp64 or None."""
     N, D = y.shape
     rows = idx.numel() if idx is not None else N
-    G = torch.empty((D, D), dtype=torch.float64, device=y.device)
-    fn = L.load().ktf_train_gram_f64 if y.dtype == torch.float64 else L.load().ktf_train_gram_f32
-    with L.on_device(y.device):
-        rc = fn(L.ptr(y), N, D, L.ptr(idx), rows, L.ptr(center), L.ptr(weights), L.ptr(G), L.ptr(ws), ws.numel(), L.stream_ptr())
-    L.check(rc, "ktf_train_gram")
+    G = _new(y, D, D, dtype=torch.float64)
+    _call(_typed("ktf_train_gram", y), y.device, L.ptr(y), N, D, L.ptr(idx), rows, L.ptr(center), L.ptr(weights), L.ptr(G), L.ptr(ws),
+          ws.numel())
     return G
 
 
@@ -1232,58 +1154,38 @@ def plda_em_project(mu, mbar, P, lam, counts):
     S, D = mu.shape
     a = torch.empty_like(mu)
     b = torch.empty_like(mu)
-    with L.on_device(mu.device):
-        rc = L.load().ktf_plda_em_project(L.ptr(mu), S, D, L.ptr(mbar), L.ptr(P), L.ptr(lam), L.ptr(counts), L.ptr(a), L.ptr(b),
-                                          L.stream_ptr())
-    L.check(rc, "ktf_plda_em_project")
+    _call("ktf_plda_em_project", mu.device, L.ptr(mu), S, D, L.ptr(mbar), L.ptr(P), L.ptr(lam), L.ptr(counts), L.ptr(a), L.ptr(b))
     return a, b
 
 
 # ----------------------------------------------------------------------------- VB-HMM resegmentation (ktf_vb_*)
-def _vb_ws(fn, name, *args, device):
-    n = int(fn(*args))
-    if n < 0:
-        L.check(n, name)
-    return torch.empty((n,), dtype=torch.uint8, device=device), n
-
-
 def vb_post_workspace_bytes(F, I):
-    n = int(L.load().ktf_vb_post_workspace_bytes(int(F), int(I)))
-    if n < 0:
-        L.check(n, "ktf_vb_post_workspace_bytes")
-    return n
+    return _size("ktf_vb_post_workspace_bytes", int(F), int(I))
 
 
 def vb_post(x, W, gconst, num_slots, ll_scale, stat_scale, sparsity_thr, truncated):
     """Thresholded posteriors over all Gaussians on frames x (F, D) fp32: W (2D, I), gconst (I) as ivector_post takes them ->
     (gauss (F, n) int32, post (F, n) fp32, loglike (F) fp32); `truncated` (1,) int32 on the device is increased by the frames with
     more than n candidates: ktf_vb_post_f32."""
-    lib = L.load()
     F, D = x.shape
     n, I = int(num_slots), gconst.shape[0]
-    gauss = torch.empty((F, n), dtype=torch.int32, device=x.device)
-    post = torch.empty((F, n), dtype=torch.float32, device=x.device)
-    ll = torch.empty((F,), dtype=torch.float32, device=x.device)
-    ws, nbytes = _vb_ws(lib.ktf_vb_post_workspace_bytes, "ktf_vb_post_workspace_bytes", F, I, device=x.device)
-    with L.on_device(x.device):
-        rc = lib.ktf_vb_post_f32(L.ptr(x), F, D, x.stride(0) if F else D, L.ptr(W), L.ptr(gconst), I, n, float(ll_scale), float(stat_scale),
-                                 float(sparsity_thr), L.ptr(gauss), L.ptr(post), L.ptr(ll), L.ptr(truncated), L.ptr(ws), nbytes,
-                                 L.stream_ptr())
-    L.check(rc, "ktf_vb_post_f32")
+    gauss = _new(x, F, n, dtype=torch.int32)
+    post = _new(x, F, n, dtype=torch.float32)
+    ll = _new(x, F, dtype=torch.float32)
+    ws = _workspace("ktf_vb_post_workspace_bytes", F, I, device=x.device)
+    _call("ktf_vb_post_f32", x.device, L.ptr(x), F, D, _ld(x), L.ptr(W), L.ptr(gconst), I, n, float(ll_scale), float(stat_scale),
+          float(sparsity_thr), L.ptr(gauss), L.ptr(post), L.ptr(ll), L.ptr(truncated), L.ptr(ws), ws.numel())
     return gauss, post, ll
 
 
 def vb_bucket(gauss, I):
     """The (frame, slot) pairs of gauss (F, n) int32 bucketed by Gaussian in ascending pair order -> (start (I + 1), pairs (F n))
     int32: ktf_vb_bucket."""
-    lib = L.load()
     F, n = gauss.shape
-    start = torch.empty((I + 1,), dtype=torch.int32, device=gauss.device)
-    pairs = torch.empty((F * n,), dtype=torch.int32, device=gauss.device)
-    ws, nbytes = _vb_ws(lib.ktf_vb_bucket_workspace_bytes, "ktf_vb_bucket_workspace_bytes", F, I, n, device=gauss.device)
-    with L.on_device(gauss.device):
-        rc = lib.ktf_vb_bucket(L.ptr(gauss), F, n, I, L.ptr(start), L.ptr(pairs), L.ptr(ws), nbytes, L.stream_ptr())
-    L.check(rc, "ktf_vb_bucket")
+    start = _new(gauss, I + 1, dtype=torch.int32)
+    pairs = _new(gauss, F * n, dtype=torch.int32)
+    ws = _workspace("ktf_vb_bucket_workspace_bytes", F, I, n, device=gauss.device)
+    _call("ktf_vb_bucket", gauss.device, L.ptr(gauss), F, n, I, L.ptr(start), L.ptr(pairs), L.ptr(ws), ws.numel())
     return start, pairs
 
 
@@ -1292,32 +1194,25 @@ def vb_speaker_stats(x, offsets, boffsets, downsample, post, start, pairs, means
     Fst (N K, I D)) fp64: ktf_vb_speaker_stats."""
     F, D = x.shape
     N, (TB, K), I = offsets.numel() - 1, q.shape, means.shape[0]
-    Nst = torch.empty((N * K, I), dtype=torch.float64, device=x.device)
-    Fst = torch.empty((N * K, I * D), dtype=torch.float64, device=x.device)
-    with L.on_device(x.device):
-        rc = L.load().ktf_vb_speaker_stats(L.ptr(x), F, D, x.stride(0) if F else D, L.ptr(offsets), L.ptr(boffsets), N, TB, int(downsample),
-                                           L.ptr(post), post.shape[1], L.ptr(start), L.ptr(pairs), I, L.ptr(means), L.ptr(q), K, L.ptr(Nst),
-                                           L.ptr(Fst), L.stream_ptr())
-    L.check(rc, "ktf_vb_speaker_stats")
+    Nst = _new(x, N * K, I, dtype=torch.float64)
+    Fst = _new(x, N * K, I * D, dtype=torch.float64)
+    _call("ktf_vb_speaker_stats", x.device, L.ptr(x), F, D, _ld(x), L.ptr(offsets), L.ptr(boffsets), N, TB, int(downsample), L.ptr(post),
+          post.shape[1], L.ptr(start), L.ptr(pairs), I, L.ptr(means), L.ptr(q), K, L.ptr(Nst), L.ptr(Fst))
     return Nst, Fst
 
 
 def vb_speaker_update(Nst, Fst, Bm, U):
     """Nst (B, I), Fst (B, I D), Bm (I D, R), U (I, P) fp64 -> a (B, R), W (B, P) packed, kl (B), h (B, I D), g (B, I):
     ktf_vb_speaker_update."""
-    lib = L.load()
     B, I = Nst.shape
     R = Bm.shape[1]
     D = Bm.shape[0] // I
     P = R * (R + 1) // 2
-    dev = Nst.device
-    f = lambda *s: torch.empty(s, dtype=torch.float64, device=dev)  # noqa: E731
+    f = lambda *s: _new(Nst, *s, dtype=torch.float64)  # noqa: E731
     a, Wp, kl, h, g = f(B, R), f(B, P), f(B), f(B, I * D), f(B, I)
-    ws, nbytes = _vb_ws(lib.ktf_vb_update_workspace_bytes, "ktf_vb_update_workspace_bytes", B, I, D, R, device=dev)
-    with L.on_device(dev):
-        rc = lib.ktf_vb_speaker_update(L.ptr(Nst), L.ptr(Fst), B, I, D, R, L.ptr(Bm), L.ptr(U), L.ptr(a), L.ptr(Wp), L.ptr(kl), L.ptr(h),
-                                       L.ptr(g), L.ptr(ws), nbytes, L.stream_ptr())
-    L.check(rc, "ktf_vb_speaker_update")
+    ws = _workspace("ktf_vb_update_workspace_bytes", B, I, D, R, device=Nst.device)
+    _call("ktf_vb_speaker_update", Nst.device, L.ptr(Nst), L.ptr(Fst), B, I, D, R, L.ptr(Bm), L.ptr(U), L.ptr(a), L.ptr(Wp), L.ptr(kl),
+          L.ptr(h), L.ptr(g), L.ptr(ws), ws.numel())
     return a, Wp, kl, h, g
 
 
@@ -1325,67 +1220,46 @@ def vb_block_loglike(x, offsets, boffsets, downsample, TB, gauss, post, means, h
     """lls (TB, K) fp64 of the blocks: ktf_vb_block_loglike."""
     F, D = x.shape
     N, I = offsets.numel() - 1, means.shape[0]
-    lls = torch.empty((TB, K), dtype=torch.float64, device=x.device)
-    with L.on_device(x.device):
-        rc = L.load().ktf_vb_block_loglike(L.ptr(x), F, D, x.stride(0) if F else D, L.ptr(offsets), L.ptr(boffsets), N, TB, int(downsample),
-                                           L.ptr(gauss), L.ptr(post), gauss.shape[1], I, L.ptr(means), L.ptr(h), L.ptr(g), int(K), L.ptr(lls),
-                                           L.stream_ptr())
-    L.check(rc, "ktf_vb_block_loglike")
+    lls = _new(x, TB, K, dtype=torch.float64)
+    _call("ktf_vb_block_loglike", x.device, L.ptr(x), F, D, _ld(x), L.ptr(offsets), L.ptr(boffsets), N, TB, int(downsample), L.ptr(gauss),
+          L.ptr(post), gauss.shape[1], I, L.ptr(means), L.ptr(h), L.ptr(g), int(K), L.ptr(lls))
     return lls
+
+
+def _forward_backward(name, size, lls, boffsets, sp, loop_prob):
+    TB, K = lls.shape
+    N = boffsets.numel() - 1
+    q, sp_out, tll = _new(lls, TB, K, dtype=torch.float64), _new(lls, N, K, dtype=torch.float64), _new(lls, N, dtype=torch.float64)
+    ws = _workspace(size, TB, N, device=lls.device)
+    _call(name, lls.device, L.ptr(lls), L.ptr(boffsets), N, TB, K, L.ptr(sp), float(loop_prob), L.ptr(q), L.ptr(sp_out), L.ptr(tll),
+          L.ptr(ws), ws.numel())
+    return q, sp_out, tll
 
 
 def vb_forward_backward(lls, boffsets, sp, loop_prob):
     """lls (TB, K), sp (N, K) fp64, boffsets (N + 1) int32 -> (q (TB, K), sp_out (N, K), tll (N)) fp64: ktf_vb_forward_backward."""
-    lib = L.load()
-    TB, K = lls.shape
-    N = boffsets.numel() - 1
-    dev = lls.device
-    q = torch.empty((TB, K), dtype=torch.float64, device=dev)
-    sp_out = torch.empty((N, K), dtype=torch.float64, device=dev)
-    tll = torch.empty((N,), dtype=torch.float64, device=dev)
-    ws, nbytes = _vb_ws(lib.ktf_vb_fb_workspace_bytes, "ktf_vb_fb_workspace_bytes", TB, N, device=dev)
-    with L.on_device(dev):
-        rc = lib.ktf_vb_forward_backward(L.ptr(lls), L.ptr(boffsets), N, TB, K, L.ptr(sp), float(loop_prob), L.ptr(q), L.ptr(sp_out),
-                                         L.ptr(tll), L.ptr(ws), nbytes, L.stream_ptr())
-    L.check(rc, "ktf_vb_forward_backward")
-    return q, sp_out, tll
+    return _forward_backward("ktf_vb_forward_backward", "ktf_vb_fb_workspace_bytes", lls, boffsets, sp, loop_prob)
 
 
 def vb_forward_backward_serial(lls, boffsets, sp, loop_prob):
     """The forward-backward in its serial form (one wave per recording walks every block), for tools/bench_vb.py to time the chunked
     scan against; the package itself never calls it. Arguments and results as vb_forward_backward: ktf_vb_forward_backward_serial."""
-    lib = L.load()
-    TB, K = lls.shape
-    N = boffsets.numel() - 1
-    dev = lls.device
-    q = torch.empty((TB, K), dtype=torch.float64, device=dev)
-    sp_out = torch.empty((N, K), dtype=torch.float64, device=dev)
-    tll = torch.empty((N,), dtype=torch.float64, device=dev)
-    ws, nbytes = _vb_ws(lib.ktf_vb_fb_serial_workspace_bytes, "ktf_vb_fb_serial_workspace_bytes", TB, N, device=dev)
-    with L.on_device(dev):
-        rc = lib.ktf_vb_forward_backward_serial(L.ptr(lls), L.ptr(boffsets), N, TB, K, L.ptr(sp), float(loop_prob), L.ptr(q), L.ptr(sp_out),
-                                                L.ptr(tll), L.ptr(ws), nbytes, L.stream_ptr())
-    L.check(rc, "ktf_vb_forward_backward_serial")
-    return q, sp_out, tll
+    return _forward_backward("ktf_vb_forward_backward_serial", "ktf_vb_fb_serial_workspace_bytes", lls, boffsets, sp, loop_prob)
 
 
 def vb_loglike_sums(loglike, offsets):
     """gsum (N) fp64 = each recording's sum of loglike (F) fp32 in a fixed order of its own: ktf_vb_loglike_sums."""
     N = offsets.numel() - 1
-    gsum = torch.empty((N,), dtype=torch.float64, device=loglike.device)
-    with L.on_device(loglike.device):
-        rc = L.load().ktf_vb_loglike_sums(L.ptr(loglike), L.ptr(offsets), N, loglike.shape[0], L.ptr(gsum), L.stream_ptr())
-    L.check(rc, "ktf_vb_loglike_sums")
+    gsum = _new(loglike, N, dtype=torch.float64)
+    _call("ktf_vb_loglike_sums", loglike.device, L.ptr(loglike), L.ptr(offsets), N, loglike.shape[0], L.ptr(gsum))
     return gsum
 
 
 def vb_bound(gsum, tll, kl, stat_scale):
     """bound (N) fp64 = stat_scale gsum + tll + the recording's K entries of kl (N K) added in order: ktf_vb_bound."""
     N = gsum.shape[0]
-    bound = torch.empty((N,), dtype=torch.float64, device=gsum.device)
-    with L.on_device(gsum.device):
-        rc = L.load().ktf_vb_bound(L.ptr(gsum), L.ptr(tll), L.ptr(kl), N, kl.numel() // N, float(stat_scale), L.ptr(bound), L.stream_ptr())
-    L.check(rc, "ktf_vb_bound")
+    bound = _new(gsum, N, dtype=torch.float64)
+    _call("ktf_vb_bound", gsum.device, L.ptr(gsum), L.ptr(tll), L.ptr(kl), N, kl.numel() // N, float(stat_scale), L.ptr(bound))
     return bound
 
 
@@ -1393,29 +1267,24 @@ def vb_bound(gsum, tll, kl, stat_scale):
 def vbx_prepare(x, phi):
     """x (TB, D), phi (D) fp64 -> (rho (TB, D) = x sqrt(phi), G (TB) = -(sum_d x^2 + D log 2 pi) / 2): ktf_vbx_prepare."""
     TB, D = x.shape
-    rho = torch.empty((TB, D), dtype=torch.float64, device=x.device)
-    G = torch.empty((TB,), dtype=torch.float64, device=x.device)
-    with L.on_device(x.device):
-        rc = L.load().ktf_vbx_prepare(L.ptr(x), TB, D, L.ptr(phi), L.ptr(rho), L.ptr(G), L.stream_ptr())
-    L.check(rc, "ktf_vbx_prepare")
+    rho = _new(x, TB, D, dtype=torch.float64)
+    G = _new(x, TB, dtype=torch.float64)
+    _call("ktf_vbx_prepare", x.device, L.ptr(x), TB, D, L.ptr(phi), L.ptr(rho), L.ptr(G))
     return rho, G
 
 
 def vbx_speaker_update(gamma, rho, phi, fa_over_fb, offsets):
     """gamma (TB, K), rho (TB, D), phi (D) fp64, offsets (N + 1) int32 -> (alpha (N, K, D), invL (N, K, D), c (N, K), kl (N, K)); the
     rows of alpha and invL of a recording without windows are zero: ktf_vbx_speaker_update."""
-    lib = L.load()
     (TB, K), D, N = gamma.shape, rho.shape[1], offsets.numel() - 1
     dev = gamma.device
     alpha = torch.zeros((N, K, D), dtype=torch.float64, device=dev)
     invL = torch.zeros((N, K, D), dtype=torch.float64, device=dev)
-    c = torch.empty((N, K), dtype=torch.float64, device=dev)
-    kl = torch.empty((N, K), dtype=torch.float64, device=dev)
-    ws, nbytes = _vb_ws(lib.ktf_vbx_update_workspace_bytes, "ktf_vbx_update_workspace_bytes", TB, N, D, device=dev)
-    with L.on_device(dev):
-        rc = lib.ktf_vbx_speaker_update(L.ptr(gamma), L.ptr(rho), TB, D, K, L.ptr(offsets), N, L.ptr(phi), float(fa_over_fb), L.ptr(alpha),
-                                        L.ptr(invL), L.ptr(c), L.ptr(kl), L.ptr(ws), nbytes, L.stream_ptr())
-    L.check(rc, "ktf_vbx_speaker_update")
+    c = _new(gamma, N, K, dtype=torch.float64)
+    kl = _new(gamma, N, K, dtype=torch.float64)
+    ws = _workspace("ktf_vbx_update_workspace_bytes", TB, N, D, device=dev)
+    _call("ktf_vbx_speaker_update", dev, L.ptr(gamma), L.ptr(rho), TB, D, K, L.ptr(offsets), N, L.ptr(phi), float(fa_over_fb), L.ptr(alpha),
+          L.ptr(invL), L.ptr(c), L.ptr(kl), L.ptr(ws), ws.numel())
     return alpha, invL, c, kl
 
 
@@ -1423,9 +1292,6 @@ def vbx_loglike(rho, G, alpha, c, Fa, offsets):
     """lls (TB, K) fp64 = Fa (rho alpha^T - c + G) per recording: ktf_vbx_loglike."""
     TB, D = rho.shape
     N, K = c.shape
-    lls = torch.empty((TB, K), dtype=torch.float64, device=rho.device)
-    with L.on_device(rho.device):
-        rc = L.load().ktf_vbx_loglike(L.ptr(rho), L.ptr(G), TB, D, K, L.ptr(offsets), N, L.ptr(alpha), L.ptr(c), float(Fa), L.ptr(lls),
-                                      L.stream_ptr())
-    L.check(rc, "ktf_vbx_loglike")
+    lls = _new(rho, TB, K, dtype=torch.float64)
+    _call("ktf_vbx_loglike", rho.device, L.ptr(rho), L.ptr(G), TB, D, K, L.ptr(offsets), N, L.ptr(alpha), L.ptr(c), float(Fa), L.ptr(lls))
     return lls

@@ -17,6 +17,7 @@ import torch
 
 from . import _lib as L
 from . import ops
+from ._host import chunks, max_under, per_device
 from .verification import _checked_map
 
 
@@ -392,12 +393,9 @@ def _gmm_frames(feats, D, lengths, mask):
 
 
 def _device_consts(gmm, device, make):
-    """The model's device arrays, uploaded once per model object and device."""
-    cache = gmm.__dict__.setdefault("_deviceConsts", {})
-    key = str(torch.device(device))
-    if key not in cache:
-        cache[key] = tuple(torch.as_tensor(np.ascontiguousarray(a), device=device) for a in make())
-    return cache[key]
+    """The model's device arrays, uploaded once per model object and device (a device given as a string is normalised first)."""
+    return per_device(gmm, torch.device(device),
+                      lambda: tuple(torch.as_tensor(np.ascontiguousarray(a), device=device) for a in make()))
 
 
 def _diag_consts(d, device):
@@ -414,16 +412,7 @@ def _full_consts(g, device):
 
 def _max_frames(nbytes, limit, n):
     """The most frames F (F * n < 2^31, at least one) for which nbytes(F) <= limit."""
-    lo, hi = 1, ((1 << 31) - 1) // max(int(n), 1)
-    if nbytes(hi) <= limit:
-        return hi
-    while hi - lo > 1:
-        mid = (lo + hi) // 2
-        if nbytes(mid) <= limit:
-            lo = mid
-        else:
-            hi = mid
-    return lo
+    return max_under(nbytes, limit, ((1 << 31) - 1) // max(int(n), 1))
 
 
 def select_gaussians(dubm, feats, n, lengths=None, mask=None):
@@ -535,18 +524,17 @@ def acc_diag_gmm(stats, gmm, feats, gselect=None, lengths=None, mask=None, works
         return 0
     stats._alloc(x.device)
     W, gc, mi, iv = _diag_consts(d, x.device)
-    chunks = 0
     with L.launch_scope(x.device):
         if gsel is None:
             per = I * 4 + I * 8 + (2 * D + 1) * 8                     # workspace, P and Xaug per frame
             step = int(max(1, min(F, int(workspace_limit) // per)))
             tmp = torch.zeros((I, 2 * D + 1), dtype=torch.float64, device=x.device)
             ll_sum = 0.0
-            for lo in range(0, F, step):
-                P, Xaug, ll = ops.gmm_post_dense(x[lo:lo + step], W, gc)
+            pieces = chunks(F, step)
+            for lo, hi in pieces:
+                P, Xaug, ll = ops.gmm_post_dense(x[lo:hi], W, gc)
                 ops.atb_f64(P, Xaug, tmp)
                 ll_sum += float(ll.double().sum())
-                chunks += 1
             stats.occ.add_(tmp[:, 0])
             stats.mean_acc.add_(tmp[:, 1:D + 1])
             stats.var_acc.add_(tmp[:, D + 1:])
@@ -557,15 +545,15 @@ def acc_diag_gmm(stats, gmm, feats, gselect=None, lengths=None, mask=None, works
             step = min(F, _max_frames(lambda f: ops.gmm_acc_workspace_bytes(f, I, D, n, False), int(workspace_limit), n))
             valid = torch.zeros((1,), dtype=torch.int32, device=x.device)
             ll_sum = 0.0
-            for lo in range(0, F, step):
-                xs, gs = x[lo:lo + step], gsel[lo:lo + step]
+            pieces = chunks(F, step)
+            for lo, hi in pieces:
+                xs, gs = x[lo:hi], gsel[lo:hi]
                 post, ll = ops.gmm_post_preselect(xs, gs, mi, iv, gc, valid)
                 ops.gmm_acc(xs, gs, post, stats.occ, stats.mean_acc, stats.var_acc)
                 ll_sum += float(ll.double().sum())
-                chunks += 1
             stats.loglike_sum += ll_sum
             stats.frames += int(valid.item())
-    return chunks
+    return len(pieces)
 
 
 def acc_full_gmm(stats, gmm, feats, gselect, lengths=None, mask=None, workspace_limit=1 << 30):
@@ -587,18 +575,18 @@ def acc_full_gmm(stats, gmm, feats, gselect, lengths=None, mask=None, workspace_
     n = gsel.shape[1]
     step = min(F, _max_frames(lambda f: ops.fgmm_workspace_bytes(f, I, D, n) + ops.gmm_acc_workspace_bytes(f, I, D, n, True),
                               int(workspace_limit), n))
-    chunks, ll_sum, frames = 0, 0.0, 0
+    pieces = chunks(F, step)
+    ll_sum, frames = 0.0, 0
     with L.launch_scope(x.device):
-        for lo in range(0, F, step):
-            xs = x[lo:lo + step]
-            gauss, post, ll = ops.fgmm_post_ll(xs, gsel[lo:lo + step], mic, ic, gc, 0.0)
+        for lo, hi in pieces:
+            xs = x[lo:hi]
+            gauss, post, ll = ops.fgmm_post_ll(xs, gsel[lo:hi], mic, ic, gc, 0.0)
             ops.gmm_acc(xs, gauss, post, stats.occ, stats.mean_acc, stats.cov_acc)
             ll_sum += float(ll.double().sum())
             frames += int((gauss[:, 0] >= 0).sum())
-            chunks += 1
     stats.loglike_sum += ll_sum
     stats.frames += frames
-    return chunks
+    return len(pieces)
 
 
 def _diag_params(d):

@@ -7,7 +7,6 @@ of cases reaches every branch of the runner; tests/golden/runner_launches.txt is
 """
 
 import contextlib
-import ctypes as C
 import difflib
 import os
 import re
@@ -24,6 +23,7 @@ for p in (os.path.dirname(HERE), os.path.join(os.path.dirname(HERE), "kaldi-tfli
 import synth  # noqa: E402
 import kaldi_tflite_amd as ktf  # noqa: E402
 from kaldi_tflite_amd import _lib as L, models  # noqa: E402
+from _recorder import STREAM, Recorder  # noqa: E402
 
 GOLDEN = os.path.join(HERE, "golden", "runner_launches.txt")
 HOST_HELPERS = re.compile(r"ktf_(\w+_)?(stats_slots|slot_rows)|ktf_flat_row_map_rows|ktf_tdnn_out_len")
@@ -34,7 +34,6 @@ EVERY_LAUNCH = {
     "ktf_mx_planes", "ktf_split_bf16_rows", "ktf_flat_row_map", "ktf_tdnn_out_lens",
     "ktf_stats_finalize", "ktf_stats_finalize_slots", "ktf_stats_finalize_flat", "ktf_stats_pool",
 }
-STREAM = object()
 
 
 # ----------------------------------------------------------------------------- topologies
@@ -111,42 +110,7 @@ CASES = [
 ]
 
 
-# ----------------------------------------------------------------------------- recorder
-class _Recorder:
-    """Stands in for the ctypes library: host size helpers go to the real one, every other call is written to `lines` and returns 0."""
-
-    def __init__(self, real):
-        self.real, self.lines, self.called, self.names = real, [], set(), None
-
-    def __getattr__(self, name):
-        if HOST_HELPERS.fullmatch(name):
-            return getattr(self.real, name)
-
-        def call(*args):
-            self.called.add(name)
-            self.lines.append(f"{name}({', '.join(self.arg(a) for a in args)})")
-            return 0
-        return call
-
-    def arg(self, a):
-        if a is STREAM:
-            return "stream"
-        if a is None:
-            return "null"
-        if isinstance(a, C.c_void_p):
-            return self.names(a.value)
-        if isinstance(a, bool):
-            return str(int(a))
-        if isinstance(a, int):
-            return str(a)
-        if isinstance(a, float):
-            return repr(a)
-        if type(a).__name__ == "CArgObject" and isinstance(a._obj, L.TdnnDesc):
-            d = a._obj
-            return "desc{" + " ".join(f"{f}={list(getattr(d, f)) if f == 'ctx' else getattr(d, f)}" for f, _ in d._fields_) + "}"
-        raise TypeError(f"unexpected argument {a!r}")
-
-
+# ----------------------------------------------------------------------------- what the recorder's lines name
 def _pointer_names(mdl, x_buf, lens):
     """address -> what it points into: a workspace role + offset, a layer's weight set, the caller's input; "tmp" for a fresh tensor."""
     def spans():
@@ -190,8 +154,7 @@ def run_case(monkeypatch, case):
         setattr(mdl, k, v)
     x_buf = torch.zeros((B, T, 32 * -(-D // 32)), dtype=torch.float32)
     lens = torch.tensor([max(1, T - 37 * i) for i in range(B)], dtype=torch.int32) if ragged else None
-    rec = _Recorder(L.load())
-    rec.names = _pointer_names(mdl, x_buf, lens)
+    rec = Recorder(L.load(), HOST_HELPERS, _pointer_names(mdl, x_buf, lens))
     get = models._Workspace.get
 
     def recorded_get(ws, role, shape, dtype, device, padded=True):
