@@ -215,6 +215,20 @@ PROTOTYPES = {
     "ktf_vbx_speaker_update": (C.c_int, [_P, _P, _i64, _i32, _i32, _P, _i32, _P, C.c_double, _P, _P, _P, _P, _P, C.c_size_t, _P]),
     "ktf_vbx_loglike": (C.c_int, [_P, _P, _i64, _i32, _i32, _P, _i32, _P, _P, C.c_double, _P, _P]),
 }
+# name -> (restype, argtypes); mirrors include/ktf_augment.h one to one (a table of its own: PROTOTYPES is ktf_hip.h's)
+AUGMENT_PROTOTYPES = {
+    "ktf_aug_partition": (_i32, []),
+    "ktf_aug_tables_floats": (_i64, []),
+    "ktf_aug_tables": (C.c_int, [_P, _P]),
+    "ktf_aug_rir_spectra_floats": (_i64, [_P, _i32, _i32]),
+    "ktf_aug_rir_prepare": (C.c_int, [_P, _P, _P, _i32, _i32, _P, _P, _P, _P]),
+    "ktf_aug_workspace_bytes": (_i64, [_P, _P, _i32, _P, _i32, _i32, _i64]),
+    "ktf_aug_convolve": (C.c_int, [_P, _i32, _i64, _P, _P, _P, _P, _i32, _P, _i32, _i32, _P, _P, _P, _P, _P, _i64, _P, _P, C.c_size_t,
+                                   _P]),
+    "ktf_aug_mix": (C.c_int, [_P, _P, _P, _P, _i32, _P, _i32, _i32, _P, _P, _P, _P, _P, _P, _P, _P, _i32, _i32, _i32, C.c_double, _P,
+                              _i32, _i64, _i64, _P, _P, C.c_size_t, _P]),
+}
+AUG_META, AUG_STATS = 8, 4          # ktf_aug_*: int32 per RIR of the bank's meta; doubles per row of the statistics
 PLDA_DENSE_NO_PCA = -1.0            # ktf_plda_dense_*: target_energy for "no PCA"
 PLDA_DENSE_MAX_DIM = 512
 PLDA_DENSE_MAX_SWEEPS = 30
@@ -231,7 +245,7 @@ _lib = None
 
 
 def load():
-    """dlopen libktf_hip.so and bind every symbol of the header. Raises if it is missing."""
+    """dlopen libktf_hip.so and bind every symbol of the headers. Raises if it is missing."""
     global _lib
     if _lib is not None:
         return _lib
@@ -240,7 +254,7 @@ def load():
             f"{LIB_PATH} not found: build it with `make -C kaldi-tflite_amd/csrc` (or __graft_entry__.build()). "
             "There is no CPU fallback.")
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in PROTOTYPES.items():
+    for name, (res, args) in list(PROTOTYPES.items()) + list(AUGMENT_PROTOTYPES.items()):
         fn = getattr(lib, name)          # AttributeError = header/library mismatch
         fn.restype = res
         fn.argtypes = args

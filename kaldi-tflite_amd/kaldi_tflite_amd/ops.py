@@ -1295,3 +1295,67 @@ def vbx_loglike(rho, G, alpha, c, Fa, offsets):
     lls = _new(rho, TB, K, dtype=torch.float64)
     _call("ktf_vbx_loglike", rho.device, L.ptr(rho), L.ptr(G), TB, D, K, L.ptr(offsets), N, L.ptr(alpha), L.ptr(c), float(Fa), L.ptr(lls))
     return lls
+
+
+# ----------------------------------------------------------------------------- waveform augmentation (include/ktf_augment.h)
+def _host_or_null(a):
+    return _host_ptr(a) if a is not None and a.size else None
+
+
+def aug_partition():
+    """P: the partition size of the convolution, in samples."""
+    return int(L.load().ktf_aug_partition())
+
+
+def aug_tables(device):
+    """The twiddle tables of the convolution's transforms, fp32 on `device`."""
+    tables = torch.empty((_size("ktf_aug_tables_floats"),), dtype=torch.float32, device=device)
+    _call("ktf_aug_tables", device, L.ptr(tables))
+    return tables
+
+
+def aug_rir_prepare(h, offsets, offsets_dev, fs, tables):
+    """h: the bank's taps one RIR after another (fp32, device); offsets: host int32 (R + 1), offsets_dev the same on the device ->
+    (meta (R, AUG_META) int32, spectra fp32): peak index, early window and partition spectra of every RIR."""
+    offsets = _host_i32(offsets)
+    R = offsets.size - 1
+    meta = _new(h, R, L.AUG_META, dtype=torch.int32)
+    spectra = _new(h, _size("ktf_aug_rir_spectra_floats", _host_ptr(offsets), R, int(fs)), dtype=torch.float32)
+    _call("ktf_aug_rir_prepare", h.device, L.ptr(h), _host_ptr(offsets), L.ptr(offsets_dev), R, int(fs), L.ptr(tables), L.ptr(meta),
+          L.ptr(spectra))
+    return meta, spectra
+
+
+def aug_workspace_bytes(n, rir_ids, rir_lengths, fs, num_additives):
+    """Bytes of the workspace aug_convolve and aug_mix share for the rows n / rir_ids (host int32) of a bank with rir_lengths."""
+    n, rir_ids, rir_lengths = _host_i32(n), _host_i32(rir_ids), _host_i32(rir_lengths)
+    return _size("ktf_aug_workspace_bytes", _host_or_null(n), _host_or_null(rir_ids), n.size, _host_or_null(rir_lengths), rir_lengths.size,
+                 int(fs), int(num_additives))
+
+
+def aug_convolve(x, n, n_dev, rir_ids, rir_ids_dev, rir_lengths, fs, h, offsets_dev, meta, spectra, tables, num_additives, stats, workspace):
+    """Steps 1 and 2 of the augmentation on x (B, T) fp32 / int16 (rows may be strided): the unshifted y into `workspace` (uint8, at
+    least aug_workspace_bytes), p_before and p_sig into stats (B, AUG_STATS) fp64. n, rir_ids, rir_lengths: host int32; *_dev: the
+    same on the device; h / offsets_dev / meta / spectra / tables: the bank as aug_rir_prepare took and left it, and aug_tables'
+    (None for a batch without an RIR)."""
+    n, rir_ids, rir_lengths = _host_i32(n), _host_i32(rir_ids), _host_i32(rir_lengths)
+    _call("ktf_aug_convolve", x.device, L.ptr(x), int(x.dtype == torch.int16), _ld(x), _host_or_null(n), L.ptr(n_dev), _host_or_null(rir_ids),
+          L.ptr(rir_ids_dev), n.size, _host_or_null(rir_lengths), rir_lengths.size, int(fs), L.ptr(h), L.ptr(offsets_dev), L.ptr(meta), L.ptr(spectra),
+          L.ptr(tables), int(num_additives), L.ptr(stats), L.ptr(workspace), workspace.numel())
+    return stats
+
+
+def aug_mix(n, n_dev, rir_ids, rir_ids_dev, rir_lengths, fs, meta, add_offsets, add_offsets_dev, adds, adds_dev, noise, noise_offsets,
+            noise_offsets_dev, shift_output, normalize_output, volume, out, stats, workspace):
+    """Steps 3 to 5 on the y aug_convolve left in `workspace`: the additives adds (host (A, 4) int32 rows noise, snr_db's fp32 bits,
+    start, duration; CSR add_offsets (B + 1) host int32) from the bank noise (fp32) / noise_offsets (host int64, M + 1), the scale and
+    the window into out (B, T_out) fp32 / int16; p_after and the scale into stats."""
+    n, rir_ids, rir_lengths = _host_i32(n), _host_i32(rir_ids), _host_i32(rir_lengths)
+    add_offsets, adds = _host_i32(add_offsets), _host_i32(adds)
+    noise_offsets = np.ascontiguousarray(noise_offsets, dtype=np.int64)
+    _call("ktf_aug_mix", out.device, _host_or_null(n), L.ptr(n_dev), _host_or_null(rir_ids), L.ptr(rir_ids_dev), n.size,
+          _host_or_null(rir_lengths), rir_lengths.size, int(fs), L.ptr(meta), _host_ptr(add_offsets), L.ptr(add_offsets_dev),
+          _host_or_null(adds), L.ptr(adds_dev), L.ptr(noise), _host_ptr(noise_offsets), L.ptr(noise_offsets_dev), noise_offsets.size - 1,
+          int(bool(shift_output)), int(bool(normalize_output)), float(volume), L.ptr(out), int(out.dtype == torch.int16), _ld(out),
+          out.shape[1], L.ptr(stats), L.ptr(workspace), workspace.numel())
+    return out, stats
