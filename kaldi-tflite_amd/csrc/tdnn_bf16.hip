@@ -1,6 +1,7 @@
 // KTF_GEMM_BF16 (one bf16 MFMA pass; outside the 1e-4 tolerance, BASELINE config 3's precision) and the small-layer
 // forms of KTF_GEMM_BF16X3: 128 x 128 register-/DMA-staged tiles, the 256 x 256 ring kernels on 32x32x16 (sigmoid / tanh) and
-// 16x16x32 MFMAs, and the 128 x 256 two-workgroups-per-CU kernel for K <= 768.
+// 16x16x32 MFMAs, and the 128 x 256 two-workgroups-per-CU kernel for K <= 768. The ring kernels keep their tile setup and their
+// K-loops here; the ring's feed, the epilogue value, the column constants and the epilogues are tdnn_ring.h's.
 #include "tdnn_ring.h"
 
 // ------------------------------------------------------------------------------------ BF16 / BF16X3
@@ -18,10 +19,10 @@ struct BfCfg {
 
 __device__ __forceinline__ u32x4 pack_bf16x8(const fv4& lo, const fv4& hi) {
     u32x4 r;
-    r.x = (unsigned)f2bf(lo.x) | ((unsigned)f2bf(lo.y) << 16);
-    r.y = (unsigned)f2bf(lo.z) | ((unsigned)f2bf(lo.w) << 16);
-    r.z = (unsigned)f2bf(hi.x) | ((unsigned)f2bf(hi.y) << 16);
-    r.w = (unsigned)f2bf(hi.z) | ((unsigned)f2bf(hi.w) << 16);
+    r.x = PACK_BF16X2(lo.x, lo.y);
+    r.y = PACK_BF16X2(lo.z, lo.w);
+    r.z = PACK_BF16X2(hi.x, hi.y);
+    r.w = PACK_BF16X2(hi.z, hi.w);
     return r;
 }
 __device__ __forceinline__ fv4 bf_residual(const fv4& v, unsigned p01, unsigned p23) {
@@ -170,18 +171,8 @@ __global__ __launch_bounds__(256) void tdnn_bf16_kernel(TdnnParams p) {
 // global_load_lds_dwordx4 (no VGPR round trip, no ds_write). The LDS image is lane-linear ([row][64] bf16, 128-B rows),
 // so bank conflicts of the ds_read_b128 fragment reads are removed by permuting the 16-B chunks of each row on the
 // SOURCE address (chunk' = chunk ^ ((row>>1)&7)) and applying the same involution on the read address.
-// 1-D grid, XCD-aware: block id -> (xcd = id % 8, slot = id / 8); an XCD walks its own M-tiles and runs all N-tiles of
-// one M-tile back to back, so the gathered activation rows are fetched into that XCD's L2 once.
-// The epilogue stages the fp32 accumulators through LDS and writes whole 256-B row segments.
-// cache policy bits of the operand DMAs (aux of global_load_lds: 1 = sc0, 2 = nt, 16 = sc1); A = activations, W = weights.
-// Measured (tools/gemm_layers.py): nt on the activations -10..-20 %, nt on the weights -10..-40 %, sc0 no change: both
-// streams live on L2 hits (other N-tiles / context offsets re-read the activations, every CU re-reads the weights).
-#ifndef KTF_AUX_A
-#define KTF_AUX_A 0
-#endif
-#ifndef KTF_AUX_W
-#define KTF_AUX_W 0
-#endif
+// 1-D grid, XCD-aware (TDNN_TILE_HEADER). The epilogue stages the fp32 accumulators through LDS and writes whole 256-B row segments.
+
 
 #define G_BM 128
 #define G_BN 128
@@ -193,19 +184,7 @@ __global__ __launch_bounds__(256) void tdnn_bf16_kernel(TdnnParams p) {
 
 __global__ __launch_bounds__(256) void tdnn_bf16g_kernel(TdnnParams p, int mtiles, int ntiles, int gtiles) {
     extern __shared__ __attribute__((aligned(16))) unsigned char gsm[];
-    const int id = blockIdx.x;
-    const int xcd = id & 7, slot = id >> 3;
-    const int g = (slot / ntiles) * 8 + xcd;     // global M-tile index
-    const int nt = slot - (slot / ntiles) * ntiles;
-    if (g >= gtiles) return;
-    const int b = g / mtiles, mt = g - b * mtiles;
-    const int len = p.lens ? p.lens[b] : (int)p.T;
-    int start;
-    const int out_len = tdnn_out_len(len, p, start);
-    if (p.out_lens && nt == 0 && mt == 0 && threadIdx.x == 0) p.out_lens[b] = out_len;
-    const int t0 = mt * G_BM;
-    if (t0 >= out_len || len <= 0) return;
-    const int n0 = nt * G_BN;
+    TDNN_TILE_HEADER(G_BM, G_BN, blockIdx.x)
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = wave >> 1, wn = wave & 1;
 
@@ -289,11 +268,8 @@ __global__ __launch_bounds__(256) void tdnn_bf16g_kernel(TdnnParams p, int mtile
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
         const int nl = wn * 64 + j * 32 + (lane & 31);
-        const int n = n0 + nl;
-        const bool nv = n < p.units;
-        const float bias = (nv && p.bias) ? p.bias[n] : 0.0f;
-        const float sc = (nv && p.scale) ? p.scale[n] : 1.0f;
-        const float sh = (nv && p.shift) ? p.shift[n] : 0.0f;
+        float bias, sc, sh;
+        COL_PRM(n0 + nl, bias, sc, sh)
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
 #pragma unroll
@@ -323,10 +299,7 @@ __global__ __launch_bounds__(256) void tdnn_bf16g_kernel(TdnnParams p, int mtile
                 if (p.y_dtype == KTF_F32) {
                     *reinterpret_cast<f32x4*>(reinterpret_cast<float*>(p.y) + off) = v;
                 } else {
-                    uint2 pk;
-                    pk.x = (unsigned)f2bf(v.x) | ((unsigned)f2bf(v.y) << 16);
-                    pk.y = (unsigned)f2bf(v.z) | ((unsigned)f2bf(v.w) << 16);
-                    *reinterpret_cast<uint2*>(reinterpret_cast<unsigned short*>(p.y) + off) = pk;
+                    *reinterpret_cast<uint2*>(reinterpret_cast<unsigned short*>(p.y) + off) = PACK_BF16X4(v.x, v.y, v.z, v.w);
                 }
             } else {
 #pragma unroll
@@ -352,28 +325,12 @@ template <int ACT, bool STATS>
 __global__ __launch_bounds__(512) void tdnn_bf16r_kernel(TdnnParams p, int mtiles, int ntiles, int gtiles,
                                                          double* __restrict__ stats) {
     extern __shared__ __attribute__((aligned(16))) unsigned char rsm[];
-    const int id = blockIdx.x;
-    const int xcd = id & 7, slot = id >> 3;
-    const int g = (slot / ntiles) * 8 + xcd;
-    const int nt = slot - (slot / ntiles) * ntiles;
-    if (g >= gtiles) return;
-    const int b = g / mtiles, mt = g - b * mtiles;
-    const int len = p.lens ? p.lens[b] : (int)p.T;
-    int start;
-    const int out_len = tdnn_out_len(len, p, start);
-    if (p.out_lens && nt == 0 && mt == 0 && threadIdx.x == 0) p.out_lens[b] = out_len;
-    const int t0 = mt * R_BM;
-    if (t0 >= out_len || len <= 0) return;
-    const int n0 = nt * R_BN;
+    TDNN_TILE_HEADER(R_BM, R_BN, blockIdx.x)
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // provably wave-uniform: LDS-DMA bases stay in SGPRs
     const int wm = wave >> 2, wn = wave & 3;
 
-    // Uniform 64-bit bases + per-lane 32-bit byte offsets: every DMA address is base(SGPR) + offset(VGPR), so the K-loop
-    // carries no 64-bit vector arithmetic (an utterance's activations and a layer's weights are both < 4 GiB).
-    const char* xb = reinterpret_cast<const char*>(p.x) + ((int64_t)b * p.T * p.ldx) * 2;
-    const char* wb = reinterpret_cast<const char*>(p.w);
-    const unsigned ldxb = (unsigned)p.ldx * 2u;
+    RING_FEED_BASES(2)
 
     // staging map: chunk q = i*512 + tid -> row q/4, LDS position q%4, global chunk (q%4) ^ ((row>>2)&3)
     int a_t[2];
@@ -396,42 +353,12 @@ __global__ __launch_bounds__(512) void tdnn_bf16r_kernel(TdnnParams p, int mtile
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.0f;
 
-    const int nk = p.ktot / R_BK;
-    const int lenm1 = len - 1;
-
-    // iterator over the stage being issued: K-step index, context offset of its rows, byte offset inside the context
-    int is_ks = 0, is_c = 0, is_db = 0, is_off = p.ctx[0];
-    const int dpad_b = p.din_pad * 2;
-#define R_DMA_A(i)                                                                                                     \
-    {                                                                                                                  \
-        int r_ = a_t[i] + is_off;                                                                                      \
-        r_ = r_ < 0 ? 0 : (r_ > lenm1 ? lenm1 : r_);                                                                   \
-        const unsigned vo_ = (unsigned)r_ * ldxb + a_cb[i] + (unsigned)is_db;                                          \
-        __builtin_amdgcn_global_load_lds((glb_ptr_t*)(xb + vo_),                                                       \
-            (lds_ptr_t*)(rsm + (is_ks & (R_NSTAGE - 1)) * R_STAGE_BYTES + wave * 1024 + (i) * 8192), 16, 0, KTF_AUX_A);\
-    }
-#define R_DMA_B(i)                                                                                                     \
-    {                                                                                                                  \
-        const unsigned vo_ = w_ob[i] + (unsigned)(is_ks * (R_BK * 2));                                                 \
-        __builtin_amdgcn_global_load_lds((glb_ptr_t*)(wb + vo_),                                                       \
-            (lds_ptr_t*)(rsm + (is_ks & (R_NSTAGE - 1)) * R_STAGE_BYTES + R_TILE_BYTES + wave * 1024 + (i) * 8192),    \
-            16, 0, KTF_AUX_W);                                                                                            \
-    }
-#define R_ADVANCE()                                                                                                    \
-    {                                                                                                                  \
-        ++is_ks;                                                                                                       \
-        is_db += R_BK * 2;                                                                                             \
-        if (is_db == dpad_b) {                                                                                         \
-            is_db = 0;                                                                                                 \
-            ++is_c;                                                                                                    \
-            is_off = (is_c < p.nctx) ? p.ctx[is_c] : 0;                                                                \
-        }                                                                                                              \
-    }
+    RING_FEED_ITER(2)
 
     // prologue: three stages in flight
     for (int s_ = 0; s_ < 3 && s_ < nk; ++s_) {
         R_DMA_A(0) R_DMA_B(0) R_DMA_A(1) R_DMA_B(1)
-        R_ADVANCE()
+        RING_ADVANCE(2)
     }
 
     const int rsw = ((lane & 31) >> 2) & 3;
@@ -504,183 +431,30 @@ __global__ __launch_bounds__(512) void tdnn_bf16r_kernel(TdnnParams p, int mtile
             }
             __builtin_amdgcn_sched_barrier(0);
         }
-        if (is_ks < nk) R_ADVANCE()
+        if (is_ks < nk) RING_ADVANCE(2)
     }
-#undef R_DMA_A
-#undef R_DMA_B
-#undef R_ADVANCE
-#define R_STAGE
-#undef R_STAGE
     __syncthreads();   // all fragment reads done before the LDS is reused by the epilogue
 
     ring_epilogue<ACT, STATS>(acc, p, stats, rsm, b, t0, n0, out_len, wm, wn, wave, lane);
 }
 
-// Non-reducing epilogue of the 16x16x32 kernel. The MFMA operands are swapped there (W fragment as A, x fragment as B), so
-// a lane's four accumulator values are four CONSECUTIVE output columns of one output row:
-//   acc[i][j][r] = out[row wm*128 + i*16 + (lane&15)][col wn*64 + j*16 + (lane>>4)*4 + r]
-// bias/ReLU/BatchNorm, the bf16 pack and the store therefore need no LDS staging and no barrier; the four stores of one i
-// (j = 0..3) complete a 128-byte line of each of the 16 rows.
-template <int ACT>
-__device__ __forceinline__ void ring_epilogue16_direct(f32x4v (&acc)[8][4], const TdnnParams& p, int b, int t0, int n0,
-                                                       int out_len, int wm, int wn, int lane) {
-    const int c = lane & 15, g = lane >> 4;
-    f32x4v bias[4], sc[4], sh[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const int n = n0 + wn * 64 + j * 16 + g * 4 + e;
-            const bool nv = n < p.units;
-            bias[j][e] = (nv && p.bias) ? p.bias[n] : 0.0f;
-            sc[j][e] = (nv && p.scale) ? p.scale[n] : 1.0f;
-            sh[j][e] = (nv && p.shift) ? p.shift[n] : 0.0f;
-        }
-    }
-    const int rows_valid = out_len - t0;
-    const int64_t out_row0 = (int64_t)b * p.Tout + t0;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        const int m = wm * 128 + i * 16 + c;
-        if (m >= rows_valid) continue;
-        const int64_t rowoff = (out_row0 + m) * p.ldy;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int n = n0 + wn * 64 + j * 16 + g * 4;
-            f32x4v v;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                float t = acc[i][j][e] + bias[j][e];
-                if (ACT == KTF_ACT_RELU) t = fmaxf(t, 0.0f);
-                else if (ACT != KTF_ACT_NONE) t = apply_act(t, ACT);
-                v[e] = t * sc[j][e] + sh[j][e];
-            }
-            const int64_t off = rowoff + n;
-            if (n + 4 <= p.units) {
-                if (p.y_dtype == KTF_F32) {
-                    *reinterpret_cast<f32x4v*>(reinterpret_cast<float*>(p.y) + off) = v;
-                } else {
-                    uint2 pk;
-                    pk.x = (unsigned)f2bf(v[0]) | ((unsigned)f2bf(v[1]) << 16);
-                    pk.y = (unsigned)f2bf(v[2]) | ((unsigned)f2bf(v[3]) << 16);
-                    *reinterpret_cast<uint2*>(reinterpret_cast<unsigned short*>(p.y) + off) = pk;
-                }
-            } else {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    if (n + e < p.units) {
-                        if (p.y_dtype == KTF_F32) reinterpret_cast<float*>(p.y)[off + e] = v[e];
-                        else reinterpret_cast<unsigned short*>(p.y)[off + e] = f2bf(v[e]);
-                    }
-                }
-            }
-        }
-    }
-}
-
-// bf16-output epilogue of the 16x16x32 kernel (swapped operands, see ring_epilogue16_direct): bias/ReLU/BatchNorm and the
-// bf16 pack happen in registers, each lane stages its four consecutive columns with one ds_write_b64 (row pitch 520 B: the
-// 16 lanes of a store group cover all 32 banks), and after ONE barrier every wave streams 32 staged rows out with 16-byte
-// stores (two 512-byte rows per wave instruction). The stores are issue-bound per instruction (T21), hence the wide form.
-#define R16_PK_PITCH 520
-#define R16_PRM_OFF (R_BM * R16_PK_PITCH)              // bias | scale | shift of the tile's 256 columns, behind the staging image
+// LDS of the 16x16x32 kernel: the ring, reused as the 256 x 520-byte staging image of r16_stage_pk, and behind it bias | scale |
+// shift of the tile's 256 columns (COL_PRM_PARK)
+#define R16_PRM_OFF (R_BM * R16_PK_PITCH)
 #define R16_LDS_BYTES (R16_PRM_OFF + 3 * R_BN * 4)      // 136,192 B
 
-// every wave streams 32 rows of the staged 256 x 256 16-bit image out with 16-byte stores (two 512-byte rows per instruction)
-__device__ __forceinline__ void r16_store_staged(const TdnnParams& p, const unsigned char* rsm, unsigned short* ybase, int b,
-                                                 int t0, int n0, int out_len, int wave, int lane) {
-    const int rows_valid = out_len - t0;
-    const int64_t out_row0 = (int64_t)b * p.Tout + t0;
-    const int n8 = n0 + (lane & 31) * 8;
-    const bool wide = (n8 + 8 <= p.units) && ((p.ldy & 7) == 0) && ((reinterpret_cast<uintptr_t>(ybase) & 15) == 0);
-#pragma unroll 4
-    for (int sp = 0; sp < 16; ++sp) {
-        const int m = wave * 32 + sp * 2 + (lane >> 5);
-        if (m < rows_valid) {
-            const unsigned char* src = rsm + m * R16_PK_PITCH + (lane & 31) * 16;
-            const uint2 lo = *reinterpret_cast<const uint2*>(src);
-            const uint2 hi = *reinterpret_cast<const uint2*>(src + 8);
-            unsigned short* yp = ybase + (out_row0 + m) * p.ldy + n8;
-            if (wide) {
-                u32x4 o;
-                o.x = lo.x; o.y = lo.y; o.z = hi.x; o.w = hi.y;
-                *reinterpret_cast<u32x4*>(yp) = o;
-            } else {
-                const unsigned w4[4] = {lo.x, lo.y, hi.x, hi.y};
-#pragma unroll
-                for (int e = 0; e < 8; ++e)
-                    if (n8 + e < p.units) yp[e] = (unsigned short)(w4[e >> 1] >> ((e & 1) * 16));
-            }
-        }
-    }
-}
-template <int ACT>
-__device__ __forceinline__ void ring_epilogue16_pk(f32x4v (&acc)[8][4], const TdnnParams& p, unsigned char* rsm, int b,
-                                                   int t0, int n0, int out_len, int wm, int wn, int wave, int lane) {
-    const int c = lane & 15, g = lane >> 4;
-    // column constants were parked in LDS when the tile started (no global loads, and no latency, at this point)
-    const float* prm = reinterpret_cast<const float*>(rsm + R16_PRM_OFF);
-    f32x4v bias[4], sc[4], sh[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int nl = wn * 64 + j * 16 + g * 4;
-        bias[j] = *reinterpret_cast<const f32x4v*>(prm + nl);
-        sc[j] = *reinterpret_cast<const f32x4v*>(prm + R_BN + nl);
-        sh[j] = *reinterpret_cast<const f32x4v*>(prm + 2 * R_BN + nl);
-    }
-    unsigned char* stg = rsm + (wm * 128 + c) * R16_PK_PITCH + (wn * 64 + g * 4) * 2;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            f32x4v v;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                float t = acc[i][j][e] + bias[j][e];
-                if (ACT == KTF_ACT_RELU) t = fmaxf(t, 0.0f);
-                else if (ACT != KTF_ACT_NONE) t = apply_act(t, ACT);
-                v[e] = t * sc[j][e] + sh[j][e];
-            }
-            uint2 pk;
-            pk.x = (unsigned)f2bf(v[0]) | ((unsigned)f2bf(v[1]) << 16);
-            pk.y = (unsigned)f2bf(v[2]) | ((unsigned)f2bf(v[3]) << 16);
-            *reinterpret_cast<uint2*>(stg + i * 16 * R16_PK_PITCH + j * 32) = pk;
-        }
-    }
-    __syncthreads();
-    r16_store_staged(p, rsm, reinterpret_cast<unsigned short*>(p.y), b, t0, n0, out_len, wave, lane);
-}
 
 template <int ACT, bool STATS>
 __device__ __forceinline__ void r16_tile(const TdnnParams& p, int mtiles, int ntiles, int gtiles,
                                          double* __restrict__ stats, unsigned char* rsm, const int id) {
-    const int xcd = id & 7, slot = id >> 3;
-    const int g = (slot / ntiles) * 8 + xcd;
-    const int nt = slot - (slot / ntiles) * ntiles;
-    if (g >= gtiles) return;
-    const int b = g / mtiles, mt = g - b * mtiles;
-    const int len = p.lens ? p.lens[b] : (int)p.T;
-    int start;
-    const int out_len = tdnn_out_len(len, p, start);
-    if (p.out_lens && nt == 0 && mt == 0 && threadIdx.x == 0) p.out_lens[b] = out_len;
-    const int t0 = mt * R_BM;
-    if (t0 >= out_len || len <= 0) return;
-    const int n0 = nt * R_BN;
+    TDNN_TILE_HEADER(R_BM, R_BN, id)
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave >> 2, wn = wave & 3;
-    if (!STATS && tid < R_BN) {
-        float* prm = reinterpret_cast<float*>(rsm + R16_PRM_OFF);
-        const int n = n0 + tid;
-        const bool nv = n < p.units;
-        prm[tid] = (nv && p.bias) ? p.bias[n] : 0.0f;
-        prm[R_BN + tid] = (nv && p.scale) ? p.scale[n] : 1.0f;
-        prm[2 * R_BN + tid] = (nv && p.shift) ? p.shift[n] : 0.0f;
-    }
+    float* prm = reinterpret_cast<float*>(rsm + R16_PRM_OFF);
+    if (!STATS && tid < R_BN) COL_PRM_PARK(prm, R_BN)
 
-    const char* xb = reinterpret_cast<const char*>(p.x) + ((int64_t)b * p.T * p.ldx) * 2;
-    const char* wb = reinterpret_cast<const char*>(p.w);
-    const unsigned ldxb = (unsigned)p.ldx * 2u;
+    RING_FEED_BASES(2)
 
     int a_t[2];
     unsigned a_cb[2], w_ob[2];
@@ -702,38 +476,10 @@ __device__ __forceinline__ void r16_tile(const TdnnParams& p, int mtiles, int nt
 #pragma unroll
             for (int r = 0; r < 4; ++r) acc[i][j][r] = 0.0f;
 
-    const int nk = p.ktot / R_BK;
-    const int lenm1 = len - 1;
-    int is_ks = 0, is_c = 0, is_db = 0, is_off = p.ctx[0];
-    const int dpad_b = p.din_pad * 2;
-#define S_DMA_A(i)                                                                                                     \
-    {                                                                                                                  \
-        int r_ = a_t[i] + is_off;                                                                                      \
-        r_ = r_ < 0 ? 0 : (r_ > lenm1 ? lenm1 : r_);                                                                   \
-        const unsigned vo_ = (unsigned)r_ * ldxb + a_cb[i] + (unsigned)is_db;                                          \
-        __builtin_amdgcn_global_load_lds((glb_ptr_t*)(xb + vo_),                                                       \
-            (lds_ptr_t*)(rsm + (is_ks & (R_NSTAGE - 1)) * R_STAGE_BYTES + wave * 1024 + (i) * 8192), 16, 0, KTF_AUX_A);\
-    }
-#define S_DMA_B(i)                                                                                                     \
-    {                                                                                                                  \
-        const unsigned vo_ = w_ob[i] + (unsigned)(is_ks * (R_BK * 2));                                                 \
-        __builtin_amdgcn_global_load_lds((glb_ptr_t*)(wb + vo_),                                                       \
-            (lds_ptr_t*)(rsm + (is_ks & (R_NSTAGE - 1)) * R_STAGE_BYTES + R_TILE_BYTES + wave * 1024 + (i) * 8192),    \
-            16, 0, KTF_AUX_W);                                                                                            \
-    }
-#define S_ADVANCE()                                                                                                    \
-    {                                                                                                                  \
-        ++is_ks;                                                                                                       \
-        is_db += R_BK * 2;                                                                                             \
-        if (is_db == dpad_b) {                                                                                         \
-            is_db = 0;                                                                                                 \
-            ++is_c;                                                                                                    \
-            is_off = (is_c < p.nctx) ? p.ctx[is_c] : 0;                                                                \
-        }                                                                                                              \
-    }
+    RING_FEED_ITER(2)
     for (int s_ = 0; s_ < 3 && s_ < nk; ++s_) {
-        S_DMA_A(0) S_DMA_B(0) S_DMA_A(1) S_DMA_B(1)
-        S_ADVANCE()
+        R_DMA_A(0) R_DMA_B(0) R_DMA_A(1) R_DMA_B(1)
+        RING_ADVANCE(2)
     }
     // fragment addressing: lane (r = lane&15, c = lane>>4) reads row R, chunk c ^ f(R); all tile rows keep (R>>2)&3 of r
     const int fr = (4 - (((lane & 15) >> 2) & 3)) & 3;
@@ -767,8 +513,8 @@ __device__ __forceinline__ void r16_tile(const TdnnParams& p, int mtiles, int nt
                 for (int i2 = 4; i2 < 8; ++i2) a[i2] = *reinterpret_cast<const bfrag8*>(sa + a_row_off + i2 * 16 * 64);
             }
             if (refill) {
-                if (i == 1) S_DMA_A(0)
-                if (i == 3) S_DMA_B(0)
+                if (i == 1) R_DMA_A(0)
+                if (i == 3) R_DMA_B(0)
             }
             __builtin_amdgcn_sched_barrier(0);
         }
@@ -784,8 +530,8 @@ __device__ __forceinline__ void r16_tile(const TdnnParams& p, int mtiles, int nt
                 for (int i2 = 0; i2 < 4; ++i2) a[i2] = *reinterpret_cast<const bfrag8*>(san + a_row_off + i2 * 16 * 64);
             }
             if (refill) {
-                if (i == 5) S_DMA_A(1)
-                if (i == 7) S_DMA_B(1)
+                if (i == 5) R_DMA_A(1)
+                if (i == 7) R_DMA_B(1)
             }
             __builtin_amdgcn_sched_barrier(0);
         }
@@ -795,18 +541,22 @@ __device__ __forceinline__ void r16_tile(const TdnnParams& p, int mtiles, int nt
 #pragma unroll
             for (int j = 0; j < 4; ++j) bq[j] = *reinterpret_cast<const bfrag8*>(sbn + b_row_off + j * 16 * 64);
         }
-        if (is_ks < nk) S_ADVANCE()
+        if (is_ks < nk) RING_ADVANCE(2)
     }
-#undef S_DMA_A
-#undef S_DMA_B
-#undef S_ADVANCE
     if (STATS) {
         ring_epilogue16<ACT, STATS>(acc, p, stats, rsm, b, t0, n0, out_len, wm, wn, wave, lane, epi16_load(p, n0, wn, lane));
     } else if (p.y_dtype == KTF_F32) {
-        ring_epilogue16_direct<ACT>(acc, p, b, t0, n0, out_len, wm, wn, lane);
+        Epi16Cols cols;
+        epi16_cols_load(cols, p, n0, wn, lane);
+        ring_epilogue16_direct<ACT, true, false>(acc, p, cols, b, t0, n0, out_len, wm * 128, wn, lane);
     } else {
         __syncthreads();          // every wave's fragment reads are done before the ring is reused as staging
-        ring_epilogue16_pk<ACT>(acc, p, rsm, b, t0, n0, out_len, wm, wn, wave, lane);
+        // column constants were parked in LDS when the tile started (no global loads, and no latency, at this point)
+        Epi16Cols cols;
+        epi16_cols_lds<R_BN, true>(cols, prm, wn, lane);
+        r16_stage_pk<ACT, true>(acc, cols, rsm, wm * 128, wn, lane);
+        __syncthreads();
+        r16_store_staged(p, rsm, reinterpret_cast<unsigned short*>(p.y), b, t0, n0, out_len, wave, lane);
     }
 }
 
@@ -835,42 +585,22 @@ __global__ __launch_bounds__(512) void tdnn_bf16r16_kernel(TdnnParams p, int mti
 #define H_STAGE_BYTES (H_A_BYTES + H_B_BYTES)        // 24 KiB
 #define H_RING_BYTES (H_NSTAGE * H_STAGE_BYTES)      // 72 KiB (bf16 staging of the tile: 128 x 520 B = 66,560 B)
 #define H_LDS_BYTES (H_RING_BYTES + 3 * H_BN * 4)    // + bias | scale | shift of the tile's columns = 76,800 B
-#define H_PK_PITCH 520
 
 
 template <int ACT, bool STATS>
 __global__ __launch_bounds__(256, 2) void tdnn_bf16h_kernel(TdnnParams p, int mtiles, int ntiles, int gtiles,
                                                             double* __restrict__ stats) {
     extern __shared__ __attribute__((aligned(16))) unsigned char rsm[];
-    const int id = blockIdx.x;
-    const int xcd = id & 7, slot = id >> 3;
-    const int g = (slot / ntiles) * 8 + xcd;
-    const int nt = slot - (slot / ntiles) * ntiles;
-    if (g >= gtiles) return;
-    const int b = g / mtiles, mt = g - b * mtiles;
-    const int len = p.lens ? p.lens[b] : (int)p.T;
-    int start;
-    const int out_len = tdnn_out_len(len, p, start);
-    if (p.out_lens && nt == 0 && mt == 0 && threadIdx.x == 0) p.out_lens[b] = out_len;
-    const int t0 = mt * H_BM;
-    if (t0 >= out_len || len <= 0) return;
-    const int n0 = nt * H_BN;
+    TDNN_TILE_HEADER(H_BM, H_BN, blockIdx.x)
     const int tid = threadIdx.x, lane = tid & 63;
     const int wn = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wave = wn;                              // one row of four waves
     const int c = lane & 15, g4 = lane >> 4;
 
     float* prm = reinterpret_cast<float*>(rsm + H_RING_BYTES);
-    {
-        const int n = n0 + tid;
-        const bool nv = n < p.units;
-        prm[tid] = (nv && p.bias) ? p.bias[n] : 0.0f;
-        prm[H_BN + tid] = (nv && p.scale) ? p.scale[n] : 1.0f;
-        prm[2 * H_BN + tid] = (nv && p.shift) ? p.shift[n] : 0.0f;
-    }
+    COL_PRM_PARK(prm, H_BN)
 
-    const char* xb = reinterpret_cast<const char*>(p.x) + ((int64_t)b * p.T * p.ldx) * 2;
-    const char* wb = reinterpret_cast<const char*>(p.w);
-    const unsigned ldxb = (unsigned)p.ldx * 2u;
+    RING_FEED_BASES(2)
 
     // LDS-DMA chunk q = i*256 + tid -> tile row q/4, LDS position q%4, global chunk (q%4) ^ f(row) (f as in the r16 kernel)
     int a_t[2];
@@ -887,34 +617,15 @@ __global__ __launch_bounds__(256, 2) void tdnn_bf16h_kernel(TdnnParams p, int mt
         w_ob[i] = (unsigned)(n0 + row) * (unsigned)p.ktot * 2u + chunk;
     }
 
-    const int nk = p.ktot / R_BK;
-    const int lenm1 = len - 1;
-    int is_ks = 0, is_slot = 0, is_c = 0, is_db = 0, is_off = p.ctx[0];
-    const int dpad_b = p.din_pad * 2;
-#define H_DMA_A(i)                                                                                                     \
-    {                                                                                                                  \
-        int r_ = a_t[i] + is_off;                                                                                      \
-        r_ = r_ < 0 ? 0 : (r_ > lenm1 ? lenm1 : r_);                                                                   \
-        const unsigned vo_ = (unsigned)r_ * ldxb + a_cb[i] + (unsigned)is_db;                                          \
-        __builtin_amdgcn_global_load_lds((glb_ptr_t*)(xb + vo_),                                                       \
-            (lds_ptr_t*)(rsm + is_slot * H_STAGE_BYTES + wn * 1024 + (i) * 4096), 16, 0, KTF_AUX_A);                   \
-    }
-#define H_DMA_B(i)                                                                                                     \
-    {                                                                                                                  \
-        const unsigned vo_ = w_ob[i] + (unsigned)(is_ks * (R_BK * 2));                                                 \
-        __builtin_amdgcn_global_load_lds((glb_ptr_t*)(wb + vo_),                                                       \
-            (lds_ptr_t*)(rsm + is_slot * H_STAGE_BYTES + H_A_BYTES + wn * 1024 + (i) * 4096), 16, 0, KTF_AUX_W);       \
-    }
+    RING_FEED_ITER(2)
+    // three stages of A | W: a wrap counter names the slot; two pieces of A and four of W per thread
+    int is_slot = 0;
+#define H_DMA_A(i) RING_DMA_A(i, is_slot, H_STAGE_BYTES, 4096)
+#define H_DMA_B(i) RING_DMA_W(i, wb, is_slot, H_STAGE_BYTES, H_A_BYTES, 4096)
 #define H_ADVANCE()                                                                                                    \
     {                                                                                                                  \
-        ++is_ks;                                                                                                       \
         is_slot = (is_slot == H_NSTAGE - 1) ? 0 : is_slot + 1;                                                         \
-        is_db += R_BK * 2;                                                                                             \
-        if (is_db == dpad_b) {                                                                                         \
-            is_db = 0;                                                                                                 \
-            ++is_c;                                                                                                    \
-            is_off = (is_c < p.nctx) ? p.ctx[is_c] : 0;                                                                \
-        }                                                                                                              \
+        RING_ADVANCE(2)                                                                                                \
     }
     for (int s_ = 0; s_ < 2 && s_ < nk; ++s_) {
         H_DMA_A(0) H_DMA_A(1) H_DMA_B(0) H_DMA_B(1) H_DMA_B(2) H_DMA_B(3)
@@ -980,156 +691,30 @@ __global__ __launch_bounds__(256, 2) void tdnn_bf16h_kernel(TdnnParams p, int mt
         }
         if (refill) H_ADVANCE()
     }
-#undef H_DMA_A
-#undef H_DMA_B
-#undef H_ADVANCE
     const int rows_valid = out_len - t0;
     if (STATS) {
-        // acc[i][j][r] = out[row i*16 + g4*4 + r][col wn*64 + j*16 + c]
-        // Column sums with a PIVOT: every lane accumulates sum(v - p) and sum((v - p)^2) in fp32, where p is the column's
-        // value in the tile's first row (the same for the four lanes that share a column), and converts to the absolute
-        // sums in fp64 once per tile: sum v = s + n p, sum v^2 = q + 2 p s + n p^2. A constant channel (dead ReLU, zero
-        // weight row) gives v - p == 0 exactly, hence var == 0 exactly as with fp64 accumulation of v, v^2 -- at 5 fp32
-        // operations per element instead of 2 fp32 + 3 fp64.
+        // natural layout: acc[i][j][r] = out[row i*16 + g4*4 + r][col wn*64 + j*16 + c]
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const int nl = wn * 64 + j * 16 + c;
             const float scj = prm[H_BN + nl], shj = prm[2 * H_BN + nl];
-            float v0 = acc[0][j][0];
-            if (ACT == KTF_ACT_RELU) v0 = fmaxf(v0, 0.0f);
-            else if (ACT != KTF_ACT_NONE) v0 = apply_act(v0, ACT);
-            v0 = v0 * scj + shj;
-            const float pv = __shfl(v0, c, 64);       // row 0 of the tile lives in the g4 == 0 lane of this column
-            float s32 = 0.0f, q32 = 0.0f;
-            int cnt = 0;
-            if (rows_valid >= H_BM) {                 // wave-uniform: full tiles carry no row predicate
-#pragma unroll
-                for (int i = 0; i < 8; ++i) {
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        float v = acc[i][j][r];
-                        if (ACT == KTF_ACT_RELU) v = fmaxf(v, 0.0f);
-                        else if (ACT != KTF_ACT_NONE) v = apply_act(v, ACT);
-                        v = v * scj + shj;
-                        const float u = v - pv;
-                        s32 += u;
-                        q32 = fmaf(u, u, q32);
-                    }
-                }
-                cnt = 32;
-            } else {
-#pragma unroll
-                for (int i = 0; i < 8; ++i) {
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const int m = i * 16 + g4 * 4 + r;
-                        float v = acc[i][j][r];
-                        if (ACT == KTF_ACT_RELU) v = fmaxf(v, 0.0f);
-                        else if (ACT != KTF_ACT_NONE) v = apply_act(v, ACT);
-                        v = v * scj + shj;
-                        if (m < rows_valid) {
-                            const float u = v - pv;
-                            s32 += u;
-                            q32 = fmaf(u, u, q32);
-                            ++cnt;
-                        }
-                    }
-                }
-            }
-            const double pd = (double)pv, sd = (double)s32, nd = (double)cnt;
-            double sm = sd + nd * pd;
-            double sq = (double)q32 + 2.0 * pd * sd + nd * pd * pd;
-            sm += __shfl_xor(sm, 16, 64); sq += __shfl_xor(sq, 16, 64);
-            sm += __shfl_xor(sm, 32, 64); sq += __shfl_xor(sq, 32, 64);
+            POOLED_SUMS16(ACT, false, true, acc, j, 0.0f, scj, shj, rows_valid, sm, sq)
             const int n = n0 + nl;
             if (lane < 16 && n < p.units) stats_out(stats, p, b, t0 >> 7, n, sm, sq);
         }
         return;
     }
-    // acc[i][j][e] = out[row i*16 + c][col wn*64 + j*16 + g4*4 + e]
-    f32x4v sc[4], sh[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        sc[j] = *reinterpret_cast<const f32x4v*>(prm + H_BN + wn * 64 + j * 16 + g4 * 4);
-        sh[j] = *reinterpret_cast<const f32x4v*>(prm + 2 * H_BN + wn * 64 + j * 16 + g4 * 4);
-    }
-    const int64_t out_row0 = (int64_t)b * p.Tout + t0;
+    // swapped layout: acc[i][j][e] = out[row i*16 + c][col wn*64 + j*16 + g4*4 + e]
+    Epi16Cols cols;
+    epi16_cols_lds<H_BN, false>(cols, prm, wn, lane);
     if (p.y_dtype == KTF_F32) {
-        float* ybase = reinterpret_cast<float*>(p.y);
-        const bool vec_ok = ((p.ldy & 3) == 0) && ((reinterpret_cast<uintptr_t>(p.y) & 15) == 0);
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            const int m = i * 16 + c;
-            if (m >= rows_valid) continue;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                f32x4v v = acc[i][j];
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    if (ACT == KTF_ACT_RELU) v[e] = fmaxf(v[e], 0.0f);
-                    else if (ACT != KTF_ACT_NONE) v[e] = apply_act(v[e], ACT);
-                }
-                v = v * sc[j] + sh[j];
-                const int n = n0 + wn * 64 + j * 16 + g4 * 4;
-                float* yp = ybase + (out_row0 + m) * p.ldy + n;
-                if (vec_ok && n + 4 <= p.units) {
-                    *reinterpret_cast<f32x4v*>(yp) = v;
-                } else {
-#pragma unroll
-                    for (int e = 0; e < 4; ++e)
-                        if (n + e < p.units) yp[e] = v[e];
-                }
-            }
-        }
+        ring_epilogue16_direct<ACT, false, true>(acc, p, cols, b, t0, n0, out_len, 0, wn, lane);
         return;
     }
     __syncthreads();                                  // all fragment reads done: the ring becomes the staging buffer
-    {
-        unsigned char* stg = rsm + c * H_PK_PITCH + (wn * 64 + g4 * 4) * 2;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                f32x4v v = acc[i][j];
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    if (ACT == KTF_ACT_RELU) v[e] = fmaxf(v[e], 0.0f);
-                    else if (ACT != KTF_ACT_NONE) v[e] = apply_act(v[e], ACT);
-                }
-                v = v * sc[j] + sh[j];
-                uint2 pk;
-                pk.x = (unsigned)f2bf(v[0]) | ((unsigned)f2bf(v[1]) << 16);
-                pk.y = (unsigned)f2bf(v[2]) | ((unsigned)f2bf(v[3]) << 16);
-                *reinterpret_cast<uint2*>(stg + i * 16 * H_PK_PITCH + j * 32) = pk;
-            }
-        }
-    }
+    r16_stage_pk<ACT, false>(acc, cols, rsm, 0, wn, lane);
     __syncthreads();
-    {
-        const int n8 = n0 + (lane & 31) * 8;
-        const bool wide = (n8 + 8 <= p.units) && ((p.ldy & 7) == 0) && ((reinterpret_cast<uintptr_t>(p.y) & 15) == 0);
-        unsigned short* ybase = reinterpret_cast<unsigned short*>(p.y);
-#pragma unroll 4
-        for (int sp = 0; sp < 16; ++sp) {
-            const int m = wn * 32 + sp * 2 + (lane >> 5);
-            if (m < rows_valid) {
-                const unsigned char* src = rsm + m * H_PK_PITCH + (lane & 31) * 16;
-                const uint2 lo = *reinterpret_cast<const uint2*>(src);
-                const uint2 hi = *reinterpret_cast<const uint2*>(src + 8);
-                unsigned short* yp = ybase + (out_row0 + m) * p.ldy + n8;
-                if (wide) {
-                    u32x4 o;
-                    o.x = lo.x; o.y = lo.y; o.z = hi.x; o.w = hi.y;
-                    *reinterpret_cast<u32x4*>(yp) = o;
-                } else {
-                    const unsigned w4[4] = {lo.x, lo.y, hi.x, hi.y};
-#pragma unroll
-                    for (int e = 0; e < 8; ++e)
-                        if (n8 + e < p.units) yp[e] = (unsigned short)(w4[e >> 1] >> ((e & 1) * 16));
-                }
-            }
-        }
-    }
+    r16_store_staged(p, rsm, reinterpret_cast<unsigned short*>(p.y), b, t0, n0, out_len, wn, lane);
 }
 
 
@@ -1179,7 +764,7 @@ int tdnn_launch_16(const TdnnParams& p, const KtfTdnnDesc* d, int64_t B, int64_t
                     });
                 });
             } else {
-                tdnn_pick<KTF_ACT_NONE, KTF_ACT_RELU, KTF_ACT_SIGMOID, KTF_ACT_TANH>(d->act, [&](auto A) {
+                tdnn_pick<KTF_ACT_SIGMOID, KTF_ACT_TANH>(d->act, [&](auto A) {
                     tdnn_pick<true, false>(stats_sums != nullptr, [&](auto ST) {
                         tdnn_launch_kernel<tdnn_bf16r_kernel<A, ST>>("tdnn_bf16r_kernel", dim3((unsigned)nblocks), dim3(512), R_LDS_BYTES, R_LDS_BYTES,
                                                                       st, p, mtiles, ntiles_r, (int)gtiles, stats_sums);

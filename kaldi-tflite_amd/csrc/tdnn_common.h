@@ -82,6 +82,26 @@ __device__ __forceinline__ int tdnn_out_len(int len, const TdnnParams& p, int& s
     return n <= 0 ? 0 : (n + p.sub - 1) / p.sub;
 }
 
+// The tile header of the kernels on the grouped 1-D walk (grouped_blocks below): block ID -> (xcd = ID % 8, slot = ID / 8); an XCD
+// walks its own M-tiles and runs all N-tiles of one M-tile back to back, so the gathered activation rows are fetched into that XCD's
+// L2 once. Declares the BM x BN tile's b (utterance), len, start (first input row: VALID padding), out_len, t0 / n0 (first output
+// row / unit) and nt (N-tile) from the kernel's p, mtiles, ntiles, gtiles; the utterance's first tile writes out_lens[b]; returns
+// from the kernel where no tile stands behind the block or the tile holds no valid row.
+// (A macro: as an inlined function filling a struct it changed the register allocation and the code of every ring kernel.)
+#define TDNN_TILE_HEADER(BM, BN, ID)                                                                   \
+    const int tile_id_ = (ID), tile_xcd_ = tile_id_ & 7, tile_slot_ = tile_id_ >> 3;                   \
+    const int tile_g_ = (tile_slot_ / ntiles) * 8 + tile_xcd_;     /* global M-tile index */           \
+    const int nt = tile_slot_ - (tile_slot_ / ntiles) * ntiles;                                        \
+    if (tile_g_ >= gtiles) return;                                                                     \
+    const int b = tile_g_ / mtiles, tile_mt_ = tile_g_ - b * mtiles;                                   \
+    const int len = p.lens ? p.lens[b] : (int)p.T;                                                     \
+    int start;                                                                                         \
+    const int out_len = tdnn_out_len(len, p, start);                                                   \
+    if (p.out_lens && nt == 0 && tile_mt_ == 0 && threadIdx.x == 0) p.out_lens[b] = out_len;           \
+    const int t0 = tile_mt_ * (BM);                                                                    \
+    if (t0 >= out_len || len <= 0) return;                                                             \
+    const int n0 = nt * (BN);
+
 __device__ __forceinline__ float apply_act(float v, int act) {
     if (act == KTF_ACT_RELU) return v < 0.0f ? 0.0f : v;      // tf.nn.relu propagates NaN (Eigen cwiseMax<PropagateNaN>): the pooled row of an
                                                               // utterance without a frame stays NaN through the layers behind the pooling; fmaxf would return 0

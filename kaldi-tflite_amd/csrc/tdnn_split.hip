@@ -1,5 +1,7 @@
 // The plane kernels of KTF_GEMM_BF16X3 (split-bf16: x = hi + lo, w = hi + lo, three bf16 MFMA passes, fp32-grade accuracy) on the
-// 256 x 256 ring tile.
+// 256 x 256 ring tile: tdnn_x3r_kernel (fp32 activations, split in registers) on tdnn_ring.h's tile header, feed and 32x32 epilogue;
+// tdnn_x3s_kernel (hi / lo planes) with a header and a feed of its own (W before the length load, flat row tiles, interleaved K) and
+// the shared 16x16 epilogue.
 #include "tdnn_ring.h"
 #include "flat_stats.h"
 
@@ -17,9 +19,8 @@ __device__ __forceinline__ void split_bf16x8(const f32x4& v0, const f32x4& v1, b
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
         const unsigned short h0 = f2bf(x[2 * e]), h1 = f2bf(x[2 * e + 1]);
-        H.u[e] = (unsigned)h0 | ((unsigned)h1 << 16);
-        const unsigned short l0 = f2bf(x[2 * e] - bf2f(h0)), l1 = f2bf(x[2 * e + 1] - bf2f(h1));
-        Lw.u[e] = (unsigned)l0 | ((unsigned)l1 << 16);
+        H.u[e] = PACK_BF16X2(x[2 * e], x[2 * e + 1]);
+        Lw.u[e] = PACK_BF16X2_LO(x[2 * e], x[2 * e + 1], h0, h1);
     }
     hi = H.f;
     lo = Lw.f;
@@ -32,28 +33,14 @@ template <int ACT, bool STATS>
 __global__ __launch_bounds__(512) void tdnn_x3r_kernel(TdnnParams p, int mtiles, int ntiles, int gtiles,
                                                        double* __restrict__ stats) {
     extern __shared__ __attribute__((aligned(16))) unsigned char rsm[];
-    const int id = blockIdx.x;
-    const int xcd = id & 7, slot = id >> 3;
-    const int g = (slot / ntiles) * 8 + xcd;
-    const int nt = slot - (slot / ntiles) * ntiles;
-    if (g >= gtiles) return;
-    const int b = g / mtiles, mt = g - b * mtiles;
-    const int len = p.lens ? p.lens[b] : (int)p.T;
-    int start;
-    const int out_len = tdnn_out_len(len, p, start);
-    if (p.out_lens && nt == 0 && mt == 0 && threadIdx.x == 0) p.out_lens[b] = out_len;
-    const int t0 = mt * R_BM;
-    if (t0 >= out_len || len <= 0) return;
-    const int n0 = nt * R_BN;
+    TDNN_TILE_HEADER(R_BM, R_BN, blockIdx.x)
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave >> 2, wn = wave & 3;
 
     constexpr int XB = 4;                              // bytes per activation element
-    const char* xb = reinterpret_cast<const char*>(p.x) + ((int64_t)b * p.T * p.ldx) * XB;
-    const char* wb = reinterpret_cast<const char*>(p.w);
+    RING_FEED_BASES(XB)
     const char* wl = reinterpret_cast<const char*>(p.w_lo);
-    const unsigned ldxb = (unsigned)p.ldx * XB;
 
     // A staging: chunk q = i*512 + tid (i < 4) -> row q/8, LDS position q%8, global chunk (q%8) ^ ((row>>1)&7)
     int a_t[4];
@@ -82,31 +69,16 @@ __global__ __launch_bounds__(512) void tdnn_x3r_kernel(TdnnParams p, int mtiles,
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.0f;
 
-    const int nk = p.ktot / R_BK;
-    const int lenm1 = len - 1;
-    int is_ks = 0, is_c = 0, is_db = 0, is_off = p.ctx[0];
-    const int dpad_b = p.din_pad * XB;
+    RING_FEED_ITER(XB)
+    // a double buffer of A fp32 | W hi | W lo: four pieces of A and two of each W plane per thread
 #define X_STAGE()                                                                                                      \
     {                                                                                                                  \
-        unsigned char* st_ = rsm + (is_ks & 1) * X_STAGE_BYTES + wave * 1024;                                          \
-        _Pragma("unroll") for (int i = 0; i < 4; ++i) {                                                                \
-            int r_ = a_t[i] + is_off;                                                                                  \
-            r_ = r_ < 0 ? 0 : (r_ > lenm1 ? lenm1 : r_);                                                               \
-            const unsigned vo_ = (unsigned)r_ * ldxb + a_cb[i] + (unsigned)is_db;                                      \
-            __builtin_amdgcn_global_load_lds((glb_ptr_t*)(xb + vo_), (lds_ptr_t*)(st_ + i * 8192), 16, 0, 0); \
-        }                                                                                                              \
+        _Pragma("unroll") for (int i = 0; i < 4; ++i) RING_DMA_A(i, is_ks & 1, X_STAGE_BYTES, 8192)                    \
         _Pragma("unroll") for (int i = 0; i < 2; ++i) {                                                                \
-            const unsigned vo_ = w_ob[i] + (unsigned)(is_ks * (R_BK * 2));                                             \
-            __builtin_amdgcn_global_load_lds((glb_ptr_t*)(wb + vo_), (lds_ptr_t*)(st_ + 32768 + i * 8192), 16, 0, 0);  \
-            __builtin_amdgcn_global_load_lds((glb_ptr_t*)(wl + vo_), (lds_ptr_t*)(st_ + 32768 + R_TILE_BYTES + i * 8192), 16, 0, 0); \
+            RING_DMA_W(i, wb, is_ks & 1, X_STAGE_BYTES, 32768, 8192)                                                   \
+            RING_DMA_W(i, wl, is_ks & 1, X_STAGE_BYTES, 32768 + R_TILE_BYTES, 8192)                                    \
         }                                                                                                              \
-        ++is_ks;                                                                                                       \
-        is_db += R_BK * XB;                                                                                            \
-        if (is_db == dpad_b) {                                                                                         \
-            is_db = 0;                                                                                                 \
-            ++is_c;                                                                                                    \
-            is_off = (is_c < p.nctx) ? p.ctx[is_c] : 0;                                                                \
-        }                                                                                                              \
+        RING_ADVANCE(XB)                                                                                               \
     }
 
     X_STAGE()
@@ -189,10 +161,7 @@ __device__ __forceinline__ void flat_stats_epilogue(f32x4v (&acc)[8][4], const T
         for (int i = 0; i < 8; ++i)
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                float v = acc[i][j][r] + prm.bias[j];
-                if (ACT == KTF_ACT_RELU) v = fmaxf(v, 0.0f);
-                else if (ACT != KTF_ACT_NONE) v = apply_act(v, ACT);
-                acc[i][j][r] = v * prm.sc[j] + prm.sh[j];
+                acc[i][j][r] = EPI_VALUE(ACT, acc[i][j][r], prm.bias[j], prm.sc[j], prm.sh[j]);
             }
     const int T = (int)p.T;
     flat_stats_runs(acc, R0, rows_valid, wm, lane,

@@ -520,6 +520,7 @@ def test_library_kernel_families():
                         "tdnn_bf16g_kernel", "tdnn_bf16r_kernel", "tdnn_bf16r16_kernel", "tdnn_bf16h_kernel", "tdnn_x3r_kernel",
                         "tdnn_x3s_kernel", "tdnn_x4s_kernel", "tdnn_mx_kernel", "tdnn_mxl_kernel",
                         "tdnn_out_lens_kernel"}, fam          # (the last one: ktf_tdnn_out_lens, lengths only)
+    assert fam["tdnn_bf16r_kernel"] == 4                # {sigmoid, tanh} x {store, pooled}: ReLU / none run on the 16x16x32 kernels
     assert fam["tdnn_x3r_kernel"] == 8                  # 4 activations x {store, pooled}: fp32 activations only
     assert fam["tdnn_x3s_kernel"] == 8 + 8 + 4          # split-bf16 (4 activations x {rows, pooled}, plain and row-group-skipping; flat rows: {ReLU, none} x {rows, pooled})
     assert fam["tdnn_x4s_kernel"] == 8                  # bf16-pair small tiles: 64 x 32 / 64 / 96 and the K-step-32 form, x {rows, pooled}
