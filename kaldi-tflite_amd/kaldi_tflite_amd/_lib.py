@@ -228,6 +228,14 @@ AUGMENT_PROTOTYPES = {
     "ktf_aug_mix": (C.c_int, [_P, _P, _P, _P, _i32, _P, _i32, _i32, _P, _P, _P, _P, _P, _P, _P, _P, _i32, _i32, _i32, C.c_double, _P,
                               _i32, _i64, _i64, _P, _P, C.c_size_t, _P]),
 }
+# name -> (restype, argtypes); mirrors include/ktf_resample.h one to one
+RESAMPLE_PROTOTYPES = {
+    "ktf_rs_tile": (_i32, []),
+    "ktf_rs_plan_sizes": (C.c_int, [_i32, _i32, C.c_double, _i32, _P, _P, _P]),
+    "ktf_rs_plan": (C.c_int, [_i32, _i32, C.c_double, _i32, _P, _P, _P, _i32]),
+    "ktf_rs_num_out": (_i64, [_i64, _i32, _i32]),
+    "ktf_rs_resample": (C.c_int, [_P, _i32, _i64, _P, _P, _i32, _i32, _i32, _P, _P, _P, _P, _P, _i32, _P, _i32, _i64, _i64, _P]),
+}
 AUG_META, AUG_STATS = 8, 4          # ktf_aug_*: int32 per RIR of the bank's meta; doubles per row of the statistics
 PLDA_DENSE_NO_PCA = -1.0            # ktf_plda_dense_*: target_energy for "no PCA"
 PLDA_DENSE_MAX_DIM = 512
@@ -240,6 +248,7 @@ ADD_DELTAS_MAX_CONTEXT = 32         # ktf_add_deltas_f32: order * window
 TRAIN_MAX_DIM = 1024                # ktf_train_*, ktf_plda_em_project
 VB_MAX_SPEAKERS, VB_FB_CHUNK = 16, 128   # ktf_vb_*: speakers per recording, blocks per chunk of the forward-backward scan
 VBX_MAX_DIM, VBX_UPDATE_ROWS = 512, 256  # ktf_vbx_*: dimensions; windows per workgroup of the speaker update
+RS_MAX_SAMPLES = 1 << 30            # ktf_rs_*: samples per row, in or out
 
 _lib = None
 
@@ -254,7 +263,7 @@ def load():
             f"{LIB_PATH} not found: build it with `make -C kaldi-tflite_amd/csrc` (or __graft_entry__.build()). "
             "There is no CPU fallback.")
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in list(PROTOTYPES.items()) + list(AUGMENT_PROTOTYPES.items()):
+    for name, (res, args) in list(PROTOTYPES.items()) + list(AUGMENT_PROTOTYPES.items()) + list(RESAMPLE_PROTOTYPES.items()):
         fn = getattr(lib, name)          # AttributeError = header/library mismatch
         fn.restype = res
         fn.argtypes = args

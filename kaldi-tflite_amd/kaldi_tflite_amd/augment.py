@@ -8,7 +8,25 @@ The semantics are the project's own, stated in include/ktf_augment.h; tests/_aug
     plan = ktf.augment.plan_additives("babble", [len(w) / 16000 for w in wavs], noises.lengths_s, seed=0)
     out, lengths = ktf.augment.augment(wavs, rirs=rirs, rir_ids=[0, 1, -1, ...], noises=noises, additives=plan)
     xvectors = extractor(out)                                      # (equal lengths; else [out[b, :l] for b, l in enumerate(lengths)])
+
+Sample-rate conversion (the rules are stated in include/ktf_resample.h, tests/_resample_ref.py restates them in
+fp64): a windowed-sinc polyphase resampler after Kaldi's LinearResample in its whole-signal mode, and speed perturbation on top.
+
+    to8k = ktf.augment.Resampler(16000, 8000)                      # the plan, computed once
+    out, lengths = to8k(wavs)                                      # wavs as augment() takes them, fp32 or int16
+    out, lengths = ktf.augment.resample(wavs, 44100, 16000)        # one-shot; equal rates return the input
+    fast, lengths = ktf.augment.speed_perturb(wavs, 1.1)           # sox `speed 1.1`: 11 -> 10, read at the old rate
+
+augment() still refuses a bank at another rate than the signals': convert the arrays first and build the bank at the new rate.
+
+    rirs8k, n = to8k(rirs16k)                                      # 16 kHz RIRs and noises for an 8 kHz recipe
+    rirs = ktf.augment.RirBank([rirs8k[r, :l].cpu().numpy() for r, l in enumerate(n)], sample_rate=8000)
+    noise8k, n = to8k(noises16k)
+    noises = ktf.augment.NoiseBank([noise8k[r, :l].cpu().numpy() for r, l in enumerate(n)], sample_rate=8000)
+    out, lengths = ktf.augment.augment(wavs8k, rirs=rirs, rir_ids=ids, noises=noises, additives=plan, sample_rate=8000)
 """
+
+import fractions
 
 import numpy as np
 import torch
@@ -291,3 +309,102 @@ def augment(wavs, lengths=None, rirs=None, rir_ids=None, noises=None, additives=
                         normalize_output, volume, out[lo:hi], stats[lo:hi], ws)
     lens = [int(v) for v in out_len]
     return (out, lens, stats) if return_stats else (out, lens)
+
+
+# ----------------------------------------------------------------------------- sample-rate conversion (include/ktf_resample.h)
+def _rate(rate, what):
+    if not is_int(rate) or rate <= 0:
+        raise ValueError(f"{what} must be a positive int, got {rate!r}")
+    return int(rate)
+
+
+class Resampler:
+    """orig_rate -> new_rate (different positive ints) with Kaldi's LinearResample rules: lowpass_cutoff in Hz (None: 0.99 of the
+    lower Nyquist frequency), num_zeros zero crossings of the sinc on each side. The polyphase plan is computed on the host here
+    (`.iu` input and `.ou` output samples per repeating unit, `.first`, `.taps`, `.weights`) and uploaded once, at the first call.
+    Only the ratio matters: Resampler(11, 10) and Resampler(17600, 16000) hold the same filter."""
+
+    def __init__(self, orig_rate, new_rate, lowpass_cutoff=None, num_zeros=6, device=None):
+        self.orig_rate, self.new_rate = _rate(orig_rate, "orig_rate"), _rate(new_rate, "new_rate")
+        if self.orig_rate == self.new_rate:
+            raise ValueError(f"Resampler: equal rates ({self.orig_rate}): nothing to resample (resample() passes such input through)")
+        if not is_int(num_zeros) or num_zeros < 1:
+            raise ValueError(f"num_zeros must be an int >= 1, got {num_zeros!r}")
+        if lowpass_cutoff is None:
+            lowpass_cutoff = 0.99 * 0.5 * min(self.orig_rate, self.new_rate)
+        if not is_real(lowpass_cutoff) or not 0 < lowpass_cutoff <= 0.5 * min(self.orig_rate, self.new_rate):
+            raise ValueError(f"lowpass_cutoff must lie in (0, {0.5 * min(self.orig_rate, self.new_rate)}], got {lowpass_cutoff!r}")
+        self.cutoff, self.num_zeros = float(lowpass_cutoff), int(num_zeros)
+        self.iu, self.ou, self.first, self.taps, self.weights = ops.rs_plan(self.orig_rate, self.new_rate, self.cutoff, self.num_zeros)
+        L.require_gpu()
+        self.device = torch.device(device) if device is not None else None
+        self._dev = None
+
+    def num_out(self, n):
+        """Output samples of n input samples."""
+        return ops.rs_num_out(n, self.orig_rate, self.new_rate)
+
+    def _plan_on(self, device):
+        if self._dev is None or self._dev[0] != device:
+            self._dev = (device,) + tuple(torch.as_tensor(a, device=device) for a in (self.first, self.taps, self.weights))
+        return self._dev[1:]
+
+    def __call__(self, wavs, lengths=None, out_dtype=None):
+        """wavs as augment() takes them, fp32 or int16 -> (out (B, T_out) on the device, out_dtype or the input's dtype, zeros past
+        each row's length; lengths, B host ints). A row's bits depend on that row alone."""
+        if out_dtype not in (None, torch.float32, torch.int16):
+            raise ValueError(f"out_dtype must be torch.float32 or torch.int16, got {out_dtype}")
+        L.require_gpu()
+        x, n = _signals(wavs, lengths)
+        if self.device is not None and x.device != self.device:
+            raise ValueError(f"the Resampler lives on {self.device}, the signals on {x.device}")
+        if n.size and int(n.max()) > L.RS_MAX_SAMPLES:
+            raise ValueError("more than 2^30 samples in a row")
+        m = [self.num_out(int(v)) for v in n]
+        B, T_out = n.size, max(m, default=0)
+        out = torch.empty((B, T_out), dtype=out_dtype or x.dtype, device=x.device)
+        with L.launch_scope(x.device):
+            first_dev, taps_dev, w_dev = self._plan_on(x.device)
+            n_dev = torch.as_tensor(n, device=x.device)
+            for lo in range(0, B, 65535):
+                hi = min(B, lo + 65535)
+                ops.rs_resample(x[lo:hi], n[lo:hi], n_dev[lo:hi], self.iu, self.ou, self.first, self.taps, first_dev, taps_dev, w_dev,
+                                out[lo:hi])
+        return out, m
+
+
+def resample(wavs, orig_rate, new_rate, lengths=None, out_dtype=None, **kw):
+    """One-shot Resampler(orig_rate, new_rate, **kw)(wavs, lengths, out_dtype). Equal rates return the input unfiltered (Kaldi's
+    ResampleWaveform would low-pass it): a (B, T) tensor as it is, anything else as the padded (B, T) device tensor."""
+    if _rate(orig_rate, "orig_rate") != _rate(new_rate, "new_rate"):
+        return Resampler(orig_rate, new_rate, **kw)(wavs, lengths, out_dtype)
+    if isinstance(wavs, torch.Tensor) and wavs.dim() == 2:
+        B, T = wavs.shape
+        n = np.full(B, T, np.int64) if lengths is None else host(lengths).astype(np.int64).reshape(-1)
+        if n.size != B or (n < 0).any() or (n > T).any():
+            raise ValueError(f"lengths must be {B} values in 0 .. {T}")
+        x = wavs
+    else:
+        L.require_gpu()
+        x, n = _signals(wavs, lengths)
+    if out_dtype not in (None, x.dtype):
+        raise ValueError(f"equal rates return the input as it is ({x.dtype}): out_dtype {out_dtype} would need a conversion")
+    return x, [int(v) for v in n]
+
+
+def speed_rates(factor):
+    """The integer rates (p, q) a speed factor resamples between: fractions.Fraction(str(factor)) = p / q."""
+    try:
+        fr = fractions.Fraction(str(factor))
+    except (ValueError, ZeroDivisionError):
+        raise ValueError(f"factor must be a positive number, got {factor!r}") from None
+    if fr <= 0:
+        raise ValueError(f"factor must be a positive number, got {factor!r}")
+    return fr.numerator, fr.denominator
+
+
+def speed_perturb(wavs, factor, lengths=None, out_dtype=None, **kw):
+    """What `sox speed factor` does (utils/data/perturb_data_dir_speed.sh: 0.9 and 1.1): a resampling p -> q for factor = p / q whose
+    result is read at the old rate, so 1.1 leaves 10 samples for every 11. factor 1 returns the input."""
+    p, q = speed_rates(factor)
+    return resample(wavs, p, q, lengths=lengths, out_dtype=out_dtype, **kw)

@@ -1359,3 +1359,38 @@ def aug_mix(n, n_dev, rir_ids, rir_ids_dev, rir_lengths, fs, meta, add_offsets, 
           int(bool(shift_output)), int(bool(normalize_output)), float(volume), L.ptr(out), int(out.dtype == torch.int16), _ld(out),
           out.shape[1], L.ptr(stats), L.ptr(workspace), workspace.numel())
     return out, stats
+
+
+# ----------------------------------------------------------------------------- sample-rate conversion (include/ktf_resample.h)
+def rs_tile():
+    """Consecutive outputs of one row per workgroup of the resampling kernel."""
+    return int(L.load().ktf_rs_tile())
+
+
+def rs_plan(fi, fo, cutoff, zeros):
+    """The polyphase plan of fi -> fo (rules 1 and 2 of ktf_resample.h), host only -> (iu, ou, first (ou,) int32, taps (ou,) int32,
+    w (ou, max taps) fp32, zero past a phase's taps)."""
+    lib = L.load()
+    sizes = (C.c_int32 * 3)()
+    at = lambda k: C.c_void_p(C.addressof(sizes) + 4 * k)  # noqa: E731
+    L.check(lib.ktf_rs_plan_sizes(int(fi), int(fo), float(cutoff), int(zeros), at(0), at(1), at(2)), "ktf_rs_plan_sizes")
+    ou, iu, max_taps = (int(v) for v in sizes)
+    first, taps, w = np.zeros(ou, np.int32), np.zeros(ou, np.int32), np.zeros((ou, max_taps), np.float32)
+    L.check(lib.ktf_rs_plan(int(fi), int(fo), float(cutoff), int(zeros), _host_ptr(first), _host_ptr(taps), _host_ptr(w), max_taps), "ktf_rs_plan")
+    return iu, ou, first, taps, w
+
+
+def rs_num_out(n, fi, fo):
+    """Output samples of n input samples (rule 3)."""
+    return _size("ktf_rs_num_out", int(n), int(fi), int(fo))
+
+
+def rs_resample(x, n, n_dev, iu, ou, first, taps, first_dev, taps_dev, w_dev, out):
+    """Rows x (B, T) fp32 / int16 (rows may be strided) of n samples (host int32; n_dev the same on the device) through the plan
+    (first / taps host int32, *_dev on the device, w_dev (ou, ldw) fp32) into out (B, T_out) fp32 / int16: zeros from a row's own
+    length on."""
+    n, first, taps = _host_i32(n), _host_i32(first), _host_i32(taps)
+    _call("ktf_rs_resample", out.device, L.ptr(x), int(x.dtype == torch.int16), _ld(x), _host_or_null(n), L.ptr(n_dev), n.size, int(iu),
+          int(ou), _host_ptr(first), _host_ptr(taps), L.ptr(first_dev), L.ptr(taps_dev), L.ptr(w_dev), _ld(w_dev), L.ptr(out),
+          int(out.dtype == torch.int16), _ld(out), out.shape[1])
+    return out
