@@ -301,6 +301,24 @@ const char* ktf_tdnn_last_kernel(void);
 
 /* number of output rows for an utterance with `len` input rows (tdnn.py:224-234) */
 int64_t ktf_tdnn_out_len(int64_t len, const KtfTdnnDesc* d);
+/* Alignment of y (and y_lo) and ldy, per kernel family of the 16-bit modes (KTF_GEMM_BF16, KTF_GEMM_BF16X3; ktf_tdnn and ktf_tdnn_split*).
+ * Always ldy >= units; columns [units, ldy) and rows at or beyond an utterance's output length are not written. Which family runs is
+ * decided by the layer (ktf_tdnn_last_kernel names it), and ldy % 4 != 0 sends ktf_tdnn to the 128 x 128 tdnn_bf16_kernel:
+ *   tdnn_bf16_kernel<...>  (KTF_GEMM_BF16 on fp32 x; KTF_GEMM_BF16X3 on fp32 x with units <= 128 or ldy % 4 != 0; bf16 x that none of
+ *                          the kernels below takes): element stores -- any ldy, y aligned to its element.
+ *   tdnn_bf16g_kernel      (bf16 x, units <= 128, din_pad % 64 == 0, ldy % 4 == 0): 16-byte stores of fp32 rows, 8-byte stores of bf16
+ *                          rows -- y 16-byte (fp32) / 8-byte (bf16) aligned. REFUSED otherwise.
+ *   tdnn_bf16h_kernel      (bf16 x, units > 128, ldy % 4 == 0, K <= 768, ReLU / none): tests at run time -- 16-byte stores where y is
+ *                          16-byte aligned and ldy % 4 == 0 (fp32) / ldy % 8 == 0 (bf16), element stores otherwise. Any y aligned to its element.
+ *   tdnn_bf16r16_kernel    (the same layers with K > 768): fp32 rows by unconditional 16-byte stores -- y 16-byte aligned, REFUSED
+ *                          otherwise; bf16 rows through the run-time test of tdnn_bf16h_kernel -- any y aligned to its element.
+ *   tdnn_bf16r_kernel, tdnn_x3r_kernel  (sigmoid / tanh; KTF_GEMM_BF16X3 on fp32 x; units > 128, ldy % 4 == 0): 16-byte stores of fp32
+ *                          rows, 8-byte stores of bf16 rows -- y 16-byte (fp32) / 8-byte (bf16) aligned. REFUSED otherwise.
+ *   tdnn_x3s_kernel        (ktf_tdnn_split, ktf_tdnn_split_flat: units > 128 and ldy % 4 == 0 or the call is refused): fp32 rows as
+ *                          above; the hi / lo planes by 16-byte stores of 8 columns at column offsets that are multiples of 8, from y and
+ *                          y_lo 8-byte aligned: with ldy % 8 == 4 every other row's stores are 8-byte aligned only, which the global
+ *                          stores of gfx950 accept (they ask for 4). REFUSED: y or y_lo not 16-byte (fp32) / 8-byte (bf16) aligned.
+ * The pooled calls (ktf_tdnn_stats, ktf_tdnn_split_stats, ktf_tdnn_split_flat_stats) write doubles into `sums`, 8-byte aligned. */
 /* ... for a batch's lengths on the device: out_lens[b] = ktf_tdnn_out_len(lens[b], d). (ktf_tdnn writes them itself; the entry points on
  * the MX planes have no such argument: a VALID-padded or subsampling layer there is followed by this call.) */
 int ktf_tdnn_out_lens(const int32_t* lens, int64_t B, const KtfTdnnDesc* d, int32_t* out_lens, void* stream);

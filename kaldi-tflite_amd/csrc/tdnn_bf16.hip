@@ -757,6 +757,7 @@ int tdnn_launch_16(const TdnnParams& p, const KtfTdnnDesc* d, int64_t B, int64_t
                     });
                 });
             } else if (d->act == KTF_ACT_RELU || d->act == KTF_ACT_NONE) {      // 16x16x32 MFMAs; sigmoid / tanh stay on the 32x32x16 kernel
+                TDNN_REQUIRE_Y_ALIGNED(p, stats_sums != nullptr || p.y_dtype != KTF_F32)      // (bf16 rows: r16_store_staged tests)
                 tdnn_pick<KTF_ACT_RELU, KTF_ACT_NONE>(d->act, [&](auto A) {
                     tdnn_pick<true, false>(stats_sums != nullptr, [&](auto ST) {
                         tdnn_launch_kernel<tdnn_bf16r16_kernel<A, ST>>("tdnn_bf16r16_kernel", dim3((unsigned)nblocks), dim3(512), R16_LDS_BYTES,
@@ -764,6 +765,7 @@ int tdnn_launch_16(const TdnnParams& p, const KtfTdnnDesc* d, int64_t B, int64_t
                     });
                 });
             } else {
+                TDNN_REQUIRE_Y_ALIGNED(p, stats_sums != nullptr)
                 tdnn_pick<KTF_ACT_SIGMOID, KTF_ACT_TANH>(d->act, [&](auto A) {
                     tdnn_pick<true, false>(stats_sums != nullptr, [&](auto ST) {
                         tdnn_launch_kernel<tdnn_bf16r_kernel<A, ST>>("tdnn_bf16r_kernel", dim3((unsigned)nblocks), dim3(512), R_LDS_BYTES, R_LDS_BYTES,
@@ -776,6 +778,7 @@ int tdnn_launch_16(const TdnnParams& p, const KtfTdnnDesc* d, int64_t B, int64_t
             const int64_t gtiles = B * (int64_t)mtiles;
             const int64_t nblocks = grouped_blocks(gtiles, ntiles_g);
             KTF_REQUIRE(nblocks < (1ll << 31), "ktf_tdnn: grid too large");
+            TDNN_REQUIRE_Y_ALIGNED(p, false)
             tdnn_launch_kernel<tdnn_bf16g_kernel>("tdnn_bf16g_kernel", dim3((unsigned)nblocks), dim3(256), G_LDS_BYTES, G_LDS_BYTES, st, p, mtiles,
                                                   ntiles_g, (int)gtiles);
         } else {

@@ -247,6 +247,17 @@ static inline int tdnn_check_desc(const KtfTdnnDesc* d, const float* scale, cons
     return KTF_OK;
 }
 
+// The alignment of y / y_lo that the vector stores of the 256 x 256 ring epilogues and of tdnn_bf16g_kernel assume (with ldy % 4 == 0, which
+// their dispatch tests): 16 bytes for fp32 rows, 8 bytes for 16-bit rows. (tdnn_bf16h_kernel, the bf16 rows of tdnn_bf16r16_kernel and the
+// 128 x 128 tdnn_bf16_kernel test or need none; include/ktf_hip.h has the table.) Pooled launches write no y.
+#define TDNN_REQUIRE_Y_ALIGNED(p, pooled)                                                                                       \
+    if (!(pooled)) {                                                                                                            \
+        const uintptr_t ymask_ = (p).y_dtype == KTF_F32 ? 15 : 7;                                                               \
+        KTF_REQUIRE(((reinterpret_cast<uintptr_t>((p).y) | reinterpret_cast<uintptr_t>((p).y_lo)) & ymask_) == 0,               \
+                    "ktf_tdnn: y (and y_lo) must be %d-byte aligned for this layer's kernel (units > 128 or a 64-multiple input width, ldy %% 4 == 0)", \
+                    (int)ymask_ + 1);                                                                                           \
+    }
+
 // per-family launchers (validation of the family's own constraints + launch); `p` is filled by tdnn_gemm.hip
 int tdnn_launch_f32(const TdnnParams& p, const KtfTdnnDesc* d, int64_t B, int64_t Tout, hipStream_t st);
 int tdnn_launch_x4(const TdnnParams& p, const KtfTdnnDesc* d, int64_t B, int64_t Tout, double* stats, hipStream_t st);   // tdnn_pair.hip

@@ -488,6 +488,7 @@ int tdnn_launch_split(const TdnnParams& p, const KtfTdnnDesc* d, int64_t B, int6
     const int64_t gtiles = B * (int64_t)mtiles;
     const int64_t nblocks = grouped_blocks(gtiles, ntiles_r);
     KTF_REQUIRE(nblocks < (1ll << 31), "ktf_tdnn: grid too large");
+    TDNN_REQUIRE_Y_ALIGNED(p, stats_sums != nullptr)
     // hi / lo planes in: the 16x16x32 plane kernel; fp32 activations in: the kernel that splits them in registers
     if (split_in && p.row_starts) {              // ktf_tdnn_split_flat: M-tiles over the batch's valid rows laid end to end
         KTF_REQUIRE(!d->valid && d->subsampling == 1, "ktf_tdnn_split_flat: SAME padding, no subsampling");

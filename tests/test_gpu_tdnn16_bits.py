@@ -5,6 +5,8 @@ The cases are the smallest shapes that reach every path of the tile header, the 
 with lens = [T, 1, 0] (and once without lens), a full M-tile plus a two-row one, a partial N-tile, wide and narrow row tails, one /
 three / twenty-five K-steps, VALID padding, subsampling, bf16 and fp32 rows, with and without the BatchNorm affine, and the fused
 pooling in its reproducible layout (KTF_TDNN_DET_STATS; the atomic form is not bit-reproducible and has its parity tests).
+"The same bits" is not "the right values": tests/test_gpu_tdnn16_values.py compares every case here (through `launch`) with an fp64
+reference, so a regenerated golden file is checked against something other than the library that wrote it.
 
     python tests/test_gpu_tdnn16_bits.py --write      # regenerate the golden file (only for a deliberate change of the arithmetic)
 """
@@ -35,9 +37,14 @@ BF16, F32 = torch.bfloat16, torch.float32
 
 
 def case(name, kernel, K=SHORT, T=130, units=260, ldy=None, act="relu", ydt=BF16, affine=True, lens=True, padding="SAME", sub=1,
-         gemm=L.GEMM_BF16, xdt=BF16, mode="store"):
+         gemm=L.GEMM_BF16, xdt=BF16, mode="store", y_view=None, atomic=False):
+    """lens: True = (T, 1, 0), False / None = no lens, or the B lengths as a tuple. y_view: y is the column slice [y_view, y_view + units)
+    of the (B, Tout, ldy) buffer instead of the buffer itself. atomic: the pooled modes without KTF_TDNN_DET_STATS ((B, 2, units), zeroed
+    by the call). (y_view and atomic: the value-only cases of test_gpu_tdnn16_values.py; no golden case sets them.)"""
+    lens = (T, 1, 0) if lens is True else (tuple(int(n) for n in lens) if lens else None)
+    assert lens is None or len(lens) == B
     return dict(name=name, kernel=kernel, ctx=K[0], din=K[1], T=T, units=units, ldy=units if ldy is None else ldy, act=act, ydt=ydt,
-                affine=affine, lens=lens, padding=padding, sub=sub, gemm=gemm, xdt=xdt, mode=mode)
+                affine=affine, lens=lens, padding=padding, sub=sub, gemm=gemm, xdt=xdt, mode=mode, y_view=y_view, atomic=atomic)
 
 
 def ring16(tag, kernel, K, T):
@@ -93,25 +100,37 @@ def all_cases():
 CASES = {c["name"]: c for c in all_cases()}
 
 
-def run(c):
-    """sha256 of the output buffer of case c (inputs from a generator seeded with the case's shape, not its name)."""
-    dev = torch.device("cuda")
+def inputs(c):
+    """The case's x, W, bias, scale, shift as numpy fp32 (scale / shift None without the affine), from a generator seeded with the
+    case's shape, not its name. No GPU."""
     T, D, U, nctx = c["T"], c["din"], c["units"], len(c["ctx"])
     rng = np.random.default_rng([T, D, U, nctx, c["sub"]])
     x = rng.standard_normal((B, T, D)).astype(np.float32)
     W = (rng.standard_normal((U, nctx * D)) / np.sqrt(nctx * D)).astype(np.float32)
     bias = rng.standard_normal(U).astype(np.float32)
-    sc = torch.as_tensor(rng.uniform(0.5, 2.0, U).astype(np.float32), device=dev) if c["affine"] else None
-    sh = torch.as_tensor(rng.uniform(-1.0, 1.0, U).astype(np.float32), device=dev) if c["affine"] else None
+    sc = rng.uniform(0.5, 2.0, U).astype(np.float32) if c["affine"] else None
+    sh = rng.uniform(-1.0, 1.0, U).astype(np.float32) if c["affine"] else None
+    return x, W, bias, sc, sh
+
+
+def launch(c):
+    """Runs case c: a dict of the inputs as numpy (x, W, bias, scale, shift, lens; None where absent), the WHOLE output buffer `out`
+    (a CUDA tensor pre-filled with the sentinel) and, for the pooled modes, what the finalize needs (lens_dev / starts, slots)."""
+    dev = torch.device("cuda")
+    T, D, U = c["T"], c["din"], c["units"]
+    x, W, bias, sc_np, sh_np = inputs(c)
+    sc = torch.as_tensor(sc_np, device=dev) if c["affine"] else None
+    sh = torch.as_tensor(sh_np, device=dev) if c["affine"] else None
     t = ktf.layers.TDNN(U, context=list(c["ctx"]), subsampling_factor=c["sub"], padding=c["padding"], activation=c["act"], name="bits")
     t.build(x.shape)
     t.set_weights([W, bias])
-    lens = torch.as_tensor(np.array([T, 1, 0], np.int32), device=dev) if c["lens"] else None
+    lens = torch.as_tensor(np.array(c["lens"], np.int32), device=dev) if c["lens"] else None
     Tout = t.outputTimesteps(T)
     mode = c["mode"]
     split = mode in ("split", "split_pooled", "flat", "flat_pooled")
     pooled = mode in ("pooled", "split_pooled", "flat_pooled")
-    flags = L.TDNN_DET_STATS if pooled else 0
+    det = pooled and not c["atomic"]
+    flags = L.TDNN_DET_STATS if det else 0
     if split:
         flags |= L.TDNN_K_INTERLEAVED | L.TDNN_W_TILED
         xin = torch.zeros((2, B, T, D), dtype=BF16, device=dev)
@@ -122,30 +141,42 @@ def run(c):
         xin = torch.as_tensor(x).to(c["xdt"]).to(dev)
         w, w_lo, b = t.device_weights(dev, c["gemm"])
         d = t.desc(c["gemm"], c["xdt"], c["ydt"], flags=flags)
-    if pooled:
+    slots = 0
+    if det:
         slots = ops.flat_stats_slots(T) if mode == "flat_pooled" else ops.stats_slots(Tout)
         out = torch.full((B, slots, 2, U), SENTINEL, dtype=torch.float64, device=dev)
+    elif pooled:
+        out = torch.full((B, 2, U), SENTINEL, dtype=torch.float64, device=dev)
     elif split and c["ydt"] == BF16:
         out = torch.full((2, B, Tout, c["ldy"]), SENTINEL, dtype=BF16, device=dev)          # hi and lo planes
     else:
         out = torch.full((B, Tout, c["ldy"]), SENTINEL, dtype=c["ydt"], device=dev)
+    y = out if c["y_view"] is None else out[..., c["y_view"]:c["y_view"] + U]
+    starts = None
     if mode in ("flat", "flat_pooled"):
         starts = ops.row_starts(lens, B, T, torch.zeros(B + 1, dtype=torch.int32, device=dev))
     if mode == "store":
-        ops.tdnn(xin, lens, d, w, w_lo, b, sc, sh, out)
+        ops.tdnn(xin, lens, d, w, w_lo, b, sc, sh, y)
     elif mode == "pooled":
-        ops.tdnn_stats(xin, lens, d, w, w_lo, b, sc, sh, out, zero=False)
+        ops.tdnn_stats(xin, lens, d, w, w_lo, b, sc, sh, out, zero=not det)
     elif mode == "split":
         planes = c["ydt"] == BF16
-        ops.tdnn_split(xin, lens, d, w, w_lo, b, sc, sh, out[0] if planes else out, out[1] if planes else None)
+        ops.tdnn_split(xin, lens, d, w, w_lo, b, sc, sh, y[0] if planes else y, y[1] if planes else None)
     elif mode == "split_pooled":
-        ops.tdnn_split_stats(xin, lens, d, w, w_lo, b, sc, sh, out, zero=False)
+        ops.tdnn_split_stats(xin, lens, d, w, w_lo, b, sc, sh, out, zero=not det)
     elif mode == "flat":
-        ops.tdnn_split_flat(xin, starts, d, w, w_lo, b, sc, sh, out[0], out[1])
+        ops.tdnn_split_flat(xin, starts, d, w, w_lo, b, sc, sh, y[0], y[1])
     else:
-        ops.tdnn_split_flat_stats(xin, starts, d, w, w_lo, b, sc, sh, out, zero=False)
+        ops.tdnn_split_flat_stats(xin, starts, d, w, w_lo, b, sc, sh, out, zero=not det)
     assert ops.last_kernel() == c["kernel"], (c["name"], ops.last_kernel())
     torch.cuda.synchronize()
+    return dict(x=x, W=W, bias=bias, scale=sc_np, shift=sh_np, lens=None if lens is None else np.array(c["lens"], np.int32), out=out,
+                lens_dev=lens, starts=starts, slots=slots)
+
+
+def run(c):
+    """sha256 of the output buffer of case c."""
+    out = launch(c)["out"]
     raw = out.view(torch.int16) if out.dtype == BF16 else out
     return hashlib.sha256(raw.cpu().numpy().tobytes()).hexdigest()
 
