@@ -1,0 +1,545 @@
+// Gradients of the trainable path (include/ktf_grad.h): the data and the weight / bias gradient of ktf_tdnn with KTF_GEMM_F32 and no
+// activation, and the gradient of the reducing statistics pooling. Products and their accumulation run on v_mfma_f32_32x32x2_f32 as in
+// tdnn_f32.hip (an fmaf chain in reduction order); nothing here uses an atomic, so every call is reproducible bit for bit.
+//
+//   ktf_grad_tdnn_data     grad_fold_kernel  -> grad_dx_kernel         dx = gather(g) * W
+//   ktf_grad_tdnn_weights  grad_dw_kernel    -> grad_dw_reduce_kernel  dW = g^T * gather(x), dbias = column sums of g
+//   ktf_grad_stats_pool    grad_pool_kernel
+//
+// Both GEMMs are register-staged, double-buffered LDS tiles of four waves (2 x 2), K-step 16, rows of 17 floats (the layout of
+// tdnn_f32_kernel): a wave owns MTM x MTN blocks of 32 x 32, `a` operand = the output's row index, `b` operand = its column index, so
+// lanes 0-31 of a store cover 32 consecutive floats of an output row. Operand elements that stand for nothing -- rows of g at or
+// beyond an utterance's output length, rows past a slot's end, columns past `units` -- are staged as 0.0f and never loaded.
+#include "tdnn_common.h"
+#include "../../include/ktf_grad.h"
+
+#define GR_BK 16
+#define GR_PITCH (GR_BK + 1)
+#define GR_THREADS 256
+
+struct GradParams {
+    TdnnParams f;           // the forward's view: x, lens, w, T, ldx, Tout, units, din_pad, nctx, sub, valid, ktot, ctx
+    const float* g;         // (B, Tout, ldg)
+    float* dx;              // (B, T, ldx)
+    float* fold;            // workspace: (B, 2, nctx, units) sums of the g rows whose x row was clamped to 0 / len - 1
+    float* slots;           // workspace: `nslots` x slot_stride floats: dW partial (units_pad, ktot), then dbias partial (units_pad)
+    int64_t ldg, slot_stride;
+    int32_t B, din, units_pad, rows, nslots;     // rows = B * Tout: the flat row space of the weight gradient
+};
+
+__device__ __forceinline__ int grad_len(const GradParams& p, int b) {
+    const int len = p.f.lens ? p.f.lens[b] : (int)p.f.T;
+    return len < 0 ? 0 : (len > (int)p.f.T ? (int)p.f.T : len);
+}
+
+// ------------------------------------------------------------------------------------ clamped rows of the data gradient
+// fold[b, e, k, u] = sum, in ascending t, of g[b, t, u] over the t < out_len whose row start + t * sub + ctx[k] lies below 0 (e = 0:
+// a prefix of the t axis) or beyond len - 1 (e = 1: a suffix). At most |ctx[0]| + |ctx[nctx - 1]| rows per (b, k).
+__global__ __launch_bounds__(GR_THREADS) void grad_fold_kernel(GradParams p) {
+    const int64_t idx = (int64_t)blockIdx.x * GR_THREADS + threadIdx.x;
+    const int64_t total = (int64_t)p.B * 2 * p.f.nctx * p.f.units;
+    if (idx >= total) return;
+    const int u = (int)(idx % p.f.units);
+    const int k = (int)((idx / p.f.units) % p.f.nctx);
+    const int e = (int)((idx / ((int64_t)p.f.units * p.f.nctx)) & 1);
+    const int b = (int)(idx / ((int64_t)p.f.units * p.f.nctx * 2));
+    const int len = grad_len(p, b);
+    int start;
+    const int out_len = tdnn_out_len(len, p.f, start);
+    float s = 0.0f;
+    if (out_len > 0) {
+        const int num = (e == 0 ? 0 : len) - start - p.f.ctx[k];
+        int cut = num <= 0 ? 0 : (num + p.f.sub - 1) / p.f.sub;      // first t that is not clamped low (e = 0) / that is clamped high (e = 1)
+        cut = cut > out_len ? out_len : cut;
+        const int t0 = e == 0 ? 0 : cut, t1 = e == 0 ? cut : out_len;
+        const float* gb = p.g + (int64_t)b * p.f.Tout * p.ldg + u;
+        for (int t = t0; t < t1; ++t) s += gb[(int64_t)t * p.ldg];
+    }
+    p.fold[idx] = s;
+}
+
+// ------------------------------------------------------------------------------------ data gradient
+// dx tile: (64 MTM) input rows x (64 MTN) features of one utterance; reduction over (context k, unit u) in steps of 16 units. Row r
+// takes from context k the g row t = (r - start - ctx[k]) / sub when that is an integer in [0, out_len); rows 0 and len - 1 add the
+// folded rows of that context. W is read as stored: (unit, k * din_pad + d).
+template <int MTM, int MTN>
+__global__ __launch_bounds__(GR_THREADS) void grad_dx_kernel(GradParams p) {
+    constexpr int BM = 64 * MTM, BN = 64 * MTN;
+    constexpr int NLA = BM / 64;                     // groups of 4 units per thread: BM rows x 4 groups
+    constexpr int NLB = BN / 64;                     // float4 per thread: 16 units x BN / 4
+    __shared__ float As[2][BM * GR_PITCH];
+    __shared__ float Bs[2][BN * GR_PITCH];
+    const int b = blockIdx.z;
+    const int T = (int)p.f.T;
+    const int len = grad_len(p, b);
+    int start;
+    const int out_len = tdnn_out_len(len, p.f, start);
+    const int r0 = blockIdx.y * BM, d0 = blockIdx.x * BN;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int wm = wave >> 1, wn = wave & 1;
+    float* dxb = p.dx + (int64_t)b * T * p.f.ldx;
+    if (r0 >= len || d0 >= p.f.din_pad) {            // nothing but zeros: rows past the utterance, or the columns [din_pad, ldx)
+        for (int q = tid; q < BM * BN; q += GR_THREADS) {
+            const int r = r0 + q / BN, d = d0 + q % BN;
+            if (r < T && d < p.f.ldx) dxb[(int64_t)r * p.f.ldx + d] = 0.0f;
+        }
+        return;
+    }
+    const float* gb = p.g + (int64_t)b * p.f.Tout * p.ldg;
+    const float* fold_lo = p.fold + ((int64_t)b * 2 + 0) * p.f.nctx * p.f.units;
+    const float* fold_hi = p.fold + ((int64_t)b * 2 + 1) * p.f.nctx * p.f.units;
+
+    int a_row[NLA], a_col[NLA], b_row[NLB], b_col[NLB];
+#pragma unroll
+    for (int i = 0; i < NLA; ++i) {
+        const int q = i * GR_THREADS + tid;
+        a_row[i] = q >> 2;
+        a_col[i] = (q & 3) * 4;
+    }
+#pragma unroll
+    for (int i = 0; i < NLB; ++i) {
+        const int q = i * GR_THREADS + tid;
+        b_row[i] = q / (BN / 4);
+        b_col[i] = (q % (BN / 4)) * 4;
+    }
+
+    f32x16 acc[MTM][MTN];
+#pragma unroll
+    for (int i = 0; i < MTM; ++i)
+#pragma unroll
+        for (int j = 0; j < MTN; ++j)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.0f;
+
+    const int nu = (p.f.units + GR_BK - 1) / GR_BK;  // W has round_up(units, 256) rows: a step past `units` reads its zero rows
+    const int nk = p.f.nctx * nu;
+    float ra[NLA][4];
+    float4 rb[NLB];
+
+    auto load_global = [&](int ks) {
+        const int k = ks / nu;
+        const int u0 = (ks - k * nu) * GR_BK;
+        const int off = p.f.ctx[k];
+#pragma unroll
+        for (int i = 0; i < NLA; ++i) {
+            const int r = r0 + a_row[i];
+            const int s = r - start - off;
+            const int t = s / p.f.sub;
+            const bool hit = r < len && s >= 0 && t * p.f.sub == s && t < out_len;
+            const bool first = r == 0, last = r == len - 1;
+            const float* gr = gb + (int64_t)(hit ? t : 0) * p.ldg;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const int u = u0 + a_col[i] + e;
+                float v = 0.0f;
+                if (u < p.f.units) {
+                    if (hit) v = gr[u];
+                    if (first) v += fold_lo[k * p.f.units + u];
+                    if (last) v += fold_hi[k * p.f.units + u];
+                }
+                ra[i][e] = v;
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < NLB; ++i) {
+            const int d = d0 + b_col[i];
+            rb[i] = d < p.f.din_pad ? *reinterpret_cast<const float4*>(reinterpret_cast<const float*>(p.f.w) + (int64_t)(u0 + b_row[i]) * p.f.ktot +
+                                                                       (int64_t)k * p.f.din_pad + d)
+                                    : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        }
+    };
+    auto store_lds = [&](int buf) {
+#pragma unroll
+        for (int i = 0; i < NLA; ++i) {
+            float* a = &As[buf][a_row[i] * GR_PITCH + a_col[i]];
+            a[0] = ra[i][0]; a[1] = ra[i][1]; a[2] = ra[i][2]; a[3] = ra[i][3];
+        }
+#pragma unroll
+        for (int i = 0; i < NLB; ++i) {                  // transposed: Bs[feature][unit of the step]
+            float* bb = &Bs[buf][b_col[i] * GR_PITCH + b_row[i]];
+            bb[0] = rb[i].x; bb[GR_PITCH] = rb[i].y; bb[2 * GR_PITCH] = rb[i].z; bb[3 * GR_PITCH] = rb[i].w;
+        }
+    };
+
+    load_global(0);
+    store_lds(0);
+    __syncthreads();
+    for (int ks = 0; ks < nk; ++ks) {
+        const int buf = ks & 1;
+        if (ks + 1 < nk) load_global(ks + 1);
+        const float* a_base = &As[buf][(wm * 32 * MTM + (lane & 31)) * GR_PITCH + (lane >> 5)];
+        const float* b_base = &Bs[buf][(wn * 32 * MTN + (lane & 31)) * GR_PITCH + (lane >> 5)];
+#pragma unroll
+        for (int kk = 0; kk < GR_BK; kk += 2) {
+            float av[MTM], bv[MTN];
+#pragma unroll
+            for (int i = 0; i < MTM; ++i) av[i] = a_base[i * 32 * GR_PITCH + kk];
+#pragma unroll
+            for (int j = 0; j < MTN; ++j) bv[j] = b_base[j * 32 * GR_PITCH + kk];
+#pragma unroll
+            for (int i = 0; i < MTM; ++i)
+#pragma unroll
+                for (int j = 0; j < MTN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[i], bv[j], acc[i][j], 0, 0, 0);
+        }
+        if (ks + 1 < nk) store_lds(buf ^ 1);
+        __syncthreads();
+    }
+
+    // accumulator layout: column = lane & 31, row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5)
+#pragma unroll
+    for (int i = 0; i < MTM; ++i)
+#pragma unroll
+        for (int j = 0; j < MTN; ++j) {
+            const int d = d0 + wn * 32 * MTN + j * 32 + (lane & 31);
+            if (d >= p.f.ldx) continue;
+#pragma unroll
+            for (int reg = 0; reg < 16; ++reg) {
+                const int r = r0 + wm * 32 * MTM + i * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5);
+                if (r < T) dxb[(int64_t)r * p.f.ldx + d] = (r < len && d < p.din) ? acc[i][j][reg] : 0.0f;
+            }
+        }
+}
+
+// ------------------------------------------------------------------------------------ weight and bias gradient
+// One workgroup = (64 MTM) units x (64 MTN) features of ONE context x one slot of KTF_GRAD_SLOT_ROWS flat rows m = b * Tout + t,
+// reduced in steps of 16 rows: a = g[m, unit], b = x[b, row(t, k), feature]. The tile goes to the slot's own copy of dW; the
+// workgroups of the first feature tile (blockIdx.x == 0) also add up the staged g rows, in row order, into the slot's dbias.
+template <int MTM, int MTN>
+__global__ __launch_bounds__(GR_THREADS) void grad_dw_kernel(GradParams p) {
+    constexpr int BM = 64 * MTM, BN = 64 * MTN;
+    constexpr int NLA = BM / 64;                     // groups of 4 units per thread: 16 rows x BM / 4
+    constexpr int NLB = BN / 64;                     // float4 per thread: 16 rows x BN / 4
+    __shared__ float As[2][BM * GR_PITCH];
+    __shared__ float Bs[2][BN * GR_PITCH];
+    const int dtiles = (p.f.din_pad + BN - 1) / BN;
+    const int k = blockIdx.x / dtiles;
+    const int d0 = (blockIdx.x - k * dtiles) * BN;
+    const int u0 = blockIdx.y * BM;
+    const int slot = blockIdx.z;
+    const int m0 = slot * KTF_GRAD_SLOT_ROWS;
+    const int m1 = m0 + KTF_GRAD_SLOT_ROWS < p.rows ? m0 + KTF_GRAD_SLOT_ROWS : p.rows;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int wm = wave >> 1, wn = wave & 1;
+    const int Tout = (int)p.f.Tout;
+    const int off = p.f.ctx[k];
+    const bool with_bias = blockIdx.x == 0;
+
+    int a_row[NLA], a_col[NLA], b_row[NLB], b_col[NLB];
+#pragma unroll
+    for (int i = 0; i < NLA; ++i) {
+        const int q = i * GR_THREADS + tid;
+        a_row[i] = q / (BM / 4);
+        a_col[i] = (q % (BM / 4)) * 4;
+    }
+#pragma unroll
+    for (int i = 0; i < NLB; ++i) {
+        const int q = i * GR_THREADS + tid;
+        b_row[i] = q / (BN / 4);
+        b_col[i] = (q % (BN / 4)) * 4;
+    }
+
+    f32x16 acc[MTM][MTN];
+#pragma unroll
+    for (int i = 0; i < MTM; ++i)
+#pragma unroll
+        for (int j = 0; j < MTN; ++j)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.0f;
+    float bsum = 0.0f;
+
+    const int nk = (m1 - m0 + GR_BK - 1) / GR_BK;
+    float ra[NLA][4];
+    float4 rb[NLB];
+
+    auto load_global = [&](int ks) {
+#pragma unroll
+        for (int i = 0; i < NLA; ++i) {
+            const int m = m0 + ks * GR_BK + a_row[i];
+            const int b = m / Tout, t = m - b * Tout;
+            bool valid = m < m1;
+            if (valid) {
+                int start;
+                valid = t < tdnn_out_len(grad_len(p, b), p.f, start);
+            }
+            const float* gr = p.g + (int64_t)m * p.ldg;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const int u = u0 + a_col[i] + e;
+                ra[i][e] = (valid && u < p.f.units) ? gr[u] : 0.0f;
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < NLB; ++i) {
+            const int m = m0 + ks * GR_BK + b_row[i];
+            const int b = m / Tout, t = m - b * Tout;
+            const int d = d0 + b_col[i];
+            rb[i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            if (m < m1 && d < p.f.din_pad) {
+                const int len = grad_len(p, b);
+                int start;
+                if (t < tdnn_out_len(len, p.f, start)) {
+                    int r = start + t * p.f.sub + off;
+                    r = r < 0 ? 0 : (r > len - 1 ? len - 1 : r);
+                    rb[i] = *reinterpret_cast<const float4*>(reinterpret_cast<const float*>(p.f.x) + ((int64_t)b * p.f.T + r) * p.f.ldx + d);
+                }
+            }
+        }
+    };
+    auto store_lds = [&](int buf) {                      // both transposed: As[unit][row of the step], Bs[feature][row of the step]
+#pragma unroll
+        for (int i = 0; i < NLA; ++i) {
+            float* a = &As[buf][a_col[i] * GR_PITCH + a_row[i]];
+            a[0] = ra[i][0]; a[GR_PITCH] = ra[i][1]; a[2 * GR_PITCH] = ra[i][2]; a[3 * GR_PITCH] = ra[i][3];
+        }
+#pragma unroll
+        for (int i = 0; i < NLB; ++i) {
+            float* bb = &Bs[buf][b_col[i] * GR_PITCH + b_row[i]];
+            bb[0] = rb[i].x; bb[GR_PITCH] = rb[i].y; bb[2 * GR_PITCH] = rb[i].z; bb[3 * GR_PITCH] = rb[i].w;
+        }
+    };
+
+    if (nk > 0) {
+        load_global(0);
+        store_lds(0);
+    }
+    __syncthreads();
+    for (int ks = 0; ks < nk; ++ks) {
+        const int buf = ks & 1;
+        if (ks + 1 < nk) load_global(ks + 1);
+        const float* a_base = &As[buf][(wm * 32 * MTM + (lane & 31)) * GR_PITCH + (lane >> 5)];
+        const float* b_base = &Bs[buf][(wn * 32 * MTN + (lane & 31)) * GR_PITCH + (lane >> 5)];
+#pragma unroll
+        for (int kk = 0; kk < GR_BK; kk += 2) {
+            float av[MTM], bv[MTN];
+#pragma unroll
+            for (int i = 0; i < MTM; ++i) av[i] = a_base[i * 32 * GR_PITCH + kk];
+#pragma unroll
+            for (int j = 0; j < MTN; ++j) bv[j] = b_base[j * 32 * GR_PITCH + kk];
+#pragma unroll
+            for (int i = 0; i < MTM; ++i)
+#pragma unroll
+                for (int j = 0; j < MTN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[i], bv[j], acc[i][j], 0, 0, 0);
+        }
+        if (with_bias && tid < BM) {
+#pragma unroll
+            for (int r = 0; r < GR_BK; ++r) bsum += As[buf][tid * GR_PITCH + r];
+        }
+        if (ks + 1 < nk) store_lds(buf ^ 1);
+        __syncthreads();
+    }
+
+    float* ws = p.slots + (int64_t)slot * p.slot_stride;
+#pragma unroll
+    for (int i = 0; i < MTM; ++i)
+#pragma unroll
+        for (int j = 0; j < MTN; ++j) {
+            const int d = d0 + wn * 32 * MTN + j * 32 + (lane & 31);
+            if (d >= p.f.din_pad) continue;
+#pragma unroll
+            for (int reg = 0; reg < 16; ++reg) {
+                const int u = u0 + wm * 32 * MTM + i * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5);
+                if (u < p.units_pad) ws[(int64_t)u * p.f.ktot + (int64_t)k * p.f.din_pad + d] = acc[i][j][reg];
+            }
+        }
+    if (with_bias && tid < BM && u0 + tid < p.units_pad) ws[(int64_t)p.units_pad * p.f.ktot + u0 + tid] = bsum;
+}
+
+// dW[u, c] = the slots' values added in slot order (zero in the pad region, which no slot is read for); then dbias likewise.
+__global__ __launch_bounds__(GR_THREADS) void grad_dw_reduce_kernel(GradParams p, float* __restrict__ dw, float* __restrict__ dbias) {
+    const int64_t idx = (int64_t)blockIdx.x * GR_THREADS + threadIdx.x;
+    const int64_t nw = (int64_t)p.units_pad * p.f.ktot;
+    if (idx < nw) {
+        const int u = (int)(idx / p.f.ktot);
+        const int d = (int)(idx % p.f.ktot) % p.f.din_pad;
+        float v = 0.0f;
+        if (u < p.f.units && d < p.din)
+            for (int s = 0; s < p.nslots; ++s) v += p.slots[(int64_t)s * p.slot_stride + idx];
+        dw[idx] = v;
+    } else if (dbias && idx - nw < p.f.units) {
+        float v = 0.0f;
+        for (int s = 0; s < p.nslots; ++s) v += p.slots[(int64_t)s * p.slot_stride + idx];
+        dbias[idx - nw] = v;
+    }
+}
+
+// ------------------------------------------------------------------------------------ gradient of the reducing statistics pooling
+// One workgroup = one utterance x 64 columns, four row groups. The column sums are taken again, in fp64 (rows j -> group j mod 4,
+// groups added as ((0 + 1) + 2) + 3), then every row of the utterance's T is written: the sampled rows below its length with the
+// gradient, evaluated in fp64 and rounded once, the others with zero.
+__global__ __launch_bounds__(GR_THREADS) void grad_pool_kernel(const float* __restrict__ x, int64_t T, int D, int64_t ldx,
+                                                               const int32_t* __restrict__ lens, int period, int include_std, float eps,
+                                                               const float* __restrict__ gout, int64_t ldg, float* __restrict__ dx,
+                                                               int64_t ld_dx) {
+    __shared__ double red[4][2][64];
+    const int b = blockIdx.y;
+    const int lc = threadIdx.x & 63, rg = threadIdx.x >> 6;
+    const int c = blockIdx.x * 64 + lc;
+    int len = lens ? lens[b] : (int)T;
+    len = len < 0 ? 0 : (len > (int)T ? (int)T : len);
+    const int nrows = (len + period - 1) / period;
+    const float* xb = x + (int64_t)b * T * ldx;
+    double s = 0.0, q = 0.0;
+    if (c < D)
+        for (int j = rg; j < nrows; j += 4) {
+            const double v = (double)xb[(int64_t)j * period * ldx + c];
+            s += v;
+            q += v * v;
+        }
+    red[rg][0][lc] = s;
+    red[rg][1][lc] = q;
+    __syncthreads();
+    if (c >= ld_dx) return;
+    float* dxb = dx + (int64_t)b * T * ld_dx + c;
+    double mean = 0.0, ca = 0.0, cb = 0.0;
+    if (c < D && nrows > 0) {
+        const double n = (double)nrows;
+        const double S = ((red[0][0][lc] + red[1][0][lc]) + red[2][0][lc]) + red[3][0][lc];
+        const double Q = ((red[0][1][lc] + red[1][1][lc]) + red[2][1][lc]) + red[3][1][lc];
+        mean = S / n;
+        const double var = Q / n - mean * mean;
+        ca = (double)gout[(int64_t)b * ldg + c] / n;
+        if (include_std && var > 0.0) cb = (double)gout[(int64_t)b * ldg + D + c] / (n * sqrt(var + (double)eps));
+    }
+    for (int t = rg; t < (int)T; t += 4) {
+        float v = 0.0f;
+        if (c < D && t < len && t % period == 0) {
+            v = (float)(cb != 0.0 ? ca + cb * ((double)xb[(int64_t)t * ldx + c] - mean) : ca);
+        }
+        dxb[(int64_t)t * ld_dx] = v;
+    }
+}
+
+// ------------------------------------------------------------------------------------ entry points
+extern "C" int32_t ktf_grad_tdnn_row_tile(void) { return KTF_GRAD_ROW_TILE; }
+extern "C" int32_t ktf_grad_tdnn_slot_rows(void) { return KTF_GRAD_SLOT_ROWS; }
+
+static int grad_check_desc(const KtfTdnnDesc* d, const char* who) {
+    KTF_REQUIRE(d != nullptr, "%s: null argument", who);
+    KTF_REQUIRE(d->gemm == KTF_GEMM_F32, "%s: gemm %d: the gradients exist for KTF_GEMM_F32 only", who, d->gemm);
+    KTF_REQUIRE(d->act == KTF_ACT_NONE, "%s: act %d: the trainable forward has no fused activation (KTF_ACT_NONE)", who, d->act);
+    KTF_REQUIRE(d->x_dtype == KTF_F32 && d->w_dtype == KTF_F32 && d->y_dtype == KTF_F32, "%s: x, w and y must be KTF_F32", who);
+    return tdnn_check_desc(d, nullptr, nullptr, who);
+}
+
+// sizes shared by the three TDNN entry points; KTF_OK or a refusal
+struct GradSizes {
+    int64_t Tout, rows, nslots, slot_stride, fold_bytes, bytes;
+    int32_t units_pad, ktot;
+};
+static int grad_sizes(int64_t B, int64_t T, const KtfTdnnDesc* d, const char* who, GradSizes* s) {
+    KTF_REQUIRE(B >= 0 && T >= 0, "%s: negative size", who);
+    KTF_REQUIRE(B <= 65535, "%s: B %lld above 65535", who, (long long)B);
+    s->Tout = ktf_tdnn_out_len(T, d);
+    s->rows = B * s->Tout;
+    KTF_REQUIRE(T <= 65535ll * KTF_GRAD_ROW_TILE, "%s: T %lld above %lld", who, (long long)T, 65535ll * KTF_GRAD_ROW_TILE);
+    KTF_REQUIRE(s->rows < (1ll << 31), "%s: B * T_out must stay below 2^31", who);
+    s->units_pad = (d->units + 255) / 256 * 256;
+    s->ktot = d->nctx * d->din_pad;
+    s->nslots = (s->rows + KTF_GRAD_SLOT_ROWS - 1) / KTF_GRAD_SLOT_ROWS;
+    KTF_REQUIRE(s->nslots <= 65535, "%s: B * T_out %lld above 65535 slots of %d rows", who, (long long)s->rows, KTF_GRAD_SLOT_ROWS);
+    s->slot_stride = (int64_t)s->units_pad * s->ktot + s->units_pad;
+    s->fold_bytes = al256(B * 2 * d->nctx * d->units * (int64_t)sizeof(float));
+    s->bytes = s->fold_bytes + al256((s->nslots > 0 ? s->nslots : 1) * s->slot_stride * (int64_t)sizeof(float));
+    return KTF_OK;
+}
+
+extern "C" int64_t ktf_grad_tdnn_workspace_bytes(int64_t B, int64_t T, const KtfTdnnDesc* d) {
+    const char* who = "ktf_grad_tdnn_workspace_bytes";
+    if (int rc = grad_check_desc(d, who)) return rc;
+    GradSizes s;
+    if (int rc = grad_sizes(B, T, d, who, &s)) return rc;
+    return s.bytes;
+}
+
+static void grad_fill(GradParams& p, const GradSizes& s, int64_t B, int64_t T, const int32_t* lens, const KtfTdnnDesc* d, const float* x,
+                      int64_t ldx, const float* w, const float* g, int64_t ldg, void* workspace) {
+    memset(&p, 0, sizeof(p));
+    p.f.x = x;
+    p.f.lens = lens;
+    p.f.w = w;
+    p.f.T = T;
+    p.f.ldx = ldx;
+    p.f.Tout = s.Tout;
+    p.f.units = d->units;
+    p.f.din_pad = d->din_pad;
+    p.f.nctx = d->nctx;
+    p.f.sub = d->subsampling;
+    p.f.valid = d->valid;
+    p.f.ktot = s.ktot;
+    for (int i = 0; i < d->nctx; ++i) p.f.ctx[i] = d->ctx[i];
+    p.g = g;
+    p.ldg = ldg;
+    p.fold = reinterpret_cast<float*>(workspace);
+    p.slots = reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + s.fold_bytes);
+    p.slot_stride = s.slot_stride;
+    p.B = (int32_t)B;
+    p.din = d->din;
+    p.units_pad = s.units_pad;
+    p.rows = (int32_t)s.rows;
+    p.nslots = (int32_t)s.nslots;
+}
+
+extern "C" int ktf_grad_tdnn_data(const float* g, int64_t ldg, int64_t B, int64_t T, const int32_t* lens, const KtfTdnnDesc* d, const float* w,
+                                  float* dx, int64_t ldx, void* workspace, size_t workspace_bytes, void* stream) {
+    const char* who = "ktf_grad_tdnn_data";
+    if (int rc = grad_check_desc(d, who)) return rc;
+    KTF_REQUIRE(g && w && dx && workspace, "%s: null argument", who);
+    GradSizes s;
+    if (int rc = grad_sizes(B, T, d, who, &s)) return rc;
+    KTF_REQUIRE(ldx >= d->din_pad && ldx % 4 == 0, "%s: ldx %lld must be a multiple of 4 and >= din_pad %d", who, (long long)ldx, d->din_pad);
+    KTF_REQUIRE(ldg >= d->units, "%s: ldg %lld < units %d", who, (long long)ldg, d->units);
+    KTF_REQUIRE(((reinterpret_cast<uintptr_t>(w) | reinterpret_cast<uintptr_t>(dx)) & 15) == 0, "%s: w and dx must be 16-byte aligned", who);
+    if (int rc = ktf_check_workspace(who, workspace, workspace_bytes, s.bytes)) return rc;
+    if (B == 0 || T == 0) return KTF_OK;
+    GradParams p;
+    grad_fill(p, s, B, T, lens, d, nullptr, ldx, w, g, ldg, workspace);
+    p.dx = dx;
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t nfold = B * 2 * d->nctx * d->units;
+    hipLaunchKernelGGL(grad_fold_kernel, dim3((unsigned)ktf_cdiv(nfold, GR_THREADS)), dim3(GR_THREADS), 0, st, p);
+    KTF_CHECK_LAUNCH(who);
+    const dim3 grid((unsigned)ktf_cdiv(ldx, 128), (unsigned)ktf_cdiv(T, KTF_GRAD_ROW_TILE), (unsigned)B);
+    hipLaunchKernelGGL((grad_dx_kernel<1, 2>), grid, dim3(GR_THREADS), 0, st, p);
+    KTF_CHECK_LAUNCH(who);
+    return KTF_OK;
+}
+
+extern "C" int ktf_grad_tdnn_weights(const float* x, int64_t B, int64_t T, int64_t ldx, const int32_t* lens, const KtfTdnnDesc* d, const float* g,
+                                     int64_t ldg, float* dw, float* dbias, void* workspace, size_t workspace_bytes, void* stream) {
+    const char* who = "ktf_grad_tdnn_weights";
+    if (int rc = grad_check_desc(d, who)) return rc;
+    KTF_REQUIRE(x && g && dw && workspace, "%s: null argument", who);
+    GradSizes s;
+    if (int rc = grad_sizes(B, T, d, who, &s)) return rc;
+    KTF_REQUIRE(ldx >= d->din_pad && ldx % 4 == 0, "%s: ldx %lld must be a multiple of 4 and >= din_pad %d", who, (long long)ldx, d->din_pad);
+    KTF_REQUIRE(ldg >= d->units, "%s: ldg %lld < units %d", who, (long long)ldg, d->units);
+    KTF_REQUIRE(((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(dw)) & 15) == 0, "%s: x and dw must be 16-byte aligned", who);
+    if (int rc = ktf_check_workspace(who, workspace, workspace_bytes, s.bytes)) return rc;
+    GradParams p;
+    grad_fill(p, s, B, T, lens, d, x, ldx, nullptr, g, ldg, workspace);
+    hipStream_t st = (hipStream_t)stream;
+    if (s.nslots > 0) {
+        const dim3 grid((unsigned)(d->nctx * ktf_cdiv(d->din_pad, 128)), (unsigned)ktf_cdiv(d->units, 128), (unsigned)s.nslots);
+        hipLaunchKernelGGL((grad_dw_kernel<2, 2>), grid, dim3(GR_THREADS), 0, st, p);
+        KTF_CHECK_LAUNCH(who);
+    }
+    const int64_t n = (int64_t)s.units_pad * s.ktot + d->units;
+    hipLaunchKernelGGL(grad_dw_reduce_kernel, dim3((unsigned)ktf_cdiv(n, GR_THREADS)), dim3(GR_THREADS), 0, st, p, dw, dbias);
+    KTF_CHECK_LAUNCH(who);
+    return KTF_OK;
+}
+
+extern "C" int ktf_grad_stats_pool(const float* x, int64_t B, int64_t T, int32_t D, int64_t ldx, const int32_t* lens, int32_t input_period,
+                                   int32_t include_std, float eps, const float* gout, int64_t ld_gout, float* dx, int64_t ld_dx, void* stream) {
+    const char* who = "ktf_grad_stats_pool";
+    KTF_REQUIRE(x && gout && dx, "%s: null argument", who);
+    KTF_REQUIRE(B >= 0 && T >= 0 && T < (1ll << 31) && D > 0 && ldx >= D && ld_dx >= D, "%s: bad sizes", who);
+    KTF_REQUIRE(input_period > 0, "%s: input_period must be > 0", who);
+    KTF_REQUIRE(B <= 65535, "%s: B %lld above 65535", who, (long long)B);
+    KTF_REQUIRE(ld_gout >= (include_std ? 2 : 1) * (int64_t)D, "%s: ld_gout too small", who);
+    if (B == 0 || T == 0) return KTF_OK;
+    hipLaunchKernelGGL(grad_pool_kernel, dim3((unsigned)ktf_cdiv(ld_dx, 64), (unsigned)B), dim3(GR_THREADS), 0, (hipStream_t)stream, x, T, D, ldx,
+                       lens, input_period, include_std, eps, gout, ld_gout, dx, ld_dx);
+    KTF_CHECK_LAUNCH(who);
+    return KTF_OK;
+}

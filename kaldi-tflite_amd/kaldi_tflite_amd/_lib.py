@@ -236,6 +236,15 @@ RESAMPLE_PROTOTYPES = {
     "ktf_rs_num_out": (_i64, [_i64, _i32, _i32]),
     "ktf_rs_resample": (C.c_int, [_P, _i32, _i64, _P, _P, _i32, _i32, _i32, _P, _P, _P, _P, _P, _i32, _P, _i32, _i64, _i64, _P]),
 }
+# name -> (restype, argtypes); mirrors include/ktf_grad.h one to one
+GRAD_PROTOTYPES = {
+    "ktf_grad_tdnn_row_tile": (_i32, []),
+    "ktf_grad_tdnn_slot_rows": (_i32, []),
+    "ktf_grad_tdnn_workspace_bytes": (_i64, [_i64, _i64, C.POINTER(TdnnDesc)]),
+    "ktf_grad_tdnn_data": (C.c_int, [_P, _i64, _i64, _i64, _P, C.POINTER(TdnnDesc), _P, _P, _i64, _P, C.c_size_t, _P]),
+    "ktf_grad_tdnn_weights": (C.c_int, [_P, _i64, _i64, _i64, _P, C.POINTER(TdnnDesc), _P, _i64, _P, _P, _P, C.c_size_t, _P]),
+    "ktf_grad_stats_pool": (C.c_int, [_P, _i64, _i64, _i32, _i64, _P, _i32, _i32, _f32, _P, _i64, _P, _i64, _P]),
+}
 AUG_META, AUG_STATS = 8, 4          # ktf_aug_*: int32 per RIR of the bank's meta; doubles per row of the statistics
 PLDA_DENSE_NO_PCA = -1.0            # ktf_plda_dense_*: target_energy for "no PCA"
 PLDA_DENSE_MAX_DIM = 512
@@ -263,7 +272,8 @@ def load():
             f"{LIB_PATH} not found: build it with `make -C kaldi-tflite_amd/csrc` (or __graft_entry__.build()). "
             "There is no CPU fallback.")
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in list(PROTOTYPES.items()) + list(AUGMENT_PROTOTYPES.items()) + list(RESAMPLE_PROTOTYPES.items()):
+    for name, (res, args) in (list(PROTOTYPES.items()) + list(AUGMENT_PROTOTYPES.items()) + list(RESAMPLE_PROTOTYPES.items())
+                              + list(GRAD_PROTOTYPES.items())):
         fn = getattr(lib, name)          # AttributeError = header/library mismatch
         fn.restype = res
         fn.argtypes = args

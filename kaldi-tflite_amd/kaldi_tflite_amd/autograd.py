@@ -1,0 +1,265 @@
+"""
+ktf.autograd -- training the x-vector network on the GPU: the TDNN affine and the reducing statistics pooling as
+`torch.autograd.Function`s over the library's kernels (forward: ktf_tdnn with KTF_GEMM_F32 / ktf_stats_pool, backward: the calls of
+include/ktf_grad.h), batch normalisation in training mode, and `TrainableSequential`, a `torch.nn.Module` made from a
+`ktf.models.Sequential` whose trained weights `export()` hands back to the inference kernels in every `gemm=` mode.
+
+The GEMMs and the pooling run in the HIP kernels on fp32; padding to the kernels' operand layouts, ReLU and the batch normalisation
+are torch ops on the same device. There is no CPU path for the kernels: tensors that are not on the GPU are refused.
+"""
+
+import torch
+
+from . import _lib as L, layers as _layers, ops
+
+
+def _desc(units, din, context, subsampling_factor, padding):
+    context = [int(c) for c in context]
+    if not 1 <= len(context) <= 16 or any(b <= a for a, b in zip(context, context[1:])):
+        raise ValueError(f"context must be 1 to 16 strictly ascending offsets, got {context}")
+    padding = str(padding).upper()
+    if padding not in ("SAME", "VALID"):
+        raise ValueError("padding should be either 'VALID' or 'SAME'")
+    if int(subsampling_factor) <= 0:
+        raise ValueError("subsampling_factor should be > 0")
+    d = L.TdnnDesc()
+    d.units, d.din, d.din_pad, d.nctx = int(units), int(din), ops.round_up(int(din), 32), len(context)
+    for i, c in enumerate(context):
+        d.ctx[i] = c
+    d.subsampling, d.valid = int(subsampling_factor), int(padding == "VALID")
+    d.act, d.gemm, d.flags = L.ACT_NONE, L.GEMM_F32, 0
+    d.x_dtype = d.w_dtype = d.y_dtype = L.KTF_F32
+    return d
+
+
+def _on_gpu(t, what):
+    if not (isinstance(t, torch.Tensor) and t.is_cuda):
+        raise L.KtfBackendError(f"{what} must be a tensor on the GPU: these functions run the library's kernels (no CPU fallback)")
+
+
+def _lens(lens, B, device):
+    if lens is None:
+        return None
+    lens = torch.as_tensor(lens, device=device).to(torch.int32).contiguous()
+    if lens.shape != (B,):
+        raise ValueError(f"lens must hold one length per utterance ({B}), got shape {tuple(lens.shape)}")
+    return lens
+
+
+def tdnn_out_lens(lens, context, subsampling_factor=1, padding="SAME"):
+    """Valid output rows of a TDNN layer per utterance (the rule of ktf_tdnn_out_len) as torch integer arithmetic; None stays None."""
+    if lens is None:
+        return None
+    start, end = 0, lens
+    if str(padding).upper() == "VALID":
+        start = -min(int(context[0]), 0)
+        end = lens - max(int(context[-1]), 0)
+    n = end - start + (int(subsampling_factor) - 1)
+    return torch.clamp(torch.div(n, int(subsampling_factor), rounding_mode="floor"), min=0).to(torch.int32)
+
+
+class _TdnnAffine(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, weight, bias, lens, context, subsampling_factor, padding):
+        B, T, D = x.shape
+        units, nctx = weight.shape[0], weight.shape[1]
+        d = _desc(units, D, context, subsampling_factor, padding)
+        Dp, Up = d.din_pad, ops.round_up(units, 256)
+        xp = torch.nn.functional.pad(x, (0, Dp - D)).contiguous()                # pad columns zero: finite, as the kernels ask
+        wp = torch.zeros((Up, nctx, Dp), dtype=torch.float32, device=x.device)
+        wp[:units, :, :D] = weight
+        Tout = ops.tdnn_out_len(T, d)
+        y = torch.zeros((B, Tout, units), dtype=torch.float32, device=x.device)  # rows at and beyond an utterance's output length stay zero
+        if B > 0 and Tout > 0:
+            ops.tdnn(xp, lens, d, wp.view(Up, nctx * Dp), None, None if bias is None else bias.contiguous(), None, None, y)
+        ctx.save_for_backward(xp, wp, lens)
+        ctx.desc, ctx.dims, ctx.has_bias = d, (D, units, nctx), bias is not None
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        xp, wp, lens = ctx.saved_tensors
+        d = ctx.desc
+        D, units, nctx = ctx.dims
+        B, T, Dp = xp.shape
+        Up = wp.shape[0]
+        g = gy.to(torch.float32).contiguous()
+        dx = dw = db = None
+        need_w = ctx.needs_input_grad[1] or (ctx.has_bias and ctx.needs_input_grad[2])
+        if B == 0 or g.shape[1] == 0:                       # no output row: nothing reaches the inputs
+            if ctx.needs_input_grad[0]:
+                dx = torch.zeros((B, T, D), dtype=torch.float32, device=xp.device)
+            if need_w:
+                dw = torch.zeros((units, nctx, D), dtype=torch.float32, device=xp.device)
+                db = torch.zeros((units,), dtype=torch.float32, device=xp.device) if ctx.has_bias else None
+            return dx, dw, db, None, None, None, None
+        ws = ops.grad_tdnn_workspace(B, T, d, xp.device)
+        if ctx.needs_input_grad[0]:
+            dxp = torch.empty_like(xp)
+            ops.grad_tdnn_data(g, lens, d, wp.view(Up, nctx * Dp), dxp, ws)
+            dx = dxp[:, :, :D]
+        if need_w:
+            dwp = torch.empty_like(wp)
+            db = torch.empty((units,), dtype=torch.float32, device=xp.device) if ctx.has_bias else None
+            ops.grad_tdnn_weights(xp, lens, d, g, dwp.view(Up, nctx * Dp), db, ws)
+            dw = dwp[:units, :, :D]
+        return dx, dw, db, None, None, None, None
+
+
+def tdnn_affine(x, weight, bias, context, lens=None, subsampling_factor=1, padding="SAME"):
+    """z[b,t,u] = bias[u] + sum_k sum_d x[b, row(t,k), d] * weight[u,k,d], row(t,k) = clip(start + t * subsampling_factor + context[k],
+    0, len_b - 1), differentiable in x, weight and bias. x (B, T, D) fp32 on the GPU; weight (units, nctx, D) -- the [u, k, d] order of
+    TDNN.device_weights; bias (units,) or None; lens (B,) or None (every utterance has T rows). Returns (B, T_out, units) with zero rows
+    at and beyond an utterance's output length (`tdnn_out_lens`); gradients arriving for those rows are ignored."""
+    _on_gpu(x, "x")
+    _on_gpu(weight, "weight")
+    if x.dim() != 3 or weight.dim() != 3 or weight.shape[2] != x.shape[2] or weight.shape[1] != len(context):
+        raise ValueError(f"expected x (B, T, D) and weight (units, {len(context)}, D), got {tuple(x.shape)} and {tuple(weight.shape)}")
+    if bias is not None and tuple(bias.shape) != (weight.shape[0],):
+        raise ValueError(f"bias shape {tuple(bias.shape)} != ({weight.shape[0]},)")
+    return _TdnnAffine.apply(x.to(torch.float32), weight.to(torch.float32), None if bias is None else bias.to(torch.float32),
+                             _lens(lens, x.shape[0], x.device), list(context), subsampling_factor, padding)
+
+
+class _StatsPooling(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, lens, include_std, epsilon, input_period):
+        B, T, D = x.shape
+        x = x.contiguous()
+        out = torch.empty((B, 2 * D if include_std else D), dtype=torch.float32, device=x.device)
+        ops.stats_pool(x, D, lens, input_period, include_std, epsilon, out)
+        ctx.save_for_backward(x, lens)
+        ctx.cfg = (include_std, epsilon, input_period)
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        x, lens = ctx.saved_tensors
+        include_std, epsilon, input_period = ctx.cfg
+        dx = torch.empty_like(x)
+        ops.grad_stats_pool(x, x.shape[2], lens, input_period, include_std, epsilon, gout.to(torch.float32).contiguous(), dx)
+        return dx, None, None, None, None
+
+
+def stats_pooling(x, lens=None, include_std=True, epsilon=1e-10, input_period=1):
+    """The reducing StatsPooling, differentiable in x: (B, T, D) fp32 on the GPU -> (B, D or 2 D), mean and
+    sqrt(relu(E[x^2] - mean^2) + epsilon) over the rows 0, input_period, ... below each utterance's length."""
+    _on_gpu(x, "x")
+    if x.dim() != 3:
+        raise ValueError(f"expected a (batch, time, feat) input, got shape {tuple(x.shape)}")
+    if int(input_period) <= 0:
+        raise ValueError("'input_period' must be > 0")
+    return _StatsPooling.apply(x.to(torch.float32), _lens(lens, x.shape[0], x.device), bool(include_std), float(epsilon), int(input_period))
+
+
+def batch_norm(x, lens, moving_mean, moving_var, gamma, momentum=0.99, epsilon=0.001, training=False):
+    """BatchNorm as the project mirrors it (keras BatchNormalization(center=False, scale=True)): y = gamma (x - mean) / sqrt(var +
+    epsilon) per feature. Training: mean and (biased) variance over the valid rows of the whole batch, and
+    moving <- moving * momentum + batch * (1 - momentum), in place, for both statistics. Evaluation: the moving statistics.
+    x (..., D); lens (B,) for a (B, T, D) input or None; rows at and beyond an utterance's length are not read and come out as zero.
+    Elementwise torch ops: it runs wherever its tensors are."""
+    mask = None
+    if lens is not None:
+        if x.dim() != 3:
+            raise ValueError("lens goes with a (batch, time, feat) input")
+        mask = (torch.arange(x.shape[1], device=x.device)[None, :] < lens.to(x.device)[:, None]).unsqueeze(-1)
+        x = torch.where(mask, x, torch.zeros((), dtype=x.dtype, device=x.device))
+    if training:
+        dims = tuple(range(x.dim() - 1))
+        if mask is None:
+            n = x.numel() // x.shape[-1]
+            mean = x.sum(dims) / n
+            var = ((x - mean) ** 2).sum(dims) / n
+        else:
+            n = mask.sum().to(x.dtype)
+            mean = x.sum(dims) / n
+            var = (torch.where(mask, x - mean, torch.zeros((), dtype=x.dtype, device=x.device)) ** 2).sum(dims) / n
+        with torch.no_grad():
+            moving_mean.mul_(momentum).add_(mean.detach().to(moving_mean.dtype), alpha=1.0 - momentum)
+            moving_var.mul_(momentum).add_(var.detach().to(moving_var.dtype), alpha=1.0 - momentum)
+    else:
+        mean, var = moving_mean, moving_var
+    y = gamma * (x - mean) * torch.rsqrt(var + epsilon)
+    return y if mask is None else torch.where(mask, y, torch.zeros((), dtype=y.dtype, device=y.device))
+
+
+class TrainableSequential(torch.nn.Module):
+    """A `ktf.models.Sequential` (or an XvectorExtractor, whose TDNN stack is taken) as a torch module: TDNN -> ReLU -> BatchNorm ...
+    -> reducing StatsPooling -> TDNN (context [0]) ... Parameters start from the layers' current weights; `forward(feats, lens)`
+    returns the last layer's output -- (B, T_out, units), or (B, units) behind the pooling -- for a head and a loss written in torch;
+    `export()` writes parameters and moving statistics back into the layers. The layers must be built (a Sequential with an Input, or
+    one that has run or loaded weights)."""
+
+    def __init__(self, seq, device=None):
+        super().__init__()
+        self.seq = getattr(seq, "xvec", seq)
+        dev = ops.default_device() if device is None else torch.device(device)
+        self.steps = []                     # (kind, the layer, index into self.params / self.stats)
+        self.params = torch.nn.ParameterList()
+        pooled = False
+        f32 = lambda a: torch.nn.Parameter(torch.as_tensor(a, dtype=torch.float32).to(dev).contiguous().clone())  # noqa: E731
+        for l in self.seq.layers:
+            if not isinstance(l, (_layers.TDNN, _layers.ReLU, _layers.BatchNorm, _layers.StatsPooling)):
+                raise NotImplementedError(f"layer '{l.name}' ({type(l).__name__}) has no gradient in ktf.autograd")
+            if not l.built and not isinstance(l, (_layers.ReLU, _layers.StatsPooling)):
+                raise ValueError(f"layer '{l.name}' is not built: give the Sequential an Input, run it or load its weights first")
+            if isinstance(l, _layers.TDNN):
+                act = l.activation.lower() if isinstance(l.activation, str) else l.activation
+                if act not in (None, "linear", "relu"):
+                    raise NotImplementedError(f"layer '{l.name}' (TDNN with activation {l.activation!r}) has no gradient in ktf.autograd")
+                if pooled and (list(l.context) != [0] or l.subsamplingFactor != 1):
+                    raise NotImplementedError(f"layer '{l.name}' (TDNN with context {l.context} behind the pooling) has no gradient in ktf.autograd")
+                at = len(self.params)
+                self.params.append(f32(l.kernel[0].transpose(2, 0, 1)))                     # keras (K, D, units) -> [u, k, d]
+                if l.useBias:
+                    self.params.append(f32(l.bias))
+                self.steps.append(("tdnn", l, at))
+            elif isinstance(l, _layers.BatchNorm):
+                at = len(self.params)
+                self.params.append(f32(l.gamma))
+                self.register_buffer(f"moving_mean_{at}", torch.as_tensor(l.moving_mean, dtype=torch.float32).to(dev).clone())
+                self.register_buffer(f"moving_var_{at}", torch.as_tensor(l.moving_variance, dtype=torch.float32).to(dev).clone())
+                self.steps.append(("bn", l, at))
+            elif isinstance(l, _layers.StatsPooling):
+                if pooled or not l.reduce:
+                    raise NotImplementedError(f"layer '{l.name}' (StatsPooling that does not reduce the time axis, or a second one) "
+                                              "has no gradient in ktf.autograd")
+                pooled = True
+                self.steps.append(("stats", l, -1))
+            else:
+                self.steps.append(("relu", l, -1))
+
+    def forward(self, feats, lens=None):
+        x, pooled = feats, False
+        lens = _lens(lens, feats.shape[0], feats.device)
+        for kind, l, at in self.steps:
+            if kind == "tdnn":
+                w, b = self.params[at], self.params[at + 1] if l.useBias else None
+                if pooled:                                         # one row per utterance: a single sequence of B rows
+                    x = tdnn_affine(x.unsqueeze(0), w, b, l.context).squeeze(0)
+                else:
+                    x = tdnn_affine(x, w, b, l.context, lens, l.subsamplingFactor, l.padding)
+                    lens = tdnn_out_lens(lens, l.context, l.subsamplingFactor, l.padding)
+                if isinstance(l.activation, str) and l.activation.lower() == "relu":
+                    x = torch.relu(x)
+            elif kind == "relu":
+                x = torch.relu(x)
+            elif kind == "bn":
+                x = batch_norm(x, None if pooled else lens, getattr(self, f"moving_mean_{at}"), getattr(self, f"moving_var_{at}"),
+                               self.params[at], l.momentum, l.epsilon, self.training)
+            else:
+                x = stats_pooling(x, lens, l.includeStd, l.epsilon, l.inputPeriod)
+                pooled = True
+        return x
+
+    def export(self):
+        """Write parameters and moving statistics back into the Sequential's layers (set_weights(..., fmt="tensorflow")): their
+        version counters invalidate device operand sets and captured graphs, and the model then runs in any gemm mode."""
+        for kind, l, at in self.steps:
+            if kind == "tdnn":
+                kernel = self.params[at].detach().permute(1, 2, 0).unsqueeze(0).cpu().numpy()        # [u, k, d] -> keras (1, K, D, units)
+                l.set_weights([kernel] + ([self.params[at + 1].detach().cpu().numpy()] if l.useBias else []), fmt="tensorflow")
+            elif kind == "bn":
+                l.set_weights([self.params[at].detach().cpu().numpy(), getattr(self, f"moving_mean_{at}").cpu().numpy(),
+                               getattr(self, f"moving_var_{at}").cpu().numpy()], fmt="tensorflow")
+        return self.seq

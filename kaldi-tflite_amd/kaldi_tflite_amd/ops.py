@@ -1394,3 +1394,39 @@ def rs_resample(x, n, n_dev, iu, ou, first, taps, first_dev, taps_dev, w_dev, ou
           int(ou), _host_ptr(first), _host_ptr(taps), L.ptr(first_dev), L.ptr(taps_dev), L.ptr(w_dev), _ld(w_dev), L.ptr(out),
           int(out.dtype == torch.int16), _ld(out), out.shape[1])
     return out
+
+
+# ----------------------------------------------------------------------------- gradients of the TDNN and the pooling (include/ktf_grad.h)
+def grad_tdnn_slot_rows():
+    """Flat rows b * T_out + t per partial sum of the weight gradient."""
+    return int(L.load().ktf_grad_tdnn_slot_rows())
+
+
+def grad_tdnn_workspace(B, T, desc, device):
+    """The workspace both TDNN gradient calls of a (B, T) batch of layer `desc` take."""
+    return _workspace("ktf_grad_tdnn_workspace_bytes", int(B), int(T), C.byref(desc), device=device)
+
+
+def grad_tdnn_data(g, lens, desc, w, dx, workspace):
+    """g (B, T_out, ldg) fp32 dense rows, w the forward operand, dx (B, T, ldx) fp32 preallocated: every element of dx is written."""
+    B, T, ldx = dx.shape
+    _call("ktf_grad_tdnn_data", dx.device, L.ptr(g), g.shape[2], B, T, L.ptr(lens), C.byref(desc), L.ptr(w), L.ptr(dx), ldx,
+          L.ptr(workspace), workspace.numel())
+    return dx
+
+
+def grad_tdnn_weights(x, lens, desc, g, dw, dbias, workspace):
+    """x (B, T, ldx) fp32 dense rows as the forward read them, g (B, T_out, ldg); dw in the forward operand's layout and dbias (units,)
+    or None, both preallocated: every element is written."""
+    B, T, ldx = x.shape
+    _call("ktf_grad_tdnn_weights", x.device, L.ptr(x), B, T, ldx, L.ptr(lens), C.byref(desc), L.ptr(g), g.shape[2], L.ptr(dw), L.ptr(dbias),
+          L.ptr(workspace), workspace.numel())
+    return dw, dbias
+
+
+def grad_stats_pool(x, D, lens, input_period, include_std, eps, gout, dx):
+    """x (B, T, ldx) fp32 dense rows, gout (B, D or 2 D) the gradient of ops.stats_pool's output, dx (B, T, ld_dx) preallocated."""
+    B, T, ldx = x.shape
+    _call("ktf_grad_stats_pool", x.device, L.ptr(x), B, T, int(D), ldx, L.ptr(lens), int(input_period), int(include_std), float(eps),
+          L.ptr(gout), gout.shape[1], L.ptr(dx), dx.shape[2])
+    return dx
