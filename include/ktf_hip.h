@@ -139,7 +139,8 @@ typedef struct KtfFrontendTables {   /* all DEVICE pointers, built once by the h
     const float* mel_w;        /* [num_mels][mel_stride] weights from mel_start            */
     const float* dct;          /* [num_mels][num_ceps] (filterbank.py melBank / dct.py dct) */
     const float* lifter;       /* [num_ceps] or NULL                                       */
-    /* optional tables of the register-resident nfft = 512 fast path (all three NULL = generic kernel); `reserved` = bins per mel work item */
+    /* optional tables of the register-resident nfft = 512 fast path (all three NULL = generic kernel); `reserved` = bins of the
+     * longest mel work item, 1..16 (checked: the shipped-configuration instances read (reserved + 6) / 4 16-byte pieces per item) */
     const float* fast_tw;      /* [64][18] per-lane FFT twiddles: (re,im) of W256^(n0 r), W64^(n1 r), W16^(n2 r), r=1..3,
                                   n0 = (l>>1)+32(l&1), n1 = (l>>1)&15, n2 = (l>>1)&3                                   */
     const int32_t* fast_mel_meta; /* [64][4] per-lane mel work item: first bin, bins (<=16), filter (-1 = idle),
@@ -170,6 +171,29 @@ int64_t ktf_num_frames_padded(int64_t n_samples, int32_t frame_size, int32_t fra
 int ktf_frontend_f32(const void* in, int64_t B, int64_t n, int32_t in_kind, const KtfFrontendCfg* cfg,
                      const KtfFrontendTables* tab, int32_t out_stage, float* out, float* energy,
                      uint64_t seed, void* stream);
+
+/* Which kernel instance ktf_frontend_f32 runs for a given call, and on what grid: the launcher takes its decision from the function
+ * behind this query, so the two cannot disagree. Host arithmetic only (no GPU call; it works without a GPU). The table POINTERS of
+ * `tab` are only tested for NULL, never followed; its two integers are read. The refusals and error codes are those of
+ * ktf_frontend_f32 itself, except for the `in` / `out` pointers, which this call does not see. */
+#define KTF_FE_NONE 0        /* nothing is launched (no utterance, or no frame)                                              */
+#define KTF_FE_FRAMING 1     /* KTF_OUT_FRAMES: the gather kernel (any frame size)                                           */
+#define KTF_FE_GENERIC 2     /* frontend_kernel<log2_nfft>: one wave per frame, FFT in LDS, nfft 64..2048                    */
+#define KTF_FE_FAST512 3     /* frontend512_kernel<dither, kind, mfix, std, nq>: register-resident nfft = 512                */
+typedef struct KtfFrontendPlan {
+    int32_t kernel;      /* KTF_FE_*                                                                                         */
+    int32_t log2_nfft;   /* 6..11 (GENERIC, FAST512: 9); 0 otherwise                                                         */
+    int32_t dither;      /* FAST512: the instance that draws dither noise                                                    */
+    int32_t kind;        /* FAST512: 1 = fp32 samples / frames read plainly, 2 = int16 samples, 0 = general (mirror padding) */
+    int32_t mfix;        /* FAST512: frame size known at compile time (400), or 0 = cfg->frame_size                          */
+    int32_t std;         /* FAST512: the shipped configuration's switches known at compile time                              */
+    int32_t nq;          /* FAST512: 16-byte pieces of the power spectrum a mel work item reads (3, 4 or 5)                  */
+    int32_t grid_x, grid_y;
+    int64_t lds_bytes;   /* dynamic LDS of the launch                                                                        */
+    int64_t T;           /* frames per utterance                                                                             */
+} KtfFrontendPlan;
+int ktf_frontend_plan(int64_t B, int64_t n, int32_t in_kind, const KtfFrontendCfg* cfg, const KtfFrontendTables* tab,
+                      int32_t out_stage, KtfFrontendPlan* plan);
 
 /* DCT.call (layers/dsp/dct.py:175-176) on its own: out[r, c] = sum_m x[r, m] * dct[m, c] (* lifter[c]). */
 int ktf_dct_f32(const float* x, int64_t rows, int32_t in_dim, int32_t out_dim, const float* dct,

@@ -355,9 +355,12 @@ __global__ void rowmat_kernel(const float* __restrict__ x, int64_t rows, int in_
     }
 }
 
+// frontend512.hip: does the register-resident nfft = 512 kernel take this call (1: yes, *p filled in; 0: no; < 0: refused), and its launch
+int ktf_frontend512_plan(int64_t B, int64_t n, int64_t T, int32_t in_kind, const KtfFrontendCfg* cfg, const KtfFrontendTables* tab,
+                         int32_t out_stage, KtfFrontendPlan* p);
 int ktf_frontend512_launch(const void* in, int64_t B, int64_t n, int32_t in_kind, const KtfFrontendCfg* cfg,
-                           const KtfFrontendTables* tab, int32_t out_stage, float* out, uint64_t seed, int64_t T,
-                           hipStream_t st);   // frontend512.hip
+                           const KtfFrontendTables* tab, int32_t out_stage, float* out, uint64_t seed, const KtfFrontendPlan* p,
+                           hipStream_t st);
 
 extern "C" int64_t ktf_num_frames(int64_t n_samples, int32_t frame_size, int32_t frame_shift) {
     if (frame_size <= 0 || frame_shift <= 0 || n_samples < frame_size) return 0;
@@ -375,13 +378,15 @@ extern "C" int64_t ktf_num_frames_padded(int64_t n_samples, int32_t frame_size, 
     return M;
 }
 
-extern "C" int ktf_frontend_f32(const void* in, int64_t B, int64_t n, int32_t in_kind, const KtfFrontendCfg* cfg,
-                                const KtfFrontendTables* tab, int32_t out_stage, float* out, float* energy,
-                                uint64_t seed, void* stream) {
+// The one place a front-end call is checked and its kernel instance, grid and LDS are decided: ktf_frontend_f32 launches what this
+// returns and ktf_frontend_plan reports it. `io` = the caller's in / out pointers are there (the query has none to show).
+static int frontend_plan(int64_t B, int64_t n, int32_t in_kind, const KtfFrontendCfg* cfg, const KtfFrontendTables* tab,
+                         int32_t out_stage, bool io, KtfFrontendPlan* p) {
+    *p = KtfFrontendPlan{};
     KTF_REQUIRE(B >= 0 && n >= 0, "ktf_frontend_f32: negative size");
     KTF_REQUIRE(cfg && tab, "ktf_frontend_f32: null argument");
     if (B == 0) return KTF_OK;                       // empty batch: nothing to read or write (pointers may be NULL)
-    KTF_REQUIRE(in && out, "ktf_frontend_f32: null argument");
+    KTF_REQUIRE(io, "ktf_frontend_f32: null argument");
     KTF_REQUIRE(in_kind >= KTF_IN_WAV && in_kind <= KTF_IN_WAV_I16, "ktf_frontend_f32: bad in_kind %d", in_kind);
     const bool wav = in_kind == KTF_IN_WAV || in_kind == KTF_IN_WAV_I16;
     const int pad_mode = wav ? cfg->pad_mode : 0;
@@ -398,20 +403,19 @@ extern "C" int ktf_frontend_f32(const void* in, int64_t B, int64_t n, int32_t in
     KTF_REQUIRE(!(in_kind == KTF_IN_WINDOWED && out_stage < KTF_OUT_FBANK), "ktf_frontend_f32: windowed input needs a FBANK/MFCC stage");
     if (out_stage == KTF_OUT_FRAMES) {
         KTF_REQUIRE(wav, "ktf_frontend_f32: KTF_OUT_FRAMES needs KTF_IN_WAV");
-        KTF_REQUIRE(B == 0 || pad_mode || n >= cfg->frame_size, "ktf_frontend_f32: input of %lld samples is shorter than a frame (%d)", (long long)n, cfg->frame_size);
-        const int64_t Tf = Tw;
-        const int64_t total = B * Tf * cfg->frame_size;
+        KTF_REQUIRE(pad_mode || n >= cfg->frame_size, "ktf_frontend_f32: input of %lld samples is shorter than a frame (%d)", (long long)n, cfg->frame_size);
+        const int64_t total = B * Tw * cfg->frame_size;
+        p->T = Tw;
         if (total == 0) return KTF_OK;
         int blk = ktf_cdiv(total, 256);
         if (blk > 4096) blk = 4096;
-        hipLaunchKernelGGL(framing_kernel, dim3(blk), dim3(256), 0, (hipStream_t)stream, in, (int)(in_kind == KTF_IN_WAV_I16),
-                           pad_mode ? (cfg->frame_size - cfg->frame_shift) / 2 : (in_kind == KTF_IN_WAV_I16 ? 0 : -1), B, n,
-                           cfg->row_stride > 0 ? (int64_t)cfg->row_stride : n, cfg->frame_size, cfg->frame_shift, Tf, out);
-        KTF_CHECK_LAUNCH("ktf_frontend_f32(framing)");
+        p->kernel = KTF_FE_FRAMING;
+        p->grid_x = blk;
+        p->grid_y = 1;
         return KTF_OK;
     }
     int log2nf = 0;
-    while ((1 << log2nf) < cfg->nfft) ++log2nf;
+    while (log2nf < 12 && (1 << log2nf) < cfg->nfft) ++log2nf;
     KTF_REQUIRE((1 << log2nf) == cfg->nfft && log2nf >= 6 && log2nf <= 11, "ktf_frontend_f32: nfft %d must be a power of two in [64, 2048]", cfg->nfft);
     KTF_REQUIRE(cfg->frame_size <= cfg->nfft, "ktf_frontend_f32: frame_size %d > nfft %d", cfg->frame_size, cfg->nfft);
     if (out_stage >= KTF_OUT_FBANK) {
@@ -424,20 +428,53 @@ extern "C" int ktf_frontend_f32(const void* in, int64_t B, int64_t n, int32_t in
     }
     if (in_kind != KTF_IN_WINDOWED && out_stage >= KTF_OUT_WINDOWED) KTF_REQUIRE(tab->window, "ktf_frontend_f32: missing window table");
     const int64_t T = wav ? Tw : n;
-    if (wav) KTF_REQUIRE(B == 0 || pad_mode || n >= cfg->frame_size, "ktf_frontend_f32: input of %lld samples is shorter than a frame (%d)", (long long)n, cfg->frame_size);
+    if (wav) KTF_REQUIRE(pad_mode || n >= cfg->frame_size, "ktf_frontend_f32: input of %lld samples is shorter than a frame (%d)", (long long)n, cfg->frame_size);
+    p->T = T;
     const int64_t rows = B * T;
     if (rows == 0) return KTF_OK;
-    if (cfg->nfft == 512 && out_stage >= KTF_OUT_FBANK && tab->fast_tw && tab->fast_mel_meta && tab->fast_mel_w &&
-        cfg->num_mels <= 32 && (out_stage == KTF_OUT_FBANK || cfg->num_ceps <= 64) && B < 65536 &&
-        T * (int64_t)512 < (1ll << 31) && n < (1ll << 31))
-        return ktf_frontend512_launch(in, B, n, in_kind, cfg, tab, out_stage, out, seed, T, (hipStream_t)stream);
-    FeLds L = fe_layout(*cfg, *tab, out_stage);
+    const int fast = ktf_frontend512_plan(B, n, T, in_kind, cfg, tab, out_stage, p);
+    if (fast != 0) return fast < 0 ? fast : KTF_OK;
+    const FeLds L = fe_layout(*cfg, *tab, out_stage);
     const size_t lds_bytes = (size_t)L.total * sizeof(float);
     KTF_REQUIRE(lds_bytes <= 160 * 1024, "ktf_frontend_f32: configuration needs %zu B of LDS (> 160 KiB)", lds_bytes);
     int blocks = ktf_cdiv(rows, FE_WAVES);
     const int max_blocks = 256 * 8;
     if (blocks > max_blocks) blocks = max_blocks;
+    p->kernel = KTF_FE_GENERIC;
+    p->log2_nfft = log2nf;
+    p->grid_x = blocks;
+    p->grid_y = 1;
+    p->lds_bytes = (int64_t)lds_bytes;
+    return KTF_OK;
+}
+
+extern "C" int ktf_frontend_plan(int64_t B, int64_t n, int32_t in_kind, const KtfFrontendCfg* cfg, const KtfFrontendTables* tab,
+                                 int32_t out_stage, KtfFrontendPlan* plan) {
+    KTF_REQUIRE(plan, "ktf_frontend_plan: null plan");
+    return frontend_plan(B, n, in_kind, cfg, tab, out_stage, true, plan);
+}
+
+extern "C" int ktf_frontend_f32(const void* in, int64_t B, int64_t n, int32_t in_kind, const KtfFrontendCfg* cfg,
+                                const KtfFrontendTables* tab, int32_t out_stage, float* out, float* energy,
+                                uint64_t seed, void* stream) {
+    KtfFrontendPlan pl;
+    const int rc = frontend_plan(B, n, in_kind, cfg, tab, out_stage, in && out, &pl);
+    if (rc != KTF_OK) return rc;
     hipStream_t st = (hipStream_t)stream;
+    const int64_t T = pl.T;
+    if (pl.kernel == KTF_FE_NONE) return KTF_OK;
+    if (pl.kernel == KTF_FE_FRAMING) {
+        const int pad_mode = cfg->pad_mode;          // (a waveform input: checked by the plan)
+        hipLaunchKernelGGL(framing_kernel, dim3(pl.grid_x), dim3(256), 0, st, in, (int)(in_kind == KTF_IN_WAV_I16),
+                           pad_mode ? (cfg->frame_size - cfg->frame_shift) / 2 : (in_kind == KTF_IN_WAV_I16 ? 0 : -1), B, n,
+                           cfg->row_stride > 0 ? (int64_t)cfg->row_stride : n, cfg->frame_size, cfg->frame_shift, T, out);
+        KTF_CHECK_LAUNCH("ktf_frontend_f32(framing)");
+        return KTF_OK;
+    }
+    if (pl.kernel == KTF_FE_FAST512) return ktf_frontend512_launch(in, B, n, in_kind, cfg, tab, out_stage, out, seed, &pl, st);
+    const FeLds L = fe_layout(*cfg, *tab, out_stage);
+    const size_t lds_bytes = (size_t)pl.lds_bytes;
+    const int blocks = pl.grid_x;
 #define FE_LAUNCH(LG)                                                                                          \
     case LG:                                                                                                   \
         if (lds_bytes > 64 * 1024)                                                                             \
@@ -445,7 +482,7 @@ extern "C" int ktf_frontend_f32(const void* in, int64_t B, int64_t n, int32_t in
         hipLaunchKernelGGL(frontend_kernel<LG>, dim3(blocks), dim3(FE_THREADS), lds_bytes, st, in, B, n, in_kind, \
                            *cfg, *tab, L, out_stage, out, energy, seed, T);                                     \
         break;
-    switch (log2nf) {
+    switch (pl.log2_nfft) {
         FE_LAUNCH(6) FE_LAUNCH(7) FE_LAUNCH(8) FE_LAUNCH(9) FE_LAUNCH(10) FE_LAUNCH(11)
         default: break;
     }

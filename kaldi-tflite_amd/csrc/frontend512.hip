@@ -641,34 +641,59 @@ __global__ __launch_bounds__(F5_THREADS, (KIND != 0 && !DITHER) ? F5_MINWAVES : 
     }
 }
 
-// launcher used by ktf_frontend_f32 (frontend.hip) when the fast tables are present and the configuration qualifies
-int ktf_frontend512_launch(const void* in, int64_t B, int64_t n, int32_t in_kind, const KtfFrontendCfg* cfg,
-                           const KtfFrontendTables* tab, int32_t out_stage, float* out, uint64_t seed, int64_t T,
-                           hipStream_t st) {
+// Does this kernel take the call, and as which instance (frontend.hip's frontend_plan asks once per call, for the launch and for
+// ktf_frontend_plan alike): 1 = yes, *p filled in; 0 = no, the generic kernel runs; < 0 = refused. Reads no table, only whether it is there.
+int ktf_frontend512_plan(int64_t B, int64_t n, int64_t T, int32_t in_kind, const KtfFrontendCfg* cfg, const KtfFrontendTables* tab,
+                         int32_t out_stage, KtfFrontendPlan* p) {
+    if (!(out_stage >= KTF_OUT_FBANK && tab->fast_tw && tab->fast_mel_meta && tab->fast_mel_w)) return 0;
+    // `reserved` is the caller's statement of the longest mel work item: an understated one would pick an instance that reads fewer pieces
+    // than the items span and drop their last weights without a word
+    KTF_REQUIRE(tab->reserved >= 1 && tab->reserved <= F5_MAXW, "ktf_frontend_f32: fast tables with reserved = %d bins per mel work item (must be 1..%d)", tab->reserved, F5_MAXW);
+    if (!(cfg->nfft == 512 && cfg->num_mels <= F5_MAXMEL && (out_stage == KTF_OUT_FBANK || cfg->num_ceps <= 64) && B < 65536 &&
+          T * (int64_t)512 < (1ll << 31) && n < (1ll << 31)))
+        return 0;
     // ~2048 workgroups in total: gx frame groups per utterance x B utterances
-    KTF_REQUIRE(B < 65536 && T * (int64_t)512 < (1ll << 31) && n < (1ll << 31), "ktf_frontend_f32(fast512): B, T or n too large");
     int gx = (int)(2048 / (B > 0 ? B : 1));
     const int gmax = ktf_cdiv(T, F5_WAVES);
     if (gx < 1) gx = 1;
     if (gx > gmax) gx = gmax;
-    const dim3 grid((unsigned)gx, (unsigned)B);
-    const size_t lds = sizeof(float) * (512 + (F5_MAXMEL + F5_MELQ * 4 + (F5_TW_LDS ? F5_TWREC : 0)) * KTF_WAVE + F5_WAVES * F5_WAVE_FLOATS);
+    const bool wav = in_kind == KTF_IN_WAV || in_kind == KTF_IN_WAV_I16;
     const bool dither = cfg->dither != 0.0f && in_kind != KTF_IN_WINDOWED;
-    const bool padded = (in_kind == KTF_IN_WAV || in_kind == KTF_IN_WAV_I16) && cfg->pad_mode;
-    const int kind = padded ? 0 : (in_kind == KTF_IN_WAV_I16 ? 2 : 1);
+    const bool padded = wav && cfg->pad_mode;
+    const bool std_cfg = !dither && !padded && cfg->frame_size == 400 && wav &&
+                         out_stage == KTF_OUT_MFCC && cfg->remove_dc && cfg->use_energy && cfg->raw_energy && cfg->preemph > 0.0f &&
+                         cfg->use_power && cfg->use_log;
+    p->kernel = KTF_FE_FAST512;
+    p->log2_nfft = 9;
+    p->dither = dither;
+    p->kind = padded ? 0 : (in_kind == KTF_IN_WAV_I16 ? 2 : 1);
+    p->mfix = (!dither && cfg->frame_size == 400) ? 400 : 0;
+    p->std = std_cfg;
+    // (at any shift an item of `reserved` bins spans (reserved + 3 + 3) / 4 aligned pieces: three up to 9 bins -- the 6-bin items of 32 mels
+    // below 2 kHz --, four up to 13 -- the 10-bin items of the 30- and 40-mel banks at 16 kHz, the 13-bin items of 23 mels --, five for 14 to 16)
+    const int nq = (tab->reserved + 6) / 4;
+    p->nq = !std_cfg ? F5_MELQ : (nq <= 3 ? 3 : nq == 4 ? 4 : F5_MELQ);
+    p->grid_x = gx;
+    p->grid_y = (int32_t)B;
+    p->lds_bytes = (int64_t)sizeof(float) * (512 + (F5_MAXMEL + F5_MELQ * 4 + (F5_TW_LDS ? F5_TWREC : 0)) * KTF_WAVE + F5_WAVES * F5_WAVE_FLOATS);
+    return 1;
+}
+
+// launcher used by ktf_frontend_f32 (frontend.hip) for a call ktf_frontend512_plan took: the instance, grid and LDS are the plan's
+int ktf_frontend512_launch(const void* in, int64_t B, int64_t n, int32_t in_kind, const KtfFrontendCfg* cfg,
+                           const KtfFrontendTables* tab, int32_t out_stage, float* out, uint64_t seed, const KtfFrontendPlan* p,
+                           hipStream_t st) {
+    const dim3 grid((unsigned)p->grid_x, (unsigned)p->grid_y);
+    const size_t lds = (size_t)p->lds_bytes;
+    const int64_t T = p->T;
+    const int kind = p->kind;
 #define F5_LAUNCH(DI, KI, MF)                                                                                          \
     hipLaunchKernelGGL((frontend512_kernel<DI, KI, MF>), grid, dim3(F5_THREADS), lds, st, in, B, n, in_kind, *cfg,    \
                        *tab, out_stage, out, seed, T)
-    const bool std_cfg = !dither && !padded && cfg->frame_size == 400 && (in_kind == KTF_IN_WAV || in_kind == KTF_IN_WAV_I16) &&
-                         out_stage == KTF_OUT_MFCC && cfg->remove_dc && cfg->use_energy && cfg->raw_energy && cfg->preemph > 0.0f &&
-                         cfg->use_power && cfg->use_log;
-    if (std_cfg) {
-        // (tab->reserved = the longest mel work item; at any shift it spans (reserved + 3 + 3) / 4 aligned pieces: four for the 10-bin items
-        // of the 30- and 40-mel banks at 16 kHz, five for the 13-bin items of 23 mels)
-        const int nq = (tab->reserved + 6) / 4;
+    if (p->std) {
 #define F5_STD(KI, NQ_) hipLaunchKernelGGL((frontend512_kernel<false, KI, 400, true, NQ_>), grid, dim3(F5_THREADS), lds, st, in, B, n, in_kind, *cfg, *tab, out_stage, out, seed, T)
-        if (kind == 2) { if (nq <= 3) F5_STD(2, 3); else if (nq == 4) F5_STD(2, 4); else F5_STD(2, F5_MELQ); }
-        else { if (nq <= 3) F5_STD(1, 3); else if (nq == 4) F5_STD(1, 4); else F5_STD(1, F5_MELQ); }
+        if (kind == 2) { if (p->nq == 3) F5_STD(2, 3); else if (p->nq == 4) F5_STD(2, 4); else F5_STD(2, F5_MELQ); }
+        else { if (p->nq == 3) F5_STD(1, 3); else if (p->nq == 4) F5_STD(1, 4); else F5_STD(1, F5_MELQ); }
 #undef F5_STD
         KTF_CHECK_LAUNCH("ktf_frontend_f32(fast512)");
         return KTF_OK;
@@ -679,8 +704,8 @@ int ktf_frontend512_launch(const void* in, int64_t B, int64_t n, int32_t in_kind
         else if (kind == 2) F5_LAUNCH(DI, 2, MF);                                                                      \
         else F5_LAUNCH(DI, 0, MF);                                                                                     \
     } while (0)
-    if (dither) F5_KINDS(true, 0);
-    else if (cfg->frame_size == 400) F5_KINDS(false, 400);
+    if (p->dither) F5_KINDS(true, 0);
+    else if (p->mfix == 400) F5_KINDS(false, 400);
     else F5_KINDS(false, 0);
 #undef F5_KINDS
 #undef F5_LAUNCH

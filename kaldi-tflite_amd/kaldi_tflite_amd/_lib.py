@@ -29,6 +29,7 @@ TDNN_MX_LOADER = 1 << 24          # ktf_tdnn_mx*: the loader-wave kernel (csrc/t
 
 IN_WAV, IN_FRAMES, IN_WINDOWED, IN_WAV_I16 = 0, 1, 2, 3
 OUT_FRAMES, OUT_WINDOWED, OUT_FBANK, OUT_MFCC = 0, 1, 2, 3
+FE_NONE, FE_FRAMING, FE_GENERIC, FE_FAST512 = 0, 1, 2, 3      # KtfFrontendPlan.kernel
 
 
 class KtfBackendError(RuntimeError):
@@ -65,6 +66,12 @@ class FrontendTables(C.Structure):
     ]
 
 
+class FrontendPlan(C.Structure):
+    _fields_ = [("kernel", C.c_int32), ("log2_nfft", C.c_int32), ("dither", C.c_int32), ("kind", C.c_int32), ("mfix", C.c_int32),
+                ("std", C.c_int32), ("nq", C.c_int32), ("grid_x", C.c_int32), ("grid_y", C.c_int32), ("lds_bytes", C.c_int64),
+                ("T", C.c_int64)]
+
+
 class VadCfg(C.Structure):
     _fields_ = [("energy_threshold", C.c_float), ("energy_mean_scale", C.c_float), ("proportion_threshold", C.c_float),
                 ("frames_context", C.c_int32), ("energy_coeff", C.c_int32)]
@@ -98,6 +105,7 @@ PROTOTYPES = {
     "ktf_num_frames": (_i64, [_i64, _i32, _i32]),
     "ktf_num_frames_padded": (_i64, [_i64, _i32, _i32, _i32]),
     "ktf_frontend_f32": (C.c_int, [_P, _i64, _i64, _i32, C.POINTER(FrontendCfg), C.POINTER(FrontendTables), _i32, _P, _P, _u64, _P]),
+    "ktf_frontend_plan": (C.c_int, [_i64, _i64, _i32, C.POINTER(FrontendCfg), C.POINTER(FrontendTables), _i32, C.POINTER(FrontendPlan)]),
     "ktf_dct_f32": (C.c_int, [_P, _i64, _i32, _i32, _P, _P, _P, _P]),
     "ktf_vad_mask_f32": (C.c_int, [_P, _i64, _i64, _i32, C.POINTER(VadCfg), _P, _P]),
     "ktf_vad_index": (C.c_int, [_P, _i64, _i64, _i32, C.POINTER(VadCfg), _P, _P, _P]),

@@ -238,6 +238,16 @@ def frontend(x, in_kind, cfg, tables, out_stage, n, B, T, seed=0, want_energy=Fa
     return (out, energy) if want_energy else out
 
 
+def frontend_plan(B, n, in_kind, cfg, tables, out_stage):
+    """Which kernel instance `frontend` runs for this call, on what grid and with how much LDS: a `FrontendPlan`
+    (ktf_frontend_plan: the launcher's own decision; host arithmetic, no GPU needed). `tables`: a FrontendTables, or the bare
+    `_lib.FrontendTables` struct (its pointers are only tested for NULL)."""
+    plan = L.FrontendPlan()
+    tab = getattr(tables, "struct", tables)
+    L.check(L.load().ktf_frontend_plan(B, n, in_kind, C.byref(cfg), C.byref(tab), out_stage, C.byref(plan)), "ktf_frontend_plan")
+    return plan
+
+
 def dct(x2d, dct_t, lifter_t, out_dim):
     lib = L.load()
     rows, in_dim = x2d.shape

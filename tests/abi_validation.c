@@ -90,6 +90,23 @@ int main(void) {
     EXPECT_EINVAL(ktf_cmvn_plan(100, 30, 29, &vp));                                                    /* ldo < D */
     if (ktf_vad_cmvn_plan(5, 998, 30, 32, &vp) != KTF_OK || vp.nsplit != 8 || !vp.lds_form || vp.stage_floats != 998 * 30 ||
         ktf_cmvn_plan(20481, 30, 30, &vp) != KTF_OK || vp.stage_floats || vp.bs_floats || vp.lds_bytes != 8192) { printf("FAIL: ktf_vad_cmvn_plan / ktf_cmvn_plan\n"); ++fails; }
+    {   /* the front-end's plan query: host arithmetic on the struct's integers, the table pointers only tested for NULL */
+        KtfFrontendCfg fc = {400, 160, 512, 30, 30, 1, 1, 1, 1, 1, 1, 0.97f, 0.0f, 0.0f, 1e-7f, 0, 0};
+        KtfFrontendTables ft = {f, f, f, (const int32_t*)l, (const int32_t*)l, f, f, f, f, (const int32_t*)l, f, 10, 10};
+        KtfFrontendPlan fp;
+        EXPECT_EINVAL(ktf_frontend_plan(1, 16000, KTF_IN_WAV, &fc, &ft, KTF_OUT_MFCC, NULL));
+        EXPECT_EINVAL(ktf_frontend_plan(1, 16000, KTF_IN_WAV, NULL, &ft, KTF_OUT_MFCC, &fp));
+        EXPECT_EINVAL(ktf_frontend_plan(1, 399, KTF_IN_WAV, &fc, &ft, KTF_OUT_MFCC, &fp));                 /* shorter than a frame */
+        ft.reserved = 0;
+        EXPECT_EINVAL(ktf_frontend_plan(1, 16000, KTF_IN_WAV, &fc, &ft, KTF_OUT_MFCC, &fp));               /* bins per mel work item: 1..16 */
+        EXPECT_EINVAL(ktf_frontend_f32(f, 1, 16000, KTF_IN_WAV, &fc, &ft, KTF_OUT_MFCC, f, NULL, 0, NULL));
+        ft.reserved = 10;
+        if (ktf_frontend_plan(3, 16000, KTF_IN_WAV_I16, &fc, &ft, KTF_OUT_MFCC, &fp) != KTF_OK || fp.kernel != KTF_FE_FAST512 || fp.kind != 2 ||
+            fp.mfix != 400 || !fp.std || fp.nq != 4 || fp.T != 98 || fp.grid_x != 13 || fp.grid_y != 3) { printf("FAIL: ktf_frontend_plan (fast512)\n"); ++fails; }
+        ft.fast_tw = NULL;
+        if (ktf_frontend_plan(3, 16000, KTF_IN_WAV_I16, &fc, &ft, KTF_OUT_MFCC, &fp) != KTF_OK || fp.kernel != KTF_FE_GENERIC || fp.log2_nfft != 9 ||
+            fp.grid_x != 74 || fp.lds_bytes <= 0) { printf("FAIL: ktf_frontend_plan (generic)\n"); ++fails; }
+    }
     t.gemm = KTF_GEMM_BF16X3; t.x_dtype = KTF_BF16; t.w_dtype = KTF_BF16; t.y_dtype = KTF_F32; t.units = 256;
     EXPECT_EINVAL(ktf_tdnn_split_flat(f, f, 1, 1, 32, NULL, NULL, &t, f, f, NULL, NULL, NULL, f, NULL, 256, NULL));        /* no row map */
     t.valid = 1;

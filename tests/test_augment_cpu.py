@@ -146,7 +146,7 @@ def test_header_symbols_are_the_augment_prototypes_and_exported():
     lib = L.load()
     for name in declared:
         assert hasattr(lib, name), name
-    assert len(L.PROTOTYPES) == 119
+    assert len(L.PROTOTYPES) == 120
     assert not set(L.PROTOTYPES) & set(L.AUGMENT_PROTOTYPES)
     core = open(os.path.join(ROOT, "include", "ktf_hip.h")).read()
     assert "ktf_aug_" not in core

@@ -31,8 +31,8 @@ HOST_HELPERS = re.compile(r"ktf_\w+_workspace_bytes")
 # Symbols this test does not have to reach: what the extraction path calls (the runner test pins those), the front-end / VAD / CMVN /
 # pooling / tail / conversion entry points of ops.py above plda_score, and the library's own bookkeeping. No back-end symbol is here.
 FRONT_END = {
-    "ktf_num_frames", "ktf_num_frames_padded", "ktf_frontend_f32", "ktf_dct_f32", "ktf_vad_mask_f32", "ktf_vad_index", "ktf_cmvn_f32",
-    "ktf_vad_cmvn", "ktf_vad_cmvn_plan", "ktf_cmvn_plan", "ktf_route_short", "ktf_tdnn_last_kernel", "ktf_split_bf16",
+    "ktf_num_frames", "ktf_num_frames_padded", "ktf_frontend_f32", "ktf_frontend_plan", "ktf_dct_f32", "ktf_vad_mask_f32", "ktf_vad_index",
+    "ktf_cmvn_f32", "ktf_vad_cmvn", "ktf_vad_cmvn_plan", "ktf_cmvn_plan", "ktf_route_short", "ktf_tdnn_last_kernel", "ktf_split_bf16",
     "ktf_affine_act_f32", "ktf_activation_f32", "ktf_convert_pad", "ktf_stats_pool_windowed_f32", "ktf_xvec_post_f32",
     "ktf_xvec_tail_f32", "ktf_plda_f64", "ktf_plda_f32",
 }

@@ -118,7 +118,7 @@ def test_header_symbols_are_the_grad_prototypes_and_exported():
     assert not set(L.GRAD_PROTOTYPES) & (set(L.PROTOTYPES) | set(L.AUGMENT_PROTOTYPES) | set(L.RESAMPLE_PROTOTYPES))
     for other in ("ktf_hip.h", "ktf_augment.h", "ktf_resample.h"):
         assert "ktf_grad_" not in open(os.path.join(ROOT, "include", other)).read()
-    assert len(L.PROTOTYPES) == 119 and lib.ktf_version() == 117
+    assert len(L.PROTOTYPES) == 120 and lib.ktf_version() == 117
     assert lib.ktf_grad_tdnn_row_tile() == 64 and lib.ktf_grad_tdnn_slot_rows() == 512
 
 
