@@ -42,16 +42,8 @@ __global__ __launch_bounds__(256) void tdnn_bf16_kernel(TdnnParams p) {
     constexpr int TILE = 128 * C::PITCH;
     constexpr int STAGE = TILE * 2 * NBUF_A;
 
-    const int b = blockIdx.z;
-    const int len = p.lens ? p.lens[b] : (int)p.T;
-    int start;
-    const int out_len = tdnn_out_len(len, p, start);
-    if (p.out_lens && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) p.out_lens[b] = out_len;
-    const int t0 = blockIdx.y * BF_BM;
-    if (t0 >= out_len || len <= 0) return;
-    const int n0 = blockIdx.x * BF_BN;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wm = wave >> 1, wn = wave & 1;
+    TDNN_TILE3D_HEADER(BF_BM, BF_BN)
+    const int wave = tid >> 6, wm = wave >> 1, wn = wave & 1;
 
     const int64_t xbase = (int64_t)b * p.T * p.ldx;
     const unsigned short* wb = reinterpret_cast<const unsigned short*>(p.w);

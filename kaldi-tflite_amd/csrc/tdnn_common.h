@@ -1,5 +1,6 @@
-// Shared by the TDNN GEMM kernel families (tdnn_f32.hip, tdnn_bf16.hip, tdnn_split.hip) and their dispatcher (tdnn_gemm.hip):
-// the kernel parameter block, the output-length rule, activations, and the per-family launchers.
+// Shared by the TDNN GEMM kernel families (tdnn_f32.hip, tdnn_pair.hip, tdnn_grad.hip, tdnn_bf16.hip, tdnn_split.hip) and their dispatcher
+// (tdnn_gemm.hip): the kernel parameter block, the output-length rule, the tile headers, activations, the epilogue value and typed stores
+// of the fp32 / pair families, the register-staged 32x32x2 main loop, and the per-family launchers.
 //
 //   y[b,t,u] = post(act(bias[u] + sum_k sum_d x[b, row(t,k), d] * W[u, k*Dp + d]))
 //   row(t,k) = clip(start + t*sub + ctx[k], 0, len_b - 1)
@@ -102,6 +103,22 @@ __device__ __forceinline__ int tdnn_out_len(int len, const TdnnParams& p, int& s
     if (t0 >= out_len || len <= 0) return;                                                             \
     const int n0 = nt * (BN);
 
+// The tile header of the kernels on a 3-D grid (x = N-tile, y = M-tile, z = utterance): tdnn_f32_kernel, tdnn_f32s_kernel,
+// tdnn_f32t_kernel, tdnn_x4s_kernel, tdnn_bf16_kernel and, with BM = 1 (t0 is its output row), tdnn_f32_rowvec_kernel. Declares b, len,
+// start, out_len, t0, n0 as TDNN_TILE_HEADER does, and tid / lane; the utterance's first tile writes out_lens[b]; returns from the kernel
+// where the tile holds no valid row. (`wave` stays with the kernels: the DMA-staged ones take it through readfirstlane.)
+// (A macro for the reason given at TDNN_TILE_HEADER; the early return has to be the kernel's own.)
+#define TDNN_TILE3D_HEADER(BM, BN)                                                                     \
+    const int b = blockIdx.z;                                                                          \
+    const int len = p.lens ? p.lens[b] : (int)p.T;                                                     \
+    int start;                                                                                         \
+    const int out_len = tdnn_out_len(len, p, start);                                                   \
+    if (p.out_lens && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) p.out_lens[b] = out_len; \
+    const int t0 = blockIdx.y * (BM);                                                                  \
+    if (t0 >= out_len || len <= 0) return;                                                             \
+    const int n0 = blockIdx.x * (BN);                                                                  \
+    const int tid = threadIdx.x, lane = tid & 63;
+
 __device__ __forceinline__ float apply_act(float v, int act) {
     if (act == KTF_ACT_RELU) return v < 0.0f ? 0.0f : v;      // tf.nn.relu propagates NaN (Eigen cwiseMax<PropagateNaN>): the pooled row of an
                                                               // utterance without a frame stays NaN through the layers behind the pooling; fmaxf would return 0
@@ -126,7 +143,53 @@ __device__ __forceinline__ float apply_act_ext(float v, int act) {
     }
 }
 
-// Epilogue for the 32x32 accumulator layout: col = lane&31, row = (reg&3) + 8*(reg>>2) + 4*(lane>>5).
+// The epilogue value of the fp32 and pair families: bias -> activation -> BatchNorm affine (not applied at all without one). A sibling
+// of tdnn_ring.h's EPI_VALUE, which differs in both: its ReLU is fmaxf (NaN -> 0) and it always multiplies. TDNN_EPI_ROW: ... as it is
+// stored in a row, i.e. as its KTF_BF16P pair where the launch asks for pairs (the pooled form of tdnn_x4s_kernel sums the value itself).
+// TDNN_STORE_Y / TDNN_STORE_Y4: the store by the rows' type, of element OFF of y / of the four consecutive units N .. N + 3 whose first
+// is element OFF (one 16-byte store for fp32 rows where VEC_OK -- TDNN_Y_VEC_OK -- and all four are units). All read the kernel's `p`.
+// (Macros: as inlined functions each of them, the one-line TDNN_Y_VEC_OK included, changed the registers and the instruction count of
+// every kernel that uses it -- tdnn_bf16_kernel 108 -> 124 VGPRs; as macros tdnn_bf16_kernel's code is the text it was.)
+#define TDNN_EPI_VALUE(ACC, BIAS, SC, SH, ACT)                                                         \
+    ({                                                                                                 \
+        float v_ = apply_act((ACC) + (BIAS), ACT);                                                     \
+        if (p.scale) v_ = v_ * (SC) + (SH);                                                            \
+        v_;                                                                                            \
+    })
+#define TDNN_EPI_ROW(ACC, BIAS, SC, SH, ACT)                                                           \
+    ({                                                                                                 \
+        float r_ = TDNN_EPI_VALUE(ACC, BIAS, SC, SH, ACT);                                             \
+        if (p.y_pair) r_ = ktf_pair(r_);                                                               \
+        r_;                                                                                            \
+    })
+#define TDNN_STORE_Y(OFF, V)                                                                           \
+    {                                                                                                  \
+        if (p.y_dtype == KTF_F32) reinterpret_cast<float*>(p.y)[OFF] = (V);                            \
+        else reinterpret_cast<unsigned short*>(p.y)[OFF] = f2bf(V);                                    \
+    }
+#define TDNN_STORE_Y4(OFF, N, V, VEC_OK)                                                               \
+    {                                                                                                  \
+        if (p.y_dtype == KTF_F32) {                                                                    \
+            float* yp_ = reinterpret_cast<float*>(p.y) + (OFF);                                        \
+            if ((VEC_OK) && (N) + 4 <= p.units) {                                                      \
+                *reinterpret_cast<fv4*>(yp_) = fv4{V[0], V[1], V[2], V[3]};                            \
+            } else {                                                                                   \
+                _Pragma("unroll") for (int e = 0; e < 4; ++e)                                          \
+                    if ((N) + e < p.units) yp_[e] = V[e];                                              \
+            }                                                                                          \
+        } else {                                                                                       \
+            unsigned short* yp_ = reinterpret_cast<unsigned short*>(p.y) + (OFF);                      \
+            _Pragma("unroll") for (int e = 0; e < 4; ++e)                                              \
+                if ((N) + e < p.units) yp_[e] = f2bf(V[e]);                                            \
+        }                                                                                              \
+    }
+#define TDNN_Y_VEC_OK ((p.ldy & 3) == 0 && (reinterpret_cast<uintptr_t>(p.y) & 15) == 0)
+
+// Row of register `reg` in the 32x32 accumulator layout of the block whose first row is `base` (column = lane & 31)
+// (base is an argument because the sum's association is part of the generated code: base + acc32_row(...) moved every caller's registers)
+__device__ __forceinline__ int acc32_row(int base, int reg, int lane) { return base + (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5); }
+
+// Epilogue for the 32x32 accumulator layout: col = lane&31, row = acc32_row(0, reg, lane).
 __device__ __forceinline__ void store_tile32(const f32x16& acc, const TdnnParams& p, int64_t out_row0, int rows_valid,
                                              int m_base, int n_base, int lane) {
     const int n = n_base + (lane & 31);
@@ -136,20 +199,17 @@ __device__ __forceinline__ void store_tile32(const f32x16& acc, const TdnnParams
     const float sh = p.shift ? p.shift[n] : 0.0f;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-        const int m = m_base + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+        const int m = acc32_row(m_base, r, lane);
         if (m < rows_valid) {
-            float v = apply_act(acc[r] + bias, p.act);
-            if (p.scale) v = v * sc + sh;
-            if (p.y_pair) v = ktf_pair(v);
+            const float v = TDNN_EPI_ROW(acc[r], bias, sc, sh, p.act);
             const int64_t off = (out_row0 + m) * p.ldy + n;
-            if (p.y_dtype == KTF_F32) reinterpret_cast<float*>(p.y)[off] = v;
-            else reinterpret_cast<unsigned short*>(p.y)[off] = f2bf(v);
+            TDNN_STORE_Y(off, v)
         }
     }
 }
 
 // Same tile with the MFMA operands swapped (W block as A, x block as B): the accumulator is the transposed tile,
-//   time row = lane&31, unit = (reg&3) + 8*(reg>>2) + 4*(lane>>5),
+//   time row = lane&31, unit = acc32_row(0, reg, lane),
 // so a lane owns four CONSECUTIVE units per register quad and the store is 16 bytes instead of four 4-byte stores (the
 // 64 scalar stores per lane of store_tile32 cost the fp32 tile kernel ~20 % of its time). Products commute and the K
 // order is unchanged: bit-identical values.
@@ -159,7 +219,7 @@ __device__ __forceinline__ void store_tile32_t(const f32x16& acc, const TdnnPara
     const int m = m_base + (lane & 31);
     if (m >= rows_valid) return;
     const int64_t rowoff = (out_row0 + m) * p.ldy;
-    const bool vec_ok = (p.ldy & 3) == 0 && (reinterpret_cast<uintptr_t>(p.y) & 15) == 0;
+    const bool vec_ok = TDNN_Y_VEC_OK;
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
         const int n = n_base + 8 * q + 4 * (lane >> 5);
@@ -167,29 +227,55 @@ __device__ __forceinline__ void store_tile32_t(const f32x16& acc, const TdnnPara
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             const bool nv = n + e < p.units;
-            const float bias = (nv && p.bias) ? p.bias[n + e] : 0.0f;
-            v[e] = apply_act(acc[q * 4 + e] + bias, ACT);
-            if (p.scale) v[e] = v[e] * (nv ? p.scale[n + e] : 1.0f) + (nv ? p.shift[n + e] : 0.0f);
-            if (p.y_pair) v[e] = ktf_pair(v[e]);
+            v[e] = TDNN_EPI_ROW(acc[q * 4 + e], (nv && p.bias) ? p.bias[n + e] : 0.0f, nv ? p.scale[n + e] : 1.0f, nv ? p.shift[n + e] : 0.0f, ACT);
         }
-        if (p.y_dtype == KTF_F32) {
-            float* yp = reinterpret_cast<float*>(p.y) + rowoff + n;
-            if (vec_ok && n + 4 <= p.units) {
-                *reinterpret_cast<fv4*>(yp) = fv4{v[0], v[1], v[2], v[3]};
-            } else {
-#pragma unroll
-                for (int e = 0; e < 4; ++e)
-                    if (n + e < p.units) yp[e] = v[e];
-            }
-        } else {
-            unsigned short* yp = reinterpret_cast<unsigned short*>(p.y) + rowoff + n;
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-                if (n + e < p.units) yp[e] = f2bf(v[e]);
-        }
+        TDNN_STORE_Y4(rowoff + n, n, v, vec_ok)
     }
 }
 
+// The register-staged, double-buffered main loop of the 32x32x2 fp32 tile GEMMs (tdnn_f32_kernel: the KTF_TDNN_REF_TILES bitwise
+// reference; grad_dx_kernel, grad_dw_kernel in tdnn_grad.hip): four waves as 2 x 2, wave (wm, wn) owns MTM x MTN blocks of 32 x 32; As /
+// Bs are the two stages of (64 MTM) / (64 MTN) rows of BK + 1 floats. load_global(ks) fetches step ks into the caller's registers,
+// store_lds(buf) writes them to stage buf (each caller's own gather and transposition), step(buf) runs once per step between the MFMAs
+// and the refill of the other stage (grad_dw_kernel's bias sum). SWAP: the b fragment is the MFMA's first operand (the transposed tile
+// of store_tile32_t). nk >= 1.
+template <int MTM, int MTN, int BK, bool SWAP, typename LoadGlobal, typename StoreLds, typename Step>
+__device__ __forceinline__ void tile32_mainloop(f32x16 (&acc)[MTM][MTN], const float* As, const float* Bs, int nk, int wm, int wn, int lane,
+                                                LoadGlobal&& load_global, StoreLds&& store_lds, Step&& step) {
+    constexpr int PITCH = BK + 1;
+#pragma unroll
+    for (int i = 0; i < MTM; ++i)
+#pragma unroll
+        for (int j = 0; j < MTN; ++j)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.0f;
+    load_global(0);
+    store_lds(0);
+    __syncthreads();
+    for (int ks = 0; ks < nk; ++ks) {
+        const int buf = ks & 1;
+        if (ks + 1 < nk) load_global(ks + 1);
+        const float* a_base = As + buf * (64 * MTM * PITCH) + (wm * 32 * MTM + (lane & 31)) * PITCH + (lane >> 5);
+        const float* b_base = Bs + buf * (64 * MTN * PITCH) + (wn * 32 * MTN + (lane & 31)) * PITCH + (lane >> 5);
+#pragma unroll
+        for (int kk = 0; kk < BK; kk += 2) {
+            float av[MTM], bv[MTN];
+#pragma unroll
+            for (int i = 0; i < MTM; ++i) av[i] = a_base[i * 32 * PITCH + kk];
+#pragma unroll
+            for (int j = 0; j < MTN; ++j) bv[j] = b_base[j * 32 * PITCH + kk];
+#pragma unroll
+            for (int i = 0; i < MTM; ++i)
+#pragma unroll
+                for (int j = 0; j < MTN; ++j)
+                    acc[i][j] = SWAP ? __builtin_amdgcn_mfma_f32_32x32x2f32(bv[j], av[i], acc[i][j], 0, 0, 0)
+                                     : __builtin_amdgcn_mfma_f32_32x32x2f32(av[i], bv[j], acc[i][j], 0, 0, 0);
+        }
+        step(buf);
+        if (ks + 1 < nk) store_lds(buf ^ 1);
+        __syncthreads();
+    }
+}
 
 // name of the kernel family the calling thread's last ktf_tdnn* call launched (ktf_tdnn_last_kernel; dispatch tests)
 extern thread_local const char* g_ktf_last_kernel;

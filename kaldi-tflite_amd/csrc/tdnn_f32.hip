@@ -1,10 +1,9 @@
 // KTF_GEMM_F32: exact fp32 products / fp32 accumulate on v_mfma_f32_32x32x2_f32 / 16x16x4_f32 (bit-identical to an fmaf chain in K
 // order): the parity path. Throughput tile (128 x 128, two workgroups per CU), single-utterance tiles (64 x 32 / 64 / 96), a
 // row-vector kernel for <= 8 output rows, and the register-staged 32x32x2 kernels kept as their bitwise reference
-// (KTF_TDNN_REF_TILES).
-#include "tdnn_common.h"
-
-typedef __attribute__((ext_vector_type(4))) float f32x4v;
+// (KTF_TDNN_REF_TILES). Shared parts: the tile header, the epilogue value and typed stores and the register-staged main loop
+// (tile32_mainloop) are tdnn_common.h's; the small tiles' constants, ring, K-loop, row epilogue and launcher are tdnn_small_tile.h's.
+#include "tdnn_small_tile.h"
 
 // ------------------------------------------------------------------------------------ F32
 // (64*MT) x (64*MT) block tile, K-step 16, 4 waves as 2x2, each wave MT x MT MFMA 32x32 tiles. MT = 2 (128x128) is the
@@ -20,16 +19,8 @@ __global__ __launch_bounds__(256) void tdnn_f32_kernel(TdnnParams p) {
     constexpr int NLD = BM * C4 / 256;               // float4 per thread and operand
     __shared__ float As[2][BM * F32_PITCH];
     __shared__ float Bs[2][BN * F32_PITCH];
-    const int b = blockIdx.z;
-    const int len = p.lens ? p.lens[b] : (int)p.T;
-    int start;
-    const int out_len = tdnn_out_len(len, p, start);
-    if (p.out_lens && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) p.out_lens[b] = out_len;
-    const int t0 = blockIdx.y * BM;
-    if (t0 >= out_len || len <= 0) return;
-    const int n0 = blockIdx.x * BN;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wm = wave >> 1, wn = wave & 1;
+    TDNN_TILE3D_HEADER(BM, BN)
+    const int wave = tid >> 6, wm = wave >> 1, wn = wave & 1;
 
     const float* xb = reinterpret_cast<const float*>(p.x) + (int64_t)b * p.T * p.ldx;
     const float* wb = reinterpret_cast<const float*>(p.w);
@@ -45,13 +36,6 @@ __global__ __launch_bounds__(256) void tdnn_f32_kernel(TdnnParams p) {
     }
 
     f32x16 acc[MT][MT];
-#pragma unroll
-    for (int i = 0; i < MT; ++i)
-#pragma unroll
-        for (int j = 0; j < MT; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.0f;
-
     const int nk = p.ktot / F32_BK;
     const int steps_per_ctx = p.din_pad / F32_BK;
     float4 ra[NLD], rb[NLD];
@@ -78,31 +62,7 @@ __global__ __launch_bounds__(256) void tdnn_f32_kernel(TdnnParams p) {
         }
     };
 
-    load_global(0);
-    store_lds(0);
-    __syncthreads();
-    for (int ks = 0; ks < nk; ++ks) {
-        const int buf = ks & 1;
-        if (ks + 1 < nk) load_global(ks + 1);
-        const float* a_base = &As[buf][(wm * 32 * MT + (lane & 31)) * F32_PITCH + (lane >> 5)];
-        const float* b_base = &Bs[buf][(wn * 32 * MT + (lane & 31)) * F32_PITCH + (lane >> 5)];
-#pragma unroll
-        for (int kk = 0; kk < F32_BK; kk += 2) {
-            float av[MT], bv[MT];
-#pragma unroll
-            for (int i = 0; i < MT; ++i) {
-                av[i] = a_base[i * 32 * F32_PITCH + kk];
-                bv[i] = b_base[i * 32 * F32_PITCH + kk];
-            }
-#pragma unroll
-            for (int i = 0; i < MT; ++i)
-#pragma unroll
-                for (int j = 0; j < MT; ++j)
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(bv[j], av[i], acc[i][j], 0, 0, 0);   // transposed tile
-        }
-        if (ks + 1 < nk) store_lds(buf ^ 1);
-        __syncthreads();
-    }
+    tile32_mainloop<MT, MT, BK, true>(acc, &As[0][0], &Bs[0][0], nk, wm, wn, lane, load_global, store_lds, [](int) {});   // transposed tile
 
     const int rows_valid = out_len - t0;
     const int64_t out_row0 = (int64_t)b * p.Tout + t0;
@@ -139,150 +99,49 @@ __global__ __launch_bounds__(256) void tdnn_f32_kernel(TdnnParams p) {
 //     much LDS fragment traffic (each operand block is read by four waves), which one workgroup per CU cannot overlap.
 //     BN = 32 (64 x 32 tiles, eight waves) when 64 x 64 tiles would leave CUs idle: twice the workgroups, half the MFMA and
 //     LDS time per CU for 1.5x the L2->LDS bytes (the same layer: 26 us).
-#define FS_BM 64
-#define FS_NSTAGE 4
+// The fp32 operand format of the small tiles (tdnn_small_tile.h): lane (row r16, quarter kq) takes element 4c + kq of its row for
+// position c -- one float of each 16-byte chunk, a ds_read_b32 per operand and MFMA. (Tried: the lane reads chunk 4g + kq whole and
+// the four lanes of a row transpose their 4 x 4 floats with v_permlane32_swap / v_permlane16_swap -- a quarter of the LDS
+// instructions, same bits, 13 % slower: the swaps are slower than the reads they replace.)
 template <int BK, int BN, int NB>
-__global__ __launch_bounds__(64 * 4 * (BN / 16 / NB)) void tdnn_f32s_kernel(TdnnParams p) {
-    static_assert(BN % (16 * NB) == 0, "a wave owns NB 16-column blocks");
-    constexpr int WN = BN / 16 / NB;                         // waves across the tile's columns, NB blocks each (one A fragment
-    constexpr int NT = 64 * 4 * WN;                          // feeds NB MFMAs); 1024 / 512 threads
-    constexpr int CH = BK / 4;                               // 16-byte chunks per row
-    constexpr int ROWB = BK * 4;                             // bytes per staged row
-    constexpr int A_BYTES = FS_BM * ROWB, W_BYTES = BN * ROWB;
-    constexpr int TILE_BYTES = A_BYTES;                      // offset of the W tile inside a stage
-    constexpr int STAGE_BYTES = A_BYTES + W_BYTES;
-    constexpr bool HALVES = (FS_BM * CH + BN * CH == NT);    // <32,64>: threads 0-511 stage A, 512-1023 stage W
-    constexpr int NA = HALVES ? 1 : (FS_BM * CH) / NT;       // DMAs per thread and stage into the A tile
-    constexpr int NW = HALVES ? 0 : (BN * CH) / NT;          // ... and into the W tile
-    constexpr int NDMA = HALVES ? 1 : NA + NW;
-    static_assert(HALVES || ((FS_BM * CH) % NT == 0 && (BN * CH) % NT == 0), "staging does not divide");
-    extern __shared__ __attribute__((aligned(16))) unsigned char fsm[];
-    const int b = blockIdx.z;
-    const int len = p.lens ? p.lens[b] : (int)p.T;
-    int start;
-    const int out_len = tdnn_out_len(len, p, start);
-    if (p.out_lens && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) p.out_lens[b] = out_len;
-    const int t0 = blockIdx.y * FS_BM;
-    if (t0 >= out_len || len <= 0) return;
-    const int n0 = blockIdx.x * BN;
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wm = wave / WN, wn = wave % WN;
-
-#include "tdnn_small_ring.inc"
-
+struct F32Frag {
+    using S = SmallTile<BK, BN, NB>;
+    static constexpr int POS = S::CH;
     f32x4v acc[NB];
+    float av[S::CH], bv[NB][S::CH];
+    int a_row_off, b_row_off, sw;
+    __device__ __forceinline__ void init(int wm, int wn, int lane) {
 #pragma unroll
-    for (int j = 0; j < NB; ++j)
+        for (int j = 0; j < NB; ++j)
 #pragma unroll
-        for (int r = 0; r < 4; ++r) acc[j][r] = 0.0f;
-    const int r16 = lane & 15, kq = lane >> 4;
-    // Fragments: lane (row r16, quarter kq) takes element 4c + kq of its row for position c -- one float of each 16-byte
-    // chunk, a ds_read_b32 per operand and MFMA. (Tried: the lane reads chunk 4g + kq whole and the four lanes of a row
-    // transpose their 4 x 4 floats with v_permlane32_swap / v_permlane16_swap -- a quarter of the LDS instructions, same
-    // bits, 13 % slower: the swaps are slower than the reads they replace.)
-    const int a_row_off = (wm * 16 + r16) * ROWB + kq * 4;
-    const int b_row_off = TILE_BYTES + (wn * NB * 16 + r16) * ROWB + kq * 4;        // block j: + j * 16 rows
-    const int sw = r16 & (CH - 1);
-    // wait until at most `n_` (0..3) of this wave's stages are still in flight (NDMA DMAs each); s_waitcnt with vmcnt = v,
-    // expcnt / lgkmcnt left at their maxima
-#define FS_VM(v_) (((v_) & 15) | (((v_) >> 4) << 14) | 0x0f70)
-#define FS_WAIT(n_)                                                                                                    \
-    {                                                                                                                  \
-        static_assert(3 * NDMA <= 63, "vmcnt range");                                                                  \
-        const int n__ = (n_);                                                                                          \
-        if (n__ >= 3) __builtin_amdgcn_s_waitcnt(FS_VM(3 * NDMA));                                                     \
-        else if (n__ == 2) __builtin_amdgcn_s_waitcnt(FS_VM(2 * NDMA));                                                \
-        else if (n__ == 1) __builtin_amdgcn_s_waitcnt(FS_VM(NDMA));                                                    \
-        else __builtin_amdgcn_s_waitcnt(FS_VM(0));                                                                     \
+            for (int r = 0; r < 4; ++r) acc[j][r] = 0.0f;
+        const int r16 = lane & 15, kq = lane >> 4;
+        a_row_off = (wm * 16 + r16) * S::ROWB + kq * 4;
+        b_row_off = S::TILE_BYTES + (wn * NB * 16 + r16) * S::ROWB + kq * 4;        // block j: + j * 16 rows
+        sw = r16 & (S::CH - 1);
     }
-    // The fragments of step ks + 1 are read under the MFMAs of step ks (one workgroup per CU, both waves of a SIMD in the
-    // same phase: read latency in front of the MFMAs was 40 % of the step). A stage is refilled four steps ahead, into
-    // the slot whose fragments every wave took during the previous step.
-    float av[CH], bv[NB][CH];
-    {
-        const int issued = nk < FS_NSTAGE ? nk : FS_NSTAGE;
-        FS_WAIT(issued - 1)
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
+    __device__ __forceinline__ void read(int c, const unsigned char* st) {
+        av[c] = *reinterpret_cast<const float*>(st + a_row_off + ((c ^ sw) << 4));
 #pragma unroll
-        for (int c = 0; c < CH; ++c) {
-            av[c] = *reinterpret_cast<const float*>(fsm + a_row_off + ((c ^ sw) << 4));
-#pragma unroll
-            for (int j = 0; j < NB; ++j)
-                bv[j][c] = *reinterpret_cast<const float*>(fsm + b_row_off + j * 16 * ROWB + ((c ^ sw) << 4));
-        }
-        __builtin_amdgcn_s_waitcnt(0xc07f);                  // lgkmcnt(0), as an instruction the compiler's counter model sees
-    }                                                        // (an inline-asm wait is not: fragments "pending" at the loop head
-                                                             // put a wait for the reads just issued in front of every MFMA)
-    for (int ks = 0; ks + 1 < nk; ++ks) {
-        const int beyond = nk - 2 - ks;                      // stages issued beyond ks + 1: min(beyond, 2)
-        FS_WAIT(beyond < 2 ? beyond : 2)
-        __builtin_amdgcn_s_barrier();                         // every wave has taken stage ks (its reads were waited for at the
-        asm volatile("" ::: "memory");                       // end of the previous step): the slot can be refilled
-        const bool refill = is_ks < nk;
-        if (refill) {
-            FS_SRC()
-            FS_ADV()
-        }
-        // One position of the K-step at a time: its MFMA(s), then the fragment reads of the same position of the next stage
-        // into the registers those MFMAs just consumed, and every CH / NDMA positions one DMA of the refill. Bursts keep all
-        // waves in LDS issue (at most 15 LDS operations of a wave are in flight) or in the texture addresser's queue while
-        // the matrix pipes idle. In-kernel stamps (K = 1536, 64 x 32 tiles, tools/b1_tile_probe.py with -DKTF_FS_ABL): K-loop
-        // 22.7 us; MFMAs + barrier alone 13.8, fragment reads + barrier alone 13.9 (256 ds_read_b32 per step and workgroup
-        // at ~4.8 cycles each), DMA stream alone 9.4: the LDS instruction rate and the MFMAs are both near their limits.
-        const unsigned char* nst = fsm + ((ks + 1) & (FS_NSTAGE - 1)) * STAGE_BYTES;
-        constexpr int DSTEP = CH / NDMA > 0 ? CH / NDMA : 1;
-#pragma unroll
-        for (int c = 0; c < CH; ++c) {
-#pragma unroll
-            for (int j = 0; j < NB; ++j) {
-                acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[c], bv[j][c], acc[j], 0, 0, 0);
-            }
-            if (c % DSTEP == 0 && c / DSTEP < NDMA) {
-                if (refill) FS_DMA(c / DSTEP)
-            }
-            av[c] = *reinterpret_cast<const float*>(nst + a_row_off + ((c ^ sw) << 4));
-#pragma unroll
-            for (int j = 0; j < NB; ++j)
-                bv[j][c] = *reinterpret_cast<const float*>(nst + b_row_off + j * 16 * ROWB + ((c ^ sw) << 4));
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        __builtin_amdgcn_s_waitcnt(0xc07f);
+        for (int j = 0; j < NB; ++j) bv[j][c] = *reinterpret_cast<const float*>(st + b_row_off + j * 16 * S::ROWB + ((c ^ sw) << 4));
     }
-#pragma unroll
-    for (int c = 0; c < CH; ++c)
+    __device__ __forceinline__ void mfma(int c) {
 #pragma unroll
         for (int j = 0; j < NB; ++j) acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[c], bv[j][c], acc[j], 0, 0, 0);
-#undef FS_WAIT
-#undef FS_VM
-#undef FS_STAGE
-#undef FS_SRC
-#undef FS_DMA
-#undef FS_ADV
-    // 16x16 accumulator layout: acc[r] = out[row 4*(lane>>4) + r][col lane&15]
-    const int rows_valid = out_len - t0;
-    const int64_t out_row0 = (int64_t)b * p.Tout + t0;
-#pragma unroll
-    for (int j = 0; j < NB; ++j) {
-        const int n = n0 + (wn * NB + j) * 16 + r16;
-        if (n >= p.units) continue;
-        const float bias = p.bias ? p.bias[n] : 0.0f;
-        const float sc = p.scale ? p.scale[n] : 1.0f;
-        const float sh = p.shift ? p.shift[n] : 0.0f;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int m = wm * 16 + kq * 4 + r;
-            if (m < rows_valid) {
-                float v = apply_act(acc[j][r] + bias, p.act);
-                if (p.scale) v = v * sc + sh;
-                if (p.y_pair) v = ktf_pair(v);
-                const int64_t off = (out_row0 + m) * p.ldy + n;
-                if (p.y_dtype == KTF_F32) reinterpret_cast<float*>(p.y)[off] = v;
-                else reinterpret_cast<unsigned short*>(p.y)[off] = f2bf(v);
-            }
-        }
     }
+    __device__ __forceinline__ float value(int j, int r) const { return acc[j][r]; }
+};
+
+template <int BK, int BN, int NB>
+__global__ __launch_bounds__(64 * 4 * (BN / 16 / NB)) void tdnn_f32s_kernel(TdnnParams p) {
+    constexpr int WN = SmallTile<BK, BN, NB>::WN;
+    extern __shared__ __attribute__((aligned(16))) unsigned char fsm[];
+    TDNN_TILE3D_HEADER(FS_BM, BN)
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wm = wave / WN, wn = wave % WN;
+    F32Frag<BK, BN, NB> f;
+    small_tile_kloop<BK, BN, NB>(p, fsm, b, len, start, t0, n0, tid, wave, wm, wn, lane, f);
+    small_tile_store<BN, NB, true>(p, f, b, t0, n0, out_len, wm, wn, lane);
 }
 
 // (3) throughput form: 128x128 tile, EIGHT waves of 2x4 blocks of v_mfma_f32_16x16x4_f32 (six scalar LDS reads feed eight
@@ -302,7 +161,7 @@ __device__ __forceinline__ void f32t_epilogue(f32x4v (&acc)[2][4], const TdnnPar
     const int r16 = lane & 15, kq = lane >> 4;
     const int rows_valid = out_len - t0;
     const int64_t out_row0 = (int64_t)b * p.Tout + t0;
-    const bool vec_ok = (p.ldy & 3) == 0 && (reinterpret_cast<uintptr_t>(p.y) & 15) == 0;
+    const bool vec_ok = TDNN_Y_VEC_OK;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         const int n = n0 + wn * 64 + j * 16 + kq * 4;
@@ -320,27 +179,9 @@ __device__ __forceinline__ void f32t_epilogue(f32x4v (&acc)[2][4], const TdnnPar
             if (m >= rows_valid) continue;
             float v[4];
 #pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                v[e] = apply_act(acc[i][j][e] + bias[e], ACT);
-                if (p.scale) v[e] = v[e] * sc[e] + sh[e];
-                if (p.y_pair) v[e] = ktf_pair(v[e]);
-            }
+            for (int e = 0; e < 4; ++e) v[e] = TDNN_EPI_ROW(acc[i][j][e], bias[e], sc[e], sh[e], ACT);
             const int64_t off = (out_row0 + m) * p.ldy + n;
-            if (p.y_dtype == KTF_F32) {
-                float* yp = reinterpret_cast<float*>(p.y) + off;
-                if (vec_ok && n + 4 <= p.units) {
-                    *reinterpret_cast<fv4*>(yp) = fv4{v[0], v[1], v[2], v[3]};
-                } else {
-#pragma unroll
-                    for (int e = 0; e < 4; ++e)
-                        if (n + e < p.units) yp[e] = v[e];
-                }
-            } else {
-                unsigned short* yp = reinterpret_cast<unsigned short*>(p.y) + off;
-#pragma unroll
-                for (int e = 0; e < 4; ++e)
-                    if (n + e < p.units) yp[e] = f2bf(v[e]);
-            }
+            TDNN_STORE_Y4(off, n, v, vec_ok)
         }
     }
 }
@@ -353,15 +194,7 @@ __global__ __launch_bounds__(512, 2) void tdnn_f32t_kernel(TdnnParams p) {
     constexpr int STAGE_BYTES = 2 * TILE_BYTES;
     constexpr int NDMA = (FT_BM * CH) / 512;                 // DMAs per thread, stage and operand: 2 (BK 32) / 1 (BK 16)
     extern __shared__ __attribute__((aligned(16))) unsigned char ftm[];
-    const int b = blockIdx.z;
-    const int len = p.lens ? p.lens[b] : (int)p.T;
-    int start;
-    const int out_len = tdnn_out_len(len, p, start);
-    if (p.out_lens && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) p.out_lens[b] = out_len;
-    const int t0 = blockIdx.y * FT_BM;
-    if (t0 >= out_len || len <= 0) return;
-    const int n0 = blockIdx.x * FT_BM;
-    const int tid = threadIdx.x, lane = tid & 63;
+    TDNN_TILE3D_HEADER(FT_BM, FT_BM)
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave >> 1, wn = wave & 1;
     // staging: chunk q = i*512 + tid of a tile -> row q/CH, LDS position q%CH holds global chunk (q%CH) ^ (row&(CH-1))
@@ -452,14 +285,9 @@ __global__ __launch_bounds__(512, 2) void tdnn_f32t_kernel(TdnnParams p) {
 #define RV_STAGE_BYTES (RV_UNITS * RV_BK * 4 + 256)            // 2 KiB of W + the row's 32 inputs (a 4-byte DMA writes 64 lanes x 4 B: stored twice)
 __global__ __launch_bounds__(64) void tdnn_f32_rowvec_kernel(TdnnParams p) {
     __shared__ __attribute__((aligned(16))) unsigned char rvm[RV_NSTAGE * RV_STAGE_BYTES];
-    const int b = blockIdx.z, t = blockIdx.y;
-    const int len = p.lens ? p.lens[b] : (int)p.T;
-    int start;
-    const int out_len = tdnn_out_len(len, p, start);
-    const int tid = threadIdx.x;
-    if (p.out_lens && blockIdx.x == 0 && t == 0 && tid == 0) p.out_lens[b] = out_len;
-    if (t >= out_len || len <= 0) return;
-    const int n0 = blockIdx.x * RV_UNITS;
+    TDNN_TILE3D_HEADER(1, RV_UNITS)                          // one-row tiles: t0 is the row (and one wave: tid is the lane)
+    const int t = t0;
+    (void)lane;
     const char* xb = reinterpret_cast<const char*>(p.x) + ((int64_t)b * p.T * p.ldx) * 4;
     const char* wb = reinterpret_cast<const char*>(p.w);
     const unsigned ldxb = (unsigned)p.ldx * 4u;
@@ -500,12 +328,11 @@ __global__ __launch_bounds__(64) void tdnn_f32_rowvec_kernel(TdnnParams p) {
     // ks + 1 are issued BEFORE the 32 FMAs of step ks (two register sets, loop unrolled by two so that no set is copied):
     // with read -> wait -> FMA per step a third of the step was exposed LDS latency. Waits are s_waitcnt instructions the
     // compiler's counter model sees (behind an inline-asm wait it re-waits for the reads just issued in front of the FMAs).
-#define RV_VM(v_) (((v_) & 15) | (((v_) >> 4) << 14) | 0x0f70)
     // stage j_ has landed: stages up to min(j_ + 14, nk - 1) have been issued, 3 DMAs each, completing in order
 #define RV_LANDED(j_)                                                                                                  \
     {                                                                                                                  \
-        if ((j_) + RV_NSTAGE - 2 <= nk - 1) __builtin_amdgcn_s_waitcnt(RV_VM(3 * (RV_NSTAGE - 2)));                    \
-        else __builtin_amdgcn_s_waitcnt(RV_VM(0));                                                                     \
+        if ((j_) + RV_NSTAGE - 2 <= nk - 1) __builtin_amdgcn_s_waitcnt(FS_VM(3 * (RV_NSTAGE - 2)));                    \
+        else __builtin_amdgcn_s_waitcnt(FS_VM(0));                                                                     \
     }
 #define RV_READ(wv_, xv_, j_)                                                                                          \
     {                                                                                                                  \
@@ -548,7 +375,6 @@ __global__ __launch_bounds__(64) void tdnn_f32_rowvec_kernel(TdnnParams p) {
         RV_STEP(w1, x1, w0, x0, ks + 1)
     }
     if (ks < nk) RV_FMA(w0, x0)                              // odd step count: the last stage sits in set 0
-#undef RV_VM
 #undef RV_LANDED
 #undef RV_READ
 #undef RV_FMA
@@ -559,15 +385,11 @@ __global__ __launch_bounds__(64) void tdnn_f32_rowvec_kernel(TdnnParams p) {
         const float bias = p.bias ? p.bias[n] : 0.0f;
         const float sc = p.scale ? p.scale[n] : 1.0f;
         const float sh = p.shift ? p.shift[n] : 0.0f;
-        float v = apply_act(acc + bias, p.act);
-        if (p.scale) v = v * sc + sh;
-        if (p.y_pair) v = ktf_pair(v);
+        const float v = TDNN_EPI_ROW(acc, bias, sc, sh, p.act);
         const int64_t off = ((int64_t)b * p.Tout + t) * p.ldy + n;
-        if (p.y_dtype == KTF_F32) reinterpret_cast<float*>(p.y)[off] = v;
-        else reinterpret_cast<unsigned short*>(p.y)[off] = f2bf(v);
+        TDNN_STORE_Y(off, v)
     }
 }
-
 
 // ------------------------------------------------------------------------------------ launcher
 int tdnn_launch_f32(const TdnnParams& p, const KtfTdnnDesc* d, int64_t B, int64_t Tout, hipStream_t st) {
@@ -579,18 +401,11 @@ int tdnn_launch_f32(const TdnnParams& p, const KtfTdnnDesc* d, int64_t B, int64_
         const dim3 grid((unsigned)ktf_cdiv(d->units, RV_UNITS), (unsigned)Tout, (unsigned)B);
         tdnn_launch_kernel<tdnn_f32_rowvec_kernel>("tdnn_f32_rowvec_kernel", grid, dim3(64), 0, 0, st, p);
     } else if (lat && wg128 < 256) {
-        auto small = [&](auto BK, auto BN) {
-            constexpr int NB = BN == 96 ? 3 : 1, lds = FS_NSTAGE * (FS_BM + BN) * BK * 4;
-            const char* name = BK == 32 ? "tdnn_f32s_kernel<32, 64>" : BN == 32 ? "tdnn_f32s_kernel<64, 32>"
-                             : BN == 64 ? "tdnn_f32s_kernel<64, 64>" : "tdnn_f32s_kernel<64, 96>";
-            const dim3 grid((unsigned)ktf_cdiv(d->units, BN), (unsigned)ktf_cdiv(Tout, FS_BM), (unsigned)B);
-            tdnn_launch_kernel<tdnn_f32s_kernel<BK, BN, NB>>(name, grid, dim3(64 * 4 * (BN / 16 / NB)), lds, lds, st, p);
-        };
-        if (d->din_pad % 64 == 0)
-            tdnn_pick<32, 64, 96>(small_tile_width(d->units, (int64_t)ktf_cdiv(Tout, FS_BM) * B),
-                                  [&](auto BN) { small(std::integral_constant<int, 64>{}, BN); });
-        else
-            small(std::integral_constant<int, 32>{}, std::integral_constant<int, 64>{});
+        static const char* const names[] = {"tdnn_f32s_kernel<32, 64>", "tdnn_f32s_kernel<64, 32>", "tdnn_f32s_kernel<64, 64>",
+                                            "tdnn_f32s_kernel<64, 96>"};
+        small_tile_launch(d, B, Tout, [&](auto BK, auto BN, auto NB, int i, dim3 grid, dim3 block, int lds) {
+            tdnn_launch_kernel<tdnn_f32s_kernel<BK, BN, NB>>(names[i], grid, block, lds, lds, st, p);
+        });
     } else if (lat) {
         tdnn_launch_kernel<tdnn_f32t_kernel<32>>("tdnn_f32t_kernel", grid128, dim3(512), FT_LDS_BYTES, FT_LDS_BYTES, st, p);
     } else if (wg128 >= 256) {

@@ -7,7 +7,7 @@
 //   ktf_grad_stats_pool    grad_pool_kernel
 //
 // Both GEMMs are register-staged, double-buffered LDS tiles of four waves (2 x 2), K-step 16, rows of 17 floats (the layout of
-// tdnn_f32_kernel): a wave owns MTM x MTN blocks of 32 x 32, `a` operand = the output's row index, `b` operand = its column index, so
+// tdnn_f32_kernel, and its main loop: tile32_mainloop in tdnn_common.h): a wave owns MTM x MTN blocks of 32 x 32, `a` operand = the output's row index, `b` operand = its column index, so
 // lanes 0-31 of a store cover 32 consecutive floats of an output row. Operand elements that stand for nothing -- rows of g at or
 // beyond an utterance's output length, rows past a slot's end, columns past `units` -- are staged as 0.0f and never loaded.
 #include "tdnn_common.h"
@@ -104,13 +104,6 @@ __global__ __launch_bounds__(GR_THREADS) void grad_dx_kernel(GradParams p) {
     }
 
     f32x16 acc[MTM][MTN];
-#pragma unroll
-    for (int i = 0; i < MTM; ++i)
-#pragma unroll
-        for (int j = 0; j < MTN; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.0f;
-
     const int nu = (p.f.units + GR_BK - 1) / GR_BK;  // W has round_up(units, 256) rows: a step past `units` reads its zero rows
     const int nk = p.f.nctx * nu;
     float ra[NLA][4];
@@ -161,31 +154,9 @@ __global__ __launch_bounds__(GR_THREADS) void grad_dx_kernel(GradParams p) {
         }
     };
 
-    load_global(0);
-    store_lds(0);
-    __syncthreads();
-    for (int ks = 0; ks < nk; ++ks) {
-        const int buf = ks & 1;
-        if (ks + 1 < nk) load_global(ks + 1);
-        const float* a_base = &As[buf][(wm * 32 * MTM + (lane & 31)) * GR_PITCH + (lane >> 5)];
-        const float* b_base = &Bs[buf][(wn * 32 * MTN + (lane & 31)) * GR_PITCH + (lane >> 5)];
-#pragma unroll
-        for (int kk = 0; kk < GR_BK; kk += 2) {
-            float av[MTM], bv[MTN];
-#pragma unroll
-            for (int i = 0; i < MTM; ++i) av[i] = a_base[i * 32 * GR_PITCH + kk];
-#pragma unroll
-            for (int j = 0; j < MTN; ++j) bv[j] = b_base[j * 32 * GR_PITCH + kk];
-#pragma unroll
-            for (int i = 0; i < MTM; ++i)
-#pragma unroll
-                for (int j = 0; j < MTN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[i], bv[j], acc[i][j], 0, 0, 0);
-        }
-        if (ks + 1 < nk) store_lds(buf ^ 1);
-        __syncthreads();
-    }
+    tile32_mainloop<MTM, MTN, GR_BK, false>(acc, &As[0][0], &Bs[0][0], nk, wm, wn, lane, load_global, store_lds, [](int) {});
 
-    // accumulator layout: column = lane & 31, row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5)
+    // accumulator layout: column = lane & 31, row = acc32_row(0, reg, lane)
 #pragma unroll
     for (int i = 0; i < MTM; ++i)
 #pragma unroll
@@ -194,7 +165,7 @@ __global__ __launch_bounds__(GR_THREADS) void grad_dx_kernel(GradParams p) {
             if (d >= p.f.ldx) continue;
 #pragma unroll
             for (int reg = 0; reg < 16; ++reg) {
-                const int r = r0 + wm * 32 * MTM + i * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5);
+                const int r = acc32_row(r0 + wm * 32 * MTM + i * 32, reg, lane);
                 if (r < T) dxb[(int64_t)r * p.f.ldx + d] = (r < len && d < p.din) ? acc[i][j][reg] : 0.0f;
             }
         }
@@ -239,12 +210,6 @@ __global__ __launch_bounds__(GR_THREADS) void grad_dw_kernel(GradParams p) {
     }
 
     f32x16 acc[MTM][MTN];
-#pragma unroll
-    for (int i = 0; i < MTM; ++i)
-#pragma unroll
-        for (int j = 0; j < MTN; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.0f;
     float bsum = 0.0f;
 
     const int nk = (m1 - m0 + GR_BK - 1) / GR_BK;
@@ -298,35 +263,13 @@ __global__ __launch_bounds__(GR_THREADS) void grad_dw_kernel(GradParams p) {
         }
     };
 
-    if (nk > 0) {
-        load_global(0);
-        store_lds(0);
-    }
-    __syncthreads();
-    for (int ks = 0; ks < nk; ++ks) {
-        const int buf = ks & 1;
-        if (ks + 1 < nk) load_global(ks + 1);
-        const float* a_base = &As[buf][(wm * 32 * MTM + (lane & 31)) * GR_PITCH + (lane >> 5)];
-        const float* b_base = &Bs[buf][(wn * 32 * MTN + (lane & 31)) * GR_PITCH + (lane >> 5)];
-#pragma unroll
-        for (int kk = 0; kk < GR_BK; kk += 2) {
-            float av[MTM], bv[MTN];
-#pragma unroll
-            for (int i = 0; i < MTM; ++i) av[i] = a_base[i * 32 * GR_PITCH + kk];
-#pragma unroll
-            for (int j = 0; j < MTN; ++j) bv[j] = b_base[j * 32 * GR_PITCH + kk];
-#pragma unroll
-            for (int i = 0; i < MTM; ++i)
-#pragma unroll
-                for (int j = 0; j < MTN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[i], bv[j], acc[i][j], 0, 0, 0);
-        }
+    // (nk >= 1: the grid has one z per slot that holds a row, so m0 < p.rows)
+    tile32_mainloop<MTM, MTN, GR_BK, false>(acc, &As[0][0], &Bs[0][0], nk, wm, wn, lane, load_global, store_lds, [&](int buf) {
         if (with_bias && tid < BM) {
 #pragma unroll
             for (int r = 0; r < GR_BK; ++r) bsum += As[buf][tid * GR_PITCH + r];
         }
-        if (ks + 1 < nk) store_lds(buf ^ 1);
-        __syncthreads();
-    }
+    });
 
     float* ws = p.slots + (int64_t)slot * p.slot_stride;
 #pragma unroll
@@ -337,7 +280,7 @@ __global__ __launch_bounds__(GR_THREADS) void grad_dw_kernel(GradParams p) {
             if (d >= p.f.din_pad) continue;
 #pragma unroll
             for (int reg = 0; reg < 16; ++reg) {
-                const int u = u0 + wm * 32 * MTM + i * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5);
+                const int u = acc32_row(u0 + wm * 32 * MTM + i * 32, reg, lane);
                 if (u < p.units_pad) ws[(int64_t)u * p.f.ktot + (int64_t)k * p.f.din_pad + d] = acc[i][j][reg];
             }
         }

@@ -132,7 +132,17 @@ def reference(c, x, W, bias, scale=None, shift=None):
     x3 = is_x3(c)
     xq = np.asarray(x, np.float32) if x3 else bf16_rne(x)
     Wq = np.asarray(W, np.float32) if x3 else bf16_rne(W)
-    xq, Wq = xq.astype(np.float64), Wq.astype(np.float64)
+    if x3:
+        return reference_on(c, xq, Wq, bias, scale, shift, lambda A, b, ktot: (3 * ktot + 1) * U32 * (1.02 * A + b) + X3_OPERANDS * A)
+    return reference_on(c, xq, Wq, bias, scale, shift, lambda A, b, ktot: (ktot + 1) * U32 * (A + b))
+
+
+def reference_on(c, xq, Wq, bias, scale, shift, dz_of, mag=None):
+    """The Ref of case c on the operands xq, Wq as the kernel sees them. dz_of(A, |bias|, Ktot): the bound on the pre-activation value
+    (items 1 and 2 of the docstring; tests/_tdnn32_ref.py passes the fp32 families' own), the epilogue's share (items 3 and 4) is added here.
+    mag: the (x, W) magnitudes that A is the sum of products of, where they are not |xq|, |Wq| themselves."""
+    xq, Wq = np.asarray(xq, np.float64), np.asarray(Wq, np.float64)
+    xa, Wa = (np.abs(xq), np.abs(Wq)) if mag is None else mag
     B, T, D = xq.shape
     U, ktot = Wq.shape
     lens = lens_of(c, B)
@@ -148,11 +158,8 @@ def reference(c, x, W, bias, scale=None, shift=None):
         if out_len[b] == 0:
             continue
         z[b, :out_len[b]] = O.tdnn(xq[b:b + 1, :n], Wq, b64, **kw)[0]
-        A[b, :out_len[b]] = O.tdnn(np.abs(xq[b:b + 1, :n]), np.abs(Wq), None, **kw)[0]
-    if x3:
-        dz = (3 * ktot + 1) * U32 * (1.02 * A + np.abs(b64)) + X3_OPERANDS * A
-    else:
-        dz = (ktot + 1) * U32 * (A + np.abs(b64))
+        A[b, :out_len[b]] = O.tdnn(xa[b:b + 1, :n], Wa, None, **kw)[0]
+    dz = dz_of(A, np.abs(b64), ktot)
     act = c["act"]
     with np.errstate(invalid="ignore"):
         a = act64(z, act)
@@ -174,12 +181,13 @@ def slot_rows(c, out_len):
     flat row space (utterance b starts at flat row sum(out_len[:b]))."""
     res = []
     s0 = 0
+    rows = c.get("slot_rows", SLOT_ROWS)                  # (the pair kernel's slots hold 64 rows: tests/_tdnn32_ref.py)
     for b, n in enumerate(int(v) for v in out_len):
         base = s0 if c["mode"] in FLAT_MODES else 0
         if n > 0:
-            first = base >> 7
-            for blk in range(first, ((base + n - 1) >> 7) + 1):
-                lo, hi = max(blk * SLOT_ROWS, base) - base, min((blk + 1) * SLOT_ROWS, base + n) - base
+            first = base // rows
+            for blk in range(first, (base + n - 1) // rows + 1):
+                lo, hi = max(blk * rows, base) - base, min((blk + 1) * rows, base + n) - base
                 res.append((b, blk - first, lo, hi))
         s0 += n
     return res
