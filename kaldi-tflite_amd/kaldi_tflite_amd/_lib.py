@@ -252,6 +252,9 @@ GRAD_PROTOTYPES = {
     "ktf_grad_tdnn_data": (C.c_int, [_P, _i64, _i64, _i64, _P, C.POINTER(TdnnDesc), _P, _P, _i64, _P, C.c_size_t, _P]),
     "ktf_grad_tdnn_weights": (C.c_int, [_P, _i64, _i64, _i64, _P, C.POINTER(TdnnDesc), _P, _i64, _P, _P, _P, C.c_size_t, _P]),
     "ktf_grad_stats_pool": (C.c_int, [_P, _i64, _i64, _i32, _i64, _P, _i32, _i32, _f32, _P, _i64, _P, _i64, _P]),
+    "ktf_grad_tdnn16_workspace_bytes": (_i64, [_i64, _i64, C.POINTER(TdnnDesc), _i32]),
+    "ktf_grad_tdnn16_data": (C.c_int, [_P, _i64, _i64, _i64, _P, C.POINTER(TdnnDesc), _P, _P, _i64, _P, C.c_size_t, _i32, _P]),
+    "ktf_grad_tdnn16_weights": (C.c_int, [_P, _i64, _i64, _i64, _P, C.POINTER(TdnnDesc), _P, _i64, _P, _P, _P, C.c_size_t, _i32, _P]),
 }
 AUG_META, AUG_STATS = 8, 4          # ktf_aug_*: int32 per RIR of the bank's meta; doubles per row of the statistics
 PLDA_DENSE_NO_PCA = -1.0            # ktf_plda_dense_*: target_energy for "no PCA"

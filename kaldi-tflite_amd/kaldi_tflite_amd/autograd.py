@@ -6,6 +6,10 @@ include/ktf_grad.h), batch normalisation in training mode, and `TrainableSequent
 
 The GEMMs and the pooling run in the HIP kernels on fp32; padding to the kernels' operand layouts, ReLU and the batch normalisation
 are torch ops on the same device. There is no CPU path for the kernels: tensors that are not on the GPU are refused.
+
+`gemm=` selects the matrix pipe of the TDNN GEMMs, forward and backward: "f32" (the exact-fp32 MFMA), "bf16" (operands rounded to
+bf16 in the kernels, fp32 accumulation) or "bf16x3" (hi / lo split operands, three products: near-fp32 values). Parameters,
+activations and gradients are fp32 tensors in every mode (include/ktf_grad.h rules 6 - 9).
 """
 
 import torch
@@ -30,6 +34,15 @@ def _desc(units, din, context, subsampling_factor, padding):
     d.act, d.gemm, d.flags = L.ACT_NONE, L.GEMM_F32, 0
     d.x_dtype = d.w_dtype = d.y_dtype = L.KTF_F32
     return d
+
+
+_GEMMS = {"f32": L.GEMM_F32, "bf16": L.GEMM_BF16, "bf16x3": L.GEMM_BF16X3}
+
+
+def _gemm_code(gemm):
+    if gemm not in _GEMMS:
+        raise ValueError(f"gemm must be one of {sorted(_GEMMS)}, got {gemm!r}")
+    return _GEMMS[gemm]
 
 
 def _on_gpu(t, what):
@@ -60,7 +73,7 @@ def tdnn_out_lens(lens, context, subsampling_factor=1, padding="SAME"):
 
 class _TdnnAffine(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, weight, bias, lens, context, subsampling_factor, padding):
+    def forward(ctx, x, weight, bias, lens, context, subsampling_factor, padding, gemm=L.GEMM_F32):
         B, T, D = x.shape
         units, nctx = weight.shape[0], weight.shape[1]
         d = _desc(units, D, context, subsampling_factor, padding)
@@ -71,9 +84,17 @@ class _TdnnAffine(torch.autograd.Function):
         Tout = ops.tdnn_out_len(T, d)
         y = torch.zeros((B, Tout, units), dtype=torch.float32, device=x.device)  # rows at and beyond an utterance's output length stay zero
         if B > 0 and Tout > 0:
-            ops.tdnn(xp, lens, d, wp.view(Up, nctx * Dp), None, None if bias is None else bias.contiguous(), None, None, y)
+            b = None if bias is None else bias.contiguous()
+            if gemm == L.GEMM_F32:
+                ops.tdnn(xp, lens, d, wp.view(Up, nctx * Dp), None, b, None, None, y)
+            else:                                                                # the 16-bit operand(s) of this call's fp32 parameter
+                fd = _desc(units, D, context, subsampling_factor, padding)
+                fd.gemm, fd.w_dtype = gemm, L.KTF_BF16
+                wh = wp.view(Up, nctx * Dp).to(torch.bfloat16)                   # round to nearest even
+                wl = (wp.view(Up, nctx * Dp) - wh.to(torch.float32)).to(torch.bfloat16) if gemm == L.GEMM_BF16X3 else None
+                ops.tdnn(xp, lens, fd, wh, wl, b, None, None, y)
         ctx.save_for_backward(xp, wp, lens)
-        ctx.desc, ctx.dims, ctx.has_bias = d, (D, units, nctx), bias is not None
+        ctx.desc, ctx.dims, ctx.has_bias, ctx.gemm = d, (D, units, nctx), bias is not None, gemm
         return y
 
     @staticmethod
@@ -92,25 +113,35 @@ class _TdnnAffine(torch.autograd.Function):
             if need_w:
                 dw = torch.zeros((units, nctx, D), dtype=torch.float32, device=xp.device)
                 db = torch.zeros((units,), dtype=torch.float32, device=xp.device) if ctx.has_bias else None
-            return dx, dw, db, None, None, None, None
-        ws = ops.grad_tdnn_workspace(B, T, d, xp.device)
+            return dx, dw, db, None, None, None, None, None
+        f32 = ctx.gemm == L.GEMM_F32
+        ws = ops.grad_tdnn_workspace(B, T, d, xp.device) if f32 else ops.grad_tdnn16_workspace(B, T, d, ctx.gemm, xp.device)
         if ctx.needs_input_grad[0]:
             dxp = torch.empty_like(xp)
-            ops.grad_tdnn_data(g, lens, d, wp.view(Up, nctx * Dp), dxp, ws)
+            if f32:
+                ops.grad_tdnn_data(g, lens, d, wp.view(Up, nctx * Dp), dxp, ws)
+            else:
+                ops.grad_tdnn16_data(g, lens, d, wp.view(Up, nctx * Dp), dxp, ws, ctx.gemm)
             dx = dxp[:, :, :D]
         if need_w:
             dwp = torch.empty_like(wp)
             db = torch.empty((units,), dtype=torch.float32, device=xp.device) if ctx.has_bias else None
-            ops.grad_tdnn_weights(xp, lens, d, g, dwp.view(Up, nctx * Dp), db, ws)
+            if f32:
+                ops.grad_tdnn_weights(xp, lens, d, g, dwp.view(Up, nctx * Dp), db, ws)
+            else:
+                ops.grad_tdnn16_weights(xp, lens, d, g, dwp.view(Up, nctx * Dp), db, ws, ctx.gemm)
             dw = dwp[:units, :, :D]
-        return dx, dw, db, None, None, None, None
+        return dx, dw, db, None, None, None, None, None
 
 
-def tdnn_affine(x, weight, bias, context, lens=None, subsampling_factor=1, padding="SAME"):
+def tdnn_affine(x, weight, bias, context, lens=None, subsampling_factor=1, padding="SAME", gemm="f32"):
     """z[b,t,u] = bias[u] + sum_k sum_d x[b, row(t,k), d] * weight[u,k,d], row(t,k) = clip(start + t * subsampling_factor + context[k],
     0, len_b - 1), differentiable in x, weight and bias. x (B, T, D) fp32 on the GPU; weight (units, nctx, D) -- the [u, k, d] order of
     TDNN.device_weights; bias (units,) or None; lens (B,) or None (every utterance has T rows). Returns (B, T_out, units) with zero rows
-    at and beyond an utterance's output length (`tdnn_out_lens`); gradients arriving for those rows are ignored."""
+    at and beyond an utterance's output length (`tdnn_out_lens`); gradients arriving for those rows are ignored. gemm: "f32", "bf16" or
+    "bf16x3" -- the forward is ktf_tdnn in that mode on the fp32 x (its 16-bit weight operand made from `weight` on every call), the
+    backward the ktf_grad_tdnn16_* calls on the fp32 x, weight and gradient."""
+    code = _gemm_code(gemm)
     _on_gpu(x, "x")
     _on_gpu(weight, "weight")
     if x.dim() != 3 or weight.dim() != 3 or weight.shape[2] != x.shape[2] or weight.shape[1] != len(context):
@@ -118,7 +149,7 @@ def tdnn_affine(x, weight, bias, context, lens=None, subsampling_factor=1, paddi
     if bias is not None and tuple(bias.shape) != (weight.shape[0],):
         raise ValueError(f"bias shape {tuple(bias.shape)} != ({weight.shape[0]},)")
     return _TdnnAffine.apply(x.to(torch.float32), weight.to(torch.float32), None if bias is None else bias.to(torch.float32),
-                             _lens(lens, x.shape[0], x.device), list(context), subsampling_factor, padding)
+                             _lens(lens, x.shape[0], x.device), list(context), subsampling_factor, padding, code)
 
 
 class _StatsPooling(torch.autograd.Function):
@@ -188,10 +219,13 @@ class TrainableSequential(torch.nn.Module):
     -> reducing StatsPooling -> TDNN (context [0]) ... Parameters start from the layers' current weights; `forward(feats, lens)`
     returns the last layer's output -- (B, T_out, units), or (B, units) behind the pooling -- for a head and a loss written in torch;
     `export()` writes parameters and moving statistics back into the layers. The layers must be built (a Sequential with an Input, or
-    one that has run or loaded weights)."""
+    one that has run or loaded weights). gemm: the mode of every TDNN GEMM, forward and backward ("f32", "bf16", "bf16x3": `tdnn_affine`),
+    the (B, units) affines behind the pooling included; parameters are fp32 and `export()` is the same in every mode."""
 
-    def __init__(self, seq, device=None):
+    def __init__(self, seq, device=None, gemm="f32"):
         super().__init__()
+        _gemm_code(gemm)
+        self.gemm = gemm
         self.seq = getattr(seq, "xvec", seq)
         dev = ops.default_device() if device is None else torch.device(device)
         self.steps = []                     # (kind, the layer, index into self.params / self.stats)
@@ -236,9 +270,9 @@ class TrainableSequential(torch.nn.Module):
             if kind == "tdnn":
                 w, b = self.params[at], self.params[at + 1] if l.useBias else None
                 if pooled:                                         # one row per utterance: a single sequence of B rows
-                    x = tdnn_affine(x.unsqueeze(0), w, b, l.context).squeeze(0)
+                    x = tdnn_affine(x.unsqueeze(0), w, b, l.context, gemm=self.gemm).squeeze(0)
                 else:
-                    x = tdnn_affine(x, w, b, l.context, lens, l.subsamplingFactor, l.padding)
+                    x = tdnn_affine(x, w, b, l.context, lens, l.subsamplingFactor, l.padding, self.gemm)
                     lens = tdnn_out_lens(lens, l.context, l.subsamplingFactor, l.padding)
                 if isinstance(l.activation, str) and l.activation.lower() == "relu":
                     x = torch.relu(x)

@@ -1434,6 +1434,27 @@ def grad_tdnn_weights(x, lens, desc, g, dw, dbias, workspace):
     return dw, dbias
 
 
+def grad_tdnn16_workspace(B, T, desc, gemm, device):
+    """The workspace both 16-bit TDNN gradient calls (`gemm` = L.GEMM_BF16 / L.GEMM_BF16X3) of a (B, T) batch of layer `desc` take."""
+    return _workspace("ktf_grad_tdnn16_workspace_bytes", int(B), int(T), C.byref(desc), int(gemm), device=device)
+
+
+def grad_tdnn16_data(g, lens, desc, w, dx, workspace, gemm):
+    """grad_tdnn_data on the bf16 MFMA: the same fp32 g, w (the fp32 forward operand) and dx; `gemm` = L.GEMM_BF16 / L.GEMM_BF16X3."""
+    B, T, ldx = dx.shape
+    _call("ktf_grad_tdnn16_data", dx.device, L.ptr(g), g.shape[2], B, T, L.ptr(lens), C.byref(desc), L.ptr(w), L.ptr(dx), ldx,
+          L.ptr(workspace), workspace.numel(), int(gemm))
+    return dx
+
+
+def grad_tdnn16_weights(x, lens, desc, g, dw, dbias, workspace, gemm):
+    """grad_tdnn_weights on the bf16 MFMA: the same fp32 x and g, dw and dbias; `gemm` = L.GEMM_BF16 / L.GEMM_BF16X3."""
+    B, T, ldx = x.shape
+    _call("ktf_grad_tdnn16_weights", x.device, L.ptr(x), B, T, ldx, L.ptr(lens), C.byref(desc), L.ptr(g), g.shape[2], L.ptr(dw), L.ptr(dbias),
+          L.ptr(workspace), workspace.numel(), int(gemm))
+    return dw, dbias
+
+
 def grad_stats_pool(x, D, lens, input_period, include_std, eps, gout, dx):
     """x (B, T, ldx) fp32 dense rows, gout (B, D or 2 D) the gradient of ops.stats_pool's output, dx (B, T, ld_dx) preallocated."""
     B, T, ldx = x.shape
