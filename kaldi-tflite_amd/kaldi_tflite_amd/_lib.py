@@ -256,7 +256,15 @@ GRAD_PROTOTYPES = {
     "ktf_grad_tdnn16_data": (C.c_int, [_P, _i64, _i64, _i64, _P, C.POINTER(TdnnDesc), _P, _P, _i64, _P, C.c_size_t, _i32, _P]),
     "ktf_grad_tdnn16_weights": (C.c_int, [_P, _i64, _i64, _i64, _P, C.POINTER(TdnnDesc), _P, _i64, _P, _P, _P, C.c_size_t, _i32, _P]),
 }
-AUG_META, AUG_STATS = 8, 4          # ktf_aug_*: int32 per RIR of the bank's meta; doubles per row of the statistics
+# name -> (restype, argtypes); mirrors include/ktf_norm.h one to one
+NORM_PROTOTYPES = {
+    "ktf_norm_slot_rows": (_i32, []),
+    "ktf_norm_workspace_bytes": (_i64, [_i64, _i64, _i32]),
+    "ktf_norm_relu_bn_forward": (C.c_int, [_P, _i64, _i64, _i64, _i32, _P, _i32, _i32, _P, _P, _P, C.c_double, C.c_double, _P, _i64, _P, _P,
+                                           C.c_size_t, _P]),
+    "ktf_norm_relu_bn_backward": (C.c_int, [_P, _i64, _P, _i64, _i64, _i64, _i32, _P, _i32, _i32, _P, _P, _P, _i64, _P, _P, C.c_size_t, _P]),
+}
+AUG_META, AUG_STATS = 8, 4         # ktf_aug_*: int32 per RIR of the bank's meta; doubles per row of the statistics
 PLDA_DENSE_NO_PCA = -1.0            # ktf_plda_dense_*: target_energy for "no PCA"
 PLDA_DENSE_MAX_DIM = 512
 PLDA_DENSE_MAX_SWEEPS = 30
@@ -284,7 +292,7 @@ def load():
             "There is no CPU fallback.")
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in (list(PROTOTYPES.items()) + list(AUGMENT_PROTOTYPES.items()) + list(RESAMPLE_PROTOTYPES.items())
-                              + list(GRAD_PROTOTYPES.items())):
+                              + list(GRAD_PROTOTYPES.items()) + list(NORM_PROTOTYPES.items())):
         fn = getattr(lib, name)          # AttributeError = header/library mismatch
         fn.restype = res
         fn.argtypes = args

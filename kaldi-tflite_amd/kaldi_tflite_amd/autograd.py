@@ -5,7 +5,8 @@ include/ktf_grad.h), batch normalisation in training mode, and `TrainableSequent
 `ktf.models.Sequential` whose trained weights `export()` hands back to the inference kernels in every `gemm=` mode.
 
 The GEMMs and the pooling run in the HIP kernels on fp32; padding to the kernels' operand layouts, ReLU and the batch normalisation
-are torch ops on the same device. There is no CPU path for the kernels: tensors that are not on the GPU are refused.
+are torch ops on the same device, or -- `relu_batch_norm`, `TrainableSequential(fused_norm=True)` -- the kernels of
+include/ktf_norm.h. There is no CPU path for the kernels: tensors that are not on the GPU are refused.
 
 `gemm=` selects the matrix pipe of the TDNN GEMMs, forward and backward: "f32" (the exact-fp32 MFMA), "bf16" (operands rounded to
 bf16 in the kernels, fp32 accumulation) or "bf16x3" (hi / lo split operands, three products: near-fp32 values). Parameters,
@@ -214,18 +215,75 @@ def batch_norm(x, lens, moving_mean, moving_var, gamma, momentum=0.99, epsilon=0
     return y if mask is None else torch.where(mask, y, torch.zeros((), dtype=y.dtype, device=y.device))
 
 
+class _ReluBatchNorm(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, z, gamma, lens, moving, momentum, epsilon, training, relu):
+        B, T, D = z.shape
+        z = z.contiguous()
+        gamma = gamma.contiguous()
+        y = torch.empty_like(z)
+        saved = torch.empty((2, D), dtype=torch.float64, device=z.device)
+        ops.norm_relu_bn_forward(z, D, lens, relu, training, gamma, moving[0], moving[1], momentum, epsilon, y, saved,
+                                 ops.norm_workspace(B, T, D, z.device))
+        ctx.save_for_backward(z, saved, gamma, lens)         # of the activation's size: z alone
+        ctx.cfg = (training, relu)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        z, saved, gamma, lens = ctx.saved_tensors
+        training, relu = ctx.cfg
+        B, T, D = z.shape
+        dz = torch.empty_like(z)
+        dgamma = torch.empty((D,), dtype=torch.float32, device=z.device) if ctx.needs_input_grad[1] else None
+        ops.norm_relu_bn_backward(gy.to(torch.float32).contiguous(), z, D, lens, relu, training, gamma, saved, dz, dgamma,
+                                  ops.norm_workspace(B, T, D, z.device))
+        return dz if ctx.needs_input_grad[0] else None, dgamma, None, None, None, None, None, None
+
+
+def relu_batch_norm(z, lens, moving_mean, moving_var, gamma, momentum=0.99, epsilon=0.001, training=False, relu=True):
+    """`batch_norm(torch.relu(z), ...)` (relu=False: `batch_norm(z, ...)`) as one pair of the library's kernels (include/ktf_norm.h),
+    differentiable in z and gamma: y = gamma (a - mean) / sqrt(var + epsilon) per feature with a = max(z, 0). z (B, T, D) with lens
+    (B,) or None, or (N, D) without lens, fp32 on the GPU; moving_mean / moving_var (D,) fp32 on the GPU, updated in place when
+    training; sums, statistics and every output value are fp64 arithmetic rounded once. Rows at and beyond an utterance's length are
+    not read and come out as zero. For the backward pass it keeps z and the (2, D) fp64 mean / inverse deviation, no other tensor of
+    the activation's size."""
+    _on_gpu(z, "z")
+    _on_gpu(gamma, "gamma")
+    _on_gpu(moving_mean, "moving_mean")
+    _on_gpu(moving_var, "moving_var")
+    if z.dim() not in (2, 3) or (z.dim() == 2 and lens is not None):
+        raise ValueError(f"expected z (B, T, D) with lens or None, or (N, D) without lens, got shape {tuple(z.shape)}")
+    D = z.shape[-1]
+    for name, t in (("moving_mean", moving_mean), ("moving_var", moving_var)):
+        if t.dtype != torch.float32 or tuple(t.shape) != (D,) or not t.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous fp32 tensor of shape ({D},): it is updated in place")
+    if tuple(gamma.shape) != (D,):
+        raise ValueError(f"gamma shape {tuple(gamma.shape)} != ({D},)")
+    z3 = z.to(torch.float32) if z.dim() == 3 else z.to(torch.float32).unsqueeze(0)
+    y = _ReluBatchNorm.apply(z3, gamma.to(torch.float32), _lens(lens, z3.shape[0], z.device), (moving_mean, moving_var), float(momentum),
+                             float(epsilon), bool(training), bool(relu))
+    return y if z.dim() == 3 else y.squeeze(0)
+
+
 class TrainableSequential(torch.nn.Module):
     """A `ktf.models.Sequential` (or an XvectorExtractor, whose TDNN stack is taken) as a torch module: TDNN -> ReLU -> BatchNorm ...
     -> reducing StatsPooling -> TDNN (context [0]) ... Parameters start from the layers' current weights; `forward(feats, lens)`
     returns the last layer's output -- (B, T_out, units), or (B, units) behind the pooling -- for a head and a loss written in torch;
     `export()` writes parameters and moving statistics back into the layers. The layers must be built (a Sequential with an Input, or
     one that has run or loaded weights). gemm: the mode of every TDNN GEMM, forward and backward ("f32", "bf16", "bf16x3": `tdnn_affine`),
-    the (B, units) affines behind the pooling included; parameters are fp32 and `export()` is the same in every mode."""
+    the (B, units) affines behind the pooling included; parameters are fp32 and `export()` is the same in every mode.
+    fused_norm=True runs every BatchNorm as `relu_batch_norm`, on both sides of the pooling: together with a ReLU (a ReLU layer, or
+    a TDNN's activation="relu") that stands immediately in front of it, with relu=False otherwise; a ReLU that no BatchNorm follows
+    stays torch.relu. Parameters, buffers, their names and `export()` are the same either way."""
 
-    def __init__(self, seq, device=None, gemm="f32"):
+    def __init__(self, seq, device=None, gemm="f32", fused_norm=False):
         super().__init__()
         _gemm_code(gemm)
+        if not isinstance(fused_norm, bool):
+            raise ValueError(f"fused_norm must be True or False, got {fused_norm!r}")
         self.gemm = gemm
+        self.fused_norm = fused_norm
         self.seq = getattr(seq, "xvec", seq)
         dev = ops.default_device() if device is None else torch.device(device)
         self.steps = []                     # (kind, the layer, index into self.params / self.stats)
@@ -266,7 +324,9 @@ class TrainableSequential(torch.nn.Module):
     def forward(self, feats, lens=None):
         x, pooled = feats, False
         lens = _lens(lens, feats.shape[0], feats.device)
-        for kind, l, at in self.steps:
+        held = False                                               # a ReLU waiting for the BatchNorm behind it (fused_norm)
+        for i, (kind, l, at) in enumerate(self.steps):
+            into_bn = self.fused_norm and i + 1 < len(self.steps) and self.steps[i + 1][0] == "bn"
             if kind == "tdnn":
                 w, b = self.params[at], self.params[at + 1] if l.useBias else None
                 if pooled:                                         # one row per utterance: a single sequence of B rows
@@ -275,9 +335,15 @@ class TrainableSequential(torch.nn.Module):
                     x = tdnn_affine(x, w, b, l.context, lens, l.subsamplingFactor, l.padding, self.gemm)
                     lens = tdnn_out_lens(lens, l.context, l.subsamplingFactor, l.padding)
                 if isinstance(l.activation, str) and l.activation.lower() == "relu":
-                    x = torch.relu(x)
+                    held = into_bn
+                    x = x if held else torch.relu(x)
             elif kind == "relu":
-                x = torch.relu(x)
+                held = into_bn
+                x = x if held else torch.relu(x)
+            elif kind == "bn" and self.fused_norm:
+                x = relu_batch_norm(x, None if pooled else lens, getattr(self, f"moving_mean_{at}"), getattr(self, f"moving_var_{at}"),
+                                    self.params[at], l.momentum, l.epsilon, self.training, relu=held)
+                held = False
             elif kind == "bn":
                 x = batch_norm(x, None if pooled else lens, getattr(self, f"moving_mean_{at}"), getattr(self, f"moving_var_{at}"),
                                self.params[at], l.momentum, l.epsilon, self.training)

@@ -1461,3 +1461,39 @@ def grad_stats_pool(x, D, lens, input_period, include_std, eps, gout, dx):
     _call("ktf_grad_stats_pool", x.device, L.ptr(x), B, T, int(D), ldx, L.ptr(lens), int(input_period), int(include_std), float(eps),
           L.ptr(gout), gout.shape[1], L.ptr(dx), dx.shape[2])
     return dx
+
+
+# ----------------------------------------------------------------------------- ReLU + BatchNorm in training (include/ktf_norm.h)
+def norm_slot_rows():
+    """Flat rows b * T + t per partial sum of the batch statistics."""
+    return int(L.load().ktf_norm_slot_rows())
+
+
+def norm_workspace(B, T, D, device):
+    """The workspace either call of a (B, T, D) batch takes."""
+    return _workspace("ktf_norm_workspace_bytes", int(B), int(T), int(D), device=device)
+
+
+def _rows_ptr(t, other):
+    """Pointer of a (B, T, ld) operand; one without rows has no storage, and `other`'s non-null pointer stands for it (the library
+    refuses null and reads no row)."""
+    return L.ptr(t if t.numel() else other)
+
+
+def norm_relu_bn_forward(z, D, lens, relu, training, gamma, moving_mean, moving_var, momentum, eps, y, saved, workspace):
+    """z (B, T, ldz) fp32 dense rows of which D columns count, y (B, T, ldy) and saved (2, D) fp64 preallocated: every element of both
+    is written; training updates moving_mean / moving_var (D,) in place."""
+    B, T, ldz = z.shape
+    _call("ktf_norm_relu_bn_forward", z.device, _rows_ptr(z, saved), ldz, B, T, int(D), L.ptr(lens), int(bool(relu)), int(bool(training)), L.ptr(gamma),
+          L.ptr(moving_mean), L.ptr(moving_var), float(momentum), float(eps), _rows_ptr(y, saved), y.shape[2], L.ptr(saved), L.ptr(workspace),
+          workspace.numel())
+    return y, saved
+
+
+def norm_relu_bn_backward(gy, z, D, lens, relu, training, gamma, saved, dz, dgamma, workspace):
+    """gy (B, T, ldg) and z (B, T, ldz) fp32 dense rows, saved as the forward call left it; dz (B, T, ld_dz) and dgamma (D,) or None
+    preallocated: every element is written."""
+    B, T, ldz = z.shape
+    _call("ktf_norm_relu_bn_backward", z.device, _rows_ptr(gy, saved), gy.shape[2], _rows_ptr(z, saved), ldz, B, T, int(D), L.ptr(lens), int(bool(relu)),
+          int(bool(training)), L.ptr(gamma), L.ptr(saved), _rows_ptr(dz, saved), dz.shape[2], L.ptr(dgamma), L.ptr(workspace), workspace.numel())
+    return dz, dgamma
