@@ -264,6 +264,19 @@ NORM_PROTOTYPES = {
                                            C.c_size_t, _P]),
     "ktf_norm_relu_bn_backward": (C.c_int, [_P, _i64, _P, _i64, _i64, _i64, _i32, _P, _i32, _i32, _P, _P, _P, _i64, _P, _P, C.c_size_t, _P]),
 }
+# name -> (restype, argtypes); mirrors include/ktf_loss.h one to one
+LOSS_PROTOTYPES = {
+    "ktf_loss_slot_rows": (_i32, []),
+    "ktf_loss_workspace_bytes": (_i64, [_i64, _i64]),
+    "ktf_loss_row_inv_norm": (C.c_int, [_P, _i64, _i64, _i64, C.c_double, _P, _P]),
+    "ktf_loss_row_inv_norm_backward": (C.c_int, [_P, _i64, _i64, _i64, C.c_double, _P, _P, _P, _i64, _P]),
+    "ktf_loss_margin_softmax_forward": (C.c_int, [_P, _i64, _i64, _i64, _P, _P, _P, _i32, C.c_double, C.c_double, _P, _P, _P, _P, C.c_size_t,
+                                                  _P]),
+    "ktf_loss_margin_softmax_backward": (C.c_int, [_P, _i64, _i64, _i64, _P, _P, _P, _i32, C.c_double, C.c_double, _P, _P, _P, _i64, _P, _P, _P,
+                                                   C.c_size_t, _P]),
+}
+LOSS_SOFTMAX, LOSS_AM, LOSS_AAM = 0, 1, 2   # ktf_loss_*: kind
+LOSS_SIN2_FLOOR = 2.0 ** -20
 AUG_META, AUG_STATS = 8, 4         # ktf_aug_*: int32 per RIR of the bank's meta; doubles per row of the statistics
 PLDA_DENSE_NO_PCA = -1.0            # ktf_plda_dense_*: target_energy for "no PCA"
 PLDA_DENSE_MAX_DIM = 512
@@ -292,7 +305,7 @@ def load():
             "There is no CPU fallback.")
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in (list(PROTOTYPES.items()) + list(AUGMENT_PROTOTYPES.items()) + list(RESAMPLE_PROTOTYPES.items())
-                              + list(GRAD_PROTOTYPES.items()) + list(NORM_PROTOTYPES.items())):
+                              + list(GRAD_PROTOTYPES.items()) + list(NORM_PROTOTYPES.items()) + list(LOSS_PROTOTYPES.items())):
         fn = getattr(lib, name)          # AttributeError = header/library mismatch
         fn.restype = res
         fn.argtypes = args

@@ -6,7 +6,9 @@ include/ktf_grad.h), batch normalisation in training mode, and `TrainableSequent
 
 The GEMMs and the pooling run in the HIP kernels on fp32; padding to the kernels' operand layouts, ReLU and the batch normalisation
 are torch ops on the same device, or -- `relu_batch_norm`, `TrainableSequential(fused_norm=True)` -- the kernels of
-include/ktf_norm.h. There is no CPU path for the kernels: tensors that are not on the GPU are refused.
+include/ktf_norm.h. `ClassifierHead` is the speaker classification head and its loss -- softmax, additive-margin and
+additive-angular-margin cosine softmax -- over `row_inv_norm` and `margin_softmax_loss`, the kernels of include/ktf_loss.h around
+a `tdnn_affine` GEMM. There is no CPU path for the kernels: tensors that are not on the GPU are refused.
 
 `gemm=` selects the matrix pipe of the TDNN GEMMs, forward and backward: "f32" (the exact-fp32 MFMA), "bf16" (operands rounded to
 bf16 in the kernels, fp32 accumulation) or "bf16x3" (hi / lo split operands, three products: near-fp32 values). Parameters,
@@ -269,7 +271,7 @@ def relu_batch_norm(z, lens, moving_mean, moving_var, gamma, momentum=0.99, epsi
 class TrainableSequential(torch.nn.Module):
     """A `ktf.models.Sequential` (or an XvectorExtractor, whose TDNN stack is taken) as a torch module: TDNN -> ReLU -> BatchNorm ...
     -> reducing StatsPooling -> TDNN (context [0]) ... Parameters start from the layers' current weights; `forward(feats, lens)`
-    returns the last layer's output -- (B, T_out, units), or (B, units) behind the pooling -- for a head and a loss written in torch;
+    returns the last layer's output -- (B, T_out, units), or (B, units) behind the pooling -- for `ClassifierHead` (below) or a head and a loss written in torch;
     `export()` writes parameters and moving statistics back into the layers. The layers must be built (a Sequential with an Input, or
     one that has run or loaded weights). gemm: the mode of every TDNN GEMM, forward and backward ("f32", "bf16", "bf16x3": `tdnn_affine`),
     the (B, units) affines behind the pooling included; parameters are fp32 and `export()` is the same in every mode.
@@ -363,3 +365,166 @@ class TrainableSequential(torch.nn.Module):
                 l.set_weights([self.params[at].detach().cpu().numpy(), getattr(self, f"moving_mean_{at}").cpu().numpy(),
                                getattr(self, f"moving_var_{at}").cpu().numpy()], fmt="tensorflow")
         return self.seq
+
+
+# ----------------------------------------------------------------------------- the classification head and its loss (include/ktf_loss.h)
+class _RowInvNorm(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, eps):
+        x = x.contiguous()
+        inv = torch.empty((x.shape[0],), dtype=torch.float32, device=x.device)
+        ops.loss_row_inv_norm(x, eps, inv)
+        ctx.save_for_backward(x, inv)
+        ctx.eps = eps
+        return inv
+
+    @staticmethod
+    def backward(ctx, ginv):
+        x, inv = ctx.saved_tensors
+        dx = torch.empty_like(x)
+        ops.loss_row_inv_norm_backward(x, ctx.eps, inv, ginv.to(torch.float32).contiguous(), dx)
+        return dx, None
+
+
+def row_inv_norm(x, eps=1e-12):
+    """1 / max(|x[r]|, eps) per row of x (rows, D) fp32 on the GPU -> (rows,), differentiable in x (zero gradient for a row that eps
+    clamped): the kernels of include/ktf_loss.h, the sum of squares in fp64 and every value rounded once."""
+    if not float(eps) > 0.0 or float(eps) == float("inf"):
+        raise ValueError(f"eps must be positive and finite, got {eps!r}")
+    if not isinstance(x, torch.Tensor) or x.dim() != 2 or x.shape[1] < 1:
+        raise ValueError(f"expected x (rows, D) with D >= 1, got shape {tuple(getattr(x, 'shape', ()))}")
+    _on_gpu(x, "x")
+    return _RowInvNorm.apply(x.to(torch.float32), float(eps))
+
+
+class _MarginSoftmax(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, z, labels, inv_x, inv_w, kind, margin, scale):
+        B, N = z.shape
+        z = z.contiguous()
+        loss = torch.empty((B,), dtype=torch.float32, device=z.device)
+        pred = torch.empty((B,), dtype=torch.int32, device=z.device)
+        lse = torch.empty((B,), dtype=torch.float64, device=z.device)
+        ops.loss_margin_softmax_forward(z, labels, inv_x, inv_w, kind, margin, scale, loss, pred, lse, ops.loss_workspace(B, N, z.device))
+        ctx.save_for_backward(z, labels, lse, inv_x, inv_w)      # of the logits' size: z alone
+        ctx.cfg = (kind, margin, scale)
+        ctx.mark_non_differentiable(pred)
+        return loss, pred
+
+    @staticmethod
+    def backward(ctx, gloss, _gpred):
+        z, labels, lse, inv_x, inv_w = ctx.saved_tensors
+        kind, margin, scale = ctx.cfg
+        B, N = z.shape
+        dz = torch.empty_like(z)
+        dix = diw = None
+        if inv_x is not None:
+            dix = torch.empty((B,), dtype=torch.float32, device=z.device)
+            diw = torch.empty((N,), dtype=torch.float32, device=z.device)
+        ops.loss_margin_softmax_backward(z, labels, inv_x, inv_w, kind, margin, scale, lse, gloss.to(torch.float32).contiguous(), dz, dix, diw,
+                                         ops.loss_workspace(B, N, z.device))
+        return dz, None, dix, diw, None, None, None
+
+
+def _loss_args(kind, margin, scale, cosine):
+    if kind not in ops.LOSS_KINDS:
+        raise ValueError(f"kind must be one of {sorted(ops.LOSS_KINDS)}, got {kind!r}")
+    margin, scale = float(margin), float(scale)
+    if not 0.0 < scale < float("inf"):
+        raise ValueError(f"scale must be positive and finite, got {scale!r}")
+    if not 0.0 <= margin < float("inf"):
+        raise ValueError(f"margin must be finite and not negative, got {margin!r}")
+    if kind == "softmax" and margin != 0.0:
+        raise ValueError(f"margin must be 0 with kind='softmax', got {margin!r}")
+    if kind == "aam" and margin >= 1.5707963267948966:
+        raise ValueError(f"margin must be below pi / 2 with kind='aam', got {margin!r}")
+    if kind != "softmax" and not cosine:
+        raise ValueError(f"kind={kind!r} needs a cosine head: give inv_norm_x and inv_norm_w (normalize=True)")
+    return margin, scale
+
+
+def margin_softmax_loss(z, labels, kind="softmax", margin=0.0, scale=1.0, inv_norm_x=None, inv_norm_w=None):
+    """Softmax cross entropy over the logits of a classification head, with the large-margin cosine variants, as one pair of the
+    library's kernels (include/ktf_loss.h) -> (loss (B,) fp32, pred (B,) int32). z (B, N) fp32 on the GPU: the dot products x_b . w_j;
+    labels (B,) integers, a label outside [0, N) marks an ignored row (loss 0, no gradient). With inv_norm_x (B,) and inv_norm_w (N,)
+    -- `row_inv_norm` of the embeddings and of the weight -- the head is a cosine head, c = z * inv_norm_x[:, None] * inv_norm_w, and
+    the logits are scale * c with the target column replaced by scale * psi(c): kind "softmax": psi(c) = c; "am": c - margin; "aam":
+    cos(theta + margin), continued by c - margin * sin(margin) beyond theta = pi - margin. Without them the head is plain (logits
+    scale * z, kind "softmax" only). pred is the column of the largest cosine without margin. Differentiable in z, inv_norm_x and
+    inv_norm_w; fp64 arithmetic rounded once, no atomics; keeps z and the (B,) fp64 log-sum-exp for the backward pass."""
+    if (inv_norm_x is None) != (inv_norm_w is None):
+        raise ValueError("inv_norm_x and inv_norm_w go together: both for a cosine head, neither for a plain one")
+    margin, scale = _loss_args(kind, margin, scale, inv_norm_x is not None)
+    if not isinstance(z, torch.Tensor) or z.dim() != 2 or z.shape[1] < 1:
+        raise ValueError(f"expected z (B, N) with N >= 1, got shape {tuple(getattr(z, 'shape', ()))}")
+    B, N = z.shape
+    labels = torch.as_tensor(labels, device=z.device)
+    if tuple(labels.shape) != (B,) or labels.dtype.is_floating_point:
+        raise ValueError(f"labels must hold one integer per row ({B}), got {labels.dtype} of shape {tuple(labels.shape)}")
+    for name, t, n in (("inv_norm_x", inv_norm_x, B), ("inv_norm_w", inv_norm_w, N)):
+        if t is not None and tuple(t.shape) != (n,):
+            raise ValueError(f"{name} shape {tuple(t.shape)} != ({n},)")
+    _on_gpu(z, "z")
+    if inv_norm_x is not None:
+        _on_gpu(inv_norm_x, "inv_norm_x")
+        _on_gpu(inv_norm_w, "inv_norm_w")
+        inv_norm_x, inv_norm_w = inv_norm_x.to(torch.float32).contiguous(), inv_norm_w.to(torch.float32).contiguous()
+    labels = labels.clamp(-1, N).to(torch.int32).contiguous()            # int64 labels beyond int32 stay out of range
+    return _MarginSoftmax.apply(z.to(torch.float32), labels, inv_norm_x, inv_norm_w, kind, margin, scale)
+
+
+class ClassifierHead(torch.nn.Module):
+    """The speaker classification head of x-vector training and its loss: weight (num_classes, dim) [and bias], the GEMM
+    `tdnn_affine(emb.unsqueeze(0), weight.unsqueeze(1), bias, [0], gemm=gemm)`, and `margin_softmax_loss` over it. normalize=True
+    (the default for kind "am" and "aam", which need it) makes it a cosine head: `row_inv_norm` of the fp32 embeddings and of the
+    fp32 weight in every gemm mode; normalize=False (the default for kind "softmax") a plain affine head, the only one that takes a
+    bias. margin defaults to 0.2 (0 for "softmax"), scale to 30 (1 for a plain head); both are plain attributes read at every call,
+    so a margin warm-up is one assignment per step. `forward(emb, labels)` -> (the mean loss of the valid rows -- 0 when there is
+    none --, pred (B,) int32); labels outside [0, num_classes) mark rows to ignore. No torch op touches a (B, num_classes) or
+    (num_classes, dim) tensor in forward or backward."""
+
+    def __init__(self, dim, num_classes, kind="aam", margin=None, scale=None, bias=False, gemm="f32", device=None, normalize=None, eps=1e-12):
+        super().__init__()
+        for name, v in (("dim", dim), ("num_classes", num_classes)):
+            if isinstance(v, bool) or not isinstance(v, int) or v < 1:
+                raise ValueError(f"{name} must be a positive integer, got {v!r}")
+        if kind not in ops.LOSS_KINDS:
+            raise ValueError(f"kind must be one of {sorted(ops.LOSS_KINDS)}, got {kind!r}")
+        if normalize is None:
+            normalize = kind != "softmax"
+        if not isinstance(normalize, bool) or not isinstance(bias, bool):
+            raise ValueError(f"normalize and bias must be True or False, got normalize={normalize!r}, bias={bias!r}")
+        if bias and normalize:
+            raise ValueError("bias goes only with a plain head (kind='softmax', normalize=False)")
+        _gemm_code(gemm)
+        self.dim, self.num_classes, self.kind, self.normalize, self.gemm, self.eps = dim, num_classes, kind, normalize, gemm, float(eps)
+        self.margin = (0.0 if kind == "softmax" else 0.2) if margin is None else margin
+        self.scale = (30.0 if normalize else 1.0) if scale is None else scale
+        _loss_args(kind, self.margin, self.scale, normalize)
+        if not self.eps > 0.0:
+            raise ValueError(f"eps must be positive, got {eps!r}")
+        dev = ops.default_device() if device is None else torch.device(device)
+        self.weight = torch.nn.Parameter(torch.randn((num_classes, dim), dtype=torch.float32, device=dev) * dim ** -0.5)
+        self.bias = torch.nn.Parameter(torch.zeros((num_classes,), dtype=torch.float32, device=dev)) if bias else None
+
+    def _logits(self, emb):
+        if not isinstance(emb, torch.Tensor) or emb.dim() != 2 or emb.shape[1] != self.dim:
+            raise ValueError(f"expected emb (B, {self.dim}), got shape {tuple(getattr(emb, 'shape', ()))}")
+        emb = emb.to(torch.float32)
+        z = tdnn_affine(emb.unsqueeze(0), self.weight.unsqueeze(1), self.bias, [0], gemm=self.gemm).squeeze(0)
+        if not self.normalize:
+            return z, None, None
+        return z, row_inv_norm(emb, self.eps), row_inv_norm(self.weight, self.eps)
+
+    def forward(self, emb, labels):
+        margin, scale = _loss_args(self.kind, self.margin, self.scale, self.normalize)
+        z, ix, iw = self._logits(emb)
+        loss, pred = margin_softmax_loss(z, labels, self.kind, margin, scale, ix, iw)
+        labels = torch.as_tensor(labels, device=loss.device)
+        valid = ((labels >= 0) & (labels < self.num_classes)).sum().clamp(min=1)
+        return loss.sum() / valid, pred                  # an ignored row's loss is 0
+
+    def cosines(self, emb):
+        """For evaluation: the (B, num_classes) cosines of a cosine head (the logits of a plain one), scaled in torch."""
+        z, ix, iw = self._logits(emb)
+        return z if ix is None else z * ix[:, None] * iw[None, :]

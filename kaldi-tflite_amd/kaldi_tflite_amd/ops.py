@@ -1497,3 +1497,67 @@ def norm_relu_bn_backward(gy, z, D, lens, relu, training, gamma, saved, dz, dgam
     _call("ktf_norm_relu_bn_backward", z.device, _rows_ptr(gy, saved), gy.shape[2], _rows_ptr(z, saved), ldz, B, T, int(D), L.ptr(lens), int(bool(relu)),
           int(bool(training)), L.ptr(gamma), L.ptr(saved), _rows_ptr(dz, saved), dz.shape[2], L.ptr(dgamma), L.ptr(workspace), workspace.numel())
     return dz, dgamma
+
+
+# ----------------------------------------------------------------------------- the classification head's loss (include/ktf_loss.h)
+LOSS_KINDS = {"softmax": 0, "am": 1, "aam": 2}
+
+
+def loss_slot_rows():
+    """Batch rows per partial sum of dinv_w."""
+    return int(L.load().ktf_loss_slot_rows())
+
+
+def loss_workspace(B, N, device):
+    """The workspace either loss call of a (B, N) batch takes."""
+    return _workspace("ktf_loss_workspace_bytes", int(B), int(N), device=device)
+
+
+def _mat(t, other):
+    """(pointer, leading dimension) of a 2-D fp32 operand whose rows are dense (a view with a row stride is fine); one without rows
+    has no storage, and `other`'s non-null pointer stands for it (the library refuses null and reads no row)."""
+    if t.dim() != 2 or t.dtype != torch.float32 or (t.shape[1] > 1 and t.stride(1) != 1):
+        raise ValueError(f"expected a 2-D fp32 tensor with dense rows, got {t.dtype} {tuple(t.shape)} strides {t.stride()}")
+    return L.ptr(t if t.numel() else other), max(_ld(t), t.shape[1])
+
+
+def loss_row_inv_norm(x, eps, inv):
+    """x (rows, D) fp32 with dense rows, inv (rows,) fp32 preallocated: inv[r] = 1 / max(|x[r]|, eps)."""
+    if x.shape[0] == 0:
+        return inv
+    px, ldx = _mat(x, inv)
+    _call("ktf_loss_row_inv_norm", x.device, px, ldx, x.shape[0], x.shape[1], float(eps), L.ptr(inv))
+    return inv
+
+
+def loss_row_inv_norm_backward(x, eps, inv, ginv, dx):
+    """The gradient of loss_row_inv_norm: ginv (rows,) -> dx (rows, lddx >= D) preallocated, every element written."""
+    if x.shape[0] == 0:
+        return dx
+    px, ldx = _mat(x, x)
+    pd, lddx = _mat(dx, dx)
+    _call("ktf_loss_row_inv_norm_backward", x.device, px, ldx, x.shape[0], x.shape[1], float(eps), L.ptr(inv), L.ptr(ginv), pd, lddx)
+    return dx
+
+
+def loss_margin_softmax_forward(z, labels, inv_x, inv_w, kind, margin, scale, loss, pred, lse, workspace):
+    """z (B, N) fp32 with dense rows, labels (B,) int32, inv_x (B,) / inv_w (N,) fp32 or both None; loss (B,) fp32, pred (B,) int32 or
+    None and lse (B,) fp64 preallocated. kind: "softmax", "am", "aam" or the KTF_LOSS_* number."""
+    B, N = z.shape
+    pz, ldz = _mat(z, workspace)
+    at = lambda t: None if t is None else (L.ptr(t) if t.numel() else L.ptr(workspace))  # noqa: E731
+    _call("ktf_loss_margin_softmax_forward", z.device, pz, ldz, B, N, at(labels), at(inv_x), at(inv_w), int(LOSS_KINDS.get(kind, kind)),
+          float(margin), float(scale), at(loss), at(pred), at(lse), L.ptr(workspace), workspace.numel())
+    return loss, pred, lse
+
+
+def loss_margin_softmax_backward(z, labels, inv_x, inv_w, kind, margin, scale, lse, gloss, dz, dinv_x, dinv_w, workspace):
+    """The gradient of sum_b gloss[b] * loss[b] (gloss None: ones): dz (B, lddz >= N), which may be z itself, and for a cosine head
+    dinv_x (B,), dinv_w (N,), all preallocated and written whole."""
+    B, N = z.shape
+    pz, ldz = _mat(z, workspace)
+    pd, lddz = _mat(dz, workspace)
+    at = lambda t: None if t is None else (L.ptr(t) if t.numel() else L.ptr(workspace))  # noqa: E731
+    _call("ktf_loss_margin_softmax_backward", z.device, pz, ldz, B, N, at(labels), at(inv_x), at(inv_w), int(LOSS_KINDS.get(kind, kind)),
+          float(margin), float(scale), at(lse), at(gloss), pd, lddz, at(dinv_x), at(dinv_w), L.ptr(workspace), workspace.numel())
+    return dz, dinv_x, dinv_w
