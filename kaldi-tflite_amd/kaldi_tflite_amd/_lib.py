@@ -18,6 +18,7 @@ _OVERRIDE = os.environ.get("KTF_LIBRARY") if os.environ.get("KTF_ALLOW_LIBRARY_O
 LIB_PATH = _OVERRIDE or os.path.join(_HERE, "libktf_hip.so")
 
 KTF_F32, KTF_BF16, KTF_BF16P = 0, 1, 3
+KTF_F16 = 2                       # ktf_egs_*: the bank's other element type (include/ktf_egs.h)
 PAIR = "bf16p"                    # stands for KTF_BF16P where a torch dtype is expected: pairs live in float32 tensors
 GEMM_F32, GEMM_BF16, GEMM_BF16X3, GEMM_F16MX, GEMM_BF16X4 = 0, 1, 2, 5, 6
 ACT_NONE, ACT_RELU, ACT_SIGMOID, ACT_TANH = 0, 1, 2, 3
@@ -91,6 +92,10 @@ class TdnnDesc(C.Structure):
                 ("ctx", C.c_int32 * 16), ("subsampling", C.c_int32), ("valid", C.c_int32), ("act", C.c_int32),
                 ("gemm", C.c_int32), ("x_dtype", C.c_int32), ("w_dtype", C.c_int32), ("y_dtype", C.c_int32),
                 ("flags", C.c_int32)]
+
+
+class EgsIndex(C.Structure):
+    _fields_ = [("spk_order", C.c_void_p), ("spk_off", C.c_void_p), ("spk_utts", C.c_void_p), ("spk_utt_len", C.c_void_p)]
 
 
 _P = C.c_void_p
@@ -275,6 +280,16 @@ LOSS_PROTOTYPES = {
     "ktf_loss_margin_softmax_backward": (C.c_int, [_P, _i64, _i64, _i64, _P, _P, _P, _i32, C.c_double, C.c_double, _P, _P, _P, _i64, _P, _P, _P,
                                                    C.c_size_t, _P]),
 }
+# name -> (restype, argtypes); mirrors include/ktf_egs.h one to one
+_U32P = C.POINTER(C.c_uint32)
+EGS_PROTOTYPES = {
+    "ktf_egs_philox": (C.c_int, [_U32P, _U32P, _U32P]),
+    "ktf_egs_draw": (C.c_int, [C.POINTER(EgsIndex), _i64, _i64, _i64, _u64, _u64, _i64, _i64, _i64, _i64, _P, _P, _P, _P]),
+    "ktf_egs_gather": (C.c_int, [_P, _i32, _i64, _i64, _i64, _P, _P, _i64, _P, _P, _i64, _i64, _P, _i64, _P]),
+    "ktf_egs_sample": (C.c_int, [C.POINTER(EgsIndex), _i64, _i64, _i64, _u64, _u64, _i64, _i64, _i64, _i64, _P, _i32, _i64, _i64, _i64, _P, _P,
+                                 _P, _i64, _P, _P, _P, _P]),
+}
+EGS_THREADS, EGS_MAX_SLICES = 256, 32   # ktf_egs_*: threads of a workgroup; workgroups per batch row at most
 LOSS_SOFTMAX, LOSS_AM, LOSS_AAM = 0, 1, 2   # ktf_loss_*: kind
 LOSS_SIN2_FLOOR = 2.0 ** -20
 AUG_META, AUG_STATS = 8, 4         # ktf_aug_*: int32 per RIR of the bank's meta; doubles per row of the statistics
@@ -305,7 +320,8 @@ def load():
             "There is no CPU fallback.")
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in (list(PROTOTYPES.items()) + list(AUGMENT_PROTOTYPES.items()) + list(RESAMPLE_PROTOTYPES.items())
-                              + list(GRAD_PROTOTYPES.items()) + list(NORM_PROTOTYPES.items()) + list(LOSS_PROTOTYPES.items())):
+                              + list(GRAD_PROTOTYPES.items()) + list(NORM_PROTOTYPES.items()) + list(LOSS_PROTOTYPES.items())
+                              + list(EGS_PROTOTYPES.items())):
         fn = getattr(lib, name)          # AttributeError = header/library mismatch
         fn.restype = res
         fn.argtypes = args

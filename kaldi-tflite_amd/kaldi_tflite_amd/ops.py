@@ -1561,3 +1561,69 @@ def loss_margin_softmax_backward(z, labels, inv_x, inv_w, kind, margin, scale, l
     _call("ktf_loss_margin_softmax_backward", z.device, pz, ldz, B, N, at(labels), at(inv_x), at(inv_w), int(LOSS_KINDS.get(kind, kind)),
           float(margin), float(scale), at(lse), at(gloss), pd, lddz, at(dinv_x), at(dinv_w), L.ptr(workspace), workspace.numel())
     return dz, dinv_x, dinv_w
+
+
+# ----------------------------------------------------------------------------- training examples (include/ktf_egs.h)
+EGS_DTYPES = {torch.float32: L.KTF_F32, torch.float16: L.KTF_F16}
+
+
+def egs_philox(ctr, key):
+    """Philox4x32-10 on the host (no GPU): ctr four and key two 32-bit words -> four 32-bit words."""
+    c, k, out = (C.c_uint32 * 4)(*ctr), (C.c_uint32 * 2)(*key), (C.c_uint32 * 4)()
+    L.check(L.load().ktf_egs_philox(c, k, out), "ktf_egs_philox")
+    return tuple(int(v) for v in out)
+
+
+def egs_index(spk_order, spk_off, spk_utts, spk_utt_len):
+    """The KtfEgsIndex of four int32 device tensors (which the caller keeps alive)."""
+    for t in (spk_order, spk_off, spk_utts, spk_utt_len):
+        if t.dtype != torch.int32 or not t.is_contiguous():
+            raise ValueError("the index arrays are contiguous int32 tensors")
+    return L.EgsIndex(spk_order.data_ptr(), spk_off.data_ptr(), spk_utts.data_ptr(), spk_utt_len.data_ptr())
+
+
+def _egs_bank(bank):
+    """(pointer, dtype code, rows, ldb, D) of a bank (rows, D) with dense rows; a view with a row stride is fine."""
+    if bank.dim() != 2 or bank.dtype not in EGS_DTYPES or (bank.shape[1] > 1 and bank.stride(1) != 1):
+        raise ValueError(f"expected a 2-D fp32 / fp16 bank with dense rows, got {bank.dtype} {tuple(bank.shape)} strides {bank.stride()}")
+    return L.ptr(bank), EGS_DTYPES[bank.dtype], bank.shape[0], max(_ld(bank), bank.shape[1]), bank.shape[1]
+
+
+def _egs_out(out, D):
+    """(pointer, ldo) of out (B, T, D) fp32 whose (T, ldo) chunks follow one another (a view with a row stride ldo >= D is fine)."""
+    ok = out.dim() == 3 and out.dtype == torch.float32 and out.shape[2] == D
+    if ok:
+        B, T = out.shape[0], out.shape[1]
+        ldo = out.stride(1) if T > 1 else (out.stride(0) if B > 1 else D)
+        ok = ldo >= D and (D == 1 or out.stride(2) == 1) and (B == 1 or out.stride(0) == T * ldo)
+    if not ok:
+        raise ValueError(f"expected out (B, T, {D}) fp32 as one (B * T, ldo) matrix, got {out.dtype} {tuple(out.shape)} strides {out.stride()}")
+    return L.ptr(out), ldo
+
+
+def egs_draw(index, S, U, n_spk, seed, step, T, b0, b_stride, utt, offset, label):
+    """Rules 1 - 7 for the global rows b0 + i * b_stride: utt, offset, label (B,) int32 preallocated."""
+    if utt.numel():
+        _call("ktf_egs_draw", utt.device, C.byref(index), int(S), int(U), int(n_spk), int(seed), int(step), int(T), int(b0), int(b_stride),
+              utt.numel(), L.ptr(utt), L.ptr(offset), L.ptr(label))
+    return utt, offset, label
+
+
+def egs_gather(bank, row0, lens, utt, offset, T, out):
+    """An explicit plan (utt, offset (B,) int32) -> out (B, T, D) fp32 preallocated, every element of its (T, ldo) chunks written."""
+    if utt.numel():
+        pb, dt, rows, ldb, D = _egs_bank(bank)
+        po, ldo = _egs_out(out, D)
+        _call("ktf_egs_gather", bank.device, pb, dt, rows, ldb, D, L.ptr(row0), L.ptr(lens), row0.numel(), L.ptr(utt), L.ptr(offset), int(T),
+              utt.numel(), po, ldo)
+    return out
+
+
+def egs_sample(index, S, n_spk, seed, step, T, b0, b_stride, bank, row0, lens, out, utt, offset, label):
+    """egs_draw and egs_gather of what it drew, in one launch."""
+    if utt.numel():
+        pb, dt, rows, ldb, D = _egs_bank(bank)
+        po, ldo = _egs_out(out, D)
+        _call("ktf_egs_sample", bank.device, C.byref(index), int(S), row0.numel(), int(n_spk), int(seed), int(step), int(T), int(b0),
+              int(b_stride), utt.numel(), pb, dt, rows, ldb, D, L.ptr(row0), L.ptr(lens), po, ldo, L.ptr(utt), L.ptr(offset), L.ptr(label))
+    return out, utt, offset, label
