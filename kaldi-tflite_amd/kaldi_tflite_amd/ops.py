@@ -858,10 +858,33 @@ def convert_pad(src, D, dst):
     return dst
 
 
+# The pooling / post / tail entry points take a base pointer and at most one row stride per tensor: a view they cannot express -- a time
+# slice x[:, :40] of a longer batch, a transposed matrix, a last stride other than 1 -- would make the kernel read other memory
+# without a word. The wrappers refuse it by name before the library is called. (A dimension of one element has no stride to speak of.)
+def _need_dense(name, t):
+    """t (or None) must be contiguous: the library gets its base pointer only."""
+    if t is not None and not t.is_contiguous():
+        raise ValueError(f"{name}: a contiguous tensor is expected, got shape {tuple(t.shape)} with strides {tuple(t.stride())}")
+
+
+def _need_rows(name, t):
+    """t (..., rows, ld): unit stride along the last axis, the leading axes dense over the row stride -- the library gets the base
+    pointer and t.stride(-2)."""
+    n = t.dim()
+    ok = t.shape[-1] <= 1 or t.stride(-1) == 1
+    if ok and n == 3 and t.shape[0] > 1 and t.shape[1] > 0:
+        ok = t.stride(0) == t.shape[1] * t.stride(1)
+    if not ok:
+        raise ValueError(f"{name}: rows of unit stride laid end to end are expected, got shape {tuple(t.shape)} with strides {tuple(t.stride())}")
+
+
 def stats_pool(x, D, lens, input_period, include_std, eps, out):
     """x (B,T,ldx) fp32/bf16; out (B, ld_out) fp32 preallocated."""
     lib = L.load()
     B, T = x.shape[0], x.shape[1]
+    _need_rows("x", x)
+    _need_rows("out", out)
+    _need_dense("lens", lens)
     dt = L.ktf_dtype(x.dtype)
     with L.on_device(x.device):
         rc = lib.ktf_stats_pool(L.ptr(x), dt, B, T, D, x.stride(1), L.ptr(lens), input_period, int(include_std), eps,
@@ -873,6 +896,7 @@ def stats_pool(x, D, lens, input_period, include_std, eps, out):
 def stats_pool_windowed(x, left, right, input_period, output_period, start, T_out, include_std, eps):
     lib = L.load()
     B, T, D = x.shape
+    _need_dense("x", x)
     out = torch.empty((B, T_out, 2 * D if include_std else D), dtype=torch.float32, device=x.device)
     with L.on_device(x.device):
         rc = lib.ktf_stats_pool_windowed_f32(L.ptr(x), B, T, D, left, right, input_period, output_period, start, T_out,
@@ -885,6 +909,8 @@ def xvec_post(x, mean, A, off, out=None):
     lib = L.load()
     B, in_dim = x.shape
     out_dim = A.shape[1]
+    for name, t in (("x", x), ("mean", mean), ("A", A), ("off", off), ("out", out)):
+        _need_dense(name, t)
     if out is None:
         out = torch.empty((B, out_dim), dtype=torch.float32, device=x.device)
     with L.on_device(x.device):
@@ -898,7 +924,15 @@ def xvec_tail(pooled, sums, slots, lens, T, D, include_std, eps, W, bias, units,
     """Fused tail (ktf_xvec_tail_f32): pooled (B, ld) fp32 rows OR fp64 sums -> tdnn6 -> mean-sub -> LDA -> length norm, one launch."""
     lib = L.load()
     B = out.shape[0]
+    if (pooled is None) == (sums is None):
+        raise ValueError("pooled / sums: exactly one of the two is expected")
     src = pooled if pooled is not None else sums
+    if pooled is not None:
+        _need_rows("pooled", pooled)
+    _need_rows("W", W)
+    for name, t in (("sums", sums), ("lens", lens), ("bias", bias), ("mean", mean), ("A", A), ("off", off), ("partial", partial),
+                    ("counters", counters), ("out", out), ("h_out", h_out)):
+        _need_dense(name, t)
     with L.on_device(src.device):
         rc = lib.ktf_xvec_tail_f32(L.ptr(pooled), pooled.stride(0) if pooled is not None else 0, L.ptr(sums), int(slots), int(slot_rows), L.ptr(lens), int(T), B,
                                    int(D), int(include_std), float(eps), L.ptr(W), W.stride(0), L.ptr(bias), int(units), L.ptr(mean), L.ptr(A),
@@ -1458,6 +1492,8 @@ def grad_tdnn16_weights(x, lens, desc, g, dw, dbias, workspace, gemm):
 def grad_stats_pool(x, D, lens, input_period, include_std, eps, gout, dx):
     """x (B, T, ldx) fp32 dense rows, gout (B, D or 2 D) the gradient of ops.stats_pool's output, dx (B, T, ld_dx) preallocated."""
     B, T, ldx = x.shape
+    for name, t in (("x", x), ("lens", lens), ("gout", gout), ("dx", dx)):
+        _need_dense(name, t)
     _call("ktf_grad_stats_pool", x.device, L.ptr(x), B, T, int(D), ldx, L.ptr(lens), int(input_period), int(include_std), float(eps),
           L.ptr(gout), gout.shape[1], L.ptr(dx), dx.shape[2])
     return dx
