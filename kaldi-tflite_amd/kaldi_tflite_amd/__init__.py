@@ -5,7 +5,7 @@ reference exposes as `import kaldi_tflite as ktf` for that path: ktf.layers, ktf
 ktf.io, ktf.kaldi_numpy.
 """
 
-from . import augment, autograd, diarization, egs, io, kaldi_numpy, layers, models, parallel, training, verification  # noqa: F401
+from . import augment, autograd, diarization, egs, io, kaldi_numpy, layers, models, optim, parallel, training, verification  # noqa: F401
 from ._lib import KtfBackendError  # noqa: F401
 
 __version__ = "0.1.0"

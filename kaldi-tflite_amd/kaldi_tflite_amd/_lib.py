@@ -94,6 +94,14 @@ class TdnnDesc(C.Structure):
                 ("flags", C.c_int32)]
 
 
+class OptimSeg(C.Structure):
+    _fields_ = [("begin", C.c_int64), ("end", C.c_int64), ("group", C.c_int32), ("max_change", C.c_float)]
+
+
+class OptimGroup(C.Structure):
+    _fields_ = [("lr", C.c_double), ("weight_decay", C.c_double)]
+
+
 class EgsIndex(C.Structure):
     _fields_ = [("spk_order", C.c_void_p), ("spk_off", C.c_void_p), ("spk_utts", C.c_void_p), ("spk_utt_len", C.c_void_p)]
 
@@ -289,6 +297,14 @@ EGS_PROTOTYPES = {
     "ktf_egs_sample": (C.c_int, [C.POINTER(EgsIndex), _i64, _i64, _i64, _u64, _u64, _i64, _i64, _i64, _i64, _P, _i32, _i64, _i64, _i64, _P, _P,
                                  _P, _i64, _P, _P, _P, _P]),
 }
+# name -> (restype, argtypes); mirrors include/ktf_optim.h one to one
+OPTIM_PROTOTYPES = {
+    "ktf_optim_slot_elems": (_i64, []),
+    "ktf_optim_workspace_bytes": (_i64, [_i64, _i32]),
+    "ktf_optim_step": (C.c_int, [_P, _P, _P, _P, _i64, _P, _P, _i32, _P, _i32, _i32, C.c_double, _i32, C.c_double, C.c_double, C.c_double,
+                                 _i64, _i32, C.c_double, C.c_double, _P, _P, C.c_size_t, _P]),
+}
+OPTIM_SGD, OPTIM_ADAM, OPTIM_MAX_GROUPS = 0, 1, 8   # ktf_optim_*: kind; groups per call
 EGS_THREADS, EGS_MAX_SLICES = 256, 32   # ktf_egs_*: threads of a workgroup; workgroups per batch row at most
 LOSS_SOFTMAX, LOSS_AM, LOSS_AAM = 0, 1, 2   # ktf_loss_*: kind
 LOSS_SIN2_FLOOR = 2.0 ** -20
@@ -321,7 +337,7 @@ def load():
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in (list(PROTOTYPES.items()) + list(AUGMENT_PROTOTYPES.items()) + list(RESAMPLE_PROTOTYPES.items())
                               + list(GRAD_PROTOTYPES.items()) + list(NORM_PROTOTYPES.items()) + list(LOSS_PROTOTYPES.items())
-                              + list(EGS_PROTOTYPES.items())):
+                              + list(EGS_PROTOTYPES.items()) + list(OPTIM_PROTOTYPES.items())):
         fn = getattr(lib, name)          # AttributeError = header/library mismatch
         fn.restype = res
         fn.argtypes = args

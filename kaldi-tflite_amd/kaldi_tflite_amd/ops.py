@@ -1663,3 +1663,52 @@ def egs_sample(index, S, n_spk, seed, step, T, b0, b_stride, bank, row0, lens, o
         _call("ktf_egs_sample", bank.device, C.byref(index), int(S), row0.numel(), int(n_spk), int(seed), int(step), int(T), int(b0),
               int(b_stride), utt.numel(), pb, dt, rows, ldb, D, L.ptr(row0), L.ptr(lens), po, ldo, L.ptr(utt), L.ptr(offset), L.ptr(label))
     return out, utt, offset, label
+
+
+# ----------------------------------------------------------------------------- the optimiser step (include/ktf_optim.h)
+OPTIM_KINDS = {"sgd": L.OPTIM_SGD, "adam": L.OPTIM_ADAM}
+
+
+def optim_slot_elems():
+    """Elements per slot of partial sums; every segment of the arenas begins at a multiple of it."""
+    return int(L.load().ktf_optim_slot_elems())
+
+
+def optim_workspace(total, n_seg, device):
+    """The workspace a step over arenas of `total` elements in n_seg segments takes."""
+    return _workspace("ktf_optim_workspace_bytes", int(total), int(n_seg), device=device)
+
+
+def optim_segments(rows, device=None):
+    """The segment table of rows (begin, end, group, max_change): the host array (a ctypes array of KtfOptimSeg; one spare entry
+    keeps an empty table addressable) and, with a device, its copy there as a uint8 tensor."""
+    host = (L.OptimSeg * max(len(rows), 1))()
+    for i, (begin, end, group, max_change) in enumerate(rows):
+        host[i] = L.OptimSeg(int(begin), int(end), int(group), float(max_change))
+    if device is None:
+        return host
+    dev = torch.frombuffer(bytearray(bytes(host)), dtype=torch.uint8).to(device)
+    return host, dev
+
+
+def optim_step(p, g, m, v, segs_host, segs_dev, n_seg, groups, kind, momentum=0.0, nesterov=False, betas=(0.9, 0.999), eps=1e-8, step=1,
+               decoupled=False, clip_norm=0.0, max_change_global=0.0, stats=None, workspace=None):
+    """One step on the arenas p, g (and m, v or None): 1-D fp32 tensors of one length. segs_host / segs_dev: optim_segments' pair;
+    groups: (lr, weight_decay) per group, read now; kind: "sgd", "adam" or the KTF_OPTIM_* number; stats: (5 + n_seg,) fp64 on the
+    device or None. No host synchronisation."""
+    total = p.numel()
+    for t in (p, g, m, v):
+        if t is not None and (t.dim() != 1 or t.dtype != torch.float32 or t.numel() != total or not t.is_contiguous()):
+            raise ValueError(f"the arenas are contiguous 1-D fp32 tensors of one length, got {t.dtype} {tuple(t.shape)}")
+    if stats is not None and (stats.dtype != torch.float64 or stats.numel() < 5 + n_seg or not stats.is_contiguous()):
+        raise ValueError(f"stats holds 5 + n_seg = {5 + n_seg} contiguous fp64 values")
+    if workspace is None:
+        workspace = optim_workspace(total, n_seg, p.device)
+    hg = (L.OptimGroup * max(len(groups), 1))()
+    for i, (lr, wd) in enumerate(groups):
+        hg[i] = L.OptimGroup(float(lr), float(wd))
+    _call("ktf_optim_step", p.device, L.ptr(p), L.ptr(g), L.ptr(m), L.ptr(v), total, C.cast(segs_host, C.c_void_p), L.ptr(segs_dev), int(n_seg),
+          C.cast(hg, C.c_void_p), len(groups), int(OPTIM_KINDS.get(kind, kind)), float(momentum), int(bool(nesterov)), float(betas[0]),
+          float(betas[1]), float(eps), int(step), int(bool(decoupled)), float(clip_norm), float(max_change_global), L.ptr(stats),
+          L.ptr(workspace), workspace.numel())
+    return p
