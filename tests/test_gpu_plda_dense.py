@@ -94,6 +94,29 @@ def test_score_dense_matches_restatement(dtype, D, target):
         assert err <= lim * max(1.0, np.abs(want).max()), (len(x), d, err)
 
 
+@pytest.mark.parametrize("dtype", [torch.float64, torch.float32])
+@pytest.mark.parametrize("D", [30, 150])
+@pytest.mark.parametrize("target", [0.1, 0.9])
+def test_score_dense_matches_restatement_off_the_tile_edges(dtype, D, target):
+    # D and the row counts around it are no multiples of the 32-wide moment tile: covariance mode (n > D) with a partly filled
+    # tile of P, Gram mode (n <= D) with a partly filled K = D, as dense scoring after an LDA to 150 has them
+    ns = [2, D - 1, D, D + 1, 2 * D + 3]
+    floor = P.RANK_FLOOR[NP[dtype]]
+    mean, T, psi = model(D)
+    xs = [x.astype(NP[dtype]) for x in recordings(ns, D, target, floor, base=7)]
+    layer = Ls.PLDA(D, mean, T, psi, dtype=dtype)
+    got = layer.score_dense(np.concatenate(xs), lengths=ns, target_energy=target)
+    dims = layer.last_dense_dims.cpu().tolist()
+    lim = 1e-8 if dtype == torch.float64 else 1e-4
+    pm, pT, pp = (np.asarray(a, NP[dtype]) for a in (mean, T, psi))      # the parameters as the layer holds them
+    for x, s, d in zip(xs, got, dims):
+        want, wd = P.score_dense(x, pm, pT, pp, target, floor)
+        assert d == wd, (len(x), d, wd)
+        assert tuple(s.shape) == want.shape
+        err = np.abs(host(s) - want).max()
+        assert err <= lim * max(1.0, np.abs(want).max()), (len(x), d, err)
+
+
 # ----------------------------------------------------------------------------- batching and the no-PCA path
 @pytest.mark.parametrize("dtype", [torch.float64, torch.float32])
 def test_batched_blocks_equal_separate_calls_bit_for_bit(dtype):
