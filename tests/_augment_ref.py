@@ -95,3 +95,104 @@ def decaying_rir(rng, L, peak):
     h = rng.standard_normal(L) * np.exp(-6.0 * np.arange(L) / max(L, 1))
     h[peak] = np.abs(h).max() * 1.5 + 1.0
     return h.astype(np.float32)
+
+
+# ----------------------------------------------------------------------------- what csrc/augment.hip's launcher and kernels choose
+# Internal constants of the kernels, mirrored here because the library does not export them (test_augment_paths_cpu.py checks
+# the shapes of test_gpu_augment_paths.py against them: a changed constant moves the edge, and that module then fails).
+AUG_J = 4                          # augment.hip:28, output blocks per workgroup of aug_conv_kernel
+DIRECT_TAPS = 64                   # include/ktf_augment.h:37 (augment.hip:29), the longest filter applied in the time domain
+AUG_THREADS = 256                  # augment_fft.h:14, threads per workgroup (aug_rir_peak_kernel: thread i % 256 reads tap i)
+WAVE = 64
+
+
+def blocks_of(samples, P):
+    """augment.hip:37."""
+    return (samples + P - 1) // P
+
+
+def early_taps(fs):
+    """augment.hip:38-39 -> (pre, post): the early window reaches pre taps before the peak and post taps from it on (nearbyint:
+    to nearest, ties to even, as Python's round)."""
+    return int(round(0.001 * fs)), int(round(0.05 * fs))
+
+
+def early_partitions(fs, P):
+    """augment.hip:40: the partitions the bank reserves per RIR for the spectra of h[s0:s1]."""
+    return blocks_of(sum(early_taps(fs)), P)
+
+
+def spectra_slots(lengths, fs, P):
+    """augment.hip:120-121 -> [(full0, early0)] per RIR of a bank: its first partition among the full spectra and among the early
+    ones, which lie behind all the full ones, npe = early_partitions(fs) per RIR."""
+    off = np.concatenate([[0], np.cumsum(lengths)])
+    R, npe = len(lengths), early_partitions(fs, P)
+    return [(int(off[r]) // P + r, int(off[R]) // P + R + r * npe) for r in range(R)]
+
+
+def conv_path(Lh):
+    """augment.hip:237: "direct" (time domain) or "transform" for a filter of Lh taps."""
+    return "direct" if Lh <= DIRECT_TAPS else "transform"
+
+
+def conv_groups(n, Lh, P):
+    """The workgroups of aug_conv_kernel that work on a row of n samples and a filter of Lh > DIRECT_TAPS taps (augment.hip:229-236,
+    :269, :289-290) -> [dict(j0, np, pend, slides)]: the workgroup owns output blocks j0 .. j0 + AUG_J - 1, runs partitions
+    0 .. pend - 1 and moves its register window of input spectra down `slides` = pend - 1 times."""
+    ny, npart = blocks_of(n + Lh - 1, P), blocks_of(Lh, P)
+    return [dict(j0=j0, np=npart, pend=min(npart, j0 + AUG_J), slides=min(npart, j0 + AUG_J) - 1) for j0 in range(0, ny, AUG_J)]
+
+
+def early_grid(max_n, max_L, fs, P):
+    """augment.hip:585-591 -> (ny, nye, the x-extent of aug_conv_kernel<true>'s grid = cdiv(min(ny, nye), AUG_J))."""
+    ny, nye = blocks_of(max_n + max_L - 1, P), blocks_of(max_n + sum(early_taps(fs)) - 1, P)
+    return ny, nye, -(-min(ny, nye) // AUG_J)
+
+
+def peak_owner(i):
+    """aug_rir_peak_kernel (augment.hip:103): -> (thread, wave) that reads tap i."""
+    t = i % AUG_THREADS
+    return t, t // WAVE
+
+
+# The shapes of test_gpu_augment_paths.py, from P = ktf_aug_partition(). Pure data; the CPU module proves what each reaches.
+def long_shapes(P):
+    """-> (signal lengths, RIR lengths): RIRs of 5, 5, 10 and 13 partitions, more than the AUG_J blocks a workgroup owns."""
+    return (1, P + 1, 2 * P + 17, 6 * P + 3), (4 * P + 1, 5 * P, 9 * P + 3, 13 * P - 1)
+
+
+EARLY_RATES = (48000, 44100)       # pre + post = 2448 and 2249 taps: three early partitions (16000 and 8000 have one)
+
+
+def wide_early_bank(P):
+    """[(L, peak)] of one bank for EARLY_RATES, in the bank's order. At 48000: a clipped window of 148 taps (one partition); 2448
+    taps (three partitions), twice, behind it; a peak on the last tap (49 taps: the early filter in the time domain, the full one
+    transformed); a RIR of exactly DIRECT_TAPS taps (all of it in the time domain)."""
+    return [(1500, 1400), (3 * P + 5, 100), (5000, 2500), (P + 200, P + 199), (DIRECT_TAPS, 20)]
+
+
+def edge_early_bank(P):
+    """[(L, peak)] of one bank at 16000 Hz (pre 16, post 800), every early window clipped by the RIR's end or its start: exactly
+    DIRECT_TAPS and DIRECT_TAPS + 1 early taps under a full RIR beyond a partition (one row takes the time-domain path in one
+    launch of aug_conv_kernel and the transform path in the other, or the transform path in both); 116 taps; an early window
+    that is the whole RIR, transformed (300 taps) and in the time domain (DIRECT_TAPS taps)."""
+    L = P + 100
+    return [(L, L + 16 - DIRECT_TAPS), (L, L + 16 - DIRECT_TAPS - 1), (1500, 1400), (300, 5), (DIRECT_TAPS, 7)]
+
+
+def early_ns(P):
+    return (1, P, 2 * P + 17)
+
+
+# aug_rir_peak_kernel's ties: (taps, the indices that hold the maximum). 45 / 300 and 45 / 290: threads 45 and 44 (34) of wave 0,
+# the lower index in the higher lane; 70 / 260 and 100 / 260: the lower index in wave 1, the higher in wave 0; 10 / 266 / 522:
+# one thread; 3 / 40 / 699 (299): three lanes, the lowest index in the lowest
+TIE_CASES = [(700, (45, 300)), (300, (45, 290)), (700, (70, 260)), (300, (100, 260)), (700, (10, 266, 522)), (700, (3, 40, 699)),
+             (300, (3, 40, 299))]
+
+
+def rir_with_peaks(rng, L, peaks):
+    """L random taps in (-1, 0.9) with the same maximum, 1.5, at every index of `peaks`."""
+    h = rng.uniform(-1.0, 0.9, L)
+    h[list(peaks)] = 1.5
+    return h.astype(np.float32)
