@@ -304,6 +304,16 @@ OPTIM_PROTOTYPES = {
     "ktf_optim_step": (C.c_int, [_P, _P, _P, _P, _i64, _P, _P, _i32, _P, _i32, _i32, C.c_double, _i32, C.c_double, C.c_double, C.c_double,
                                  _i64, _i32, C.c_double, C.c_double, _P, _P, C.c_size_t, _P]),
 }
+# name -> (restype, argtypes); mirrors include/ktf_head.h one to one
+HEAD_PROTOTYPES = {
+    "ktf_head_slot_rows": (_i32, []),
+    "ktf_head_workspace_bytes": (_i64, [_i64, _i64, _i64]),
+    "ktf_head_forward": (C.c_int, [_P, _i64, _i64, _i64, _i64, _P, _P, _P, _i32, C.c_double, C.c_double, _i32, C.c_double, C.c_double, _P, _P,
+                                   _P, _P, _P, _P, C.c_size_t, _P]),
+    "ktf_head_backward": (C.c_int, [_P, _i64, _i64, _i64, _i64, _P, _P, _P, _i32, C.c_double, C.c_double, _i32, C.c_double, C.c_double, _P, _P,
+                                    _P, _P, _i64, _P, _P, _P, C.c_size_t, _P]),
+}
+HEAD_MAX_CENTERS, HEAD_MAX_TOPK = 8, 64   # ktf_head_*: sub-centres per class; penalised classes per row
 OPTIM_SGD, OPTIM_ADAM, OPTIM_MAX_GROUPS = 0, 1, 8   # ktf_optim_*: kind; groups per call
 EGS_THREADS, EGS_MAX_SLICES = 256, 32   # ktf_egs_*: threads of a workgroup; workgroups per batch row at most
 LOSS_SOFTMAX, LOSS_AM, LOSS_AAM = 0, 1, 2   # ktf_loss_*: kind
@@ -337,7 +347,7 @@ def load():
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in (list(PROTOTYPES.items()) + list(AUGMENT_PROTOTYPES.items()) + list(RESAMPLE_PROTOTYPES.items())
                               + list(GRAD_PROTOTYPES.items()) + list(NORM_PROTOTYPES.items()) + list(LOSS_PROTOTYPES.items())
-                              + list(EGS_PROTOTYPES.items()) + list(OPTIM_PROTOTYPES.items())):
+                              + list(EGS_PROTOTYPES.items()) + list(OPTIM_PROTOTYPES.items()) + list(HEAD_PROTOTYPES.items())):
         fn = getattr(lib, name)          # AttributeError = header/library mismatch
         fn.restype = res
         fn.argtypes = args

@@ -8,7 +8,8 @@ The GEMMs and the pooling run in the HIP kernels on fp32; padding to the kernels
 are torch ops on the same device, or -- `relu_batch_norm`, `TrainableSequential(fused_norm=True)` -- the kernels of
 include/ktf_norm.h. `ClassifierHead` is the speaker classification head and its loss -- softmax, additive-margin and
 additive-angular-margin cosine softmax -- over `row_inv_norm` and `margin_softmax_loss`, the kernels of include/ktf_loss.h around
-a `tdnn_affine` GEMM. There is no CPU path for the kernels: tensors that are not on the GPU are refused.
+a `tdnn_affine` GEMM; with sub-centres, an inter-top-k penalty or label smoothing switched on, the kernels of include/ktf_head.h.
+There is no CPU path for the kernels: tensors that are not on the GPU are refused.
 
 `gemm=` selects the matrix pipe of the TDNN GEMMs, forward and backward: "f32" (the exact-fp32 MFMA), "bf16" (operands rounded to
 bf16 in the kernels, fp32 accumulation) or "bf16x3" (hi / lo split operands, three products: near-fp32 values). Parameters,
@@ -443,25 +444,74 @@ def _loss_args(kind, margin, scale, cosine):
     return margin, scale
 
 
-def margin_softmax_loss(z, labels, kind="softmax", margin=0.0, scale=1.0, inv_norm_x=None, inv_norm_w=None):
-    """Softmax cross entropy over the logits of a classification head, with the large-margin cosine variants, as one pair of the
-    library's kernels (include/ktf_loss.h) -> (loss (B,) fp32, pred (B,) int32). z (B, N) fp32 on the GPU: the dot products x_b . w_j;
-    labels (B,) integers, a label outside [0, N) marks an ignored row (loss 0, no gradient). With inv_norm_x (B,) and inv_norm_w (N,)
-    -- `row_inv_norm` of the embeddings and of the weight -- the head is a cosine head, c = z * inv_norm_x[:, None] * inv_norm_w, and
-    the logits are scale * c with the target column replaced by scale * psi(c): kind "softmax": psi(c) = c; "am": c - margin; "aam":
-    cos(theta + margin), continued by c - margin * sin(margin) beyond theta = pi - margin. Without them the head is plain (logits
-    scale * z, kind "softmax" only). pred is the column of the largest cosine without margin. Differentiable in z, inv_norm_x and
-    inv_norm_w; fp64 arithmetic rounded once, no atomics; keeps z and the (B,) fp64 log-sum-exp for the backward pass."""
+class _HeadLoss(torch.autograd.Function):
+    """include/ktf_head.h: sub-centres, the inter-top-k penalty and label smoothing."""
+
+    @staticmethod
+    def forward(ctx, z, labels, inv_x, inv_w, kind, margin, scale, K, topk, penalty, smoothing):
+        B = z.shape[0]
+        N = z.shape[1] // K
+        z = z.contiguous()
+        loss = torch.empty((B,), dtype=torch.float32, device=z.device)
+        pred = torch.empty((B,), dtype=torch.int32, device=z.device)
+        sub_y = torch.empty((B,), dtype=torch.int32, device=z.device)
+        lse = torch.empty((B,), dtype=torch.float64, device=z.device)
+        hard = torch.empty((B, max(topk, 1)), dtype=torch.int32, device=z.device)
+        ops.head_forward(z, K, labels, inv_x, inv_w, kind, margin, scale, topk, penalty, smoothing, loss, pred, lse, hard, sub_y,
+                         ops.head_workspace(B, N, K, z.device))
+        ctx.save_for_backward(z, labels, lse, hard, inv_x, inv_w)    # of the logits' size: z alone
+        ctx.cfg = (kind, margin, scale, K, topk, penalty, smoothing)
+        ctx.mark_non_differentiable(pred, sub_y)
+        return loss, pred, sub_y
+
+    @staticmethod
+    def backward(ctx, gloss, _gpred, _gsub):
+        z, labels, lse, hard, inv_x, inv_w = ctx.saved_tensors
+        kind, margin, scale, K, topk, penalty, smoothing = ctx.cfg
+        B = z.shape[0]
+        dz = torch.empty_like(z)
+        dix = diw = None
+        if inv_x is not None:
+            dix = torch.empty((B,), dtype=torch.float32, device=z.device)
+            diw = torch.empty((z.shape[1],), dtype=torch.float32, device=z.device)
+        ops.head_backward(z, K, labels, inv_x, inv_w, kind, margin, scale, topk, penalty, smoothing, lse, hard,
+                          gloss.to(torch.float32).contiguous(), dz, dix, diw, ops.head_workspace(B, z.shape[1] // K, K, z.device))
+        return dz, None, dix, diw, None, None, None, None, None, None, None
+
+
+def _head_args(sub_centers, top_k, penalty, label_smoothing, cosine):
+    for name, v, hi in (("sub_centers", sub_centers, L.HEAD_MAX_CENTERS), ("top_k", top_k, L.HEAD_MAX_TOPK)):
+        lo = 1 if name == "sub_centers" else 0
+        if isinstance(v, bool) or not isinstance(v, int) or not lo <= v <= hi:
+            raise ValueError(f"{name} must be an integer in [{lo}, {hi}], got {v!r}")
+    penalty, label_smoothing = float(penalty), float(label_smoothing)
+    if not 0.0 <= penalty < float("inf"):
+        raise ValueError(f"penalty must be finite and not negative, got {penalty!r}")
+    if top_k == 0 and penalty != 0.0:
+        raise ValueError(f"penalty must be 0 with top_k=0, got {penalty!r}")
+    if not 0.0 <= label_smoothing < 1.0:
+        raise ValueError(f"label_smoothing must be in [0, 1), got {label_smoothing!r}")
+    if sub_centers > 1 and not cosine:
+        raise ValueError(f"sub_centers={sub_centers} needs a cosine head: give inv_norm_x and inv_norm_w (normalize=True)")
+    if top_k > 0 and not cosine:
+        raise ValueError(f"top_k={top_k} needs a cosine head: give inv_norm_x and inv_norm_w (normalize=True)")
+    return penalty, label_smoothing
+
+
+def _head_loss(z, labels, kind, margin, scale, inv_norm_x, inv_norm_w, sub_centers, top_k, penalty, label_smoothing):
+    """margin_softmax_loss with the selected centre of the target class as a third result (None on the path of ktf_loss.h)."""
     if (inv_norm_x is None) != (inv_norm_w is None):
         raise ValueError("inv_norm_x and inv_norm_w go together: both for a cosine head, neither for a plain one")
     margin, scale = _loss_args(kind, margin, scale, inv_norm_x is not None)
-    if not isinstance(z, torch.Tensor) or z.dim() != 2 or z.shape[1] < 1:
-        raise ValueError(f"expected z (B, N) with N >= 1, got shape {tuple(getattr(z, 'shape', ()))}")
-    B, N = z.shape
+    penalty, label_smoothing = _head_args(sub_centers, top_k, penalty, label_smoothing, inv_norm_x is not None)
+    if not isinstance(z, torch.Tensor) or z.dim() != 2 or z.shape[1] < 1 or z.shape[1] % sub_centers:
+        raise ValueError(f"expected z (B, N * sub_centers) with N >= 1 and sub_centers = {sub_centers}, "
+                         f"got shape {tuple(getattr(z, 'shape', ()))}")
+    B, N = z.shape[0], z.shape[1] // sub_centers
     labels = torch.as_tensor(labels, device=z.device)
     if tuple(labels.shape) != (B,) or labels.dtype.is_floating_point:
         raise ValueError(f"labels must hold one integer per row ({B}), got {labels.dtype} of shape {tuple(labels.shape)}")
-    for name, t, n in (("inv_norm_x", inv_norm_x, B), ("inv_norm_w", inv_norm_w, N)):
+    for name, t, n in (("inv_norm_x", inv_norm_x, B), ("inv_norm_w", inv_norm_w, N * sub_centers)):
         if t is not None and tuple(t.shape) != (n,):
             raise ValueError(f"{name} shape {tuple(t.shape)} != ({n},)")
     _on_gpu(z, "z")
@@ -470,7 +520,30 @@ def margin_softmax_loss(z, labels, kind="softmax", margin=0.0, scale=1.0, inv_no
         _on_gpu(inv_norm_w, "inv_norm_w")
         inv_norm_x, inv_norm_w = inv_norm_x.to(torch.float32).contiguous(), inv_norm_w.to(torch.float32).contiguous()
     labels = labels.clamp(-1, N).to(torch.int32).contiguous()            # int64 labels beyond int32 stay out of range
-    return _MarginSoftmax.apply(z.to(torch.float32), labels, inv_norm_x, inv_norm_w, kind, margin, scale)
+    if sub_centers == 1 and top_k == 0 and label_smoothing == 0.0:       # the kernels of ktf_loss.h, as before there were others
+        return _MarginSoftmax.apply(z.to(torch.float32), labels, inv_norm_x, inv_norm_w, kind, margin, scale) + (None,)
+    return _HeadLoss.apply(z.to(torch.float32), labels, inv_norm_x, inv_norm_w, kind, margin, scale, sub_centers, top_k, penalty,
+                           label_smoothing)
+
+
+def margin_softmax_loss(z, labels, kind="softmax", margin=0.0, scale=1.0, inv_norm_x=None, inv_norm_w=None, sub_centers=1, top_k=0,
+                        penalty=0.0, label_smoothing=0.0):
+    """Softmax cross entropy over the logits of a classification head, with the large-margin cosine variants, as one pair of the
+    library's kernels (include/ktf_loss.h) -> (loss (B,) fp32, pred (B,) int32). z (B, N) fp32 on the GPU: the dot products x_b . w_j;
+    labels (B,) integers, a label outside [0, N) marks an ignored row (loss 0, no gradient). With inv_norm_x (B,) and inv_norm_w (N,)
+    -- `row_inv_norm` of the embeddings and of the weight -- the head is a cosine head, c = z * inv_norm_x[:, None] * inv_norm_w, and
+    the logits are scale * c with the target column replaced by scale * psi(c): kind "softmax": psi(c) = c; "am": c - margin; "aam":
+    cos(theta + margin), continued by c - margin * sin(margin) beyond theta = pi - margin. Without them the head is plain (logits
+    scale * z, kind "softmax" only). pred is the column of the largest cosine without margin. Differentiable in z, inv_norm_x and
+    inv_norm_w; fp64 arithmetic rounded once, no atomics; keeps z and the (B,) fp64 log-sum-exp for the backward pass.
+
+    Three switches, separately or together, run the kernels of include/ktf_head.h instead (with all of them off nothing changes):
+    sub_centers = K > 1 (cosine head): z is (B, N * K), column j * K + k the centre k of class j, inv_norm_w (N * K,); a class's cosine
+    is the largest of its centres', and only that centre gets a gradient. top_k > 0 (cosine head): the top_k classes other than the
+    target with the largest cosines (ties: the lower class) get `penalty` added to their cosine. label_smoothing = e in [0, 1): the
+    target distribution is (1 - e) on the label plus e / N everywhere. That path keeps z, the log-sum-exp and the (B, top_k) int32
+    list of penalised classes, and pred is the class (not the column) of the largest cosine."""
+    return _head_loss(z, labels, kind, margin, scale, inv_norm_x, inv_norm_w, sub_centers, top_k, penalty, label_smoothing)[:2]
 
 
 class ClassifierHead(torch.nn.Module):
@@ -481,9 +554,16 @@ class ClassifierHead(torch.nn.Module):
     bias. margin defaults to 0.2 (0 for "softmax"), scale to 30 (1 for a plain head); both are plain attributes read at every call,
     so a margin warm-up is one assignment per step. `forward(emb, labels)` -> (the mean loss of the valid rows -- 0 when there is
     none --, pred (B,) int32); labels outside [0, num_classes) mark rows to ignore. No torch op touches a (B, num_classes) or
-    (num_classes, dim) tensor in forward or backward."""
+    (num_classes, dim) tensor in forward or backward.
 
-    def __init__(self, dim, num_classes, kind="aam", margin=None, scale=None, bias=False, gemm="f32", device=None, normalize=None, eps=1e-12):
+    sub_centers = K > 1 gives every class K centres: weight is (num_classes * K, dim), class-major (row j * K + k is centre k of class
+    j); top_k, penalty and label_smoothing are those of `margin_softmax_loss` and, like margin and scale, plain attributes read at
+    every call. With one of them set the loss runs the kernels of include/ktf_head.h; with none, those of include/ktf_loss.h as
+    before. A head with K > 1 counts in training mode, in the buffer `center_counts` (num_classes, K) int64, how often each centre
+    was the one its class's target rows selected; `dominant()` reduces the head to those centres."""
+
+    def __init__(self, dim, num_classes, kind="aam", margin=None, scale=None, bias=False, gemm="f32", device=None, normalize=None, eps=1e-12,
+                 sub_centers=1, top_k=0, penalty=0.0, label_smoothing=0.0):
         super().__init__()
         for name, v in (("dim", dim), ("num_classes", num_classes)):
             if isinstance(v, bool) or not isinstance(v, int) or v < 1:
@@ -501,11 +581,17 @@ class ClassifierHead(torch.nn.Module):
         self.margin = (0.0 if kind == "softmax" else 0.2) if margin is None else margin
         self.scale = (30.0 if normalize else 1.0) if scale is None else scale
         _loss_args(kind, self.margin, self.scale, normalize)
+        self.sub_centers, self.top_k, self.penalty, self.label_smoothing = sub_centers, top_k, penalty, label_smoothing
+        _head_args(sub_centers, top_k, penalty, label_smoothing, normalize)
         if not self.eps > 0.0:
             raise ValueError(f"eps must be positive, got {eps!r}")
         dev = ops.default_device() if device is None else torch.device(device)
-        self.weight = torch.nn.Parameter(torch.randn((num_classes, dim), dtype=torch.float32, device=dev) * dim ** -0.5)
+        self.weight = torch.nn.Parameter(torch.randn((num_classes * sub_centers, dim), dtype=torch.float32, device=dev) * dim ** -0.5)
         self.bias = torch.nn.Parameter(torch.zeros((num_classes,), dtype=torch.float32, device=dev)) if bias else None
+        if sub_centers > 1:                              # a head with one centre per class keeps the state_dict it always had
+            self.register_buffer("center_counts", torch.zeros((num_classes, sub_centers), dtype=torch.int64, device=dev))
+        else:
+            self.center_counts = None
 
     def _logits(self, emb):
         if not isinstance(emb, torch.Tensor) or emb.dim() != 2 or emb.shape[1] != self.dim:
@@ -518,13 +604,45 @@ class ClassifierHead(torch.nn.Module):
 
     def forward(self, emb, labels):
         margin, scale = _loss_args(self.kind, self.margin, self.scale, self.normalize)
+        _head_args(self.sub_centers, self.top_k, self.penalty, self.label_smoothing, self.normalize)
         z, ix, iw = self._logits(emb)
-        loss, pred = margin_softmax_loss(z, labels, self.kind, margin, scale, ix, iw)
+        loss, pred, sub_y = _head_loss(z, labels, self.kind, margin, scale, ix, iw, self.sub_centers, self.top_k, self.penalty,
+                                       self.label_smoothing)
         labels = torch.as_tensor(labels, device=loss.device)
-        valid = ((labels >= 0) & (labels < self.num_classes)).sum().clamp(min=1)
+        ok = (labels >= 0) & (labels < self.num_classes)
+        if self.training and self.center_counts is not None:    # sub_y is -1 on an ignored row
+            at = labels.clamp(0, self.num_classes - 1).to(torch.int64) * self.sub_centers + sub_y.clamp(min=0).to(torch.int64)
+            self.center_counts.view(-1).index_add_(0, at, ok.to(torch.int64))
+        valid = ok.sum().clamp(min=1)
         return loss.sum() / valid, pred                  # an ignored row's loss is 0
 
     def cosines(self, emb):
-        """For evaluation: the (B, num_classes) cosines of a cosine head (the logits of a plain one), scaled in torch."""
+        """For evaluation: the (B, num_classes) cosines of a cosine head (the logits of a plain one), scaled in torch; with
+        sub-centres the largest of each class's centres."""
         z, ix, iw = self._logits(emb)
-        return z if ix is None else z * ix[:, None] * iw[None, :]
+        c = z if ix is None else z * ix[:, None] * iw[None, :]
+        return c if self.sub_centers == 1 else c.view(c.shape[0], self.num_classes, self.sub_centers).amax(dim=2)
+
+    def dominant(self):
+        """A new head with sub_centers=1 that holds, for every class, the centre `center_counts` names most often (the lowest k among
+        equal counts): the usual clean-up after sub-centre training. Every other setting is this head's."""
+        K = self.sub_centers
+        new = ClassifierHead(self.dim, self.num_classes, self.kind, self.margin, self.scale, self.bias is not None, self.gemm,
+                             self.weight.device, self.normalize, self.eps, 1, self.top_k, self.penalty, self.label_smoothing)
+        with torch.no_grad():
+            if K == 1:
+                new.weight.copy_(self.weight)
+            else:
+                best = dominant_centers(self.center_counts)
+                rows = torch.arange(self.num_classes, device=self.weight.device) * K + best.to(self.weight.device)
+                new.weight.copy_(self.weight.index_select(0, rows))
+            if self.bias is not None:
+                new.bias.copy_(self.bias)
+        return new.train(self.training)
+
+
+def dominant_centers(counts):
+    """counts (N, K) integers -> (N,) int64: the most counted centre of every class, the lowest k among equal counts."""
+    counts = torch.as_tensor(counts).to(torch.int64)
+    K = counts.shape[1]
+    return (counts * K + torch.arange(K - 1, -1, -1, device=counts.device)).argmax(dim=1)    # the keys of a row are distinct

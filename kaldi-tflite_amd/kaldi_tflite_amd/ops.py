@@ -1599,6 +1599,53 @@ def loss_margin_softmax_backward(z, labels, inv_x, inv_w, kind, margin, scale, l
     return dz, dinv_x, dinv_w
 
 
+# ------------------------------------------------- the head's loss with sub-centres, inter-top-k and smoothing (include/ktf_head.h)
+def head_slot_rows():
+    """Batch rows per partial sum of dinv_w."""
+    return int(L.load().ktf_head_slot_rows())
+
+
+def head_workspace(B, N, K, device):
+    """The workspace either head call of a (B, N classes x K centres) batch takes."""
+    return _workspace("ktf_head_workspace_bytes", int(B), int(N), int(K), device=device)
+
+
+def _head_classes(z, K):
+    K = int(K)
+    if K < 1 or z.shape[1] % K:
+        raise ValueError(f"sub_centers {K} does not divide the {z.shape[1]} columns of z")
+    return z.shape[1] // K, K
+
+
+def head_forward(z, K, labels, inv_x, inv_w, kind, margin, scale, topk, penalty, smoothing, loss, pred, lse, hard, sub_y, workspace):
+    """z (B, N * K) fp32 with dense rows, class-major; labels (B,) int32, inv_x (B,) / inv_w (N * K,) fp32 or both None; loss (B,)
+    fp32, pred (B,) int32 or None, lse (B,) fp64, hard (B, max(topk, 1)) int32 (None allowed when topk = 0) and sub_y (B,) int32 or
+    None preallocated. kind as in loss_margin_softmax_forward."""
+    B = z.shape[0]
+    N, K = _head_classes(z, K)
+    pz, ldz = _mat(z, workspace)
+    at = lambda t: None if t is None else (L.ptr(t) if t.numel() else L.ptr(workspace))  # noqa: E731
+    _call("ktf_head_forward", z.device, pz, ldz, B, N, K, at(labels), at(inv_x), at(inv_w), int(LOSS_KINDS.get(kind, kind)), float(margin),
+          float(scale), int(topk), float(penalty), float(smoothing), at(loss), at(pred), at(lse), at(hard), at(sub_y), L.ptr(workspace),
+          workspace.numel())
+    return loss, pred, lse, hard, sub_y
+
+
+def head_backward(z, K, labels, inv_x, inv_w, kind, margin, scale, topk, penalty, smoothing, lse, hard, gloss, dz, dinv_x, dinv_w,
+                  workspace):
+    """The gradient of sum_b gloss[b] * loss[b] (gloss None: ones) with the forward call's lse and hard: dz (B, lddz >= N * K), which
+    may be z itself, and for a cosine head dinv_x (B,), dinv_w (N * K,), all preallocated and written whole."""
+    B = z.shape[0]
+    N, K = _head_classes(z, K)
+    pz, ldz = _mat(z, workspace)
+    pd, lddz = _mat(dz, workspace)
+    at = lambda t: None if t is None else (L.ptr(t) if t.numel() else L.ptr(workspace))  # noqa: E731
+    _call("ktf_head_backward", z.device, pz, ldz, B, N, K, at(labels), at(inv_x), at(inv_w), int(LOSS_KINDS.get(kind, kind)), float(margin),
+          float(scale), int(topk), float(penalty), float(smoothing), at(lse), at(hard), at(gloss), pd, lddz, at(dinv_x), at(dinv_w),
+          L.ptr(workspace), workspace.numel())
+    return dz, dinv_x, dinv_w
+
+
 # ----------------------------------------------------------------------------- training examples (include/ktf_egs.h)
 EGS_DTYPES = {torch.float32: L.KTF_F32, torch.float16: L.KTF_F16}
 
