@@ -1,7 +1,7 @@
 /*
  * ktf_head.h -- the classification head's loss with sub-centres, an inter-top-k penalty and label smoothing: a second family of loss
  * calls next to ktf_loss.h, whose rules (cited below as "ktf_loss.h, rule n"), conventions and error codes hold here unless a rule says
- * otherwise (kernels: csrc/head_train.hip). The inverse norms are those of
+ * otherwise (kernels: csrc/loss_train.hip). The inverse norms are those of
  * ktf_loss.h, rules N1 and N2; the GEMM of the head is the affine's. All arithmetic is fp64 on the fp32 inputs, every operation rounded
  * on its own (no fused multiply-add), every output rounded once; no floating-point atomics.
  *

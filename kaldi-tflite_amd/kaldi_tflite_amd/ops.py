@@ -1557,6 +1557,12 @@ def _mat(t, other):
     return L.ptr(t if t.numel() else other), max(_ld(t), t.shape[1])
 
 
+def _ptr_or(other):
+    """t -> the pointer of an optional 1-D operand of the loss calls: None for None; a tensor without elements (B = 0) has no storage,
+    and `other`'s non-null pointer stands for it as in _mat."""
+    return lambda t: None if t is None else L.ptr(t if t.numel() else other)
+
+
 def loss_row_inv_norm(x, eps, inv):
     """x (rows, D) fp32 with dense rows, inv (rows,) fp32 preallocated: inv[r] = 1 / max(|x[r]|, eps)."""
     if x.shape[0] == 0:
@@ -1581,7 +1587,7 @@ def loss_margin_softmax_forward(z, labels, inv_x, inv_w, kind, margin, scale, lo
     None and lse (B,) fp64 preallocated. kind: "softmax", "am", "aam" or the KTF_LOSS_* number."""
     B, N = z.shape
     pz, ldz = _mat(z, workspace)
-    at = lambda t: None if t is None else (L.ptr(t) if t.numel() else L.ptr(workspace))  # noqa: E731
+    at = _ptr_or(workspace)
     _call("ktf_loss_margin_softmax_forward", z.device, pz, ldz, B, N, at(labels), at(inv_x), at(inv_w), int(LOSS_KINDS.get(kind, kind)),
           float(margin), float(scale), at(loss), at(pred), at(lse), L.ptr(workspace), workspace.numel())
     return loss, pred, lse
@@ -1593,7 +1599,7 @@ def loss_margin_softmax_backward(z, labels, inv_x, inv_w, kind, margin, scale, l
     B, N = z.shape
     pz, ldz = _mat(z, workspace)
     pd, lddz = _mat(dz, workspace)
-    at = lambda t: None if t is None else (L.ptr(t) if t.numel() else L.ptr(workspace))  # noqa: E731
+    at = _ptr_or(workspace)
     _call("ktf_loss_margin_softmax_backward", z.device, pz, ldz, B, N, at(labels), at(inv_x), at(inv_w), int(LOSS_KINDS.get(kind, kind)),
           float(margin), float(scale), at(lse), at(gloss), pd, lddz, at(dinv_x), at(dinv_w), L.ptr(workspace), workspace.numel())
     return dz, dinv_x, dinv_w
@@ -1624,7 +1630,7 @@ def head_forward(z, K, labels, inv_x, inv_w, kind, margin, scale, topk, penalty,
     B = z.shape[0]
     N, K = _head_classes(z, K)
     pz, ldz = _mat(z, workspace)
-    at = lambda t: None if t is None else (L.ptr(t) if t.numel() else L.ptr(workspace))  # noqa: E731
+    at = _ptr_or(workspace)
     _call("ktf_head_forward", z.device, pz, ldz, B, N, K, at(labels), at(inv_x), at(inv_w), int(LOSS_KINDS.get(kind, kind)), float(margin),
           float(scale), int(topk), float(penalty), float(smoothing), at(loss), at(pred), at(lse), at(hard), at(sub_y), L.ptr(workspace),
           workspace.numel())
@@ -1639,7 +1645,7 @@ def head_backward(z, K, labels, inv_x, inv_w, kind, margin, scale, topk, penalty
     N, K = _head_classes(z, K)
     pz, ldz = _mat(z, workspace)
     pd, lddz = _mat(dz, workspace)
-    at = lambda t: None if t is None else (L.ptr(t) if t.numel() else L.ptr(workspace))  # noqa: E731
+    at = _ptr_or(workspace)
     _call("ktf_head_backward", z.device, pz, ldz, B, N, K, at(labels), at(inv_x), at(inv_w), int(LOSS_KINDS.get(kind, kind)), float(margin),
           float(scale), int(topk), float(penalty), float(smoothing), at(lse), at(hard), at(gloss), pd, lddz, at(dinv_x), at(dinv_w),
           L.ptr(workspace), workspace.numel())
