@@ -4,10 +4,7 @@
 //           layers/plda/plda.py:163-263 of the reference.
 #include "common.h"
 #include "plda_common.h"
-
-// tf.nn.relu of the variance (stats_pooling.py:238, 293): a NaN -- the 0 / 0 of a window without a sampled frame -- stays a NaN (fmax
-// would return 0 and the standard deviation sqrt(epsilon))
-__device__ __forceinline__ double relu_keep_nan(double v) { return v < 0.0 ? 0.0 : v; }
+#include "pooled_stats.h"
 
 // ------------------------------------------------------------------------------------ stats pooling (reduce)
 // One workgroup = one utterance x CW columns; row groups stride the time axis, each thread owns two adjacent columns
@@ -322,22 +319,11 @@ __global__ __launch_bounds__(XT_THREADS) void xvec_tail_kernel(const float* __re
         } else {
             const int len = lens ? lens[b] : (int)T;
             if (skip_empty && len <= 0) continue;              // (workgroup-uniform; no barrier of this iteration has been reached)
-            const double n = (double)len;
-            const int used = slots ? (len + slot_rows - 1) / slot_rows : 1;
+            const int used = slots ? PoolSlots{slot_rows, 0}.used(len) : 1;
             for (int c = tid; c < D; c += XT_THREADS) {
-                double sv = 0.0, q = 0.0;
-                if (slots == 0) {
-                    sv = sums[(b * 2) * D + c];
-                    q = sums[(b * 2 + 1) * D + c];
-                } else {
-                    for (int k = 0; k < used; ++k) {
-                        sv += sums[((b * slots + k) * 2) * D + c];
-                        q += sums[((b * slots + k) * 2 + 1) * D + c];
-                    }
-                }
-                const double m = sv / n;
-                xs[c] = (float)m;
-                if (include_std) xs[D + c] = (float)sqrt(relu_keep_nan(q / n - m * m) + (double)eps);
+                const PooledMoments m = pooled_moments(sums, slots, used, b, D, c, (double)len, include_std, eps);
+                xs[c] = m.mean;
+                if (include_std) xs[D + c] = m.std;
             }
             for (int i = in_dim + tid; i < XT_MAXIT * 256; i += XT_THREADS) xs[i] = 0.0f;
         }

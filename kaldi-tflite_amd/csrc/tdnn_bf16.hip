@@ -690,9 +690,9 @@ __global__ __launch_bounds__(256, 2) void tdnn_bf16h_kernel(TdnnParams p, int mt
         for (int j = 0; j < 4; ++j) {
             const int nl = wn * 64 + j * 16 + c;
             const float scj = prm[H_BN + nl], shj = prm[2 * H_BN + nl];
-            POOLED_SUMS16(ACT, false, true, acc, j, 0.0f, scj, shj, rows_valid, sm, sq)
+            const PooledSums t = pooled_sums16<8, true>(lane, rows_valid, [&](int i, int r) { return EPI_VALUE_NB(ACT, acc[i][j][r], scj, shj); });
             const int n = n0 + nl;
-            if (lane < 16 && n < p.units) stats_out(stats, p, b, t0 >> 7, n, sm, sq);
+            if (lane < 16 && n < p.units) stats_out(stats, p, b, pool_block128().slot_of(t0), n, t.s, t.q);
         }
         return;
     }

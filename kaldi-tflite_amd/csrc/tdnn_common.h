@@ -15,6 +15,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "pooled_stats.h"
 
 // Fixed choices of the split-plane kernel (each was an A/B in round 2; DESIGN.md section 5 has the numbers)
 #define KTF_X3_Y_NT 1         // the 16-bit activation planes are written with non-temporal stores (the XCD's L2 keeps weights / shared tiles)
@@ -45,7 +46,7 @@ struct TdnnParams {
     int32_t ctx[16];
     int32_t wtiled;         // KTF_TDNN_W_TILED: W stored as the kernel's LDS images, one contiguous 16 KiB block per (N-tile, K-step)
     int32_t kinter;         // KTF_TDNN_K_INTERLEAVED: K runs (32-wide feature chunk, context, feature) instead of (context, feature)
-    int32_t stat_slots;     // fused pooling: 0 = fp64 atomics into (B, 2, units); > 0 = one slot per 128-row block (KTF_TDNN_DET_STATS)
+    int32_t stat_slots;     // fused pooling: 0 = fp64 atomics into (B, 2, units); > 0 = the kernel's PoolSlots::slots (KTF_TDNN_DET_STATS)
     int32_t y_pair;         // fp32-sized output slots hold the KTF_BF16P pair of the value (y_dtype is KTF_F32 to the store paths)
     const int32_t* row_starts;  // ktf_tdnn_split_flat: (B + 1) exclusive prefix sums of lens (flat row tiling of tdnn_x3s_kernel), else NULL
     const int32_t* row_map;     // ... and optionally ktf_flat_row_map's table: (output row or -1, frame, utterance length, utterance) per flat row
@@ -57,19 +58,6 @@ __device__ __forceinline__ float ktf_pair(float v) {
     const unsigned hi = f2bf(v);
     const unsigned lo = f2bf(v - bf2f((unsigned short)hi));
     return __uint_as_float(hi | (lo << 16));
-}
-
-// Adds (slots == 0) or stores (slots > 0: block `slot` of utterance b is written by exactly one wave) a column's partial sums.
-__device__ __forceinline__ void stats_out(double* __restrict__ stats, const TdnnParams& p, int b, int slot, int n, double s, double q) {
-    if (p.stat_slots > 0) {
-        double* dst = stats + (((int64_t)b * p.stat_slots + slot) * 2) * p.units + n;
-        dst[0] = s;
-        dst[p.units] = q;
-    } else {
-        double* dst = stats + ((int64_t)b * 2) * p.units + n;
-        atomicAdd(dst, s);
-        atomicAdd(dst + p.units, q);
-    }
 }
 
 __device__ __forceinline__ int tdnn_out_len(int len, const TdnnParams& p, int& start) {

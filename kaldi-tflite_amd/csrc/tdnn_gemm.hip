@@ -124,8 +124,6 @@ extern "C" int ktf_tdnn_out_lens(const int32_t* lens, int64_t B, const KtfTdnnDe
     return KTF_OK;
 }
 
-extern "C" int64_t ktf_flat_stats_slots(int64_t T) { return T <= 0 ? 1 : (T + 254) / 128; }
-
 static int tdnn_launch(const void* x, int64_t B, int64_t T, int64_t ldx, const int32_t* lens, const KtfTdnnDesc* d,
                        const void* w, const void* w_lo, const float* bias, const float* scale, const float* shift,
                        void* y, int64_t ldy, int32_t* out_lens, double* stats_sums, void* stream,
@@ -179,7 +177,8 @@ static int tdnn_launch(const void* x, int64_t B, int64_t T, int64_t ldx, const i
     p.units = d->units; p.din_pad = d->din_pad; p.nctx = d->nctx; p.sub = d->subsampling; p.valid = d->valid;
     p.act = act_pass ? KTF_ACT_NONE : d->act; p.y_dtype = y_pair ? KTF_F32 : d->y_dtype; p.y_pair = y_pair ? 1 : 0; p.ktot = d->nctx * d->din_pad;
     if (act_pass) p.scale = p.shift = nullptr;          // (the BatchNorm affine follows the activation: applied by the pass)
-    p.stat_slots = (stats_sums && (d->flags & KTF_TDNN_DET_STATS)) ? (int32_t)(row_starts ? ktf_flat_stats_slots(Tout) : ktf_stats_slots(Tout)) : 0;
+    const PoolSlots pool = row_starts ? pool_flat128() : pool_slots_tdnn(d->gemm);
+    p.stat_slots = (stats_sums && (d->flags & KTF_TDNN_DET_STATS)) ? (int32_t)pool.slots(Tout) : 0;
     p.kinter = (d->flags & KTF_TDNN_K_INTERLEAVED) ? 1 : 0;
     p.wtiled = (d->flags & KTF_TDNN_W_TILED) ? 1 : 0;
     if (p.wtiled) KTF_REQUIRE((split_in && d->units > 128 && ldy % 4 == 0), "ktf_tdnn: KTF_TDNN_W_TILED is implemented by the split-plane kernel only");
@@ -200,7 +199,6 @@ static int tdnn_launch(const void* x, int64_t B, int64_t T, int64_t ldx, const i
         KTF_REQUIRE(d->x_dtype == KTF_BF16P && d->w_dtype == KTF_BF16P && !w_lo, "ktf_tdnn: KTF_GEMM_BF16X4 takes x and w of KTF_BF16P (w_lo NULL)");
         KTF_REQUIRE(stats_sums || y_pair || d->y_dtype == KTF_F32, "ktf_tdnn: KTF_GEMM_BF16X4 writes KTF_F32 or KTF_BF16P rows");
         KTF_REQUIRE(!(d->flags & ~KTF_TDNN_DET_STATS), "ktf_tdnn: KTF_GEMM_BF16X4 takes no KTF_TDNN_* flag but KTF_TDNN_DET_STATS");
-        p.stat_slots = (stats_sums && (d->flags & KTF_TDNN_DET_STATS)) ? (int32_t)ktf_tdnn_stats_slots(Tout, d->gemm) : 0;
         return tdnn_launch_x4(p, d, B, Tout, stats_sums, st);
     }
     if (d->gemm == KTF_GEMM_BF16 || d->gemm == KTF_GEMM_BF16X3) {
@@ -354,14 +352,11 @@ extern "C" int ktf_split_bf16_rows(const float* src, int64_t B, int64_t T, int32
     return KTF_OK;
 }
 
-// 128-row blocks, rounded up to whole 256-row tiles (a 256-row tile always writes both of its blocks)
-extern "C" int64_t ktf_stats_slots(int64_t T) { return T <= 0 ? 2 : 2 * ((T + 255) / 256); }
-// ... of ktf_tdnn_stats by GEMM mode: KTF_GEMM_BF16X4 pools per 64-row tile (csrc/tdnn_pair.hip), the others per 128-row block
-extern "C" int32_t ktf_tdnn_slot_rows(int32_t gemm) { return gemm == KTF_GEMM_BF16X4 ? 64 : 128; }
-extern "C" int64_t ktf_tdnn_stats_slots(int64_t T, int32_t gemm) {
-    if (gemm != KTF_GEMM_BF16X4) return ktf_stats_slots(T);
-    return T <= 0 ? 1 : (T + 63) / 64;
-}
+// KTF_TDNN_DET_STATS slots (pooled_stats.h): of the 256-row tiles, of ktf_tdnn_stats by GEMM mode, of flat row tiles
+extern "C" int64_t ktf_stats_slots(int64_t T) { return pool_block128().slots(T); }
+extern "C" int32_t ktf_tdnn_slot_rows(int32_t gemm) { return pool_slots_tdnn(gemm).slot_rows; }
+extern "C" int64_t ktf_tdnn_stats_slots(int64_t T, int32_t gemm) { return pool_slots_tdnn(gemm).slots(T); }
+extern "C" int64_t ktf_flat_stats_slots(int64_t T) { return pool_flat128().slots(T); }
 
 // mean / std from the fp64 column sums of ktf_tdnn_stats: out[b, c] = mean, out[b, D + c] = sqrt(relu(E[x^2]-mean^2)+eps), NaN kept
 __global__ void stats_finalize_kernel(const double* __restrict__ sums, int64_t slots, int slot_rows, const int32_t* __restrict__ lens, int64_t T,
@@ -373,27 +368,11 @@ __global__ void stats_finalize_kernel(const double* __restrict__ sums, int64_t s
         const int c = (int)(e - b * D);
         const int rs0 = row_starts ? row_starts[b] : 0;
         const int len = row_starts ? row_starts[b + 1] - rs0 : (lens ? lens[b] : (int)T);
-        const double n = (double)len;
-        double s = 0.0, q = 0.0;
-        if (slots == 0) {
-            s = sums[(b * 2) * D + c];
-            q = sums[(b * 2 + 1) * D + c];
-        } else {
-            // blocks holding valid rows, added in block order (flat row tiles: the 128-row blocks of the flat row space the utterance touches)
-            const int used = row_starts ? (len > 0 ? ((rs0 + len - 1) >> 7) - (rs0 >> 7) + 1 : 0) : (len + slot_rows - 1) / slot_rows;
-            for (int k = 0; k < used; ++k) {
-                s += sums[((b * slots + k) * 2) * D + c];
-                q += sums[((b * slots + k) * 2 + 1) * D + c];
-            }
-        }
-        const double mean = s / n;
-        out[b * ldo + c] = (float)mean;
-        if (include_std) {
-            // relu as tf.nn.relu (stats_pooling.py:238): a NaN variance -- an utterance without a frame (0 / 0), NaN activations -- stays NaN;
-            // fmax(NaN, 0) = 0 made sqrt(eps) of it (tools/fuzz_models.py seed 9102: an utterance a VALID-padded layer leaves no frame of)
-            const double var = q / n - mean * mean;
-            out[b * ldo + D + c] = (float)sqrt((var < 0.0 ? 0.0 : var) + (double)eps);
-        }
+        // (flat row tiles: the blocks of the flat row space the utterance touches)
+        const int used = slots ? PoolSlots{slot_rows, 0}.used(len, rs0) : 1;
+        const PooledMoments m = pooled_moments(sums, slots, used, b, D, c, (double)len, include_std, eps);
+        out[b * ldo + c] = m.mean;
+        if (include_std) out[b * ldo + D + c] = m.std;
     }
 }
 

@@ -587,7 +587,8 @@ static int mx_launch(const void* xh, const void* xl4, const void* x4, const void
     if (p.Tout <= 0) return KTF_OK;
     KTF_REQUIRE(plain || !(d->flags & KTF_TDNN_MX_LOADER), "%s: the loader-wave kernel takes SAME padding without subsampling", who);
     const bool loader = (d->flags & KTF_TDNN_MX_LOADER) != 0;
-    p.stat_slots = (stats && (d->flags & KTF_TDNN_DET_STATS)) ? (int32_t)ktf_mx_stats_slots(T, d->flags) : 0;
+    const PoolSlots pool = (row_starts && !loader) ? pool_flat128() : pool_slots_mx(d->flags);
+    p.stat_slots = (stats && (d->flags & KTF_TDNN_DET_STATS)) ? (int32_t)pool.slots(T) : 0;
     for (int i = 0; i < d->nctx; ++i) {
         KTF_REQUIRE(d->ctx[i] >= -128 && d->ctx[i] <= 127, "%s: context offsets outside [-128, 127]", who);
         p.ctx_pk[i >> 3] |= (unsigned long long)(unsigned char)(signed char)d->ctx[i] << ((i & 7) * 8);
@@ -602,7 +603,6 @@ static int mx_launch(const void* xh, const void* xl4, const void* x4, const void
     }
     if (row_starts) {                           // flat row tiles: M-tiles over the batch's valid rows laid end to end
         KTF_REQUIRE(row_map && plain && o != MX_OUT_F32 && !loader, "%s: flat row tiles take the row table, SAME padding, no subsampling, a plane or pooled output", who);
-        p.stat_slots = (stats && (d->flags & KTF_TDNN_DET_STATS)) ? (int32_t)ktf_flat_stats_slots(T) : 0;
         KTF_REQUIRE(B <= 4095 && B * T * (int64_t)p.nch_in * 64 < (1ll << 32) - (1ll << 20) && B * T < (1ll << 31) / (p.nch_out > 0 ? p.nch_out : 1),
                     "%s: flat row tiles need B <= 4095 and B * T * din_pad * 2 < 2^32", who);
         p.row_starts = row_starts; p.row_map = row_map;
@@ -656,8 +656,8 @@ extern "C" int ktf_tdnn_mx_flat(const void* xh, const void* xl4, const void* x4,
                      row_starts, row_map);
 }
 
-// ... and ktf_tdnn_mx_stats on them: one partial sum per run of an utterance's rows in a wave's 128-row block (flat_stats.h), slots and finalize
-// as ktf_tdnn_split_flat_stats
+// ... and ktf_tdnn_mx_stats on them: one partial sum per run of an utterance's rows in a wave's 128-row block (flat_stats_runs), slots and
+// finalize as ktf_tdnn_split_flat_stats
 extern "C" int ktf_tdnn_mx_flat_stats(const void* xh, const void* xl4, const void* x4, const void* xs, int64_t B, int64_t T, const int32_t* row_starts,
                                       const int32_t* row_map, const KtfTdnnDesc* d, const void* wh, const void* wq, const float* bias,
                                       const float* scale, const float* shift, double* sums, void* stream) {
@@ -674,10 +674,6 @@ extern "C" int ktf_tdnn_mx_stats(const void* xh, const void* xl4, const void* x4
                      "ktf_tdnn_mx_stats");
 }
 
-// KTF_TDNN_DET_STATS slots of ktf_tdnn_mx_stats: the 256-row kernel writes one slot per 128-row block (ktf_stats_slots), the loader
-// kernel one per 96-row block of its 192-row tiles
-extern "C" int32_t ktf_mx_slot_rows(int32_t flags) { return (flags & KTF_TDNN_MX_LOADER) ? 96 : 128; }
-extern "C" int64_t ktf_mx_stats_slots(int64_t T, int32_t flags) {
-    if (!(flags & KTF_TDNN_MX_LOADER)) return ktf_stats_slots(T);
-    return T <= 0 ? 2 : 2 * ((T + 191) / 192);
-}
+// KTF_TDNN_DET_STATS slots of ktf_tdnn_mx_stats
+extern "C" int32_t ktf_mx_slot_rows(int32_t flags) { return pool_slots_mx(flags).slot_rows; }
+extern "C" int64_t ktf_mx_stats_slots(int64_t T, int32_t flags) { return pool_slots_mx(flags).slots(T); }

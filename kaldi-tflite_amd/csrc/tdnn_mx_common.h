@@ -2,7 +2,6 @@
 // tile on eight matrix waves + four loader waves): operand types, the parameter block, the E8M0 scale rule.
 #pragma once
 #include "tdnn_common.h"
-#include "flat_stats.h"
 #include <type_traits>
 
 typedef __attribute__((ext_vector_type(8))) int i32x8;
@@ -229,18 +228,6 @@ __device__ __forceinline__ void mx_encode32(const float (&v)[32], u32x4 (&hp)[4]
 
 // ------------------------------------------------------------------------------------ shared by the epilogues (tdnn_mx_epilogue.inc)
 __device__ __forceinline__ float mx_act(float v, int act) { return act == KTF_ACT_RELU ? fmaxf(v, 0.0f) : v; }
-
-__device__ __forceinline__ void mx_stats_out(double* __restrict__ stats, const MxParams& p, int b, int slot, int n, double s, double q) {
-    if (p.stat_slots > 0) {
-        double* dst = stats + (((int64_t)b * p.stat_slots + slot) * 2) * p.units + n;
-        dst[0] = s;
-        dst[p.units] = q;
-    } else {
-        double* dst = stats + ((int64_t)b * 2) * p.units + n;
-        atomicAdd(dst, s);
-        atomicAdd(dst + p.units, q);
-    }
-}
 
 // tdnn_mxl.hip: the loader-wave kernel (include/ktf_hip.h, KTF_TDNN_MX_LOADER); `p` as filled by mx_launch
 int mxl_launch(const MxParams& p, int64_t B, int act, int out_kind, double* stats, hipStream_t st);

@@ -15,7 +15,7 @@
         }
     }
     if constexpr (OUT == MX_OUT_STATS && FLAT) {
-        // fused StatsPooling on flat row tiles (flat_stats.h): the finished values replace the accumulators, then one partial sum per run
+        // fused StatsPooling on flat row tiles (flat_stats_runs, pooled_stats.h): the finished values replace the accumulators, then one partial sum per run
 #pragma unroll
         for (int j = 0; j < 4; ++j)
 #pragma unroll
@@ -31,39 +31,17 @@
                         },
                         [&](int bb, int slot, int j, double s, double q) {
                             const int n = n0 + wn * 64 + j * 16 + (lane & 15);
-                            if (n < p.units) mx_stats_out(stats, p, bb, slot, n, s, q);
+                            if (n < p.units) stats_out(stats, p, bb, slot, n, s, q);
                         });
         return;
     } else if constexpr (OUT == MX_OUT_STATS) {
-        // fused StatsPooling (stats_pooling.py:231-240): per column the sum and the sum of squares of the wave's 128 rows, taken in
-        // fp32 relative to a pivot (row 0 of the block: a constant column -- a dead ReLU unit -- gives exactly 0 and 0), then fp64
+        // fused StatsPooling (stats_pooling.py:231-240): per column the sums of the wave's 128 rows (pooled_sums16, pooled_stats.h)
         const int rv = rows_valid - wm * 128;
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            float v0 = mx_act(acc[0][j][0] + ebias[j], ACT) * esc[j] + esh[j];
-            const float pv = __shfl(v0, lane & 15, 64);
-            float s32 = 0.0f, q32 = 0.0f;
-            int cnt = 0;
-#pragma unroll
-            for (int i = 0; i < 8; ++i) {
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const float v = mx_act(acc[i][j][r] + ebias[j], ACT) * esc[j] + esh[j];
-                    if (rv >= 128 || i * 16 + q4 * 4 + r < rv) {
-                        const float u = v - pv;
-                        s32 += u;
-                        q32 = fmaf(u, u, q32);
-                        ++cnt;
-                    }
-                }
-            }
-            const double pd = (double)pv, sd = (double)s32, nd = (double)cnt;
-            double s = sd + nd * pd;
-            double q = (double)q32 + 2.0 * pd * sd + nd * pd * pd;
-            s += __shfl_xor(s, 16, 64); q += __shfl_xor(q, 16, 64);
-            s += __shfl_xor(s, 32, 64); q += __shfl_xor(q, 32, 64);
+            const PooledSums t = pooled_sums16<8, false>(lane, rv, [&](int i, int r) { return mx_act(acc[i][j][r] + ebias[j], ACT) * esc[j] + esh[j]; });
             const int n = n0 + wn * 64 + j * 16 + (lane & 15);
-            if (lane < 16 && n < p.units) mx_stats_out(stats, p, b, (t0 >> 7) + wm, n, s, q);
+            if (lane < 16 && n < p.units) stats_out(stats, p, b, pool_block128().slot_of(t0 + wm * 128), n, t.s, t.q);
         }
         return;
     } else {

@@ -390,8 +390,7 @@ __global__ __launch_bounds__(768) void tdnn_mxl_kernel(MxlParams q) {
 #undef XL_PHASE
 
     if constexpr (OUT == MX_OUT_STATS) {
-        // fused StatsPooling (stats_pooling.py:231-240): per unit the sum and the sum of squares of the wave's rows, in fp32 relative
-        // to a pivot (row 0 of the wave's block: a constant column -- a dead ReLU unit -- gives exactly 0 and 0), then fp64.
+        // fused StatsPooling (stats_pooling.py:231-240): per unit the sums of the wave's 96 rows (pooled_sums16, pooled_stats.h).
         // Accumulator (i, j)[r] = row 16 i + 4 q4 + r, unit block j, column r16.
         const int rv = vend - wm * 96;               // valid rows of this wave's block
         if (rv <= 0) return;
@@ -399,40 +398,9 @@ __global__ __launch_bounds__(768) void tdnn_mxl_kernel(MxlParams q) {
         for (int j = 0; j < 4; ++j) {
             const int ul = mx_unit(wn * 4 + j, r16);
             const float esc = prm[256 + ul], esh = prm[512 + ul];
-            const float v0 = xl_act(acc[0][j][0], ACT) * esc + esh;
-            const float pv = __shfl(v0, lane & 15, 64);
-            float s32 = 0.0f, q32 = 0.0f;
-            int cnt = 0;
-#pragma unroll
-            for (int i = 0; i < 6; ++i) {
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const float v = xl_act(acc[i][j][r], ACT) * esc + esh;
-                    if (rv >= 96 || i * 16 + q4 * 4 + r < rv) {
-                        const float u = v - pv;
-                        s32 += u;
-                        q32 = fmaf(u, u, q32);
-                        ++cnt;
-                    }
-                }
-            }
-            const double pd = (double)pv, sd = (double)s32, nd = (double)cnt;
-            double s = sd + nd * pd;
-            double qq = (double)q32 + 2.0 * pd * sd + nd * pd * pd;
-            s += __shfl_xor(s, 16, 64); qq += __shfl_xor(qq, 16, 64);
-            s += __shfl_xor(s, 32, 64); qq += __shfl_xor(qq, 32, 64);
+            const PooledSums t = pooled_sums16<6, false>(lane, rv, [&](int i, int r) { return xl_act(acc[i][j][r], ACT) * esc + esh; });
             const int n = n0 + ul;
-            if (lane < 16 && n < p.units) {
-                if (p.stat_slots > 0) {              // one slot per 96-row block of the utterance, written by exactly one wave
-                    double* dst = q.stats + (((int64_t)b0 * p.stat_slots + (t0 / 96 + wm)) * 2) * p.units + n;
-                    dst[0] = s;
-                    dst[p.units] = qq;
-                } else {
-                    double* dst = q.stats + ((int64_t)b0 * 2) * p.units + n;
-                    atomicAdd(dst, s);
-                    atomicAdd(dst + p.units, qq);
-                }
-            }
+            if (lane < 16 && n < p.units) stats_out(q.stats, p, b0, pool_block96().slot_of(t0 + wm * 96), n, t.s, t.q);
         }
         return;
     } else {

@@ -62,7 +62,7 @@ struct PairFrag {
 };
 
 // STATS: fused StatsPooling (stats_pooling.py:231-240): the tile's fp64 column sums / sums of squares over its 64 rows go to `stats`
-// (one slot per 64-row block with KTF_TDNN_DET_STATS, else atomics); the layer output is never written.
+// (pool_tile64() slots with KTF_TDNN_DET_STATS, else atomics); the layer output is never written.
 template <int BK, int BN, int NB, bool STATS>
 __global__ __launch_bounds__(64 * 4 * (BN / 16 / NB)) void tdnn_x4s_kernel(TdnnParams p, double* __restrict__ stats) {
     constexpr int WN = SmallTile<BK, BN, NB>::WN, NT = SmallTile<BK, BN, NB>::NT;
@@ -118,16 +118,13 @@ __global__ __launch_bounds__(64 * 4 * (BN / 16 / NB)) void tdnn_x4s_kernel(TdnnP
                     s += red[(w_ * 2 + 0) * BN + cl];
                     q += red[(w_ * 2 + 1) * BN + cl];
                 }
-                stats_out(stats, p, b, blockIdx.y, n, s, q);
+                stats_out(stats, p, b, pool_tile64().slot_of(t0), n, s, q);
             }
         }
         return;
     }
     small_tile_store<BN, NB, false>(p, f, b, t0, n0, out_len, wm, wn, lane);
 }
-
-// KTF_TDNN_DET_STATS slots of ktf_tdnn_stats with KTF_GEMM_BF16X4: one per 64-row tile
-#define X4_SLOT_ROWS 64
 
 int tdnn_launch_x4(const TdnnParams& p, const KtfTdnnDesc* d, int64_t B, int64_t Tout, double* stats, hipStream_t st) {
     // tile width as for the fp32 small tiles (tdnn_launch_f32; the host pads W's rows to 128 here)

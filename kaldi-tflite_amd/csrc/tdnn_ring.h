@@ -150,7 +150,7 @@ __device__ __forceinline__ void ring_epilogue(f32x16 (&acc)[4][2], const TdnnPar
             s += __shfl_xor(s, 32, 64);      // the two half-waves hold the same column
             q += __shfl_xor(q, 32, 64);
             const int n = n0 + wn * 64 + j * 32 + (lane & 31);
-            if (lane < 32 && n < p.units) stats_out(stats, p, b, (t0 >> 7) + wm, n, s, q);
+            if (lane < 32 && n < p.units) stats_out(stats, p, b, pool_block128().slot_of(t0 + wm * 128), n, s, q);
         }
         return;
     }
@@ -265,48 +265,6 @@ __device__ __forceinline__ void st16(u32x4* dst, const u32x4& v) {
     else *dst = v;
 }
 
-// Fused pooling of column j of a wave's 128-row block (natural layout): sum and sum of squares over the block's first `rv` rows
-// (may be <= 0). A lane holds 32 rows of the column. Their sums are taken in fp32 RELATIVE TO A PIVOT p (row 0 of the block, the same
-// for the four lanes that share the column: a constant column -- a dead ReLU unit, a zero weight row -- gives exactly 0 and 0, not
-// fp32 cancellation noise, hence var == 0 exactly as with fp64 accumulation) and only the per-lane results go to fp64:
-// sum v = s + n p, sum v^2 = q + 2 p s + n p^2 -- 32 x 3 fp32 operations per column instead of 32 x 3 fp64 ones (the fp64 form was
-// 4.3 us per tile, a fifth of a K = 512 tile's K-loop). The wave-uniform "full block" case carries no row predicate: FULL_LOOP
-// gives it a loop of its own, else it is the first term of the predicate.
-// -> double S, Q (declared here). BIAS_ false: the accumulators were preloaded with it.
-#define POOLED_SUMS16(ACT, BIAS_, FULL_LOOP, acc, j, bias, sc, sh, rv, S, Q)                                           \
-    const float v0_ = EPI_VALUE_IF(ACT, BIAS_, acc[0][j][0], bias, sc, sh);                                            \
-    const float pv = __shfl(v0_, lane & 15, 64);          /* row 0 of the block lives in the g4 == 0 lane of this column */ \
-    float s32 = 0.0f, q32 = 0.0f;                                                                                      \
-    int cnt = 0;                                                                                                       \
-    if (FULL_LOOP && (rv) >= 128) {                                                                                    \
-        _Pragma("unroll") for (int i = 0; i < 8; ++i) {                                                                \
-            _Pragma("unroll") for (int r = 0; r < 4; ++r) {                                                            \
-                const float v = EPI_VALUE_IF(ACT, BIAS_, acc[i][j][r], bias, sc, sh);                                  \
-                const float u = v - pv;                                                                                \
-                s32 += u;                                                                                              \
-                q32 = fmaf(u, u, q32);                                                                                 \
-            }                                                                                                          \
-        }                                                                                                              \
-        cnt = 32;                                                                                                      \
-    } else {                                                                                                           \
-        _Pragma("unroll") for (int i = 0; i < 8; ++i) {                                                                \
-            _Pragma("unroll") for (int r = 0; r < 4; ++r) {                                                            \
-                const float v = EPI_VALUE_IF(ACT, BIAS_, acc[i][j][r], bias, sc, sh);                                  \
-                if ((!FULL_LOOP && (rv) >= 128) || i * 16 + (lane >> 4) * 4 + r < (rv)) {                              \
-                    const float u = v - pv;                                                                            \
-                    s32 += u;                                                                                          \
-                    q32 = fmaf(u, u, q32);                                                                             \
-                    ++cnt;                                                                                             \
-                }                                                                                                      \
-            }                                                                                                          \
-        }                                                                                                              \
-    }                                                                                                                  \
-    const double pd = (double)pv, sd = (double)s32, nd = (double)cnt;                                                  \
-    double S = sd + nd * pd;                                                                                           \
-    double Q = (double)q32 + 2.0 * pd * sd + nd * pd * pd;                                                             \
-    S += __shfl_xor(S, 16, 64); Q += __shfl_xor(Q, 16, 64);      /* the four 16-lane groups hold the same column */    \
-    S += __shfl_xor(S, 32, 64); Q += __shfl_xor(Q, 32, 64);
-
 // FLAT (tdnn_x3s_kernel's flat row tiling; row-major outputs only): tile row m is output row rowmap[m] of the (B * Tout)-row output
 // (an LDS table behind the staging image), t0 = 0 and out_len = the tile's valid rows.
 template <int ACT, bool STATS, bool FLAT = false>
@@ -322,9 +280,9 @@ __device__ __forceinline__ void ring_epilogue16(f32x4v (&acc)[8][4], const TdnnP
         const int rv = rows_valid - wm * 128;                  // valid rows of this wave's block (may be <= 0)
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            POOLED_SUMS16(ACT, true, false, acc, j, bias[j], sc[j], sh[j], rv, s, q)
+            const PooledSums t = pooled_sums16<8, false>(lane, rv, [&](int i, int r) { return EPI_VALUE(ACT, acc[i][j][r], bias[j], sc[j], sh[j]); });
             const int n = n0 + wn * 64 + j * 16 + (lane & 15);
-            if (lane < 16 && n < p.units) stats_out(stats, p, b, (t0 >> 7) + wm, n, s, q);
+            if (lane < 16 && n < p.units) stats_out(stats, p, b, pool_block128().slot_of(t0 + wm * 128), n, t.s, t.q);
         }
         return;
     }

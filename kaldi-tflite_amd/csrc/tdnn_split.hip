@@ -3,7 +3,6 @@
 // tdnn_x3s_kernel (hi / lo planes) with a header and a feed of its own (W before the length load, flat row tiles, interleaved K) and
 // the shared 16x16 epilogue.
 #include "tdnn_ring.h"
-#include "flat_stats.h"
 
 // ------------------------------------------------------------------------------------ BF16X3, 256x256 tile
 // Split-bf16 on the 256x256 structure: fp32 activations are staged RAW (256 rows x 32 k x 4 B = 128-byte rows, chunk
@@ -150,7 +149,7 @@ __global__ __launch_bounds__(512) void tdnn_x3r_kernel(TdnnParams p, int mtiles,
 #define XS_FLAT_OFF XS_LDS_BYTES                        // rs[260] | out_row[256] | t[256] | len[256]
 #define XS_FLAT_BYTES (260 * 4 + 3 * 256 * 4)
 
-// Fused pooling on flat row tiles (flat_stats.h): the finished values replace the accumulators, then one partial sum per run of an
+// Fused pooling on flat row tiles (flat_stats_runs, pooled_stats.h): the finished values replace the accumulators, then one partial sum per run of an
 // utterance's rows in the wave's 128-row block. `tab`: out_row[256] | t[256] | len[256] of the tile's rows.
 template <int ACT>
 __device__ __forceinline__ void flat_stats_epilogue(f32x4v (&acc)[8][4], const TdnnParams& p, double* __restrict__ stats, const int* tab,

@@ -444,12 +444,12 @@ class Sequential:
         act = "relu" if relu else None
         if can_pool:                                     # BatchNorm applied in the epilogue; on flat row tiles if flat_pooling
             rows = rows if self.flat_pooling else None
-            slots = (ops.flat_stats_slots(T) if rows is not None else ops.stats_slots(T, mx_flags=mxf)) if self.deterministic else 0
+            slots, slot_rows = self._pool_slots(T, rows is not None, mx_flags=mxf)
             d = l.desc(c.gemm, torch.float32, torch.float32, act=act, flags=mxf | (L.TDNN_DET_STATS if slots else 0))
             scale, shift = bn.affine_device(c.dev) if bn is not None else (None, None)
             fn, where = (ops.tdnn_mx_flat_stats, rows) if rows is not None else (ops.tdnn_mx_stats, c.lens)
             self._pool_in_epilogue(c, si, l, nxt[1], B, T, lambda sums, zero: fn(c.mxp, where, d, wh, wq, bias, scale, shift, sums, zero=zero),
-                                   slots, ops.mx_slot_rows(mxf), rows)
+                                   slots, slot_rows, rows)
             return
         nl = nxt[1] if nxt is not None and nxt[0] == "tdnn" else None
         in_route = nl is not None and nl.effective_gemm(c.gemm, nxt[2]) == c.gemm and nl.inputDim == l.units
@@ -491,11 +491,11 @@ class Sequential:
         scale, shift = bn.affine_device(c.dev) if bn is not None else (None, None)
         act = "relu" if relu else None
         if can_pool:
-            slots = (ops.flat_stats_slots(T) if rows is not None else ops.stats_slots(T)) if self.deterministic else 0
+            slots, slot_rows = self._pool_slots(T, rows is not None, gemm=c.gemm)
             d = l.desc(c.gemm, torch.bfloat16, torch.bfloat16, act=act, flags=kflag | (L.TDNN_DET_STATS if slots else 0))
             fn, where = (ops.tdnn_split_flat_stats, rows) if rows is not None else (ops.tdnn_split_stats, c.lens)
             self._pool_in_epilogue(c, si, l, nxt[1], B, T, lambda sums, zero: fn(planes, where, d, w, w_lo, bias, scale, shift, sums, zero=zero),
-                                   slots, rows=rows, pad_cols=True)
+                                   slots, slot_rows, rows, pad_cols=True)
             return
         Tout, ldy = l.outputTimesteps(T), ops.round_up(l.units, 32)
         out_lens = torch.empty_like(c.lens) if c.lens is not None and (l.padding == "VALID" or l.subsamplingFactor != 1) else None
@@ -523,13 +523,13 @@ class Sequential:
         if can_pool and (pair_in or (gemm in (L.GEMM_BF16, L.GEMM_BF16X3) and l.effective_gemm(gemm, relu) == gemm)):
             g = L.GEMM_BF16X4 if pair_in else gemm       # pooled in the epilogue of the pair / one-pass bf16 / split-bf16 kernel
             x = _gemm_rows(c.x, L.act_torch_dtype(g))
-            slots = (ops.tdnn_stats_slots(x.shape[1], g) if pair_in else ops.stats_slots(x.shape[1])) if self.deterministic else 0
+            slots, slot_rows = self._pool_slots(x.shape[1], False, gemm=g)
             w, w_lo, bias = l.device_weights(c.dev, g)
             scale, shift = bn.affine_device(c.dev) if bn is not None else (None, None)
             d = l.desc(g, L.PAIR if pair_in else x.dtype, x.dtype, act="relu" if relu else None, flags=L.TDNN_DET_STATS if slots else 0)
             self._pool_in_epilogue(c, si, l, nxt[1], x.shape[0], x.shape[1],
                                    lambda sums, zero: ops.tdnn_stats(x, c.lens, d, w, w_lo, bias, scale, shift, sums, zero=zero),
-                                   slots, ops.tdnn_slot_rows(g) if pair_in else 128, pad_cols=not pair_in)
+                                   slots, slot_rows, pad_cols=not pair_in)
             return
         g = L.GEMM_F32 if c.pooled else l.effective_gemm(gemm, relu)
         ydt = torch.float32 if (c.pooled or g != gemm) else L.act_torch_dtype(gemm)
@@ -562,7 +562,19 @@ class Sequential:
         c.set_lens(None)
         c.pooled = True
 
-    def _pool_in_epilogue(self, c, si, l, sp, B, T, launch, slots, slot_rows=128, rows=None, pad_cols=False):
+    def _pool_slots(self, T, flat, mx_flags=None, gemm=None):
+        """(slots, slot_rows) of a pooled step's fp64 partial sums over utterances of up to T rows (the slot rule of csrc/pooled_stats.h): on
+        flat row tiles, else of the f16mx kernel that `mx_flags` selects, else of ktf_tdnn_stats' kernel for `gemm`. slots is 0 -- one
+        slot, accumulated in any order -- unless self.deterministic."""
+        if flat:
+            slots, slot_rows = ops.flat_stats_slots(T), 128
+        elif mx_flags is not None:
+            slots, slot_rows = ops.stats_slots(T, mx_flags=mx_flags), ops.mx_slot_rows(mx_flags)
+        else:
+            slots, slot_rows = ops.tdnn_stats_slots(T, gemm), ops.tdnn_slot_rows(gemm)
+        return (slots if self.deterministic else 0), slot_rows
+
+    def _pool_in_epilogue(self, c, si, l, sp, B, T, launch, slots, slot_rows, rows=None, pad_cols=False):
         """[affine, relu, batchnorm] of step si -> the reducing StatsPooling `sp` behind it, inside the GEMM epilogue (the layer output is
         never written). `launch(sums, zero)` runs the layer into fp64 partial sums: `slots` per utterance of `slot_rows` rows each
         (KTF_TDNN_DET_STATS), or one slot accumulated in any order (slots 0); `rows`: the FlatRows of flat row tiles (partial sums per run

@@ -39,7 +39,7 @@ truncation is off by up to a whole one).  hi / lo planes: hi as a bf16 row; |hi 
 rounds y - hi, at most v |y|, to v^2 |y| = 2^-16 |y|); |lo| <= half a bf16 ulp of hi (y - hi is at most that, and that is a bf16 number).
 Rows at or beyond out_len[b] and columns outside [y_view, y_view + units) keep the sentinel bit for bit.
 
-Pooled sums (POOLED_SUMS16, csrc/tdnn_ring.h; flat_stats_runs, csrc/flat_stats.h).  A slot holds S = sum y, Q = sum y^2 over the
+Pooled sums (pooled_sums16 and flat_stats_runs, csrc/pooled_stats.h).  A slot holds S = sum y, Q = sum y^2 over the
 rows of one 128-row block (of the utterance, or of the flat row space) that belong to the utterance. From the rows' values:
 |sum y - sum want| <= sum dy and |sum y^2 - sum want^2| <= sum (2 |want| dy + dy^2). The 16x16 kernels sum in fp32 relative to the
 pivot p = the slot's first row: each of a column's four lanes takes 32 rows or fewer, u_i = fl(y_i - p) (one rounding), s = sum u_i

@@ -1,5 +1,5 @@
 """fp64 reference, error bounds and comparisons for the KTF_GEMM_F16MX TDNN kernels (csrc/tdnn_mx.hip, csrc/tdnn_mxl.hip, csrc/tdnn_mx_epilogue.inc,
-csrc/tdnn_mx_common.h), on top of tests/_tdnn16_ref.py (numpy only; no GPU, and no torch until a function needs the codecs of
+csrc/tdnn_mx_common.h, csrc/pooled_stats.h), on top of tests/_tdnn16_ref.py (numpy only; no GPU, and no torch until a function needs the codecs of
 kaldi_tflite_amd/mx.py): the same `case` dicts, Ref, Result, `check` vocabulary, SENTINEL and the lens pattern (T, 1, 0, T - 1, T // 2 + 1).
 
 A `case` (`case()` below) names one launch: the kernel `family` ("tile": tdnn_mx_kernel on per-utterance 256-row tiles, "flat":
