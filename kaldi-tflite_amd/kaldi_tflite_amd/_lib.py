@@ -313,6 +313,14 @@ HEAD_PROTOTYPES = {
     "ktf_head_backward": (C.c_int, [_P, _i64, _i64, _i64, _i64, _P, _P, _P, _i32, C.c_double, C.c_double, _i32, C.c_double, C.c_double, _P, _P,
                                     _P, _P, _i64, _P, _P, _P, C.c_size_t, _P]),
 }
+# name -> (restype, argtypes); mirrors include/ktf_attn.h one to one
+ATTN_PROTOTYPES = {
+    "ktf_attn_pool": (C.c_int, [_P, _i64, _i64, _i32, _i64, _P, _i32, _i64, _P, _i32, _f32, _P, _i64, _P, _P, _P]),
+    "ktf_attn_pool_backward_workspace_bytes": (_i64, [_i64, _i32, _i32]),
+    "ktf_attn_pool_backward": (C.c_int, [_P, _i64, _i64, _i32, _i64, _P, _i32, _i64, _P, _i32, _f32, _P, _P, _P, _i64, _P, _i64, _P, _i64, _P,
+                                         C.c_size_t, _P]),
+}
+ATTN_MAX_BATCH, ATTN_MAX_ROWS, ATTN_MAX_DIM = 65535, 1 << 30, 1 << 20   # ktf_attn_*: utterances, frames and channels per call
 HEAD_MAX_CENTERS, HEAD_MAX_TOPK = 8, 64   # ktf_head_*: sub-centres per class; penalised classes per row
 OPTIM_SGD, OPTIM_ADAM, OPTIM_MAX_GROUPS = 0, 1, 8   # ktf_optim_*: kind; groups per call
 EGS_THREADS, EGS_MAX_SLICES = 256, 32   # ktf_egs_*: threads of a workgroup; workgroups per batch row at most
@@ -347,7 +355,8 @@ def load():
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in (list(PROTOTYPES.items()) + list(AUGMENT_PROTOTYPES.items()) + list(RESAMPLE_PROTOTYPES.items())
                               + list(GRAD_PROTOTYPES.items()) + list(NORM_PROTOTYPES.items()) + list(LOSS_PROTOTYPES.items())
-                              + list(EGS_PROTOTYPES.items()) + list(OPTIM_PROTOTYPES.items()) + list(HEAD_PROTOTYPES.items())):
+                              + list(EGS_PROTOTYPES.items()) + list(OPTIM_PROTOTYPES.items()) + list(HEAD_PROTOTYPES.items())
+                              + list(ATTN_PROTOTYPES.items())):
         fn = getattr(lib, name)          # AttributeError = header/library mismatch
         fn.restype = res
         fn.argtypes = args

@@ -187,6 +187,48 @@ def stats_pooling(x, lens=None, include_std=True, epsilon=1e-10, input_period=1)
     return _StatsPooling.apply(x.to(torch.float32), _lens(lens, x.shape[0], x.device), bool(include_std), float(epsilon), int(input_period))
 
 
+class _AttentiveStatsPooling(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, e, lens, include_std, epsilon):
+        B, T, D = x.shape
+        H = e.shape[2]
+        x, e = x.contiguous(), e.contiguous()
+        out = torch.empty((B, 2 * D if include_std else D), dtype=torch.float32, device=x.device)
+        norm = torch.empty((B, H, 2), dtype=torch.float64, device=x.device)
+        stats = torch.empty((B, 2, D), dtype=torch.float64, device=x.device)
+        ops.attn_pool(x, e, lens, include_std, epsilon, out, norm, stats)
+        ctx.save_for_backward(x, e, lens, norm, stats)           # of the activation's size: x and e alone
+        ctx.cfg = (include_std, epsilon)
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        x, e, lens, norm, stats = ctx.saved_tensors
+        include_std, epsilon = ctx.cfg
+        dx, de = torch.empty_like(x), torch.empty_like(e)
+        ops.attn_pool_backward(x, e, lens, include_std, epsilon, norm, stats, gout.to(torch.float32).contiguous(), dx, de,
+                               ops.attn_pool_backward_workspace(x.shape[0], x.shape[2], e.shape[2], x.device))
+        return dx, de, None, None, None
+
+
+def attentive_stats_pooling(x, e, lens=None, include_std=True, epsilon=1e-10):
+    """Attentive statistics pooling (include/ktf_attn.h), differentiable in x and e: x (B, T, D) and the attention logits e (B, T, H)
+    fp32 on the GPU, 1 <= H <= D and D % H == 0 (channel c is weighted by head c // (D / H)) -> (B, D or 2 D): the mean and
+    sqrt(relu(E[x^2] - mean^2) + epsilon) of x under w = softmax of e over the rows below each utterance's length. For the backward
+    pass it keeps x, e, lens and two small fp64 tensors ((B, H, 2) and (B, 2, D)), nothing else of the activation's size."""
+    if not (isinstance(x, torch.Tensor) and isinstance(e, torch.Tensor)) or x.dim() != 3 or e.dim() != 3 or x.shape[:2] != e.shape[:2]:
+        raise ValueError(f"expected x (B, T, D) and e (B, T, H), got shapes {tuple(getattr(x, 'shape', ()))} and {tuple(getattr(e, 'shape', ()))}")
+    D, H = x.shape[2], e.shape[2]
+    if H < 1 or H > D or D % H:
+        raise ValueError(f"the {H} heads of e must divide the {D} channels of x")
+    if not 0.0 <= float(epsilon) < float("inf"):
+        raise ValueError(f"epsilon must be finite and not negative, got {epsilon!r}")
+    _on_gpu(x, "x")
+    _on_gpu(e, "e")
+    return _AttentiveStatsPooling.apply(x.to(torch.float32), e.to(torch.float32), _lens(lens, x.shape[0], x.device), bool(include_std),
+                                        float(epsilon))
+
+
 def batch_norm(x, lens, moving_mean, moving_var, gamma, momentum=0.99, epsilon=0.001, training=False):
     """BatchNorm as the project mirrors it (keras BatchNormalization(center=False, scale=True)): y = gamma (x - mean) / sqrt(var +
     epsilon) per feature. Training: mean and (biased) variance over the valid rows of the whole batch, and
@@ -271,7 +313,7 @@ def relu_batch_norm(z, lens, moving_mean, moving_var, gamma, momentum=0.99, epsi
 
 class TrainableSequential(torch.nn.Module):
     """A `ktf.models.Sequential` (or an XvectorExtractor, whose TDNN stack is taken) as a torch module: TDNN -> ReLU -> BatchNorm ...
-    -> reducing StatsPooling -> TDNN (context [0]) ... Parameters start from the layers' current weights; `forward(feats, lens)`
+    -> reducing StatsPooling or AttentiveStatsPooling (its two affines and `attentive_stats_pooling`) -> TDNN (context [0]) ... Parameters start from the layers' current weights; `forward(feats, lens)`
     returns the last layer's output -- (B, T_out, units), or (B, units) behind the pooling -- for `ClassifierHead` (below) or a head and a loss written in torch;
     `export()` writes parameters and moving statistics back into the layers. The layers must be built (a Sequential with an Input, or
     one that has run or loaded weights). gemm: the mode of every TDNN GEMM, forward and backward ("f32", "bf16", "bf16x3": `tdnn_affine`),
@@ -294,7 +336,7 @@ class TrainableSequential(torch.nn.Module):
         pooled = False
         f32 = lambda a: torch.nn.Parameter(torch.as_tensor(a, dtype=torch.float32).to(dev).contiguous().clone())  # noqa: E731
         for l in self.seq.layers:
-            if not isinstance(l, (_layers.TDNN, _layers.ReLU, _layers.BatchNorm, _layers.StatsPooling)):
+            if not isinstance(l, (_layers.TDNN, _layers.ReLU, _layers.BatchNorm, _layers.StatsPooling, _layers.AttentiveStatsPooling)):
                 raise NotImplementedError(f"layer '{l.name}' ({type(l).__name__}) has no gradient in ktf.autograd")
             if not l.built and not isinstance(l, (_layers.ReLU, _layers.StatsPooling)):
                 raise ValueError(f"layer '{l.name}' is not built: give the Sequential an Input, run it or load its weights first")
@@ -321,6 +363,17 @@ class TrainableSequential(torch.nn.Module):
                                               "has no gradient in ktf.autograd")
                 pooled = True
                 self.steps.append(("stats", l, -1))
+            elif isinstance(l, _layers.AttentiveStatsPooling):
+                act = l.attentionActivation.lower() if isinstance(l.attentionActivation, str) else l.attentionActivation
+                if pooled or act not in ("tanh", "relu"):
+                    raise NotImplementedError(f"layer '{l.name}' (AttentiveStatsPooling with activation {l.attentionActivation!r}, or a "
+                                              "second pooling) has no gradient in ktf.autograd")
+                pooled = True
+                at = len(self.params)
+                for t in (l.hidden, l.logits):                     # W1 [u, k, d], b1, W2 [u, k, d], b2
+                    self.params.append(f32(t.kernel[0].transpose(2, 0, 1)))
+                    self.params.append(f32(t.bias))
+                self.steps.append(("attn", l, at))
             else:
                 self.steps.append(("relu", l, -1))
 
@@ -350,6 +403,12 @@ class TrainableSequential(torch.nn.Module):
             elif kind == "bn":
                 x = batch_norm(x, None if pooled else lens, getattr(self, f"moving_mean_{at}"), getattr(self, f"moving_var_{at}"),
                                self.params[at], l.momentum, l.epsilon, self.training)
+            elif kind == "attn":
+                h = tdnn_affine(x, self.params[at], self.params[at + 1], [0], lens, gemm=self.gemm)
+                h = torch.tanh(h) if l.attentionActivation.lower() == "tanh" else torch.relu(h)
+                e = tdnn_affine(h, self.params[at + 2], self.params[at + 3], [0], lens, gemm=self.gemm)
+                x = attentive_stats_pooling(x, e, lens, l.includeStd, l.epsilon)
+                pooled = True
             else:
                 x = stats_pooling(x, lens, l.includeStd, l.epsilon, l.inputPeriod)
                 pooled = True
@@ -365,6 +424,9 @@ class TrainableSequential(torch.nn.Module):
             elif kind == "bn":
                 l.set_weights([self.params[at].detach().cpu().numpy(), getattr(self, f"moving_mean_{at}").cpu().numpy(),
                                getattr(self, f"moving_var_{at}").cpu().numpy()], fmt="tensorflow")
+            elif kind == "attn":
+                w1, b1, w2, b2 = (self.params[at + k].detach().cpu().numpy() for k in range(4))
+                l.set_weights([w1[:, 0, :].T, b1, w2[:, 0, :].T, b2], fmt="tensorflow")
         return self.seq
 
 

@@ -1165,6 +1165,122 @@ class StatsPooling(Layer):
         return self.reduce_all(x, D).reshape(B, 1, od)
 
 
+class AttentiveStatsPooling(Layer):
+    """Attentive statistics pooling (Okabe et al. 2018): e = W2^T act(W1^T h + b1) + b2 per frame, a softmax of e over the frames of
+    the utterance, and the weighted mean (+ standard deviation) of h under it (include/ktf_attn.h). `heads` = 1: one weight per frame;
+    1 < heads < D: channel c is weighted by head c // (D / heads); heads = D: one weight per frame and channel. The two affines are
+    context-[0] TDNN layers held by this layer; the weights in keras order are [W1 (D, A), b1 (A,), W2 (A, H), b2 (H,)]."""
+
+    def __init__(self, attention_units, heads=1, include_std=True, epsilon=1e-10, attention_activation="tanh", name=None, **kwargs):
+        super().__init__(trainable=True, name=name, **kwargs)
+        self.attentionUnits, self.heads = int(attention_units), int(heads)
+        if self.attentionUnits < 1 or self.heads < 1:
+            raise ValueError("'attention_units' and 'heads' must be >= 1")
+        if float(epsilon) < 0 or not np.isfinite(float(epsilon)):
+            raise ValueError("'epsilon' must be finite and >= 0")
+        self.includeStd = bool(include_std)
+        self.epsilon = float(epsilon)
+        self.attentionActivation = attention_activation
+        self.reduce = True             # the whole utterance, as a StatsPooling(reduce_time_axis=True): the fused runner's tail treats it alike
+        self.hidden = TDNN(self.attentionUnits, [0], activation=attention_activation, name=self.name + ".hidden")
+        self.logits = TDNN(self.heads, [0], name=self.name + ".logits")
+        self.gemm = "f32"
+        self.batchAxis, self.timeAxis, self.featAxis = 0, 1, -1
+
+    @property
+    def _version(self):
+        return self.hidden._version + self.logits._version
+
+    def build(self, input_shape):
+        D = input_shape[self.featAxis]
+        if D % self.heads:
+            raise ValueError(f"'heads' = {self.heads} does not divide the {D} input channels")
+        self.inputDim = D
+        if not self.hidden.built or self.hidden.inputDim != D:
+            self.hidden.build((None, None, D))
+        if not self.logits.built:
+            self.logits.build((None, None, self.attentionUnits))
+        self.built = True
+
+    def compute_output_shape(self, input_shape):
+        D = input_shape[self.featAxis]
+        return (input_shape[self.batchAxis], 1, 2 * D if self.includeStd else D)
+
+    def get_config(self):
+        c = super().get_config()
+        c.update({"attention_units": self.attentionUnits, "heads": self.heads, "include_std": self.includeStd, "epsilon": self.epsilon,
+                  "attention_activation": self.attentionActivation})
+        return c
+
+    def get_weights(self):
+        if not (self.hidden.built and self.logits.built):
+            return []
+        return [self.hidden.kernel[0, 0], self.hidden.bias, self.logits.kernel[0, 0], self.logits.bias]
+
+    def set_weights(self, weights, fmt="tensorflow"):
+        """[W1, b1, W2, b2]; fmt "tensorflow": W1 (D, A), W2 (A, H) as get_weights() gives them, "kaldi": (A, D) and (H, A)."""
+        fmt = fmt.lower()
+        if fmt not in ["kaldi", "tensorflow"]:
+            raise ValueError(f"expected 'fmt' to be either 'kaldi' or 'tensorflow', got {fmt}")
+        if len(weights) != 4:
+            raise ValueError(f"expected a weight list of length 4, got {len(weights)}")
+        w1, b1, w2, b2 = (np.asarray(w, np.float32) for w in weights)
+        if fmt == "kaldi":
+            w1, w2 = w1.T, w2.T
+        A, H = self.attentionUnits, self.heads
+        D = self.inputDim if self.built else (w1.shape[0] if w1.ndim == 2 else -1)
+        for name, w, shape in (("W1", w1, (D, A)), ("b1", b1.reshape(-1), (A,)), ("W2", w2, (A, H)), ("b2", b2.reshape(-1), (H,))):
+            if w.shape != shape:
+                raise ValueError(f"{name}: expected shape {shape}, got {w.shape}")
+        if D % H:
+            raise ValueError(f"'heads' = {H} does not divide the {D} input channels")
+        self.hidden.set_weights([w1[None, None], b1], fmt="tensorflow")
+        self.logits.set_weights([w2[None, None], b2], fmt="tensorflow")
+        self.inputDim = D
+        self.built = True
+
+    @staticmethod
+    def attention_gemm(gemm):
+        """The arithmetic of the two attention affines in a call of mode `gemm`: their output goes through exp, so they never run in
+        one-pass bf16 or f16mx -- fp32 for an fp32 call, split-bf16 for every other."""
+        return L.GEMM_F32 if gemm == L.GEMM_F32 else L.GEMM_BF16X3
+
+    def attend(self, x, lens=None, gemm=L.GEMM_F32, scratch=None):
+        """x (B, T, D) fp32 rows the GEMM can read (TDNN.forward) -> the logits e (B, T, H), a view of a buffer whose pad columns are
+        finite. `scratch(role, shape, dtype)`: where the two outputs go (default: fresh zeroed tensors)."""
+        B, T, _ = x.shape
+        A, H = self.attentionUnits, self.heads
+        lda, lde = ops.round_up(A, 32), ops.round_up(H, 8)
+        new = scratch or (lambda role, shape, dtype: torch.zeros(shape, dtype=dtype, device=x.device))
+        g = self.attention_gemm(gemm)
+        h = self.hidden.forward(x, lens=lens, gemm=g, ldy=lda, out=new("attn_hidden", (B, T, lda), torch.float32))
+        e = self.logits.forward(h[:, :, :A], lens=lens, gemm=g, ldy=lde, out=new("attn_logits", (B, T, lde), torch.float32))
+        return e[:, :, :H]
+
+    def pool(self, x, lens=None, gemm=L.GEMM_F32, out=None, scratch=None):
+        """x as in attend() -> (B, D or 2 D) fp32 in `out` (B, ld_out) if given. No host synchronisation."""
+        B, T, D = x.shape
+        if D != self.inputDim:
+            raise ValueError(f"expected input feature dim {self.inputDim}, got {D}")
+        od = 2 * D if self.includeStd else D
+        if out is None:
+            out = torch.empty((B, od), dtype=torch.float32, device=x.device)
+        e = self.attend(x, lens, gemm, scratch)
+        new = scratch or (lambda role, shape, dtype: torch.empty(shape, dtype=dtype, device=x.device))
+        norm = new("attn_norm", (B, self.heads, 2), torch.float64)
+        ops.attn_pool(x, e, lens, self.includeStd, self.epsilon, out, norm, None, D=D, H=self.heads)
+        return out
+
+    def call(self, inputs):
+        x = inputs
+        if x.dim() != 3:
+            raise ValueError(f"expected a (batch, time, feat) input, got shape {tuple(x.shape)}")
+        B, T, D = x.shape
+        gemm = _GEMM[self.gemm]
+        rows = self.hidden.prepare_input(x.to(torch.float32), self.attention_gemm(gemm))
+        return self.pool(rows[:, :, :D], None, gemm).reshape(B, 1, -1)
+
+
 # =============================================================================== plda
 class PLDA(Layer):
     """layers/plda/plda.py:24 — PLDA transform + pairwise log-likelihood-ratio scoring."""

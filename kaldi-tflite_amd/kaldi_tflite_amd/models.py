@@ -20,7 +20,7 @@ from . import _lib as L
 from . import ops
 from ._host import is_real
 from .io import KaldiNnet3Reader, ReadKaldiArray
-from .layers import TDNN, BatchNorm, CMVN, Framing, MFCC, ReLU, StatsPooling, VAD, _GEMM, WEIGHTS_EPOCH, _f32_rows
+from .layers import TDNN, AttentiveStatsPooling, BatchNorm, CMVN, Framing, MFCC, ReLU, StatsPooling, VAD, _GEMM, WEIGHTS_EPOCH, _f32_rows
 from .mx import Planes
 
 
@@ -40,14 +40,15 @@ _LAYER_KINDS = (
     (("relu",), ReLU, "{}.relu", False),
     (("batchnorm", "bn"), BatchNorm, "{}.batchnorm", False),
     (("stats", "stats_extraction", "stats_pooling"), StatsPooling, "{}", True),
+    (("attentive_stats", "attentive_stats_pooling"), AttentiveStatsPooling, "{}", True),
 )
 _KIND_OF = {alias: row for row in _LAYER_KINDS for alias in row[0]}
 
 
 def cfg2layers(layerCfg):
     """One entry of `model_config.layers` -> the layers it stands for, in order. `type` is a kind or a list of kinds
-    ("affine" | "tdnn", "relu", "batchnorm" | "bn", "stats" | "stats_extraction" | "stats_pooling"); the entry's `cfg`
-    holds the keyword arguments of its parametrised layer. KeyError without a `type`, ValueError for an unknown one."""
+    ("affine" | "tdnn", "relu", "batchnorm" | "bn", "stats" | "stats_extraction" | "stats_pooling", "attentive_stats" |
+    "attentive_stats_pooling"); the entry's `cfg` holds the keyword arguments of its parametrised layer. KeyError without a `type`, ValueError for an unknown one."""
     kinds = layerCfg.get("type") or []
     if isinstance(kinds, str):
         kinds = [kinds]
@@ -258,7 +259,7 @@ class Sequential:
     def weights_signature(self):
         """Changes whenever a TDNN / BatchNorm layer's weights change (set_weights, a re-build): captured graphs
         are tied to it."""
-        return tuple((id(l), l._version) for l in self.layers if isinstance(l, (TDNN, BatchNorm)))
+        return tuple((id(l), l._version) for l in self.layers if isinstance(l, (TDNN, BatchNorm, AttentiveStatsPooling)))
 
     def get_layer(self, name):
         for l in self.layers:
@@ -295,6 +296,10 @@ class Sequential:
                 i = j
             elif isinstance(l, StatsPooling) and l.reduce:
                 steps.append(("stats", l))
+                pooled = True
+                i += 1
+            elif isinstance(l, AttentiveStatsPooling) and not pooled:
+                steps.append(("attn", l))
                 pooled = True
                 i += 1
             elif isinstance(l, (ReLU, BatchNorm)):
@@ -358,7 +363,7 @@ class Sequential:
     def _tail_step(self, steps):
         """Index of the last step if it is a plain affine (context [0], no activation / BatchNorm) right after a reducing
         StatsPooling -- the tail XvectorExtractor fuses with its LDA / length-norm step -- else -1."""
-        if len(steps) >= 2 and steps[-1][0] == "tdnn" and steps[-2][0] == "stats":
+        if len(steps) >= 2 and steps[-1][0] == "tdnn" and steps[-2][0] in ("stats", "attn"):
             _, l, relu, bn = steps[-1]
             if (not relu and bn is None and l.activation in (None, "linear") and l.kernelWidth == 1 and l.padding == "SAME"
                     and l.subsamplingFactor == 1 and l.units <= 512 and l.inputDim <= 3072):
@@ -414,6 +419,8 @@ class Sequential:
                 self._step_generic(c, si, st, nxt, can_pool, out_role)
             elif st[0] == "stats":
                 self._step_stats(c, si, st[1])
+            elif st[0] == "attn":
+                self._step_attn(c, si, st[1])
             else:
                 c.x = st[1](c.x.to(torch.float32).contiguous())
         if c.pooled:
@@ -532,7 +539,7 @@ class Sequential:
                                    slots, slot_rows, pad_cols=not pair_in)
             return
         g = L.GEMM_F32 if c.pooled else l.effective_gemm(gemm, relu)
-        ydt = torch.float32 if (c.pooled or g != gemm) else L.act_torch_dtype(gemm)
+        ydt = torch.float32 if (c.pooled or g != gemm or (nxt is not None and nxt[0] == "attn")) else L.act_torch_dtype(gemm)
         pair_ok = lambda t, r: t.activation in (None, "linear") or (t.activation == "relu" and not r)  # noqa: E731
         pair_out = (c.pairs and not c.pooled and g == L.GEMM_F32 and pair_ok(l, relu) and nxt is not None and nxt[0] == "tdnn"
                     and pair_ok(nxt[1], nxt[2]) and nxt[1].inputDim == l.units)
@@ -559,6 +566,20 @@ class Sequential:
         if si + 1 == c.tail_at:                          # (lens: KTF_TAIL_SKIP_EMPTY of the short-utterance pass reads them)
             c.defer(sp, B, D, T, pooled=sbuf)
         c.x = sbuf[:, :od].unsqueeze(0)                  # (1, B, od): the pooled vectors form ONE B-row matrix
+        c.set_lens(None)
+        c.pooled = True
+
+    def _step_attn(self, c, si, ap):
+        """An AttentiveStatsPooling: two affines over the fp32 frame-level rows for the logits (fp32 in an fp32 call, split-bf16 in
+        every other: AttentiveStatsPooling.attention_gemm), then the pooling kernels; from there on as _step_stats."""
+        x = _gemm_rows(c.x, torch.float32)
+        B, T, D = x.shape
+        od = 2 * D if ap.includeStd else D
+        sbuf = c.ws.get("pooled", (B, ops.round_up(od, 32)), torch.float32, c.dev)
+        ap.pool(x, c.lens, c.gemm, out=sbuf, scratch=lambda role, shape, dtype: c.ws.get(role, shape, dtype, c.dev))
+        if si + 1 == c.tail_at:
+            c.defer(ap, B, D, T, pooled=sbuf)
+        c.x = sbuf[:, :od].unsqueeze(0)
         c.set_lens(None)
         c.pooled = True
 

@@ -1652,6 +1652,71 @@ def head_backward(z, K, labels, inv_x, inv_w, kind, margin, scale, topk, penalty
     return dz, dinv_x, dinv_w
 
 
+# ----------------------------------------------------------------------------- attentive statistics pooling (include/ktf_attn.h)
+def _attn_rows(name, t):
+    """(pointer, row stride) of a (B, T, ld) fp32 operand of the attentive pooling."""
+    if t.dim() != 3 or t.dtype != torch.float32:
+        raise ValueError(f"{name}: a 3-D fp32 tensor is expected, got {t.dtype} {tuple(t.shape)}")
+    _need_rows(name, t)
+    return L.ptr(t), (t.stride(1) if t.shape[1] else t.shape[2])
+
+
+def _attn_mat(name, t, dtype=torch.float32):
+    if t.dim() != 2 or t.dtype != dtype:
+        raise ValueError(f"{name}: a 2-D {dtype} tensor is expected, got {t.dtype} {tuple(t.shape)}")
+    _need_rows(name, t)
+    return L.ptr(t), _ld(t)
+
+
+def _attn_sizes(x, e, D, H):
+    if x.dim() != 3 or e.dim() != 3 or x.shape[:2] != e.shape[:2]:
+        raise ValueError(f"x (B, T, ldx) and e (B, T, lde) with the same B and T are expected, got {tuple(x.shape)} and {tuple(e.shape)}")
+    D = x.shape[2] if D is None else int(D)
+    H = e.shape[2] if H is None else int(H)
+    return x.shape[0], x.shape[1], D, H
+
+
+def attn_pool(x, e, lens, include_std, eps, out, norm, stats=None, D=None, H=None):
+    """x (B, T, ldx) and e (B, T, lde) fp32 rows with D channels / H heads (default: every column), lens (B,) int32 or None; out
+    (B, ld_out) fp32, norm (B, H, 2) fp64 and stats (B, 2, D) fp64 (or None) preallocated."""
+    B, T, D, H = _attn_sizes(x, e, D, H)
+    if B == 0:
+        return out, norm, stats
+    px, ldx = _attn_rows("x", x)
+    pe, lde = _attn_rows("e", e)
+    po, ldo = _attn_mat("out", out)
+    for name, t in (("lens", lens), ("norm", norm), ("stats", stats)):
+        _need_dense(name, t)
+    _call("ktf_attn_pool", x.device, px, B, T, D, ldx, pe, H, lde, L.ptr(lens), int(bool(include_std)), float(eps), po, ldo, L.ptr(norm),
+          L.ptr(stats))
+    return out, norm, stats
+
+
+def attn_pool_backward_workspace(B, D, H, device):
+    """The workspace attn_pool_backward takes for B utterances of D channels and H heads."""
+    return _workspace("ktf_attn_pool_backward_workspace_bytes", int(B), int(D), int(H), device=device)
+
+
+def attn_pool_backward(x, e, lens, include_std, eps, norm, stats, gout, dx, de, workspace, D=None, H=None):
+    """The gradient of attn_pool's out: gout (B, ld_gout) -> dx (B, T, ld_dx) and de (B, T, ld_de) preallocated, every element
+    written; norm and stats are the forward call's."""
+    B, T, D, H = _attn_sizes(x, e, D, H)
+    if B == 0 or T == 0:
+        return dx, de
+    px, ldx = _attn_rows("x", x)
+    pe, lde = _attn_rows("e", e)
+    pg, ldg = _attn_mat("gout", gout)
+    pdx, ld_dx = _attn_rows("dx", dx)
+    pde, ld_de = _attn_rows("de", de)
+    if dx.shape[:2] != x.shape[:2] or de.shape[:2] != e.shape[:2]:
+        raise ValueError(f"dx {tuple(dx.shape)} / de {tuple(de.shape)} do not have the rows of x {tuple(x.shape)}")
+    for name, t in (("lens", lens), ("norm", norm), ("stats", stats), ("workspace", workspace)):
+        _need_dense(name, t)
+    _call("ktf_attn_pool_backward", x.device, px, B, T, D, ldx, pe, H, lde, L.ptr(lens), int(bool(include_std)), float(eps), L.ptr(norm),
+          L.ptr(stats), pg, ldg, pdx, ld_dx, pde, ld_de, L.ptr(workspace), 0 if workspace is None else workspace.numel())
+    return dx, de
+
+
 # ----------------------------------------------------------------------------- training examples (include/ktf_egs.h)
 EGS_DTYPES = {torch.float32: L.KTF_F32, torch.float16: L.KTF_F16}
 
