@@ -30,6 +30,12 @@
 // LDS once; tiles none of whose rows is clamped (INTERIOR: three in four on 998-frame utterances, all tiles of a single-context layer) run a
 // K-loop without a vector instruction for addresses; the A-row DMAs go out in the LDS-latency gap behind each K-step's barrier, every other
 // DMA alone behind an MFMA group (docs/lab_notes_r6.md: what each of these is worth, and what was tried and is not here).
+// Which layer takes which form of the tile (mx_launch decides; the x-vector network in brackets):
+//   per-utterance tiles                 fp32 row output, VALID padding, subsampling: one K-loop, every row clamped per K-step
+//   FLAT, several contexts or an offset [tdnn1-3] the K-step table; interior tiles take the K-loop without address arithmetic, the others the clamped one
+//   FLAT + SINGLE, one context at 0     [tdnn4, tdnn5 + pooling] the interior K-loop alone, compiled without the table, the clamped DMA form and the
+//                                       row state -- 223-233 registers where the general form needs 246-256; the registers take M's first nineteen
+//                                       fragment reads, issued under the last four MFMA groups of F3 (docs/lab_notes_r7.md)
 //
 // Replaces: layers/tdnn/tdnn.py:251-280 (+ keras ReLU, batchnorm.py:78-88, stats_pooling.py:211-240 when fused).
 #include "tdnn_mx_common.h"
@@ -120,10 +126,16 @@ extern "C" int ktf_mx_planes(const float* src, int64_t B, int64_t T, int32_t D, 
 // belong to several utterances: a thread keeps (frame, last frame, first record) of the rows it fetches, context offsets clamp against
 // the row's own utterance, and the epilogue scatters rows through the same table. `mtiles` carries B. Same operands into the same MFMAs
 // in the same order: the planes are bit-identical to the per-utterance tiles'.
-template <int ACT, int OUT, bool PADK, bool FLAT = false>
+// SINGLE (a flat-tile layer with ONE context at offset 0: tdnn4, tdnn5 + pooling): known when the launcher picks the kernel, so the tile is
+// compiled with the interior K-loop alone -- K-step k is chunk k at offset 0, its base one running scalar (+ k * T); no K-step table (no LDS
+// region, no writes, no reads, no readfirstlane block), no clamped DMA behind the first stage, no row state live across the loop. The registers
+// that frees take the M-phase's first fragments, read under the last MFMA groups of F3 (below). Same operands into the same MFMAs in the same
+// order as the general form.
+template <int ACT, int OUT, bool PADK, bool FLAT = false, bool SINGLE = false>
 __device__ __forceinline__ void mx_tile(const MxParams& p, const int id, int mtiles, int ntiles, int gtiles, double* __restrict__ stats,
                                         unsigned char* rsm) {
     static_assert(!FLAT || OUT != MX_OUT_F32, "flat row tiles: plane output or fused pooling");
+    static_assert(!SINGLE || FLAT, "the single-context form is a flat-tile form");
     // Every kernel argument the tile needs before its first DMA is consumed in ONE place: the compiler otherwise loads the 240-byte parameter
     // block in five or six dependent pieces (s_load, wait, s_load, wait ...), each a trip to the scalar cache in front of the first DMA
     // issue -- a microsecond of the ~2.5 a tile spends before its first MFMA. One batch of scalar loads, one wait; placed BEHIND the tile's
@@ -235,6 +247,11 @@ __device__ __forceinline__ void mx_tile(const MxParams& p, const int id, int mti
     int kb[5], ko[5];                                     // table entries of K-steps 4 ss .. 4 ss + 4 (scalar registers)
     kb[0] = MX_KQ_BIAS;
     ko[0] = MX_CTX(0);
+    // SINGLE: no table entries -- K-step 4 ss + e is chunk 4 ss + e at offset 0: (the super-step's running chunk base) + e * (records per chunk)
+    [[maybe_unused]] int kq_ss = MX_KQ_BIAS, tq_ss = (int)p.T;
+#define MX_KSO(e_) (SINGLE ? kq_ss + (e_) * tq_ss : kb[e_] + ko[e_])
+    // ... and -- interior tiles -- of the lane's own rows
+    [[maybe_unused]] const unsigned va0 = (a_ub[0] + (unsigned)a_row[0]) * 64u + a_cb[0], va1 = (a_ub[1] + (unsigned)a_row[1]) * 64u + a_cb[1];
     // one 16-byte-per-lane DMA of the half stage of K-step ks_ (table entry e_ of the super-step): n_ = 0, 1 the A image (rows 0-127 / 128-255);
     // _E: rows clamped to their utterance, _I: interior tiles (below)
 #define MX_DMA_A_E(ks_, e_, n_)                                                                                        \
@@ -247,19 +264,23 @@ __device__ __forceinline__ void mx_tile(const MxParams& p, const int id, int mti
     }
 #define MX_DMA_A_I(ks_, e_, n_)                                                                                        \
     __builtin_amdgcn_raw_ptr_buffer_load_lds(r_xh, MX_LDS_AT(wave_k, ((ks_) & 1) * MX_STAGE + (n_) * 8192), 16, (n_) ? va1 : va0, \
-                                             (kb[e_] + ko[e_]) << 6, 0, 0);
+                                             MX_KSO(e_) << 6, 0, 0);
 #define MX_DMA_A(ks_, e_, n_) { if constexpr (INTERIOR) MX_DMA_A_I(ks_, e_, n_) else MX_DMA_A_E(ks_, e_, n_) }
     // ... n_ = 0, 1 the halves of the W image
 #define MX_DMA_W(ks_, n_)                                                                                              \
     __builtin_amdgcn_raw_ptr_buffer_load_lds(r_wh, MX_LDS_AT(wave_k, ((ks_) & 1) * MX_STAGE + MX_TILE + (n_) * 8192), 16, vw, \
                                              (ks_) * MX_TILE + (n_) * 8192, 0, 0);
-    MX_DMA_W(0, 0) MX_DMA_W(0, 1) MX_DMA_A_E(0, 0, 0) MX_DMA_A_E(0, 0, 1)
+    MX_DMA_W(0, 0) MX_DMA_W(0, 1)
+    if constexpr (SINGLE) { MX_DMA_A_I(0, 0, 0) MX_DMA_A_I(0, 0, 1) } else { MX_DMA_A_E(0, 0, 0) MX_DMA_A_E(0, 0, 1) }
     const __amdgpu_buffer_rsrc_t r_xl4 = mx_rsrc_pinned(p.xl4 + (ub - MX_KQ_BIAS) * 16);
     const __amdgpu_buffer_rsrc_t r_x4 = mx_rsrc_pinned(p.x4 + (ub - MX_KQ_BIAS) * 16);
     const __amdgpu_buffer_rsrc_t r_xs = mx_rsrc_pinned(p.xs + (ub - MX_KQ_BIAS) * 4);
-    if constexpr (FLAT) {
+    // (SINGLE: one context at offset 0 -- no row is ever clamped; rows beyond the batch's last read row 0 of the plane and are not stored)
+    if constexpr (FLAT && !SINGLE) {
         if (p.nctx == 1 && MX_CTX(0) == 0) {
-            interior = true;      // one context at offset 0: no row is ever clamped (rows beyond the batch's last read row 0 of the plane and are not stored)
+            // (mx_launch sends these layers to SINGLE; the test stays because without it the allocator gives the pooled ReLU instantiation
+            // two more spilled registers -- docs/lab_notes_r7.md)
+            interior = true;
         } else if (out_len == 256) {
             const i32x4 e0 = flat_row(0), e1 = flat_row(255);
             interior = __builtin_amdgcn_readfirstlane(e0.w) == __builtin_amdgcn_readfirstlane(e1.w) &&
@@ -267,8 +288,6 @@ __device__ __forceinline__ void mx_tile(const MxParams& p, const int id, int mti
                        __builtin_amdgcn_readfirstlane(e1.y) + MX_CTX(p.nctx - 1) <= __builtin_amdgcn_readfirstlane(e1.z) - 1;
         }
     }
-    // ... and -- interior tiles -- of the lane's own rows
-    [[maybe_unused]] const unsigned va0 = (a_ub[0] + (unsigned)a_row[0]) * 64u + a_cb[0], va1 = (a_ub[1] + (unsigned)a_row[1]) * 64u + a_cb[1];
     [[maybe_unused]] const unsigned vs16 = (s_ub + (unsigned)s_row) * 16u, vs4 = (s_ub + (unsigned)s_row) * 4u;
 
     const int sa_k0 = (int)(unsigned)(size_t)(lds_ptr_t*)(rsm + (wave & 3) * 1024 + (wave >> 2) * 4096);     // side A: the wave's pieces of the e2m1 images (+ plane, K block pair)
@@ -336,13 +355,15 @@ __device__ __forceinline__ void mx_tile(const MxParams& p, const int id, int mti
                 else reinterpret_cast<float*>(prm_w + 2048)[lane] = 0.0f;
             }
         }
-        for (int k = tid; k < nkp + 4; k += 512) {        // the K-step table (the first stage is on its way); first read in F2 of super-step 0
-            const int kk = k + 1 < p.nk ? k + 1 : 0;
-            const int ch = kk / p.nctx, ci = kk - ch * p.nctx;
-            tkb[k] = ch * (int)p.T + MX_KQ_BIAS;
-            tko[k] = MX_CTX(ci);
+        if constexpr (!SINGLE) {
+            for (int k = tid; k < nkp + 4; k += 512) {    // the K-step table (the first stage is on its way); first read in F2 of super-step 0
+                const int kk = k + 1 < p.nk ? k + 1 : 0;
+                const int ch = kk / p.nctx, ci = kk - ch * p.nctx;
+                tkb[k] = ch * (int)p.T + MX_KQ_BIAS;
+                tko[k] = MX_CTX(ci);
+            }
         }
-        {                                                 // K-steps 1 .. 4 directly (scalar, once per tile): no barrier in front of the loop
+        if constexpr (!SINGLE) {                          // K-steps 1 .. 4 directly (scalar, once per tile): no barrier in front of the loop
             int ch = 0, ci = 0;
 #pragma unroll
             for (int e = 1; e <= 4; ++e) {
@@ -364,6 +385,53 @@ __device__ __forceinline__ void mx_tile(const MxParams& p, const int id, int mti
             // loop-invariant scalar register; laundered per DMA it cost a copy and an add more each)
             int wave_k = wave_k0, sa_k = sa_k0, sa_ks = sa_ks0;
             asm volatile("" : "+s"(wave_k), "+s"(sa_k), "+s"(sa_ks));
+            if constexpr (SINGLE) asm volatile("" : "+s"(tq_ss));       // (its multiples are made per DMA, not kept in scalar registers of their own)
+            // M's resident B fragments and the first row block's A fragments, and the LDS addresses they are read from (made in m_addr below).
+            // General form: all nineteen reads at the head of M. SINGLE: under the last four MFMA groups of F3 (the side areas are complete
+            // since F3's barrier), in the order M uses them -- the first scaled MFMA waits with a counted lgkmcnt for reads long under way.
+            u32x4 w4[4], wl6a[4];
+            u32x2 wl6b[4];
+            unsigned wsc[4];
+            u32x4 l_n, h_n;
+            unsigned s_n;
+            const unsigned char *pa16, *pa4, *pw16, *pw8, *pw4;
+            auto m_addr = [&]() {
+                // Fragment addresses: five byte offsets made here from the two record indices (which pass through an empty asm: the offsets
+                // are then recomputed per super-step instead of living in loop-invariant registers -- that spilled), each laundered once more so
+                // that every read below is `ds_read base offset:constant`: written as record arithmetic the compiler re-derived each of the
+                // ~40 addresses with two or three vector instructions (55 per wave and super-step, in front of and between the scaled MFMAs).
+                int tl;                                  // the lane index, made afresh (v_mbcnt: no register lives across the loop for it)
+                asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(tl));
+                const int sw_rec = ((tl & 63) >> 4) * 256 + wn * 64 + (tl & 15);      // side W record of column block 0 (+ 16 per block)
+                const int sa_rec = ((tl & 63) >> 4) * 256 + wm * 128 + (tl & 15);                      // side A record of row block 0 (+ 16 per block)
+                unsigned o_a16 = MX_SA_OFF + sa_rec * 16, o_a4 = MX_SA_OFF + 32768 + sa_rec * 4;
+                asm volatile("" : "+v"(o_a16), "+v"(o_a4));
+                pa16 = rsm + o_a16;
+                pa4 = rsm + o_a4;
+                unsigned o_w16 = MX_SW_OFF + sw_rec * 16, o_w8 = MX_SW_OFF + 32768 + sw_rec * 8, o_w4 = MX_SW_OFF + 40960 + sw_rec * 4;
+                asm volatile("" : "+v"(o_w16), "+v"(o_w8), "+v"(o_w4));
+                pw16 = rsm + o_w16;
+                pw8 = rsm + o_w8;
+                pw4 = rsm + o_w4;
+            };
+            // the B fragments of all four column blocks stay resident (44 registers) while the eight row blocks stream past them
+            // once: read per column half, the A side crossed the LDS twice and the M-step ran at the LDS's read rate
+            // (3,008 clk of reads against 2,048 clk of MFMA per CU; now 1,856)
+            auto m_read = [&](auto step) {               // step 0: fp4 image of w; 1: its scales, fp4 residual of x and its scales; 2: fp4 image of x, fp6 residual of w; 3: its last third
+                constexpr int S = decltype(step)::value;
+#pragma unroll
+                for (int jj = 0; jj < 4; ++jj) {
+                    if constexpr (S == 0) w4[jj] = *reinterpret_cast<const u32x4*>(pw16 + jj * 256);
+                    if constexpr (S == 1) wsc[jj] = *reinterpret_cast<const unsigned*>(pw4 + jj * 64);
+                    if constexpr (S == 2) wl6a[jj] = *reinterpret_cast<const u32x4*>(pw16 + 16384 + jj * 256);
+                    if constexpr (S == 3) wl6b[jj] = *reinterpret_cast<const u32x2*>(pw8 + jj * 128);
+                }
+                if constexpr (S == 1) {
+                    l_n = *reinterpret_cast<const u32x4*>(pa16);
+                    s_n = *reinterpret_cast<const unsigned*>(pa4);
+                }
+                if constexpr (S == 2) h_n = *reinterpret_cast<const u32x4*>(pa16 + 16384);
+            };
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const int ks = 4 * ss + j;
@@ -422,8 +490,17 @@ __device__ __forceinline__ void mx_tile(const MxParams& p, const int id, int mti
                     // same instructions spread over six gaps instead of bursts in four are 1.7 % of the GEMM time, docs/lab_notes_r6.md 2a)
                     if (j == 0) {
                         if (i == 1) {
-                            sk_b[0] = wave_hi ? kb[1] : kb[0]; sk_o[0] = wave_hi ? ko[1] : ko[0];
-                            sk_b[1] = wave_hi ? kb[3] : kb[2]; sk_o[1] = wave_hi ? ko[3] : ko[2];
+                            if constexpr (SINGLE) {       // K blocks (wave >> 2) and 2 + (wave >> 2); padded K-steps re-read chunk 0 (their weights are zero)
+                                const int blk = wave_hi ? 1 : 0;
+                                sk_b[0] = kq_ss + (wave_hi ? tq_ss : 0);
+                                sk_b[1] = sk_b[0] + 2 * tq_ss;
+                                if (PADK && 4 * ss + blk >= p.nk) sk_b[0] = MX_KQ_BIAS;
+                                if (PADK && 4 * ss + 2 + blk >= p.nk) sk_b[1] = MX_KQ_BIAS;
+                                sk_o[0] = sk_o[1] = 0;
+                            } else {
+                                sk_b[0] = wave_hi ? kb[1] : kb[0]; sk_o[0] = wave_hi ? ko[1] : ko[0];
+                                sk_b[1] = wave_hi ? kb[3] : kb[2]; sk_o[1] = wave_hi ? ko[3] : ko[2];
+                            }
                         }
                         if (i == 2) MX_DMA_SA(0)
                         if (i == 3) MX_DMA_SA(1)
@@ -440,7 +517,13 @@ __device__ __forceinline__ void mx_tile(const MxParams& p, const int id, int mti
                         if (i == 6) MX_DMA_SW(ss, 4)
                         if (i == 7) MX_DMA_SW(ss, 5)
                     }
-                    if (j == 2 && i == 3) {               // the table entries of K-steps 4 ss + 5 .. 4 ss + 8
+                    if (SINGLE && j == 3) {               // M's first fragments (above): F3's groups 2 .. 7 carry no other DMA or read
+                        if (i == 4) { m_addr(); m_read(std::integral_constant<int, 0>{}); }
+                        if (i == 5) m_read(std::integral_constant<int, 1>{});
+                        if (i == 6) m_read(std::integral_constant<int, 2>{});
+                        if (i == 7) m_read(std::integral_constant<int, 3>{});
+                    }
+                    if (!SINGLE && j == 2 && i == 3) {    // the table entries of K-steps 4 ss + 5 .. 4 ss + 8
                         tb_n = *reinterpret_cast<const i32x4*>(tkb + 4 * ss + 4);
                         to_n = *reinterpret_cast<const i32x4*>(tko + 4 * ss + 4);
                     }
@@ -451,40 +534,19 @@ __device__ __forceinline__ void mx_tile(const MxParams& p, const int id, int mti
             // M: the two block-scaled terms of this super-step (side data complete since the barrier of F3).
             __builtin_amdgcn_sched_barrier(0);
             {
-                // Fragment addresses: five byte offsets made here from the two record indices (which pass through an empty asm: the offsets
-                // are then recomputed per super-step instead of living in loop-invariant registers -- that spilled), each laundered once more so
-                // that every read below is `ds_read base offset:constant`: written as record arithmetic the compiler re-derived each of the
-                // ~40 addresses with two or three vector instructions (55 per wave and super-step, in front of and between the scaled MFMAs).
-                // are then recomputed per super-step instead of living in loop-invariant registers
-                int tl;                                  // the lane index, made afresh (v_mbcnt: no register lives across the loop for it)
-                asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(tl));
-                const int sw_rec = ((tl & 63) >> 4) * 256 + wn * 64 + (tl & 15);      // side W record of column block 0 (+ 16 per block)
-                const int sa_rec = ((tl & 63) >> 4) * 256 + wm * 128 + (tl & 15);                      // side A record of row block 0 (+ 16 per block)
-                unsigned o_a16 = MX_SA_OFF + sa_rec * 16, o_a4 = MX_SA_OFF + 32768 + sa_rec * 4;
-                asm volatile("" : "+v"(o_a16), "+v"(o_a4));
-                const unsigned char* const pa16 = rsm + o_a16;
-                const unsigned char* const pa4 = rsm + o_a4;
-                // the B fragments of all four column blocks stay resident (44 registers) while the eight row blocks stream past them
-                // once: read per column half, the A side crossed the LDS twice and the M-step ran at the LDS's read rate
-                // (3,008 clk of reads against 2,048 clk of MFMA per CU; now 1,856)
-                unsigned o_w16 = MX_SW_OFF + sw_rec * 16, o_w8 = MX_SW_OFF + 32768 + sw_rec * 8, o_w4 = MX_SW_OFF + 40960 + sw_rec * 4;
-                asm volatile("" : "+v"(o_w16), "+v"(o_w8), "+v"(o_w4));
-                const unsigned char* const pw16 = rsm + o_w16;
-                const unsigned char* const pw8 = rsm + o_w8;
-                const unsigned char* const pw4 = rsm + o_w4;
-                u32x4 w4[4], wl6a[4];
-                u32x2 wl6b[4];
-                unsigned wsc[4];
+                if constexpr (!SINGLE) {
+                    m_addr();
 #pragma unroll
-                for (int jj = 0; jj < 4; ++jj) {
-                    w4[jj] = *reinterpret_cast<const u32x4*>(pw16 + jj * 256);
-                    wl6a[jj] = *reinterpret_cast<const u32x4*>(pw16 + 16384 + jj * 256);
-                    wl6b[jj] = *reinterpret_cast<const u32x2*>(pw8 + jj * 128);
-                    wsc[jj] = *reinterpret_cast<const unsigned*>(pw4 + jj * 64);
+                    for (int jj = 0; jj < 4; ++jj) {
+                        w4[jj] = *reinterpret_cast<const u32x4*>(pw16 + jj * 256);
+                        wl6a[jj] = *reinterpret_cast<const u32x4*>(pw16 + 16384 + jj * 256);
+                        wl6b[jj] = *reinterpret_cast<const u32x2*>(pw8 + jj * 128);
+                        wsc[jj] = *reinterpret_cast<const unsigned*>(pw4 + jj * 64);
+                    }
+                    l_n = *reinterpret_cast<const u32x4*>(pa16);
+                    h_n = *reinterpret_cast<const u32x4*>(pa16 + 16384);
+                    s_n = *reinterpret_cast<const unsigned*>(pa4);
                 }
-                u32x4 l_n = *reinterpret_cast<const u32x4*>(pa16);
-                u32x4 h_n = *reinterpret_cast<const u32x4*>(pa16 + 16384);
-                unsigned s_n = *reinterpret_cast<const unsigned*>(pa4);
 #pragma unroll
                 for (int i = 0; i < 8; ++i) {
                     const u32x4 l = l_n, h = h_n;
@@ -506,7 +568,8 @@ __device__ __forceinline__ void mx_tile(const MxParams& p, const int id, int mti
                         const i32x8 bw = i32x8{(int)wl6a[jj].x, (int)wl6a[jj].y, (int)wl6a[jj].z, (int)wl6a[jj].w, (int)wl6b[jj].x, (int)wl6b[jj].y, 0, 0};
                         acc[i][jj] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(ah, bw, acc[i][jj], 4, 2, 1, asc, 1, wsc[jj]);
                     }
-                    if (i == 3) {                        // the next super-step's table entries become scalars (read in F2: long landed)
+                    if (SINGLE && i == 3) kq_ss += 4 * tq_ss;
+                    if (!SINGLE && i == 3) {             // the next super-step's table entries become scalars (read in F2: long landed)
                         kb[0] = kb[4];
                         ko[0] = ko[4];
 #pragma unroll
@@ -520,12 +583,15 @@ __device__ __forceinline__ void mx_tile(const MxParams& p, const int id, int mti
             }
         }
     };
-    if constexpr (FLAT) {
+    if constexpr (SINGLE) {
+        kloop(std::true_type{});
+    } else if constexpr (FLAT) {
         if (interior) kloop(std::true_type{});
         else kloop(std::false_type{});
     } else {
         kloop(std::false_type{});
     }
+#undef MX_KSO
 #undef MX_DMA_A
 #undef MX_DMA_A_E
 #undef MX_DMA_A_I
@@ -547,6 +613,15 @@ template <int ACT, int OUT, bool PADK, bool FLAT = false>
 __global__ __launch_bounds__(512) void tdnn_mx_kernel(MxParams p, int mtiles, int ntiles, int gtiles, double* __restrict__ stats) {
     extern __shared__ __attribute__((aligned(16))) unsigned char rsm[];
     mx_tile<ACT, OUT, PADK, FLAT>(p, blockIdx.x, mtiles, ntiles, gtiles, stats, rsm);
+}
+// ... and the SINGLE form of the flat tile (one context at offset 0). A kernel of its own name instead of a fifth template argument of
+// tdnn_mx_kernel: the library's set of tdnn_mx_kernel instantiations is pinned at the twenty above (tests/test_host_cpu.py), this form's eight
+// are pinned by tests/test_mx_single_cpu.py, and a kernel trace tells the two forms of a step's flat launches apart. To the caller both are
+// the family "tdnn_mx_kernel<flat>".
+template <int ACT, int OUT, bool PADK>
+__global__ __launch_bounds__(512) void mx_single_kernel(MxParams p, int mtiles, int ntiles, int gtiles, double* __restrict__ stats) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char rsm[];
+    mx_tile<ACT, OUT, PADK, true, true>(p, blockIdx.x, mtiles, ntiles, gtiles, stats, rsm);
 }
 
 // x planes (see the head of this file) -> one TDNN layer. Exactly one of {y planes, yf, stats} is written.
@@ -618,8 +693,13 @@ static int mx_launch(const void* xh, const void* xl4, const void* x4, const void
         tdnn_pick<MX_OUT_STATS, MX_OUT_PLANES>(o, [&](auto O) {
             tdnn_pick<KTF_ACT_RELU, KTF_ACT_NONE>(d->act, [&](auto A) {
                 tdnn_pick<true, false>((p.nk & 3) != 0, [&](auto PADK) {
-                    tdnn_launch_kernel<tdnn_mx_kernel<A, O, PADK, true>>("tdnn_mx_kernel<flat>", dim3((unsigned)fblocks), dim3(512), MX_LDS_TOTAL(p.nss * 4),
-                                                                         MX_LDS_TOTAL(MX_KQ_MAX_STEPS), st, p, (int)B, ntiles, (int)ftiles, stats);
+                    // one context at offset 0 (no row of the layer is ever clamped): the SINGLE instantiation, which has no K-step table in LDS
+                    if (d->nctx == 1 && d->ctx[0] == 0)
+                        tdnn_launch_kernel<mx_single_kernel<A, O, PADK>>("tdnn_mx_kernel<flat>", dim3((unsigned)fblocks), dim3(512), MX_LDS_BYTES, MX_LDS_BYTES,
+                                                                         st, p, (int)B, ntiles, (int)ftiles, stats);
+                    else
+                        tdnn_launch_kernel<tdnn_mx_kernel<A, O, PADK, true>>("tdnn_mx_kernel<flat>", dim3((unsigned)fblocks), dim3(512), MX_LDS_TOTAL(p.nss * 4),
+                                                                             MX_LDS_TOTAL(MX_KQ_MAX_STEPS), st, p, (int)B, ntiles, (int)ftiles, stats);
                 });
             });
         });
