@@ -9,6 +9,8 @@ are torch ops on the same device, or -- `relu_batch_norm`, `TrainableSequential(
 include/ktf_norm.h. `ClassifierHead` is the speaker classification head and its loss -- softmax, additive-margin and
 additive-angular-margin cosine softmax -- over `row_inv_norm` and `margin_softmax_loss`, the kernels of include/ktf_loss.h around
 a `tdnn_affine` GEMM; with sub-centres, an inter-top-k penalty or label smoothing switched on, the kernels of include/ktf_head.h.
+`dense_affine` is that GEMM as a kernel family of its own (include/ktf_dense.h: a short dense batch against a tall weight, no
+padded operand), which `ClassifierHead(affine="dense")` runs instead.
 There is no CPU path for the kernels: tensors that are not on the GPU are refused.
 
 `gemm=` selects the matrix pipe of the TDNN GEMMs, forward and backward: "f32" (the exact-fp32 MFMA), "bf16" (operands rounded to
@@ -154,6 +156,61 @@ def tdnn_affine(x, weight, bias, context, lens=None, subsampling_factor=1, paddi
         raise ValueError(f"bias shape {tuple(bias.shape)} != ({weight.shape[0]},)")
     return _TdnnAffine.apply(x.to(torch.float32), weight.to(torch.float32), None if bias is None else bias.to(torch.float32),
                              _lens(lens, x.shape[0], x.device), list(context), subsampling_factor, padding, code)
+
+
+def _rows_dense(t):
+    """t as the dense calls take it: fp32 with dense rows that do not overlap -- a row-strided view stays a view, anything else
+    (a transposed tensor, rows expanded from one as autograd hands them to the backward of a sum) is copied."""
+    t = t.to(torch.float32)
+    dense = t.shape[1] <= 1 or t.stride(1) == 1
+    apart = t.shape[0] <= 1 or t.stride(0) >= t.shape[1]
+    return t if dense and apart else t.contiguous()
+
+
+class _DenseAffine(torch.autograd.Function):
+    """include/ktf_dense.h: x and weight are saved as they are, and every call reads them in place."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, gemm):
+        z = torch.empty((x.shape[0], weight.shape[0]), dtype=torch.float32, device=x.device)
+        ops.dense_forward(x, weight, bias, gemm, z)
+        ctx.save_for_backward(x, weight)
+        ctx.gemm, ctx.has_bias = gemm, bias is not None
+        return z
+
+    @staticmethod
+    def backward(ctx, gz):
+        x, weight = ctx.saved_tensors
+        g = _rows_dense(gz)
+        dx = dw = db = None
+        if ctx.needs_input_grad[0]:
+            dx = torch.empty_like(x, memory_format=torch.contiguous_format)
+            ops.dense_grad_data(g, weight, ctx.gemm, dx, ops.dense_workspace(x.shape[0], weight.shape[0], x.shape[1], x.device))
+        if ctx.needs_input_grad[1] or (ctx.has_bias and ctx.needs_input_grad[2]):
+            dw = torch.empty_like(weight, memory_format=torch.contiguous_format)
+            if ctx.has_bias:
+                db = torch.empty((weight.shape[0],), dtype=torch.float32, device=x.device)
+            ops.dense_grad_weights(g, x, ctx.gemm, dw, db)
+        return dx, dw, db, None
+
+
+def dense_affine(x, weight, bias=None, gemm="f32"):
+    """z[m,n] = bias[n] + sum_d x[m,d] * weight[n,d], differentiable in x, weight and bias: the GEMM of a classification head as the
+    kernels of include/ktf_dense.h -- a short dense batch x (M, D) against a tall weight (N, D), both fp32 on the GPU, read as they
+    stand in memory (row-strided views included): no padded and no 16-bit copy of an operand is made, forward or backward, and the
+    backward runs only the gradients that are asked for. bias (N,) or None. gemm: "f32", "bf16" or "bf16x3" as in `tdnn_affine`.
+    Returns (M, N) fp32."""
+    code = _gemm_code(gemm)
+    _on_gpu(x, "x")
+    _on_gpu(weight, "weight")
+    if x.dim() != 2 or weight.dim() != 2 or weight.shape[1] != x.shape[1] or x.shape[1] < 1 or weight.shape[0] < 1:
+        raise ValueError(f"expected x (M, D) and weight (N, D) with N, D >= 1, got {tuple(x.shape)} and {tuple(weight.shape)}")
+    if bias is not None:
+        _on_gpu(bias, "bias")
+        if tuple(bias.shape) != (weight.shape[0],):
+            raise ValueError(f"bias shape {tuple(bias.shape)} != ({weight.shape[0]},)")
+        bias = bias.to(torch.float32).contiguous()
+    return _DenseAffine.apply(_rows_dense(x), _rows_dense(weight), bias, code)
 
 
 class _StatsPooling(torch.autograd.Function):
@@ -622,11 +679,18 @@ class ClassifierHead(torch.nn.Module):
     j); top_k, penalty and label_smoothing are those of `margin_softmax_loss` and, like margin and scale, plain attributes read at
     every call. With one of them set the loss runs the kernels of include/ktf_head.h; with none, those of include/ktf_loss.h as
     before. A head with K > 1 counts in training mode, in the buffer `center_counts` (num_classes, K) int64, how often each centre
-    was the one its class's target rows selected; `dominant()` reduces the head to those centres."""
+    was the one its class's target rows selected; `dominant()` reduces the head to those centres.
+
+    affine selects the GEMM's route: "tdnn" (the default) is the `tdnn_affine` call above, which pads and copies the weight operand
+    on every call; "dense" is `dense_affine(emb, weight, bias, gemm=gemm)`, the kernels of include/ktf_dense.h on emb and weight as
+    they stand in memory, forward and backward, in the same three gemm modes."""
 
     def __init__(self, dim, num_classes, kind="aam", margin=None, scale=None, bias=False, gemm="f32", device=None, normalize=None, eps=1e-12,
-                 sub_centers=1, top_k=0, penalty=0.0, label_smoothing=0.0):
+                 sub_centers=1, top_k=0, penalty=0.0, label_smoothing=0.0, affine="tdnn"):
         super().__init__()
+        if affine not in ("tdnn", "dense"):
+            raise ValueError(f"affine must be 'tdnn' or 'dense', got {affine!r}")
+        self.affine = affine
         for name, v in (("dim", dim), ("num_classes", num_classes)):
             if isinstance(v, bool) or not isinstance(v, int) or v < 1:
                 raise ValueError(f"{name} must be a positive integer, got {v!r}")
@@ -659,7 +723,10 @@ class ClassifierHead(torch.nn.Module):
         if not isinstance(emb, torch.Tensor) or emb.dim() != 2 or emb.shape[1] != self.dim:
             raise ValueError(f"expected emb (B, {self.dim}), got shape {tuple(getattr(emb, 'shape', ()))}")
         emb = emb.to(torch.float32)
-        z = tdnn_affine(emb.unsqueeze(0), self.weight.unsqueeze(1), self.bias, [0], gemm=self.gemm).squeeze(0)
+        if self.affine == "dense":
+            z = dense_affine(emb, self.weight, self.bias, gemm=self.gemm)
+        else:
+            z = tdnn_affine(emb.unsqueeze(0), self.weight.unsqueeze(1), self.bias, [0], gemm=self.gemm).squeeze(0)
         if not self.normalize:
             return z, None, None
         return z, row_inv_norm(emb, self.eps), row_inv_norm(self.weight, self.eps)
@@ -690,7 +757,7 @@ class ClassifierHead(torch.nn.Module):
         equal counts): the usual clean-up after sub-centre training. Every other setting is this head's."""
         K = self.sub_centers
         new = ClassifierHead(self.dim, self.num_classes, self.kind, self.margin, self.scale, self.bias is not None, self.gemm,
-                             self.weight.device, self.normalize, self.eps, 1, self.top_k, self.penalty, self.label_smoothing)
+                             self.weight.device, self.normalize, self.eps, 1, self.top_k, self.penalty, self.label_smoothing, self.affine)
         with torch.no_grad():
             if K == 1:
                 new.weight.copy_(self.weight)

@@ -1717,6 +1717,66 @@ def attn_pool_backward(x, e, lens, include_std, eps, norm, stats, gout, dx, de, 
     return dx, de
 
 
+# ----------------------------------------------------------------------------- the head's dense affine (include/ktf_dense.h)
+def dense_slot_cols():
+    """Columns of g per partial sum of the data gradient."""
+    return int(L.load().ktf_dense_slot_cols())
+
+
+def dense_workspace(M, N, D, device):
+    """The workspace dense_grad_data takes for g (M, N) against w (N, D)."""
+    return _workspace("ktf_dense_workspace_bytes", int(M), int(N), int(D), device=device)
+
+
+def _dense_shapes(*operands):
+    """(name, tensor, rows, columns) of a dense call's operands: every shape is what the first operand's makes it."""
+    for name, t, r, c in operands:
+        if tuple(t.shape) != (r, c):
+            raise ValueError(f"{name}: expected shape ({r}, {c}), got {tuple(t.shape)}")
+        if r > 1 and t.stride(0) < c:                # (_mat checks the columns; rows expanded from one would be read past their storage)
+            raise ValueError(f"{name}: rows overlap in memory (strides {tuple(t.stride())})")
+
+
+def dense_forward(x, w, bias, gemm, z):
+    """z[m,n] = bias[n] + sum_d x[m,d] * w[n,d]: x (M, D), w (N, D), z (M, N) preallocated, all fp32 with dense rows (row-strided
+    views pass with their leading dimension), bias (N,) fp32 or None; gemm a KTF_GEMM_* number. Every element of z's rows is written."""
+    M, D = x.shape
+    N = w.shape[0]
+    _dense_shapes(("x", x, M, D), ("w", w, N, D), ("z", z, M, N))
+    _need_dense("bias", bias)
+    px, ldx = _mat(x, w)
+    pw, ldw = _mat(w, w)
+    pz, ldz = _mat(z, w)
+    _call("ktf_dense_forward", x.device, px, ldx, pw, ldw, L.ptr(bias), M, N, D, int(gemm), pz, ldz)
+    return z
+
+
+def dense_grad_data(g, w, gemm, dx, workspace):
+    """dx[m,d] = sum_n g[m,n] * w[n,d]: g (M, N), w (N, D), dx (M, D) preallocated; workspace from dense_workspace."""
+    M, N = g.shape
+    D = w.shape[1]
+    _dense_shapes(("g", g, M, N), ("w", w, N, D), ("dx", dx, M, D))
+    _need_dense("workspace", workspace)
+    pg, ldg = _mat(g, w)
+    pw, ldw = _mat(w, w)
+    pd, lddx = _mat(dx, w)
+    _call("ktf_dense_grad_data", g.device, pg, ldg, pw, ldw, M, N, D, int(gemm), pd, lddx, L.ptr(workspace), workspace.numel())
+    return dx
+
+
+def dense_grad_weights(g, x, gemm, dw, dbias=None):
+    """dw[n,d] = sum_m g[m,n] * x[m,d] and, with dbias (N,) fp32, dbias[n] = sum_m g[m,n]: g (M, N), x (M, D), dw (N, D) preallocated."""
+    M, N = g.shape
+    D = x.shape[1]
+    _dense_shapes(("g", g, M, N), ("x", x, M, D), ("dw", dw, N, D))
+    _need_dense("dbias", dbias)
+    pg, ldg = _mat(g, dw)
+    px, ldx = _mat(x, dw)
+    pd, lddw = _mat(dw, dw)
+    _call("ktf_dense_grad_weights", g.device, pg, ldg, px, ldx, M, N, D, int(gemm), pd, lddw, L.ptr(dbias))
+    return dw, dbias
+
+
 # ----------------------------------------------------------------------------- training examples (include/ktf_egs.h)
 EGS_DTYPES = {torch.float32: L.KTF_F32, torch.float16: L.KTF_F16}
 

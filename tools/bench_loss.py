@@ -40,7 +40,11 @@ from bench_norm import alternate  # noqa: E402
 
 def torch_head(emb, weight, labels, kind, margin, scale):
     """The cosine head as it is usually written in torch -> (mean loss, pred)."""
-    c = F.normalize(emb) @ F.normalize(weight).T
+    return torch_head_from_cosines(F.normalize(emb) @ F.normalize(weight).T, labels, kind, margin, scale)
+
+
+def torch_head_from_cosines(c, labels, kind, margin, scale):
+    """... from the (B, classes) cosines on."""
     if kind == "am":
         phi = c - margin
     elif kind == "aam":
