@@ -1074,6 +1074,146 @@ def _f32_rows(x):
     return x.to(torch.float32).contiguous()
 
 
+# =============================================================================== res2net
+class Res2Conv(Layer):
+    """The hierarchical, grouped, dilated convolution of a Res2Net block (include/ktf_res2.h): the C input channels are cut into `scale`
+    groups of width C / scale; group 0 passes through, group i >= 1 is a three-tap convolution at distance `dilation` (edge rows
+    replicated, as TDNN(padding="SAME")) of X_i + Y_{i-1}, then `activation` ("relu" or None) and, with `batch_norm`, the folded inference
+    BatchNorm y * norm_scale + norm_shift. One launch, inference only. The weights in keras order are [kernel (scale-1, 3, w, w) as
+    [g, k, in, out], bias (scale-1, w), norm_scale (scale-1, w), norm_shift (scale-1, w)] (without the ones the layer does not have)."""
+
+    MIN_WIDTH, MAX_WIDTH = 16, 128
+    # the kernel's arithmetic for a call's mode: it has no f16mx form, and runs such a call in the fp32-grade split-bf16
+    MODES = {"f32": L.GEMM_F32, "float32": L.GEMM_F32, "bf16": L.GEMM_BF16, "bfloat16": L.GEMM_BF16, "bf16x3": L.GEMM_BF16X3,
+             "f16mx": L.GEMM_BF16X3, L.GEMM_F32: L.GEMM_F32, L.GEMM_BF16: L.GEMM_BF16, L.GEMM_BF16X3: L.GEMM_BF16X3,
+             L.GEMM_F16MX: L.GEMM_BF16X3}
+
+    def __init__(self, scale, dilation=1, activation="relu", use_bias=True, batch_norm=True, name=None, **kwargs):
+        super().__init__(trainable=True, name=name, **kwargs)
+        self.scale, self.dilation = int(scale), int(dilation)
+        if not 2 <= self.scale <= 8:
+            raise ValueError(f"'scale' must be in [2, 8], got {scale}")
+        if not 1 <= self.dilation <= 8:
+            raise ValueError(f"'dilation' must be in [1, 8], got {dilation}")
+        act = activation.lower() if isinstance(activation, str) else activation
+        if act not in (None, "linear", "relu"):
+            raise ValueError(f"activation must be 'relu' or None, got {activation!r}")
+        self.activation = activation
+        self.useBias, self.batchNorm = bool(use_bias), bool(batch_norm)
+        self.gemm = "f32"
+        self.batchAxis, self.timeAxis, self.featAxis = 0, 1, -1
+        self.kernel = self.bias = self.normScale = self.normShift = None
+        self._dev = {}
+        self._version = 0      # bumped whenever the weights change: models refuse stale captured graphs
+
+    def _width(self, C):
+        if C % self.scale:
+            raise ValueError(f"'scale' = {self.scale} does not divide the {C} input channels")
+        w = C // self.scale
+        if w % 16 or not self.MIN_WIDTH <= w <= self.MAX_WIDTH:
+            raise ValueError(f"group width {w} = {C} / {self.scale} is not a multiple of 16 in [{self.MIN_WIDTH}, {self.MAX_WIDTH}]")
+        return w
+
+    def build(self, input_shape):
+        C = input_shape[self.featAxis]
+        w = self._width(C)
+        self.inputDim, self.width = C, w
+        G = self.scale - 1
+        if self.kernel is None or self.kernel.shape != (G, 3, w, w):
+            rng = np.random.default_rng(zlib.crc32(self.name.encode()))      # (from the name: every rank draws the same, as TDNN.build)
+            lim = np.sqrt(6.0 / (3 * w + 3 * w))
+            self.kernel = rng.uniform(-lim, lim, (G, 3, w, w)).astype(np.float32)
+            lb = np.sqrt(6.0 / (w + 1))
+            self.bias = rng.uniform(-lb, lb, (G, w)).astype(np.float32) if self.useBias else None
+            self.normScale = np.ones((G, w), np.float32) if self.batchNorm else None
+            self.normShift = np.zeros((G, w), np.float32) if self.batchNorm else None
+            self._version += 1
+            WEIGHTS_EPOCH[0] += 1
+        self._dev = {}
+        self.built = True
+
+    def get_config(self):
+        c = super().get_config()
+        c.update({"scale": self.scale, "dilation": self.dilation, "activation": self.activation, "use_bias": self.useBias,
+                  "batch_norm": self.batchNorm})
+        return c
+
+    def get_weights(self):
+        if self.kernel is None:
+            return []
+        return [self.kernel] + ([self.bias] if self.useBias else []) + ([self.normScale, self.normShift] if self.batchNorm else [])
+
+    def set_weights(self, weights, fmt="tensorflow"):
+        """[kernel, bias, norm_scale, norm_shift] (without bias / the norm pair where the layer has none). fmt "tensorflow": kernel
+        (scale-1, 3, w, w) as [g, k, in, out], what get_weights() gives; "torch": (scale-1, w_out, w_in, 3), the Conv1d.weight tensors of
+        the block's convolutions stacked."""
+        fmt = fmt.lower()
+        if fmt not in ["tensorflow", "torch"]:
+            raise ValueError(f"expected 'fmt' to be either 'tensorflow' or 'torch', got {fmt}")
+        want = 1 + int(self.useBias) + 2 * int(self.batchNorm)
+        if len(weights) != want:
+            raise ValueError(f"expected a weight list of length {want}, got {len(weights)}")
+        arrs = [np.asarray(getattr(a, "detach", lambda: a)(), np.float32) for a in weights]
+        kernel = arrs.pop(0)
+        if fmt == "torch" and kernel.ndim == 4:
+            kernel = kernel.transpose(0, 3, 2, 1)
+        G = self.scale - 1
+        w = self.width if self.built else (kernel.shape[-1] if kernel.ndim == 4 else -1)
+        if kernel.shape != (G, 3, w, w):
+            raise ValueError(f"kernel: expected shape {(G, 3, w, w)} as [g, k, in, out], got {kernel.shape}")
+        self._width(w * self.scale)
+        rest = [a.reshape(G, -1) if a.size == G * w else a for a in arrs]
+        for a in rest:
+            if a.shape != (G, w):
+                raise ValueError(f"bias / norm_scale / norm_shift: expected shape {(G, w)}, got {a.shape}")
+        self.kernel = np.ascontiguousarray(kernel)
+        self.bias = np.ascontiguousarray(rest.pop(0)) if self.useBias else None
+        self.normScale, self.normShift = (np.ascontiguousarray(a) for a in rest) if self.batchNorm else (None, None)
+        self.inputDim, self.width = w * self.scale, w
+        self._dev = {}
+        self._version += 1
+        WEIGHTS_EPOCH[0] += 1
+        self.built = True
+
+    @staticmethod
+    def fold_batch_norm(mean, var, gamma, beta, eps):
+        """(scale, shift) of the inference BatchNorm y = gamma (x - mean) / sqrt(var + eps) + beta, computed in float64."""
+        mean, var, gamma, beta = (np.asarray(a, np.float64) for a in (mean, var, gamma, beta))
+        scale = gamma / np.sqrt(var + float(eps))
+        return scale.astype(np.float32), (beta - mean * scale).astype(np.float32)
+
+    def device_weights(self, device):
+        """(w (scale-1, 3 width, width), bias, norm_scale, norm_shift) on the device, fp32 in every mode (the 16-bit modes split in
+        registers): one set per device, dropped when the weights change."""
+        key = str(device)
+        if key not in self._dev:
+            G, w = self.scale - 1, self.width
+            up = lambda a: None if a is None else ops.to_device_f32(a, device)      # noqa: E731
+            self._dev[key] = (up(self.kernel.reshape(G, 3 * w, w)), up(self.bias), up(self.normScale), up(self.normShift))
+        return self._dev[key]
+
+    def forward(self, x, lens=None, gemm="f32", out=None):
+        """The one launch: x (B, T, C) fp32, a view of rows whose stride is a multiple of 4; lens (B,) int32 or None; `gemm` a mode
+        name or KTF_GEMM_* number; out (B, T, C) fp32 view of rows likewise (default: fresh zeroed rows). Rows at or beyond an
+        utterance's length are left as they are."""
+        if gemm not in self.MODES:
+            raise ValueError(f"gemm must be one of {sorted(k for k in self.MODES if isinstance(k, str))}")
+        B, T, C = x.shape
+        if C != self.inputDim:
+            raise ValueError(f"expected input feature dim {self.inputDim}, got {C}")
+        if out is None:
+            out = torch.zeros((B, T, C), dtype=torch.float32, device=x.device)
+        w, bias, nscale, nshift = self.device_weights(x.device)
+        act = L.ACT_RELU if isinstance(self.activation, str) and self.activation.lower() == "relu" else L.ACT_NONE
+        return ops.res2_conv(x, lens, self.scale, self.dilation, w, bias, nscale, nshift, act, self.MODES[gemm], out, C=C)
+
+    def call(self, inputs):
+        x = inputs
+        if x.dim() != 3:
+            raise ValueError(f"expected a (batch, time, feat) input, got shape {tuple(x.shape)}")
+        return self.forward(_f32_rows(x), None, self.gemm)
+
+
 # =============================================================================== stats
 class StatsPooling(Layer):
     """layers/stats/stats_pooling.py:26 — mean (+ std) pooling over the whole utterance or sliding windows."""

@@ -20,7 +20,8 @@ from . import _lib as L
 from . import ops
 from ._host import is_real
 from .io import KaldiNnet3Reader, ReadKaldiArray
-from .layers import TDNN, AttentiveStatsPooling, BatchNorm, CMVN, Framing, MFCC, ReLU, StatsPooling, VAD, _GEMM, WEIGHTS_EPOCH, _f32_rows
+from .layers import (TDNN, AttentiveStatsPooling, BatchNorm, CMVN, Framing, MFCC, ReLU, Res2Conv, StatsPooling, VAD, _GEMM, WEIGHTS_EPOCH,
+                     _f32_rows)
 from .mx import Planes
 
 
@@ -41,6 +42,7 @@ _LAYER_KINDS = (
     (("batchnorm", "bn"), BatchNorm, "{}.batchnorm", False),
     (("stats", "stats_extraction", "stats_pooling"), StatsPooling, "{}", True),
     (("attentive_stats", "attentive_stats_pooling"), AttentiveStatsPooling, "{}", True),
+    (("res2_conv",), Res2Conv, "{}", True),
 )
 _KIND_OF = {alias: row for row in _LAYER_KINDS for alias in row[0]}
 
@@ -48,7 +50,7 @@ _KIND_OF = {alias: row for row in _LAYER_KINDS for alias in row[0]}
 def cfg2layers(layerCfg):
     """One entry of `model_config.layers` -> the layers it stands for, in order. `type` is a kind or a list of kinds
     ("affine" | "tdnn", "relu", "batchnorm" | "bn", "stats" | "stats_extraction" | "stats_pooling", "attentive_stats" |
-    "attentive_stats_pooling"); the entry's `cfg` holds the keyword arguments of its parametrised layer. KeyError without a `type`, ValueError for an unknown one."""
+    "attentive_stats_pooling", "res2_conv"); the entry's `cfg` holds the keyword arguments of its parametrised layer. KeyError without a `type`, ValueError for an unknown one."""
     kinds = layerCfg.get("type") or []
     if isinstance(kinds, str):
         kinds = [kinds]
@@ -259,7 +261,7 @@ class Sequential:
     def weights_signature(self):
         """Changes whenever a TDNN / BatchNorm layer's weights change (set_weights, a re-build): captured graphs
         are tied to it."""
-        return tuple((id(l), l._version) for l in self.layers if isinstance(l, (TDNN, BatchNorm, AttentiveStatsPooling)))
+        return tuple((id(l), l._version) for l in self.layers if isinstance(l, (TDNN, BatchNorm, AttentiveStatsPooling, Res2Conv)))
 
     def get_layer(self, name):
         for l in self.layers:
@@ -301,6 +303,9 @@ class Sequential:
             elif isinstance(l, AttentiveStatsPooling) and not pooled:
                 steps.append(("attn", l))
                 pooled = True
+                i += 1
+            elif isinstance(l, Res2Conv) and not pooled:
+                steps.append(("res2", l))
                 i += 1
             elif isinstance(l, (ReLU, BatchNorm)):
                 steps.append(("eltwise", l))
@@ -421,6 +426,8 @@ class Sequential:
                 self._step_stats(c, si, st[1])
             elif st[0] == "attn":
                 self._step_attn(c, si, st[1])
+            elif st[0] == "res2":
+                self._step_res2(c, st[1], out_role)
             else:
                 c.x = st[1](c.x.to(torch.float32).contiguous())
         if c.pooled:
@@ -539,7 +546,7 @@ class Sequential:
                                    slots, slot_rows, pad_cols=not pair_in)
             return
         g = L.GEMM_F32 if c.pooled else l.effective_gemm(gemm, relu)
-        ydt = torch.float32 if (c.pooled or g != gemm or (nxt is not None and nxt[0] == "attn")) else L.act_torch_dtype(gemm)
+        ydt = torch.float32 if (c.pooled or g != gemm or (nxt is not None and nxt[0] in ("attn", "res2"))) else L.act_torch_dtype(gemm)
         pair_ok = lambda t, r: t.activation in (None, "linear") or (t.activation == "relu" and not r)  # noqa: E731
         pair_out = (c.pairs and not c.pooled and g == L.GEMM_F32 and pair_ok(l, relu) and nxt is not None and nxt[0] == "tdnn"
                     and pair_ok(nxt[1], nxt[2]) and nxt[1].inputDim == l.units)
@@ -582,6 +589,15 @@ class Sequential:
         c.x = sbuf[:, :od].unsqueeze(0)
         c.set_lens(None)
         c.pooled = True
+
+    def _step_res2(self, c, l, out_role):
+        """A Res2Conv: one launch from fp32 rows to fp32 rows in the call's arithmetic (Res2Conv.MODES: f16mx runs split-bf16); the
+        lengths stay, and the layer behind starts its route from fp32 rows as a first layer does."""
+        x = _gemm_rows(c.x, torch.float32)
+        B, T, C = x.shape
+        ldy = ops.round_up(C, 32)
+        ybuf = c.ws.get(out_role + ("p" if ldy != C else ""), (B, T, ldy), torch.float32, c.dev, padded=ldy != C)
+        c.x = l.forward(x, lens=c.lens, gemm=c.gemm, out=ybuf[:, :, :C])
 
     def _pool_slots(self, T, flat, mx_flags=None, gemm=None):
         """(slots, slot_rows) of a pooled step's fp64 partial sums over utterances of up to T rows (the slot rule of csrc/pooled_stats.h): on
@@ -1325,7 +1341,7 @@ class XvectorExtractor:
         sig = self.xvec.weights_signature()
         keep = [cap_ws, cap_xws, dict(self._post_dev)]
         for l in self.xvec.layers:
-            if isinstance(l, TDNN):
+            if isinstance(l, (TDNN, Res2Conv)):
                 keep.append(dict(l._dev))
             elif isinstance(l, BatchNorm):
                 keep.append(l._dev)

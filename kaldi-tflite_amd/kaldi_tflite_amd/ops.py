@@ -1777,6 +1777,36 @@ def dense_grad_weights(g, x, gemm, dw, dbias=None):
     return dw, dbias
 
 
+# ----------------------------------------------------------------------------- the Res2Net dilated convolution (include/ktf_res2.h)
+def res2_row_tile(width, scale, dilation, gemm=L.GEMM_F32):
+    """Output rows per workgroup that res2_conv uses for this group width, scale and dilation."""
+    return _size("ktf_res2_row_tile", int(width), int(scale), int(dilation), int(gemm))
+
+
+def res2_conv(x, lens, scale, dilation, w, bias, nscale, nshift, act, gemm, y, C=None):
+    """x (B, T, ldx) and y (B, T, ldy) fp32 rows with C = scale * wd channels (default: every column of x), lens (B,) int32 or None;
+    w (scale-1, 3 wd, wd), bias / nscale / nshift (scale-1, wd) fp32 or None; act and gemm the KTF_ACT_* / KTF_GEMM_* numbers. Rows
+    of y at or beyond an utterance's length and its pad columns are left as they are."""
+    if x.dim() != 3 or y.dim() != 3 or x.shape[:2] != y.shape[:2]:
+        raise ValueError(f"x (B, T, ldx) and y (B, T, ldy) with the same B and T are expected, got {tuple(x.shape)} and {tuple(y.shape)}")
+    B, T = x.shape[0], x.shape[1]
+    C = x.shape[2] if C is None else int(C)
+    px, ldx = _attn_rows("x", x)
+    py, ldy = _attn_rows("y", y)
+    s = int(scale)
+    wd = C // s if s >= 2 and C > 0 and C % s == 0 else None      # (a C the library will refuse: it gets to say why)
+    for name, t, shape in (("w", w, (s - 1, 3 * wd, wd) if wd else None), ("bias", bias, (s - 1, wd) if wd else None),
+                           ("nscale", nscale, (s - 1, wd) if wd else None), ("nshift", nshift, (s - 1, wd) if wd else None), ("lens", lens, (B,))):
+        if t is None:
+            continue
+        _need_dense(name, t)
+        if t.dtype != (torch.int32 if name == "lens" else torch.float32) or (shape is not None and tuple(t.shape) != shape):
+            raise ValueError(f"{name}: expected {shape} {'int32' if name == 'lens' else 'fp32'}, got {t.dtype} {tuple(t.shape)}")
+    _call("ktf_res2_conv", x.device, px, B, T, C, ldx, L.ptr(lens), s, int(dilation), L.ptr(w), L.ptr(bias), L.ptr(nscale), L.ptr(nshift),
+          int(act), int(gemm), py, ldy)
+    return y
+
+
 # ----------------------------------------------------------------------------- training examples (include/ktf_egs.h)
 EGS_DTYPES = {torch.float32: L.KTF_F32, torch.float16: L.KTF_F16}
 
