@@ -21,16 +21,7 @@
 // eight rows of W. F32 feeds them to eight v_mfma_f32_16x16x4_f32 (step s takes element s of every group), the 16-bit modes round or
 // split them in registers into the fragment of one v_mfma_f32_16x16x32_bf16. W is read straight from global memory: every workgroup
 // reads the same 3 wd wd floats per stage (48 KiB at wd = 64, 192 KiB at wd = 128), which live in L2, and one path serves every width.
-#include "common.h"
-#include "../../include/ktf_res2.h"
-
-typedef __attribute__((ext_vector_type(8))) __bf16 r2_bfrag8;
-typedef __attribute__((ext_vector_type(4))) unsigned r2_u32x4;
-typedef __attribute__((ext_vector_type(4))) float r2_fv4;
-
-#define R2_THREADS 512
-#define R2_LDS_BYTES 163840      // gfx950: 160 KiB per workgroup
-#define R2_MAX_TILE 128
+#include "res2_common.h"
 
 struct Res2Params {
     const float* x;
@@ -43,33 +34,10 @@ struct Res2Params {
     int64_t T, ldx, ldy;
     int32_t scale, dil, act, R, NR;
     int32_t x_vec, y_vec, w_vec;     // the base pointer is 16-byte aligned: 16-byte accesses (the bits are the same without)
+    float* a;                        // ktf_res2_conv_train with the norm pair: act(Z_i) before the norm, (B, T, lda), group i at (i - 1) wd
+    int64_t lda;
+    int32_t a_vec;
 };
-
-__device__ __forceinline__ r2_fv4 r2_load4(const float* p, bool vec) {
-    if (vec) return *reinterpret_cast<const r2_fv4*>(p);
-    return r2_fv4{p[0], p[1], p[2], p[3]};
-}
-__device__ __forceinline__ void r2_store4(float* p, r2_fv4 v, bool vec) {
-    if (vec) {
-        *reinterpret_cast<r2_fv4*>(p) = v;
-    } else {
-        p[0] = v[0], p[1] = v[1], p[2] = v[2], p[3] = v[3];
-    }
-}
-
-// eight fp32 -> the lane's bf16 fragment: hi = bf16(v), round to nearest even; X3: lo = bf16(v - hi)
-template <bool X3>
-__device__ __forceinline__ void r2_split8(const float (&v)[8], r2_bfrag8& hi, r2_bfrag8& lo) {
-    r2_u32x4 h, l = {0u, 0u, 0u, 0u};
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const unsigned short h0 = f2bf(v[2 * i]), h1 = f2bf(v[2 * i + 1]);
-        h[i] = (unsigned)h0 | ((unsigned)h1 << 16);
-        if (X3) l[i] = (unsigned)f2bf(v[2 * i] - bf2f(h0)) | ((unsigned)f2bf(v[2 * i + 1] - bf2f(h1)) << 16);
-    }
-    hi = __builtin_bit_cast(r2_bfrag8, h);
-    lo = __builtin_bit_cast(r2_bfrag8, l);
-}
 
 template <int MODE, int NCB>
 __global__ __launch_bounds__(R2_THREADS) void res2_conv_kernel(Res2Params p) {
@@ -208,18 +176,20 @@ __global__ __launch_bounds__(R2_THREADS) void res2_conv_kernel(Res2Params p) {
                 const bool own = t >= t0 && t < t0 + R;
 #pragma unroll
                 for (int q = 0; q < NCB; ++q) {
-                    r2_fv4 v;
+                    r2_fv4 v, av;
 #pragma unroll
                     for (int i = 0; i < 4; ++i) {
                         const int e = 4 * q + i;
                         float z = acc[rb][e % NCB][e / NCB];
                         if (p.bias) z += p.bias[pc + e];
                         if (p.act == KTF_ACT_RELU) z = z < 0.0f ? 0.0f : z;
+                        av[i] = z;
                         if (p.nscale) z = __fadd_rn(__fmul_rn(z, p.nscale[pc + e]), p.nshift[pc + e]);
                         v[i] = z;
                     }
                     const int c = c0 + 4 * q;
                     if (own) r2_store4(yb + (int64_t)t * p.ldy + j * W + c, v, yv);
+                    if (own && p.a) r2_store4(p.a + ((int64_t)b * p.T + t) * p.lda + pc + 4 * q, av, p.a_vec);
                     if (j + 1 < s) {
                         const r2_fv4 xn = r2_load4(xb + (int64_t)t * p.ldx + (j + 1) * W + c, xv);
                         *reinterpret_cast<r2_fv4*>(nxt + (t - tb) * PITCH + c) = xn + v;
@@ -235,15 +205,6 @@ __global__ __launch_bounds__(R2_THREADS) void res2_conv_kernel(Res2Params p) {
 }
 
 // ------------------------------------------------------------------------------------ host
-static int r2_check_shape(const char* who, int32_t width, int32_t scale, int32_t dilation, int32_t gemm) {
-    KTF_REQUIRE(scale >= 2 && scale <= 8, "%s: scale %d outside [2, 8]", who, (int)scale);
-    KTF_REQUIRE(width >= 16 && width <= 128 && width % 16 == 0, "%s: group width %d is not a multiple of 16 in [16, 128]", who, (int)width);
-    KTF_REQUIRE(dilation >= 1 && dilation <= 8, "%s: dilation %d outside [1, 8]", who, (int)dilation);
-    KTF_REQUIRE(gemm == KTF_GEMM_F32 || gemm == KTF_GEMM_BF16 || gemm == KTF_GEMM_BF16X3, "%s: gemm %d is not KTF_GEMM_F32, _BF16 or _BF16X3", who,
-                (int)gemm);
-    return KTF_OK;
-}
-
 static int r2_lds_bytes(int R, int width, int scale, int dilation) { return 2 * (R + 2 * (scale - 1) * dilation) * (width + 4) * 4; }
 
 extern "C" int32_t ktf_res2_row_tile(int32_t width, int32_t scale, int32_t dilation, int32_t gemm) {
@@ -273,17 +234,12 @@ static void r2_launch_mode(const Res2Params& p, int ncb, dim3 grid, int lds, hip
     }
 }
 
-extern "C" int ktf_res2_conv(const float* x, int64_t B, int64_t T, int32_t C, int64_t ldx, const int32_t* lens, int32_t scale, int32_t dilation,
-                             const float* w, const float* bias, const float* nscale, const float* nshift, int32_t act, int32_t gemm, float* y,
-                             int64_t ldy, void* stream) {
-    const char* who = "ktf_res2_conv";
-    KTF_REQUIRE(B >= 0 && T >= 0 && C > 0, "%s: negative size (B %lld, T %lld, C %d)", who, (long long)B, (long long)T, (int)C);
-    KTF_REQUIRE(B <= KTF_RES2_MAX_BATCH && T <= KTF_RES2_MAX_ROWS, "%s: B %lld above %d or T %lld above %d", who, (long long)B, KTF_RES2_MAX_BATCH,
-                (long long)T, KTF_RES2_MAX_ROWS);
-    KTF_REQUIRE(scale >= 2 && scale <= 8, "%s: scale %d outside [2, 8]", who, (int)scale);
-    KTF_REQUIRE(C % scale == 0, "%s: C %% scale != 0 (C %d, scale %d)", who, (int)C, (int)scale);
-    const int32_t wd = C / scale;
-    if (int rc = r2_check_shape(who, wd, scale, dilation, gemm)) return rc;
+// the forward of both entry points: `train` asks for a exactly when the norm pair is there (include/ktf_res2.h rule 7)
+static int r2_forward(const char* who, bool train, const float* x, int64_t B, int64_t T, int32_t C, int64_t ldx, const int32_t* lens, int32_t scale,
+                      int32_t dilation, const float* w, const float* bias, const float* nscale, const float* nshift, int32_t act, int32_t gemm,
+                      float* y, int64_t ldy, float* a, int64_t lda, void* stream) {
+    int32_t wd = 0;
+    if (int rc = r2_check_sizes(who, B, T, C, scale, dilation, gemm, &wd)) return rc;
     KTF_REQUIRE(ldx >= C && ldy >= C, "%s: ldx %lld or ldy %lld below C %d", who, (long long)ldx, (long long)ldy, (int)C);
     KTF_REQUIRE(ldx % 4 == 0 && ldy % 4 == 0, "%s: ldx %lld and ldy %lld must be multiples of 4", who, (long long)ldx, (long long)ldy);
     KTF_REQUIRE(ldx < (1ll << 31) && ldy < (1ll << 31), "%s: a leading dimension reaches 2^31", who);
@@ -299,11 +255,25 @@ extern "C" int ktf_res2_conv(const float* x, int64_t B, int64_t T, int32_t C, in
         const uintptr_t xn = (uintptr_t)(nx - ldx + C) * 4, yn = (uintptr_t)ny * 4;
         KTF_REQUIRE(!(x0 < y0 + yn && y0 < x0 + xn), "%s: y overlaps x", who);
     }
+    if (train) {
+        KTF_REQUIRE((a != nullptr) == (nscale != nullptr) || rows == 0, "%s: a goes with nscale / nshift: it is missing or misplaced", who);
+        if (nscale) {
+            const int64_t Ca = (int64_t)(scale - 1) * wd;
+            int64_t na = 0;
+            KTF_REQUIRE(lda >= Ca && lda % 4 == 0 && lda < (1ll << 31), "%s: lda %lld below %lld, not a multiple of 4 or at 2^31", who, (long long)lda,
+                        (long long)Ca);
+            KTF_REQUIRE(!__builtin_mul_overflow(rows, lda, &na) && na < (1ll << 60), "%s: B * T * lda reaches 2^60", who);
+            if (rows > 0) {
+                const uintptr_t a0 = (uintptr_t)a, an = (uintptr_t)na * 4, x0 = (uintptr_t)x, y0 = (uintptr_t)y;
+                KTF_REQUIRE(!(a0 < x0 + (uintptr_t)nx * 4 && x0 < a0 + an) && !(a0 < y0 + (uintptr_t)ny * 4 && y0 < a0 + an), "%s: a overlaps x or y", who);
+            }
+        }
+    }
     if (rows == 0) return KTF_OK;
 
     const int R = ktf_res2_row_tile(wd, scale, dilation, gemm);
     Res2Params p = {x, lens, w, bias, nscale, nshift, y, T, ldx, ldy, scale, dilation, act, R, R + 2 * (scale - 1) * dilation,
-                    ((uintptr_t)x & 15) == 0, ((uintptr_t)y & 15) == 0, ((uintptr_t)w & 15) == 0};
+                    ((uintptr_t)x & 15) == 0, ((uintptr_t)y & 15) == 0, ((uintptr_t)w & 15) == 0, train ? a : nullptr, lda, ((uintptr_t)a & 15) == 0};
     const dim3 grid((unsigned)ktf_cdiv(T, R), (unsigned)B);
     const int lds = r2_lds_bytes(R, wd, scale, dilation);
     hipStream_t st = (hipStream_t)stream;
@@ -312,4 +282,16 @@ extern "C" int ktf_res2_conv(const float* x, int64_t B, int64_t T, int32_t C, in
     else r2_launch_mode<KTF_GEMM_BF16X3>(p, wd / 16, grid, lds, st);
     KTF_CHECK_LAUNCH(who);
     return KTF_OK;
+}
+
+extern "C" int ktf_res2_conv(const float* x, int64_t B, int64_t T, int32_t C, int64_t ldx, const int32_t* lens, int32_t scale, int32_t dilation,
+                             const float* w, const float* bias, const float* nscale, const float* nshift, int32_t act, int32_t gemm, float* y,
+                             int64_t ldy, void* stream) {
+    return r2_forward("ktf_res2_conv", false, x, B, T, C, ldx, lens, scale, dilation, w, bias, nscale, nshift, act, gemm, y, ldy, nullptr, 0, stream);
+}
+
+extern "C" int ktf_res2_conv_train(const float* x, int64_t B, int64_t T, int32_t C, int64_t ldx, const int32_t* lens, int32_t scale, int32_t dilation,
+                                   const float* w, const float* bias, const float* nscale, const float* nshift, int32_t act, int32_t gemm, float* y,
+                                   int64_t ldy, float* a, int64_t lda, void* stream) {
+    return r2_forward("ktf_res2_conv_train", true, x, B, T, C, ldx, lens, scale, dilation, w, bias, nscale, nshift, act, gemm, y, ldy, a, lda, stream);
 }

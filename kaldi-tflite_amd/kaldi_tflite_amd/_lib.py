@@ -332,6 +332,13 @@ DENSE_PROTOTYPES = {
 RES2_PROTOTYPES = {
     "ktf_res2_conv": (C.c_int, [_P, _i64, _i64, _i32, _i64, _P, _i32, _i32, _P, _P, _P, _P, _i32, _i32, _P, _i64, _P]),
     "ktf_res2_row_tile": (_i32, [_i32, _i32, _i32, _i32]),
+    "ktf_res2_conv_train": (C.c_int, [_P, _i64, _i64, _i32, _i64, _P, _i32, _i32, _P, _P, _P, _P, _i32, _i32, _P, _i64, _P, _i64, _P]),
+    "ktf_res2_grad_row_tile": (_i32, [_i32, _i32, _i32, _i32]),
+    "ktf_res2_grad_slots": (_i32, [_i64, _i64, _i32, _i32]),
+    "ktf_res2_grad_scratch_floats": (_i32, [_i64, _i64, _i32, _i32]),
+    "ktf_res2_grad_data": (C.c_int, [_P, _i64, _i64, _i32, _i64, _P, _i32, _i32, _P, _P, _P, _i64, _P, _i64, _i32, _i32, _P, _i64, _P, _i64, _P]),
+    "ktf_res2_grad_weights": (C.c_int, [_P, _i64, _i64, _i32, _i64, _P, _i32, _i32, _P, _P, _i64, _P, _i64, _P, _i64, _i32, _i32, _P, _P, _P, _P,
+                                        _P, _i64, _P]),
 }
 RES2_MAX_BATCH, RES2_MAX_ROWS = 65535, 1 << 30   # ktf_res2_*: utterances and frames per call
 ATTN_MAX_BATCH, ATTN_MAX_ROWS, ATTN_MAX_DIM = 65535, 1 << 30, 1 << 20   # ktf_attn_*: utterances, frames and channels per call

@@ -286,6 +286,65 @@ def attentive_stats_pooling(x, e, lens=None, include_std=True, epsilon=1e-10):
                                         float(epsilon))
 
 
+class _Res2Conv(torch.autograd.Function):
+    """include/ktf_res2.h rules 7 - 13: saves x, y, a (with the norm pair only) and lens."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, nscale, nshift, lens, scale, dilation, act, gemm):
+        B, T, C = x.shape
+        x = x.contiguous()
+        w = weight.contiguous()
+        y = torch.zeros_like(x)                                   # rows at and beyond an utterance's length stay zero
+        a = None if nscale is None else torch.empty((B, T, C - C // scale), dtype=torch.float32, device=x.device)
+        c = lambda t: None if t is None else t.contiguous()       # noqa: E731
+        ops.res2_conv_train(x, lens, scale, dilation, w, c(bias), c(nscale), c(nshift), act, gemm, y, a)
+        ctx.save_for_backward(x, y, a, lens, w, c(nscale))
+        ctx.cfg = (scale, dilation, act, gemm, bias is not None)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        x, y, a, lens, w, nscale = ctx.saved_tensors
+        scale, dilation, act, gemm, has_bias = ctx.cfg
+        B, T, C = x.shape
+        wd = C // scale
+        g = gy.to(torch.float32).contiguous()
+        dx = torch.empty_like(x)
+        gt = torch.empty((B, T, C - wd), dtype=torch.float32, device=x.device)
+        ops.res2_grad_data(g, lens, scale, dilation, w, nscale, y, a, act, gemm, dx, gt)      # always: the weights call reads its gt
+        dw = db = dsc = dsh = None
+        need = ctx.needs_input_grad
+        if need[1] or (has_bias and need[2]) or (nscale is not None and (need[3] or need[4])):
+            new = lambda: torch.empty((scale - 1, wd), dtype=torch.float32, device=x.device)      # noqa: E731
+            dw = torch.empty_like(w)
+            db = new() if has_bias else None
+            dsc, dsh = (new(), new()) if nscale is not None else (None, None)
+            ops.res2_grad_weights(x, lens, scale, dilation, nscale, y, a, gt, act, gemm, dw, db, dsc, dsh,
+                                  ops.res2_grad_scratch(B, T, wd, scale, x.device))
+        return dx if need[0] else None, dw, db, dsc, dsh, None, None, None, None, None
+
+
+def res2_conv(x, weight, bias, nscale, nshift, scale, dilation, lens=None, activation="relu", gemm="f32"):
+    """The Res2Net dilated convolution (include/ktf_res2.h), differentiable in x, weight, bias, nscale and nshift: x (B, T, C) fp32 on
+    the GPU with C = scale * wd; weight (scale-1, 3 wd, wd) as [g][k wd + c_in][c_out]; bias (scale-1, wd) or None; nscale / nshift
+    (scale-1, wd), a per-channel affine behind the activation, or both None; activation "relu" or None. One launch forward (which also
+    keeps the activation in front of the affine when there is one), two and a small one backward. Returns (B, T, C) with zero rows at
+    and beyond an utterance's length; gradients arriving for those rows are ignored. gemm: "f32", "bf16" or "bf16x3"."""
+    code = _gemm_code(gemm)
+    _on_gpu(x, "x")
+    _on_gpu(weight, "weight")
+    act = activation.lower() if isinstance(activation, str) else activation
+    if act not in (None, "linear", "relu"):
+        raise ValueError(f"activation must be 'relu' or None, got {activation!r}")
+    if (nscale is None) != (nshift is None):
+        raise ValueError("nscale and nshift go together")
+    if x.dim() != 3:
+        raise ValueError(f"expected a (batch, time, feat) input, got shape {tuple(x.shape)}")
+    f32 = lambda t: None if t is None else t.to(torch.float32)      # noqa: E731
+    return _Res2Conv.apply(x.to(torch.float32), weight.to(torch.float32), f32(bias), f32(nscale), f32(nshift), _lens(lens, x.shape[0], x.device),
+                           int(scale), int(dilation), L.ACT_RELU if act == "relu" else L.ACT_NONE, code)
+
+
 def batch_norm(x, lens, moving_mean, moving_var, gamma, momentum=0.99, epsilon=0.001, training=False):
     """BatchNorm as the project mirrors it (keras BatchNormalization(center=False, scale=True)): y = gamma (x - mean) / sqrt(var +
     epsilon) per feature. Training: mean and (biased) variance over the valid rows of the whole batch, and
@@ -370,6 +429,8 @@ def relu_batch_norm(z, lens, moving_mean, moving_var, gamma, momentum=0.99, epsi
 
 class TrainableSequential(torch.nn.Module):
     """A `ktf.models.Sequential` (or an XvectorExtractor, whose TDNN stack is taken) as a torch module: TDNN -> ReLU -> BatchNorm ...
+    (in front of the pooling also Res2Conv, as `res2_conv`: kernel, bias and -- batch_norm=True -- norm_scale / norm_shift trained as a
+    per-channel affine; batch statistics inside the block are not taken, since stage i + 1 reads stage i normalised)
     -> reducing StatsPooling or AttentiveStatsPooling (its two affines and `attentive_stats_pooling`) -> TDNN (context [0]) ... Parameters start from the layers' current weights; `forward(feats, lens)`
     returns the last layer's output -- (B, T_out, units), or (B, units) behind the pooling -- for `ClassifierHead` (below) or a head and a loss written in torch;
     `export()` writes parameters and moving statistics back into the layers. The layers must be built (a Sequential with an Input, or
@@ -393,7 +454,8 @@ class TrainableSequential(torch.nn.Module):
         pooled = False
         f32 = lambda a: torch.nn.Parameter(torch.as_tensor(a, dtype=torch.float32).to(dev).contiguous().clone())  # noqa: E731
         for l in self.seq.layers:
-            if not isinstance(l, (_layers.TDNN, _layers.ReLU, _layers.BatchNorm, _layers.StatsPooling, _layers.AttentiveStatsPooling)):
+            if not isinstance(l, (_layers.TDNN, _layers.ReLU, _layers.BatchNorm, _layers.StatsPooling, _layers.AttentiveStatsPooling,
+                                  _layers.Res2Conv)):
                 raise NotImplementedError(f"layer '{l.name}' ({type(l).__name__}) has no gradient in ktf.autograd")
             if not l.built and not isinstance(l, (_layers.ReLU, _layers.StatsPooling)):
                 raise ValueError(f"layer '{l.name}' is not built: give the Sequential an Input, run it or load its weights first")
@@ -408,6 +470,14 @@ class TrainableSequential(torch.nn.Module):
                 if l.useBias:
                     self.params.append(f32(l.bias))
                 self.steps.append(("tdnn", l, at))
+            elif isinstance(l, _layers.Res2Conv):
+                if pooled:
+                    raise NotImplementedError(f"layer '{l.name}' (Res2Conv behind the pooling) has no gradient in ktf.autograd")
+                at = len(self.params)                              # kernel (scale-1, 3 w, w), bias, norm_scale, norm_shift (those it has)
+                self.params.append(f32(l.kernel.reshape(l.scale - 1, 3 * l.width, l.width)))
+                for t in ([l.bias] if l.useBias else []) + ([l.normScale, l.normShift] if l.batchNorm else []):
+                    self.params.append(f32(t))
+                self.steps.append(("res2", l, at))
             elif isinstance(l, _layers.BatchNorm):
                 at = len(self.params)
                 self.params.append(f32(l.gamma))
@@ -453,6 +523,11 @@ class TrainableSequential(torch.nn.Module):
             elif kind == "relu":
                 held = into_bn
                 x = x if held else torch.relu(x)
+            elif kind == "res2":
+                rest = list(self.params[at + 1:at + 1 + int(l.useBias) + 2 * int(l.batchNorm)])
+                b = rest.pop(0) if l.useBias else None
+                nsc, nsh = rest if l.batchNorm else (None, None)
+                x = res2_conv(x, self.params[at], b, nsc, nsh, l.scale, l.dilation, lens, l.activation, self.gemm)
             elif kind == "bn" and self.fused_norm:
                 x = relu_batch_norm(x, None if pooled else lens, getattr(self, f"moving_mean_{at}"), getattr(self, f"moving_var_{at}"),
                                     self.params[at], l.momentum, l.epsilon, self.training, relu=held)
@@ -481,6 +556,10 @@ class TrainableSequential(torch.nn.Module):
             elif kind == "bn":
                 l.set_weights([self.params[at].detach().cpu().numpy(), getattr(self, f"moving_mean_{at}").cpu().numpy(),
                                getattr(self, f"moving_var_{at}").cpu().numpy()], fmt="tensorflow")
+            elif kind == "res2":
+                n = 1 + int(l.useBias) + 2 * int(l.batchNorm)
+                ws = [self.params[at + k].detach().cpu().numpy() for k in range(n)]
+                l.set_weights([ws[0].reshape(l.scale - 1, 3, l.width, l.width)] + ws[1:], fmt="tensorflow")
             elif kind == "attn":
                 w1, b1, w2, b2 = (self.params[at + k].detach().cpu().numpy() for k in range(4))
                 l.set_weights([w1[:, 0, :].T, b1, w2[:, 0, :].T, b2], fmt="tensorflow")

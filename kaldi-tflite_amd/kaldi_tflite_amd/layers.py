@@ -1079,7 +1079,7 @@ class Res2Conv(Layer):
     """The hierarchical, grouped, dilated convolution of a Res2Net block (include/ktf_res2.h): the C input channels are cut into `scale`
     groups of width C / scale; group 0 passes through, group i >= 1 is a three-tap convolution at distance `dilation` (edge rows
     replicated, as TDNN(padding="SAME")) of X_i + Y_{i-1}, then `activation` ("relu" or None) and, with `batch_norm`, the folded inference
-    BatchNorm y * norm_scale + norm_shift. One launch, inference only. The weights in keras order are [kernel (scale-1, 3, w, w) as
+    BatchNorm y * norm_scale + norm_shift. One launch; training goes through ktf.autograd.res2_conv. The weights in keras order are [kernel (scale-1, 3, w, w) as
     [g, k, in, out], bias (scale-1, w), norm_scale (scale-1, w), norm_shift (scale-1, w)] (without the ones the layer does not have)."""
 
     MIN_WIDTH, MAX_WIDTH = 16, 128

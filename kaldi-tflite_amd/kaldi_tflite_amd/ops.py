@@ -1807,6 +1807,86 @@ def res2_conv(x, lens, scale, dilation, w, bias, nscale, nshift, act, gemm, y, C
     return y
 
 
+def _res2_rows(C, **rows):
+    """(pointer, row stride) per (B, T, ld) fp32 operand of the Res2 training calls (None: a null pointer), all with the same B and T;
+    -> B, T, C (default: every column of the first operand), {name: (pointer, ld)}."""
+    first = next(iter(rows.values()))
+    if first.dim() != 3:
+        raise ValueError(f"a (B, T, ld) tensor is expected, got {tuple(first.shape)}")
+    out = {}
+    for name, t in rows.items():
+        if t is None:
+            out[name] = (None, 0)
+            continue
+        if t.dim() != 3 or t.shape[:2] != first.shape[:2]:
+            raise ValueError(f"{name}: (B, T, ld) with B, T = {tuple(first.shape[:2])} is expected, got {tuple(t.shape)}")
+        out[name] = _attn_rows(name, t)
+    return first.shape[0], first.shape[1], first.shape[2] if C is None else int(C), out
+
+
+def _res2_params(s, C, **params):
+    """The (scale-1, ...) fp32 parameters and the int32 lens of a Res2 call: dense, of their dtype and shape (a C the library will
+    refuse passes: it gets to say why)."""
+    wd = C // s if s >= 2 and C > 0 and C % s == 0 else None
+    for name, t in params.items():
+        if t is None:
+            continue
+        _need_dense(name, t)
+        shape = None if wd is None or name == "lens" else ((s - 1, 3 * wd, wd) if name in ("w", "dw") else (s - 1, wd))
+        if t.dtype != (torch.int32 if name == "lens" else torch.float32) or (shape is not None and tuple(t.shape) != shape):
+            raise ValueError(f"{name}: expected {shape} {'int32' if name == 'lens' else 'fp32'}, got {t.dtype} {tuple(t.shape)}")
+
+
+def res2_conv_train(x, lens, scale, dilation, w, bias, nscale, nshift, act, gemm, y, a, C=None):
+    """res2_conv for training: also writes a (B, T, lda) fp32, the (scale-1) wd columns of act(Z_i) before the norm -- required exactly
+    when nscale is given, None otherwise. y has the bits of res2_conv."""
+    B, T, C, r = _res2_rows(C, x=x, y=y, a=a)
+    s = int(scale)
+    _res2_params(s, C, w=w, bias=bias, nscale=nscale, nshift=nshift, lens=lens)
+    _call("ktf_res2_conv_train", x.device, r["x"][0], B, T, C, r["x"][1], L.ptr(lens), s, int(dilation), L.ptr(w), L.ptr(bias), L.ptr(nscale),
+          L.ptr(nshift), int(act), int(gemm), r["y"][0], r["y"][1], r["a"][0], r["a"][1])
+    return y, a
+
+
+def res2_grad_row_tile(width, scale, dilation, gemm=L.GEMM_F32):
+    """Rows of dx per workgroup of res2_grad_data."""
+    return _size("ktf_res2_grad_row_tile", int(width), int(scale), int(dilation), int(gemm))
+
+
+def res2_grad_slots(B, T, width, scale):
+    """Row slots of res2_grad_weights for a (B, T) batch: a function of these four numbers only."""
+    return _size("ktf_res2_grad_slots", int(B), int(T), int(width), int(scale))
+
+
+def res2_grad_scratch(B, T, width, scale, device):
+    """The fp32 scratch res2_grad_weights takes."""
+    return torch.empty((_size("ktf_res2_grad_scratch_floats", int(B), int(T), int(width), int(scale)),), dtype=torch.float32, device=device)
+
+
+def res2_grad_data(g, lens, scale, dilation, w, nscale, y, a, act, gemm, dx, gt, C=None):
+    """The data gradient in one launch: g (B, T, ldg) = dL/dy -> dx (B, T, lddx), rows at and beyond an utterance's length zero, and
+    gt (B, T, ldgt), the (scale-1) wd columns of G_i + dU_{i+1} that res2_grad_weights takes. y and a are res2_conv_train's."""
+    B, T, C, r = _res2_rows(C, g=g, y=y, a=a, dx=dx, gt=gt)
+    s = int(scale)
+    _res2_params(s, C, w=w, nscale=nscale, lens=lens)
+    _call("ktf_res2_grad_data", g.device, r["g"][0], B, T, C, r["g"][1], L.ptr(lens), s, int(dilation), L.ptr(w), L.ptr(nscale), r["y"][0], r["y"][1],
+          r["a"][0], r["a"][1], int(act), int(gemm), r["dx"][0], r["dx"][1], r["gt"][0], r["gt"][1])
+    return dx, gt
+
+
+def res2_grad_weights(x, lens, scale, dilation, nscale, y, a, gt, act, gemm, dw, dbias, dnscale, dnshift, scratch, C=None):
+    """dw (scale-1, 3 wd, wd) and dbias / dnscale / dnshift (scale-1, wd; each may be None) from x, the training forward's y and a, and
+    the gt of res2_grad_data; scratch from res2_grad_scratch."""
+    B, T, C, r = _res2_rows(C, x=x, y=y, a=a, gt=gt)
+    s = int(scale)
+    _res2_params(s, C, nscale=nscale, lens=lens, dw=dw, dbias=dbias, dnscale=dnscale, dnshift=dnshift)
+    _need_dense("scratch", scratch)
+    _call("ktf_res2_grad_weights", x.device, r["x"][0], B, T, C, r["x"][1], L.ptr(lens), s, int(dilation), L.ptr(nscale), r["y"][0], r["y"][1],
+          r["a"][0], r["a"][1], r["gt"][0], r["gt"][1], int(act), int(gemm), L.ptr(dw), L.ptr(dbias), L.ptr(dnscale), L.ptr(dnshift),
+          L.ptr(scratch), 0 if scratch is None else scratch.numel())
+    return dw, dbias, dnscale, dnshift
+
+
 # ----------------------------------------------------------------------------- training examples (include/ktf_egs.h)
 EGS_DTYPES = {torch.float32: L.KTF_F32, torch.float16: L.KTF_F16}
 
