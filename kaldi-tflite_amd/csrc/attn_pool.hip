@@ -13,6 +13,7 @@
 // shares its wave with others: its slots beyond the channel count hold +0, so the first stages of the butterfly add +0 and are
 // replaced by one `+ 0.0`, which gives the same bits.
 #include "common.h"
+#include "canon_sum.h"
 #include "../../include/ktf_attn.h"
 
 // An utterance without a row (rule 10): the finalize of stats_pool_kernel (pool_post.hip) on its sums s = q = 0 and n = 0, in that
@@ -32,23 +33,6 @@ __device__ __forceinline__ void ap_empty_row(double s, double q, double n, int i
 #define AP_THREADS 1024
 
 __device__ __forceinline__ double ap_keep_nan_relu(double v) { return v < 0.0 ? 0.0 : v; }    // NaN < 0 is false: NaN stays
-
-// the canonical total of one column of red[RG][..][CW] (slot g of RG at r[g * stride])
-template <int RG>
-__device__ __forceinline__ double ap_total(const double* r, int stride) {
-    double s = 0.;
-#pragma unroll
-    for (int g = 0; g < 16; ++g) {
-        if (RG == 16) s += r[g * stride];
-        else s += ((r[g * stride] + r[(g + 16) * stride]) + r[(g + 32) * stride]) + r[(g + 48) * stride];
-    }
-    return s;
-}
-
-__device__ __forceinline__ int ap_len(const int32_t* lens, int b, int64_t T) {
-    int len = lens ? lens[b] : (int)T;
-    return len < 0 ? 0 : (len > (int)T ? (int)T : len);
-}
 
 // ------------------------------------------------------------------------------------ m and Z of every (utterance, head)
 template <int CW>

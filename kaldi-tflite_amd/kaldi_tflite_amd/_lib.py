@@ -341,6 +341,14 @@ RES2_PROTOTYPES = {
                                         _P, _i64, _P]),
 }
 RES2_MAX_BATCH, RES2_MAX_ROWS = 65535, 1 << 30   # ktf_res2_*: utterances and frames per call
+# name -> (restype, argtypes); mirrors include/ktf_se.h one to one
+SE_PROTOTYPES = {
+    "ktf_se_gate": (C.c_int, [_P, _i64, _i64, _i32, _i64, _P, _i64, _P, _P, _P, _P, _P, _i32, _P, _i64, _P, _P]),
+    "ktf_se_gate_train": (C.c_int, [_P, _i64, _i64, _i32, _i64, _P, _i64, _P, _P, _P, _P, _P, _i32, _P, _i64, _P, _P, _P, _P]),
+    "ktf_se_gate_backward_workspace_bytes": (_i64, [_i64, _i32, _i32]),
+    "ktf_se_gate_backward": (C.c_int, [_P, _i64, _i64, _i32, _i64, _P, _i64, _P, _P, _P, _i32, _P, _P, _P, _P, _i64, _P, _P, _P, _P, _P,
+                                       C.c_size_t, _P]),
+}
 ATTN_MAX_BATCH, ATTN_MAX_ROWS, ATTN_MAX_DIM = 65535, 1 << 30, 1 << 20   # ktf_attn_*: utterances, frames and channels per call
 HEAD_MAX_CENTERS, HEAD_MAX_TOPK = 8, 64   # ktf_head_*: sub-centres per class; penalised classes per row
 OPTIM_SGD, OPTIM_ADAM, OPTIM_MAX_GROUPS = 0, 1, 8   # ktf_optim_*: kind; groups per call
@@ -377,7 +385,8 @@ def load():
     for name, (res, args) in (list(PROTOTYPES.items()) + list(AUGMENT_PROTOTYPES.items()) + list(RESAMPLE_PROTOTYPES.items())
                               + list(GRAD_PROTOTYPES.items()) + list(NORM_PROTOTYPES.items()) + list(LOSS_PROTOTYPES.items())
                               + list(EGS_PROTOTYPES.items()) + list(OPTIM_PROTOTYPES.items()) + list(HEAD_PROTOTYPES.items())
-                              + list(ATTN_PROTOTYPES.items()) + list(DENSE_PROTOTYPES.items()) + list(RES2_PROTOTYPES.items())):
+                              + list(ATTN_PROTOTYPES.items()) + list(DENSE_PROTOTYPES.items()) + list(RES2_PROTOTYPES.items())
+                              + list(SE_PROTOTYPES.items())):
         fn = getattr(lib, name)          # AttributeError = header/library mismatch
         fn.restype = res
         fn.argtypes = args

@@ -345,6 +345,57 @@ def res2_conv(x, weight, bias, nscale, nshift, scale, dilation, lens=None, activ
                            int(scale), int(dilation), L.ACT_RELU if act == "relu" else L.ACT_NONE, code)
 
 
+class _SqueezeExcite(torch.autograd.Function):
+    """include/ktf_se.h: saves x, lens, mean, hid and gate (and the two weight matrices), nothing else of the activation's size."""
+
+    @staticmethod
+    def forward(ctx, x, w1, b1, w2, b2, lens, residual):
+        B, T, C = x.shape
+        x, w1, w2 = x.contiguous(), w1.contiguous(), w2.contiguous()
+        c = lambda t: None if t is None else t.contiguous()       # noqa: E731
+        y = torch.empty_like(x) if lens is None else torch.zeros_like(x)      # rows at and beyond an utterance's length stay zero
+        mean = torch.empty((B, C), dtype=torch.float64, device=x.device)
+        hid = torch.empty((B, w1.shape[1]), dtype=torch.float64, device=x.device)
+        gate = torch.empty((B, C), dtype=torch.float32, device=x.device)
+        ops.se_gate_train(x, c(residual), lens, w1, c(b1), w2, c(b2), y, mean, hid, gate)
+        ctx.save_for_backward(x, lens, mean, hid, gate, w1, w2)
+        ctx.has = (b1 is not None, b2 is not None, residual is not None)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        x, lens, mean, hid, gate, w1, w2 = ctx.saved_tensors
+        has_b1, has_b2, has_r = ctx.has
+        B, T, C = x.shape
+        H = w1.shape[1]
+        g = gy.to(torch.float32).contiguous()
+        need = ctx.needs_input_grad
+        new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=x.device)      # noqa: E731
+        dx = torch.empty_like(x)
+        dw1 = new(C, H) if need[1] else None
+        db1 = new(H) if has_b1 and need[2] else None
+        dw2 = new(H, C) if need[3] else None
+        db2 = new(C) if has_b2 and need[4] else None
+        ops.se_gate_backward(g, x, lens, w1, w2, mean, hid, gate, dx, dw1, db1, dw2, db2, ops.se_gate_backward_workspace(B, C, H, x.device))
+        return dx if need[0] else None, dw1, db1, dw2, db2, None, (gy if has_r and need[6] else None)
+
+
+def squeeze_excite(x, w1, b1, w2, b2, lens=None, residual=None):
+    """The squeeze-excitation gate with the skip connection fused in (include/ktf_se.h), differentiable in x, w1, b1, w2, b2 and
+    residual: x and residual (or None) (B, T, C) fp32 on the GPU, w1 (C, H), b1 (H,) or None, w2 (H, C), b2 (C,) or None ->
+    x * sigmoid(relu(mean_t(x) w1 + b1) w2 + b2) + residual, (B, T, C) with zero rows at and beyond an utterance's length; gradients
+    arriving for those rows are ignored, except that the residual's gradient is the arriving gradient itself. Three launches
+    forward, four backward. One arithmetic: there is no gemm mode."""
+    if not isinstance(x, torch.Tensor) or x.dim() != 3:
+        raise ValueError(f"expected a (batch, time, feat) input, got shape {tuple(getattr(x, 'shape', ()))}")
+    if residual is not None and residual.shape != x.shape:
+        raise ValueError(f"the residual has shape {tuple(residual.shape)}, the input {tuple(x.shape)}")
+    _on_gpu(x, "x")
+    _on_gpu(w1, "w1")
+    f32 = lambda t: None if t is None else t.to(torch.float32)      # noqa: E731
+    return _SqueezeExcite.apply(x.to(torch.float32), f32(w1), f32(b1), f32(w2), f32(b2), _lens(lens, x.shape[0], x.device), f32(residual))
+
+
 def batch_norm(x, lens, moving_mean, moving_var, gamma, momentum=0.99, epsilon=0.001, training=False):
     """BatchNorm as the project mirrors it (keras BatchNormalization(center=False, scale=True)): y = gamma (x - mean) / sqrt(var +
     epsilon) per feature. Training: mean and (biased) variance over the valid rows of the whole batch, and
@@ -429,7 +480,7 @@ def relu_batch_norm(z, lens, moving_mean, moving_var, gamma, momentum=0.99, epsi
 
 class TrainableSequential(torch.nn.Module):
     """A `ktf.models.Sequential` (or an XvectorExtractor, whose TDNN stack is taken) as a torch module: TDNN -> ReLU -> BatchNorm ...
-    (in front of the pooling also Res2Conv, as `res2_conv`: kernel, bias and -- batch_norm=True -- norm_scale / norm_shift trained as a
+    (in front of the pooling also SqueezeExcite, as `squeeze_excite`, with the output of the layer `residual_from` names kept for it, and Res2Conv, as `res2_conv`: kernel, bias and -- batch_norm=True -- norm_scale / norm_shift trained as a
     per-channel affine; batch statistics inside the block are not taken, since stage i + 1 reads stage i normalised)
     -> reducing StatsPooling or AttentiveStatsPooling (its two affines and `attentive_stats_pooling`) -> TDNN (context [0]) ... Parameters start from the layers' current weights; `forward(feats, lens)`
     returns the last layer's output -- (B, T_out, units), or (B, units) behind the pooling -- for `ClassifierHead` (below) or a head and a loss written in torch;
@@ -451,11 +502,12 @@ class TrainableSequential(torch.nn.Module):
         dev = ops.default_device() if device is None else torch.device(device)
         self.steps = []                     # (kind, the layer, index into self.params / self.stats)
         self.params = torch.nn.ParameterList()
+        self.keep = set()                   # names of the layers whose output a SqueezeExcite adds as its residual
         pooled = False
         f32 = lambda a: torch.nn.Parameter(torch.as_tensor(a, dtype=torch.float32).to(dev).contiguous().clone())  # noqa: E731
         for l in self.seq.layers:
             if not isinstance(l, (_layers.TDNN, _layers.ReLU, _layers.BatchNorm, _layers.StatsPooling, _layers.AttentiveStatsPooling,
-                                  _layers.Res2Conv)):
+                                  _layers.Res2Conv, _layers.SqueezeExcite)):
                 raise NotImplementedError(f"layer '{l.name}' ({type(l).__name__}) has no gradient in ktf.autograd")
             if not l.built and not isinstance(l, (_layers.ReLU, _layers.StatsPooling)):
                 raise ValueError(f"layer '{l.name}' is not built: give the Sequential an Input, run it or load its weights first")
@@ -478,6 +530,16 @@ class TrainableSequential(torch.nn.Module):
                 for t in ([l.bias] if l.useBias else []) + ([l.normScale, l.normShift] if l.batchNorm else []):
                     self.params.append(f32(t))
                 self.steps.append(("res2", l, at))
+            elif isinstance(l, _layers.SqueezeExcite):
+                if pooled:
+                    raise NotImplementedError(f"layer '{l.name}' (SqueezeExcite behind the pooling) has no gradient in ktf.autograd")
+                at = len(self.params)                              # W1 (C, H), b1, W2 (H, C), b2
+                for t in l.get_weights():
+                    self.params.append(f32(t))
+                if l.residualFrom is not None:                     # (the Sequential's plan checks the name, the widths and the lengths)
+                    self.seq._plan()
+                    self.keep.add(l.residualFrom)
+                self.steps.append(("se", l, at))
             elif isinstance(l, _layers.BatchNorm):
                 at = len(self.params)
                 self.params.append(f32(l.gamma))
@@ -508,7 +570,13 @@ class TrainableSequential(torch.nn.Module):
         x, pooled = feats, False
         lens = _lens(lens, feats.shape[0], feats.device)
         held = False                                               # a ReLU waiting for the BatchNorm behind it (fused_norm)
+        kept = {}
         for i, (kind, l, at) in enumerate(self.steps):
+            if i and self.steps[i - 1][1].name in self.keep:
+                if held:
+                    raise NotImplementedError(f"layer '{self.steps[i - 1][1].name}' is a residual source whose ReLU is fused into the BatchNorm "
+                                              "behind it (fused_norm): name the BatchNorm")
+                kept[self.steps[i - 1][1].name] = x
             into_bn = self.fused_norm and i + 1 < len(self.steps) and self.steps[i + 1][0] == "bn"
             if kind == "tdnn":
                 w, b = self.params[at], self.params[at + 1] if l.useBias else None
@@ -528,6 +596,8 @@ class TrainableSequential(torch.nn.Module):
                 b = rest.pop(0) if l.useBias else None
                 nsc, nsh = rest if l.batchNorm else (None, None)
                 x = res2_conv(x, self.params[at], b, nsc, nsh, l.scale, l.dilation, lens, l.activation, self.gemm)
+            elif kind == "se":
+                x = squeeze_excite(x, *self.params[at:at + 4], lens=lens, residual=kept.pop(l.residualFrom) if l.residualFrom else None)
             elif kind == "bn" and self.fused_norm:
                 x = relu_batch_norm(x, None if pooled else lens, getattr(self, f"moving_mean_{at}"), getattr(self, f"moving_var_{at}"),
                                     self.params[at], l.momentum, l.epsilon, self.training, relu=held)
@@ -560,6 +630,8 @@ class TrainableSequential(torch.nn.Module):
                 n = 1 + int(l.useBias) + 2 * int(l.batchNorm)
                 ws = [self.params[at + k].detach().cpu().numpy() for k in range(n)]
                 l.set_weights([ws[0].reshape(l.scale - 1, 3, l.width, l.width)] + ws[1:], fmt="tensorflow")
+            elif kind == "se":
+                l.set_weights([self.params[at + k].detach().cpu().numpy() for k in range(4)], fmt="tensorflow")
             elif kind == "attn":
                 w1, b1, w2, b2 = (self.params[at + k].detach().cpu().numpy() for k in range(4))
                 l.set_weights([w1[:, 0, :].T, b1, w2[:, 0, :].T, b2], fmt="tensorflow")

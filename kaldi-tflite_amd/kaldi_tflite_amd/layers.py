@@ -1214,6 +1214,113 @@ class Res2Conv(Layer):
         return self.forward(_f32_rows(x), None, self.gemm)
 
 
+# =============================================================================== squeeze-excitation
+class SqueezeExcite(Layer):
+    """The squeeze-excitation gate of an SE-Res2Block with the block's skip connection fused in (include/ktf_se.h):
+    y = x * sigmoid(relu(mean_t(x) W1 + b1) W2 + b2) + residual, the mean over the frames below each utterance's length, in three
+    launches; training goes through ktf.autograd.squeeze_excite. `bottleneck` is the width H of the hidden layer; `residual_from`
+    names the earlier frame-level layer of the same Sequential whose output is added (None: no skip connection). The weights in
+    keras order are [W1 (C, H), b1 (H,), W2 (H, C), b2 (C,)]. There is one arithmetic: every `gemm` mode of a model runs it."""
+
+    MAX_DIM, MAX_HIDDEN = 4096, 1024
+
+    def __init__(self, bottleneck, residual_from=None, name=None, **kwargs):
+        super().__init__(trainable=True, name=name, **kwargs)
+        self.bottleneck = int(bottleneck)
+        if not 1 <= self.bottleneck <= self.MAX_HIDDEN:
+            raise ValueError(f"'bottleneck' must be in [1, {self.MAX_HIDDEN}], got {bottleneck}")
+        if residual_from is not None and not isinstance(residual_from, str):
+            raise ValueError(f"'residual_from' is a layer name or None, got {residual_from!r}")
+        self.residualFrom = residual_from
+        self.batchAxis, self.timeAxis, self.featAxis = 0, 1, -1
+        self.w1 = self.b1 = self.w2 = self.b2 = None
+        self._dev = {}
+        self._version = 0      # bumped whenever the weights change: models refuse stale captured graphs
+
+    def _check_dim(self, C):
+        if C < 4 or C % 4 or C > self.MAX_DIM:
+            raise ValueError(f"the {C} input channels are not a multiple of 4 in [4, {self.MAX_DIM}]")
+
+    def build(self, input_shape):
+        C, H = input_shape[self.featAxis], self.bottleneck
+        self._check_dim(C)
+        self.inputDim = C
+        if self.w1 is None or self.w1.shape != (C, H):
+            rng = np.random.default_rng(zlib.crc32(self.name.encode()))      # (from the name: every rank draws the same, as TDNN.build)
+            lim = np.sqrt(6.0 / (C + H))
+            self.w1 = rng.uniform(-lim, lim, (C, H)).astype(np.float32)
+            self.w2 = rng.uniform(-lim, lim, (H, C)).astype(np.float32)
+            self.b1, self.b2 = np.zeros(H, np.float32), np.zeros(C, np.float32)
+            self._version += 1
+            WEIGHTS_EPOCH[0] += 1
+        self._dev = {}
+        self.built = True
+
+    def get_config(self):
+        c = super().get_config()
+        c.update({"bottleneck": self.bottleneck, "residual_from": self.residualFrom})
+        return c
+
+    def get_weights(self):
+        return [] if self.w1 is None else [self.w1, self.b1, self.w2, self.b2]
+
+    def set_weights(self, weights, fmt="tensorflow"):
+        """[W1, b1, W2, b2]. fmt "tensorflow": W1 (C, H), W2 (H, C), what get_weights() gives; "torch": the weights of the two
+        Conv1d(kernel_size=1) / Linear modules, (H, C) and (C, H), a trailing kernel axis of 1 accepted."""
+        fmt = fmt.lower()
+        if fmt not in ["tensorflow", "torch"]:
+            raise ValueError(f"expected 'fmt' to be either 'tensorflow' or 'torch', got {fmt}")
+        if len(weights) != 4:
+            raise ValueError(f"expected a weight list of length 4, got {len(weights)}")
+        w1, b1, w2, b2 = (np.asarray(getattr(a, "detach", lambda: a)(), np.float32) for a in weights)
+        if fmt == "torch":
+            w1, w2 = (a[..., 0] if a.ndim == 3 and a.shape[-1] == 1 else a for a in (w1, w2))
+            w1, w2 = (a.T if a.ndim == 2 else a for a in (w1, w2))
+        H = self.bottleneck
+        C = self.inputDim if self.built else (w1.shape[0] if w1.ndim == 2 else -1)
+        if w1.shape != (C, H) or w2.shape != (H, C):
+            raise ValueError(f"expected W1 {(C, H)} and W2 {(H, C)}, got {w1.shape} and {w2.shape}")
+        if b1.reshape(-1).shape != (H,) or b2.reshape(-1).shape != (C,):
+            raise ValueError(f"expected b1 {(H,)} and b2 {(C,)}, got {b1.shape} and {b2.shape}")
+        self._check_dim(C)
+        self.w1, self.w2 = np.ascontiguousarray(w1), np.ascontiguousarray(w2)
+        self.b1, self.b2 = np.ascontiguousarray(b1.reshape(-1)), np.ascontiguousarray(b2.reshape(-1))
+        self.inputDim = C
+        self._dev = {}
+        self._version += 1
+        WEIGHTS_EPOCH[0] += 1
+        self.built = True
+
+    def device_weights(self, device):
+        """(w1, b1, w2, b2) fp32 on the device: one set per device, dropped when the weights change."""
+        key = str(device)
+        if key not in self._dev:
+            self._dev[key] = tuple(ops.to_device_f32(a, device) for a in (self.w1, self.b1, self.w2, self.b2))
+        return self._dev[key]
+
+    def forward(self, x, lens=None, residual=None, out=None, gate=None):
+        """The three launches: x and residual (or None) (B, T, C) fp32 views of rows whose stride is a multiple of 4; lens (B,) int32
+        or None; out likewise (default: fresh zeroed rows; it may be `residual`); gate: a workspace of ops.se_gate_floats(B, C) fp32
+        (default: fresh). Rows at or beyond an utterance's length are left as they are."""
+        B, T, C = x.shape
+        if C != self.inputDim:
+            raise ValueError(f"expected input feature dim {self.inputDim}, got {C}")
+        if residual is not None and tuple(residual.shape) != (B, T, C):
+            raise ValueError(f"the residual has shape {tuple(residual.shape)}, the input {(B, T, C)}")
+        if out is None:
+            out = torch.zeros((B, T, C), dtype=torch.float32, device=x.device)
+        if gate is None:
+            gate = torch.empty((ops.se_gate_floats(B, C),), dtype=torch.float32, device=x.device)
+        w1, b1, w2, b2 = self.device_weights(x.device)
+        return ops.se_gate(x, residual, lens, w1, b1, w2, b2, out, gate, C=C)
+
+    def call(self, inputs, residual=None):
+        x = inputs
+        if x.dim() != 3:
+            raise ValueError(f"expected a (batch, time, feat) input, got shape {tuple(x.shape)}")
+        return self.forward(_f32_rows(x), None, None if residual is None else _f32_rows(_to_device(residual)))
+
+
 # =============================================================================== stats
 class StatsPooling(Layer):
     """layers/stats/stats_pooling.py:26 — mean (+ std) pooling over the whole utterance or sliding windows."""

@@ -20,7 +20,7 @@ from . import _lib as L
 from . import ops
 from ._host import is_real
 from .io import KaldiNnet3Reader, ReadKaldiArray
-from .layers import (TDNN, AttentiveStatsPooling, BatchNorm, CMVN, Framing, MFCC, ReLU, Res2Conv, StatsPooling, VAD, _GEMM, WEIGHTS_EPOCH,
+from .layers import (TDNN, AttentiveStatsPooling, BatchNorm, CMVN, Framing, MFCC, ReLU, Res2Conv, SqueezeExcite, StatsPooling, VAD, _GEMM, WEIGHTS_EPOCH,
                      _f32_rows)
 from .mx import Planes
 
@@ -43,6 +43,7 @@ _LAYER_KINDS = (
     (("stats", "stats_extraction", "stats_pooling"), StatsPooling, "{}", True),
     (("attentive_stats", "attentive_stats_pooling"), AttentiveStatsPooling, "{}", True),
     (("res2_conv",), Res2Conv, "{}", True),
+    (("squeeze_excite",), SqueezeExcite, "{}", True),
 )
 _KIND_OF = {alias: row for row in _LAYER_KINDS for alias in row[0]}
 
@@ -50,7 +51,7 @@ _KIND_OF = {alias: row for row in _LAYER_KINDS for alias in row[0]}
 def cfg2layers(layerCfg):
     """One entry of `model_config.layers` -> the layers it stands for, in order. `type` is a kind or a list of kinds
     ("affine" | "tdnn", "relu", "batchnorm" | "bn", "stats" | "stats_extraction" | "stats_pooling", "attentive_stats" |
-    "attentive_stats_pooling", "res2_conv"); the entry's `cfg` holds the keyword arguments of its parametrised layer. KeyError without a `type`, ValueError for an unknown one."""
+    "attentive_stats_pooling", "res2_conv", "squeeze_excite"); the entry's `cfg` holds the keyword arguments of its parametrised layer. KeyError without a `type`, ValueError for an unknown one."""
     kinds = layerCfg.get("type") or []
     if isinstance(kinds, str):
         kinds = [kinds]
@@ -138,6 +139,7 @@ class _RunState:
         self.ws, self.dev, self.x, self.lens, self.gemm, self.pairs = ws, x.device, x, lens, gemm, pairs
         self.tail_at, self.tail, self.deferred = tail_at, tail, None
         self.mxp = self.planes = self.pending_bn = None
+        self.resid = None                                # fp32 rows kept for a SqueezeExcite(residual_from=...)
         self.x_pair = self.pooled = self.skip = False
         self._rows, self._rows_for = None, None
 
@@ -261,7 +263,7 @@ class Sequential:
     def weights_signature(self):
         """Changes whenever a TDNN / BatchNorm layer's weights change (set_weights, a re-build): captured graphs
         are tied to it."""
-        return tuple((id(l), l._version) for l in self.layers if isinstance(l, (TDNN, BatchNorm, AttentiveStatsPooling, Res2Conv)))
+        return tuple((id(l), l._version) for l in self.layers if isinstance(l, (TDNN, BatchNorm, AttentiveStatsPooling, Res2Conv, SqueezeExcite)))
 
     def get_layer(self, name):
         for l in self.layers:
@@ -279,9 +281,36 @@ class Sequential:
         """Group [TDNN(no act), ReLU, BatchNorm] runs; returns None if a layer outside the fusable set is present."""
         steps, i, Ls = [], 0, self.layers
         pooled = False
+        # for SqueezeExcite(residual_from=...): layer name -> (its step, output width, count of length-changing layers so far), or None
+        # for a layer whose output a fused step never writes; `width` / `cuts` follow the frame-level rows
+        named, width, cuts = {}, None, 0
         while i < len(Ls):
             l = Ls[i]
-            if isinstance(l, TDNN):
+            if not pooled:
+                for k in range(i, len(Ls)):                  # (a TDNN's ReLU / BatchNorm: only the last layer of the step has an output)
+                    named.setdefault(Ls[k].name, None)
+                    if not (isinstance(Ls[k], (TDNN, ReLU)) and k + 1 < len(Ls) and isinstance(Ls[k + 1], (ReLU, BatchNorm))):
+                        break
+            if isinstance(l, SqueezeExcite):
+                if pooled:
+                    return None
+                src = None
+                if l.residualFrom is not None:
+                    if named.get(l.residualFrom) is None:
+                        raise ValueError(f"layer '{l.name}': residual_from = '{l.residualFrom}' names no earlier frame-level layer of this model "
+                                         "in front of the pooling whose output is written (the last layer of a fused TDNN / ReLU / BatchNorm run)")
+                    src, swidth, scuts = named[l.residualFrom]
+                    if swidth is not None and width is not None and swidth != width:
+                        raise ValueError(f"layer '{l.name}': the residual from '{l.residualFrom}' has width {swidth}, the input {width}")
+                    if scuts != cuts:
+                        raise ValueError(f"layer '{l.name}': a subsampling or context-shrinking layer between '{l.residualFrom}' and this one "
+                                         "changes the lengths")
+                    if any(st[0] == "se" and st[2] is not None and src < k for k, st in enumerate(steps)):
+                        raise ValueError(f"layer '{l.name}': one residual is outstanding at a time")
+                steps.append(("se", l, src))
+                named[l.name] = (len(steps) - 1, width, cuts)
+                i += 1
+            elif isinstance(l, TDNN):
                 # behind a reducing StatsPooling the runner stacks the pooled vectors as ONE B-row matrix: right for a layer that looks
                 # at its own frame only (every x-vector network); any other context would read the neighbouring UTTERANCES' rows
                 if pooled and (list(l.context) != [0] or l.subsamplingFactor != 1):
@@ -295,6 +324,10 @@ class Sequential:
                     bn = Ls[j]
                     j += 1
                 steps.append(("tdnn", l, relu, bn))
+                width = l.units
+                cuts += int((l.padding == "VALID" and list(l.context) != [0]) or l.subsamplingFactor != 1)
+                if not pooled:
+                    named[Ls[j - 1].name] = (len(steps) - 1, width, cuts)
                 i = j
             elif isinstance(l, StatsPooling) and l.reduce:
                 steps.append(("stats", l))
@@ -306,9 +339,12 @@ class Sequential:
                 i += 1
             elif isinstance(l, Res2Conv) and not pooled:
                 steps.append(("res2", l))
+                named[l.name] = (len(steps) - 1, width, cuts)
                 i += 1
             elif isinstance(l, (ReLU, BatchNorm)):
                 steps.append(("eltwise", l))
+                if not pooled:
+                    named[l.name] = (len(steps) - 1, width, cuts)
                 i += 1
             else:
                 return None
@@ -388,6 +424,7 @@ class Sequential:
         gemm, pairs = self._batch_route(x.shape[0], x.shape[1], mode=mode)
         tail_at = self._tail_step(steps) if defer_tail else -1
         c = _RunState(self._ws, x, lens, gemm, pairs, tail_at, steps[tail_at][1] if tail_at >= 0 else None)
+        sources = {t[2] for t in steps if t[0] == "se"} - {None}      # steps whose output is a SqueezeExcite's residual: fp32 rows, kept
         for si, st in enumerate(steps):
             if c.skip:                                   # (pooled in the epilogue of the layer in front of it)
                 c.skip = False
@@ -395,9 +432,14 @@ class Sequential:
             if si == tail_at and c.deferred is not None:
                 return c.deferred
             nxt = steps[si + 1] if si + 1 < len(steps) else None
+            source = si in sources
+            if source:
+                nxt = ("se", None, si)
             # layer si reads what layer si-1 wrote: two arenas alternate; outputs with pad columns and the single rows
             # after the pooling get arenas of their own, so that in steady state no role changes shape (a change costs a fill)
             out_role = f"act{si & 1}" + ("s" if c.pooled else "") + ("p" if st[0] == "tdnn" and st[1].units % 32 else "")
+            if source:                                   # a role of its own, held until the gate has run
+                out_role = "resid" + ("p" if st[0] == "tdnn" and st[1].units % 32 else "")
             own = can_pool = False                       # own: a frame-level layer on the kernels of the call's mode
             if st[0] == "tdnn":
                 _, l, relu, _ = st
@@ -410,6 +452,8 @@ class Sequential:
                     own = l.effective_gemm(gemm, relu) == gemm
             if own and gemm == L.GEMM_F16MX:
                 self._step_mx(c, si, st, nxt, can_pool, out_role)
+                if source:
+                    c.resid = c.x
                 continue
             if c.mxp is not None:
                 raise RuntimeError("internal: MX planes reached a layer that cannot read them")
@@ -417,6 +461,8 @@ class Sequential:
                 raise RuntimeError("internal: a deferred BatchNorm reached a layer that cannot fold it")
             if own and gemm == L.GEMM_BF16X3 and self.split_planes and l.units > 128:
                 self._step_planes(c, si, st, nxt, can_pool, out_role)
+                if source:
+                    c.resid = c.x
                 continue
             if c.planes is not None:
                 raise RuntimeError("internal: split planes reached a layer that cannot read them")
@@ -428,8 +474,12 @@ class Sequential:
                 self._step_attn(c, si, st[1])
             elif st[0] == "res2":
                 self._step_res2(c, st[1], out_role)
+            elif st[0] == "se":
+                self._step_se(c, st[1], st[2] is not None, out_role)
             else:
                 c.x = st[1](c.x.to(torch.float32).contiguous())
+            if source:
+                c.resid = _gemm_rows(c.x, torch.float32)
         if c.pooled:
             return c.x.reshape(c.x.shape[1], 1, c.x.shape[2])
         return c.x
@@ -546,7 +596,7 @@ class Sequential:
                                    slots, slot_rows, pad_cols=not pair_in)
             return
         g = L.GEMM_F32 if c.pooled else l.effective_gemm(gemm, relu)
-        ydt = torch.float32 if (c.pooled or g != gemm or (nxt is not None and nxt[0] in ("attn", "res2"))) else L.act_torch_dtype(gemm)
+        ydt = torch.float32 if (c.pooled or g != gemm or (nxt is not None and nxt[0] in ("attn", "res2", "se"))) else L.act_torch_dtype(gemm)
         pair_ok = lambda t, r: t.activation in (None, "linear") or (t.activation == "relu" and not r)  # noqa: E731
         pair_out = (c.pairs and not c.pooled and g == L.GEMM_F32 and pair_ok(l, relu) and nxt is not None and nxt[0] == "tdnn"
                     and pair_ok(nxt[1], nxt[2]) and nxt[1].inputDim == l.units)
@@ -598,6 +648,17 @@ class Sequential:
         ldy = ops.round_up(C, 32)
         ybuf = c.ws.get(out_role + ("p" if ldy != C else ""), (B, T, ldy), torch.float32, c.dev, padded=ldy != C)
         c.x = l.forward(x, lens=c.lens, gemm=c.gemm, out=ybuf[:, :, :C])
+
+    def _step_se(self, c, l, residual, out_role):
+        """A SqueezeExcite: three launches from fp32 rows (and the kept residual rows) to fp32 rows, the same arithmetic in every mode
+        (include/ktf_se.h has one); the lengths stay, and the layer behind starts its route from fp32 rows as a first layer does."""
+        x = _gemm_rows(c.x, torch.float32)
+        B, T, C = x.shape
+        ldy = ops.round_up(C, 32)
+        ybuf = c.ws.get(out_role + ("p" if ldy != C else ""), (B, T, ldy), torch.float32, c.dev, padded=ldy != C)
+        gate = c.ws.get("se_gate", (ops.se_gate_floats(B, C),), torch.float32, c.dev, padded=False)
+        resid, c.resid = (c.resid, None) if residual else (None, c.resid)
+        c.x = l.forward(x, lens=c.lens, residual=resid, out=ybuf[:, :, :C], gate=gate)
 
     def _pool_slots(self, T, flat, mx_flags=None, gemm=None):
         """(slots, slot_rows) of a pooled step's fp64 partial sums over utterances of up to T rows (the slot rule of csrc/pooled_stats.h): on

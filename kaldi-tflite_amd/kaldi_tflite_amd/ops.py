@@ -1887,6 +1887,81 @@ def res2_grad_weights(x, lens, scale, dilation, nscale, y, a, gt, act, gemm, dw,
     return dw, dbias, dnscale, dnshift
 
 
+# ----------------------------------------------------------------------------- the squeeze-excitation gate (include/ktf_se.h)
+def se_gate_floats(B, C):
+    """Floats of the workspace se_gate takes as `gate`: the gate in the first B C of them, the fp64 means behind it."""
+    return (int(B) * int(C) + 63) // 64 * 64 + 2 * int(B) * int(C)
+
+
+def _se_args(C, rows, w1, b1, w2, b2, lens, **dense):
+    """The operands of a ktf_se_* call: `rows` {name: (B, T, ld) fp32 or None} with one B and T -> B, T, C (default: every column of
+    the first), H, {name: (pointer, ld)}. Shapes and dtypes are checked here; sizes the library refuses pass: it gets to say why."""
+    B, T, C, r = _res2_rows(C, **rows)
+    if w1 is None or w1.dim() != 2:
+        raise ValueError("w1: a (C, H) fp32 tensor is expected")
+    H = w1.shape[1]
+    for name, t, shape in (("w1", w1, (C, H)), ("b1", b1, (H,)), ("w2", w2, (H, C)), ("b2", b2, (C,)), ("lens", lens, (B,))):
+        if t is None:
+            if name in ("w1", "w2"):
+                raise ValueError(f"{name}: a {shape} fp32 tensor is expected")
+            continue
+        _need_dense(name, t)
+        if t.dtype != (torch.int32 if name == "lens" else torch.float32) or tuple(t.shape) != shape:
+            raise ValueError(f"{name}: expected {shape} {'int32' if name == 'lens' else 'fp32'}, got {t.dtype} {tuple(t.shape)}")
+    for name, (t, dtype, shape) in dense.items():
+        if t is None:
+            continue
+        _need_dense(name, t)
+        if t.dtype != dtype or (shape is not None and tuple(t.shape) != shape):
+            raise ValueError(f"{name}: expected {shape} {dtype}, got {t.dtype} {tuple(t.shape)}")
+    return B, T, C, H, r
+
+
+def se_gate(x, residual, lens, w1, b1, w2, b2, y, gate, C=None):
+    """y = x * sigmoid(relu(mean_t(x) w1 + b1) w2 + b2) (+ residual): x, residual (or None) and y (B, T, ld) fp32 rows with C channels
+    (default: every column of x), lens (B,) int32 or None, w1 (C, H), b1 (H,) or None, w2 (H, C), b2 (C,) or None; gate a 1-D fp32
+    workspace of se_gate_floats(B, C). y may be `residual` itself. Rows of y at or beyond an utterance's length are left as they are."""
+    B, T, C, H, r = _se_args(C, dict(x=x, r=residual, y=y), w1, b1, w2, b2, lens)
+    if gate is None or gate.dim() != 1 or gate.dtype != torch.float32 or gate.numel() < se_gate_floats(B, C) or not gate.is_contiguous():
+        raise ValueError(f"gate: a contiguous 1-D fp32 workspace of {se_gate_floats(B, C)} elements is expected")
+    _call("ktf_se_gate", x.device, r["x"][0], B, T, C, r["x"][1], r["r"][0], r["r"][1], L.ptr(lens), L.ptr(w1), L.ptr(b1), L.ptr(w2), L.ptr(b2), H,
+          r["y"][0], r["y"][1], L.ptr(gate))
+    return y
+
+
+def se_gate_train(x, residual, lens, w1, b1, w2, b2, y, mean, hid, gate, C=None):
+    """se_gate for training: also writes mean (B, C) fp64, hid (B, H) fp64 and gate (B, C) fp32. y has the bits of se_gate."""
+    B0 = x.shape[0] if x.dim() == 3 else 0
+    Cc = (x.shape[2] if C is None else int(C)) if x.dim() == 3 else 0
+    Hh = w1.shape[1] if w1 is not None and w1.dim() == 2 else 0
+    B, T, C, H, r = _se_args(C, dict(x=x, r=residual, y=y), w1, b1, w2, b2, lens, mean=(mean, torch.float64, (B0, Cc)),
+                             hid=(hid, torch.float64, (B0, Hh)), gate=(gate, torch.float32, (B0, Cc)))
+    _call("ktf_se_gate_train", x.device, r["x"][0], B, T, C, r["x"][1], r["r"][0], r["r"][1], L.ptr(lens), L.ptr(w1), L.ptr(b1), L.ptr(w2),
+          L.ptr(b2), H, r["y"][0], r["y"][1], L.ptr(mean), L.ptr(hid), L.ptr(gate))
+    return y, mean, hid, gate
+
+
+def se_gate_backward_workspace(B, C, H, device):
+    """The workspace se_gate_backward takes for B utterances of C channels and H bottleneck units."""
+    return _workspace("ktf_se_gate_backward_workspace_bytes", int(B), int(C), int(H), device=device)
+
+
+def se_gate_backward(g, x, lens, w1, w2, mean, hid, gate, dx, dw1, db1, dw2, db2, workspace, C=None):
+    """g (B, T, ldg) = dL/dy -> dx (B, T, lddx), rows at and beyond an utterance's length zero, and dw1 (C, H), db1 (H,), dw2 (H, C),
+    db2 (C,) (each may be None); mean, hid and gate are se_gate_train's. The residual's gradient is g itself."""
+    B0 = x.shape[0] if x.dim() == 3 else 0
+    Cc = (g.shape[2] if C is None else int(C)) if g.dim() == 3 else 0
+    Hh = w1.shape[1] if w1 is not None and w1.dim() == 2 else 0
+    B, T, C, H, r = _se_args(C, dict(g=g, x=x, dx=dx), w1, None, w2, None, lens, mean=(mean, torch.float64, (B0, Cc)),
+                             hid=(hid, torch.float64, (B0, Hh)), gate=(gate, torch.float32, (B0, Cc)), dw1=(dw1, torch.float32, (Cc, Hh)),
+                             db1=(db1, torch.float32, (Hh,)), dw2=(dw2, torch.float32, (Hh, Cc)), db2=(db2, torch.float32, (Cc,)),
+                             workspace=(workspace, torch.uint8, None))
+    _call("ktf_se_gate_backward", g.device, r["g"][0], B, T, C, r["g"][1], r["x"][0], r["x"][1], L.ptr(lens), L.ptr(w1), L.ptr(w2), H, L.ptr(mean),
+          L.ptr(hid), L.ptr(gate), r["dx"][0], r["dx"][1], L.ptr(dw1), L.ptr(db1), L.ptr(dw2), L.ptr(db2), L.ptr(workspace),
+          0 if workspace is None else workspace.numel())
+    return dx, dw1, db1, dw2, db2
+
+
 # ----------------------------------------------------------------------------- training examples (include/ktf_egs.h)
 EGS_DTYPES = {torch.float32: L.KTF_F32, torch.float16: L.KTF_F16}
 
