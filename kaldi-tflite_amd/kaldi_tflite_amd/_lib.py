@@ -349,6 +349,12 @@ SE_PROTOTYPES = {
     "ktf_se_gate_backward": (C.c_int, [_P, _i64, _i64, _i32, _i64, _P, _i64, _P, _P, _P, _i32, _P, _P, _P, _P, _i64, _P, _P, _P, _P, _P,
                                        C.c_size_t, _P]),
 }
+# name -> (restype, argtypes); mirrors include/ktf_agg.h one to one
+AGG_PROTOTYPES = {
+    "ktf_agg_conv": (C.c_int, [_P, _P, _P, _i32, _i64, _i64, _P, _P, _i64, _P, _P, _P, _i32, _i32, _i32, _P, _i64, _P]),
+    "ktf_agg_row_tile": (_i32, [_i32, _i32, _i32]),
+}
+AGG_MAX_SOURCES, AGG_MAX_WIDTH, AGG_MAX_UNITS = 4, 4096, 8192   # ktf_agg_*: tensors per call, channels of one, outputs
 ATTN_MAX_BATCH, ATTN_MAX_ROWS, ATTN_MAX_DIM = 65535, 1 << 30, 1 << 20   # ktf_attn_*: utterances, frames and channels per call
 HEAD_MAX_CENTERS, HEAD_MAX_TOPK = 8, 64   # ktf_head_*: sub-centres per class; penalised classes per row
 OPTIM_SGD, OPTIM_ADAM, OPTIM_MAX_GROUPS = 0, 1, 8   # ktf_optim_*: kind; groups per call
@@ -386,7 +392,7 @@ def load():
                               + list(GRAD_PROTOTYPES.items()) + list(NORM_PROTOTYPES.items()) + list(LOSS_PROTOTYPES.items())
                               + list(EGS_PROTOTYPES.items()) + list(OPTIM_PROTOTYPES.items()) + list(HEAD_PROTOTYPES.items())
                               + list(ATTN_PROTOTYPES.items()) + list(DENSE_PROTOTYPES.items()) + list(RES2_PROTOTYPES.items())
-                              + list(SE_PROTOTYPES.items())):
+                              + list(SE_PROTOTYPES.items()) + list(AGG_PROTOTYPES.items())):
         fn = getattr(lib, name)          # AttributeError = header/library mismatch
         fn.restype = res
         fn.argtypes = args

@@ -478,10 +478,90 @@ def relu_batch_norm(z, lens, moving_mean, moving_var, gamma, momentum=0.99, epsi
     return y if z.dim() == 3 else y.squeeze(0)
 
 
+class _Aggregate(torch.autograd.Function):
+    """include/ktf_agg.h forward; the backward is composed from the TDNN gradient kernels, one context-[0] data / weights call per source
+    on that source's slice of the weight (a fused multi-destination gradient kernel is not part of the library)."""
+
+    @staticmethod
+    def forward(ctx, weight, bias, lens, gemm, *xs):
+        B, T = xs[0].shape[0], xs[0].shape[1]
+        xs = [x.contiguous() for x in xs]
+        w = weight.contiguous()
+        units = w.shape[0]
+        y = torch.zeros((B, T, ops.round_up(units, 4)), dtype=torch.float32, device=w.device)      # rows at and beyond an utterance's length stay zero
+        if B > 0 and T > 0:
+            ops.agg_conv(xs, lens, w, None if bias is None else bias.contiguous(), None, None, L.ACT_NONE, gemm, y[:, :, :units])
+        y = y if y.shape[2] == units else y[:, :, :units].contiguous()
+        ctx.save_for_backward(w, lens, *xs)
+        ctx.gemm, ctx.has_bias = gemm, bias is not None
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        w, lens, *xs = ctx.saved_tensors
+        units = w.shape[0]
+        B, T = xs[0].shape[0], xs[0].shape[1]
+        g = gy.to(torch.float32).contiguous()
+        need_w = ctx.needs_input_grad[0] or (ctx.has_bias and ctx.needs_input_grad[1])
+        dw = torch.zeros_like(w) if need_w else None
+        db = torch.zeros((units,), dtype=torch.float32, device=w.device) if need_w and ctx.has_bias else None
+        dxs = [torch.zeros_like(x) if ctx.needs_input_grad[4 + s] else None for s, x in enumerate(xs)]
+        if B == 0 or T == 0:
+            return (dw, db, None, None, *dxs)
+        f32 = ctx.gemm == L.GEMM_F32
+        Up, off = ops.round_up(units, 256), 0
+        for s, x in enumerate(xs):
+            C = x.shape[2]
+            d = _desc(units, C, [0], 1, "SAME")
+            Dp = d.din_pad
+            wp = torch.zeros((Up, Dp), dtype=torch.float32, device=w.device)
+            wp[:units, :C] = w[:, off:off + C]
+            xp = torch.nn.functional.pad(x, (0, Dp - C)).contiguous()
+            ws = ops.grad_tdnn_workspace(B, T, d, x.device) if f32 else ops.grad_tdnn16_workspace(B, T, d, ctx.gemm, x.device)
+            if dxs[s] is not None:
+                dxp = torch.empty_like(xp)
+                if f32:
+                    ops.grad_tdnn_data(g, lens, d, wp, dxp, ws)
+                else:
+                    ops.grad_tdnn16_data(g, lens, d, wp, dxp, ws, ctx.gemm)
+                dxs[s] = dxp[:, :, :C]
+            if need_w:
+                dwp = torch.empty_like(wp)
+                dbs = db if s == 0 else None                      # (the bias gradient is the same sum in every call: taken once)
+                if f32:
+                    ops.grad_tdnn_weights(xp, lens, d, g, dwp, dbs, ws)
+                else:
+                    ops.grad_tdnn16_weights(xp, lens, d, g, dwp, dbs, ws, ctx.gemm)
+                dw[:, off:off + C] = dwp[:units, :C]
+            off += C
+        return (dw, db, None, None, *dxs)
+
+
+def aggregate(xs, weight, bias, lens=None, gemm="f32"):
+    """Multi-layer feature aggregation (include/ktf_agg.h), z = concat(xs) weight^T + bias without the concatenation, differentiable in
+    every x, weight and bias: xs a list of 2 .. 4 (B, T, C_s) fp32 tensors on the GPU, every C_s a multiple of 32; weight (units, sum C_s),
+    the Conv1d(K, units, 1) weight; bias (units,) or None; lens (B,) or None. Returns (B, T, units) with zero rows at and beyond an
+    utterance's length; gradients arriving for those rows are ignored. No activation and no norm: ReLU and BatchNorm stay modules of
+    their own, as for `tdnn_affine`. gemm: "f32", "bf16" or "bf16x3" -- the forward is ktf_agg_conv in that mode, the backward one
+    context-[0] ktf_grad_tdnn* data / weights call per source on that source's weight slice (no fused multi-destination kernel)."""
+    code = _gemm_code(gemm)
+    xs = list(xs)
+    for x in xs:
+        _on_gpu(x, "every x")
+    _on_gpu(weight, "weight")
+    if len(xs) < 2 or any(x.dim() != 3 or x.shape[:2] != xs[0].shape[:2] for x in xs) or weight.dim() != 2 or weight.shape[1] != sum(x.shape[2] for x in xs):
+        raise ValueError(f"expected two or more x (B, T, C_s) and weight (units, sum C_s), got {[tuple(x.shape) for x in xs]} and {tuple(weight.shape)}")
+    if bias is not None and tuple(bias.shape) != (weight.shape[0],):
+        raise ValueError(f"bias shape {tuple(bias.shape)} != ({weight.shape[0]},)")
+    return _Aggregate.apply(weight.to(torch.float32), None if bias is None else bias.to(torch.float32), _lens(lens, xs[0].shape[0], xs[0].device), code,
+                            *(x.to(torch.float32) for x in xs))
+
+
 class TrainableSequential(torch.nn.Module):
     """A `ktf.models.Sequential` (or an XvectorExtractor, whose TDNN stack is taken) as a torch module: TDNN -> ReLU -> BatchNorm ...
     (in front of the pooling also SqueezeExcite, as `squeeze_excite`, with the output of the layer `residual_from` names kept for it, and Res2Conv, as `res2_conv`: kernel, bias and -- batch_norm=True -- norm_scale / norm_shift trained as a
-    per-channel affine; batch statistics inside the block are not taken, since stage i + 1 reads stage i normalised)
+    per-channel affine; batch statistics inside the block are not taken, since stage i + 1 reads stage i normalised; and Aggregate, as
+    `aggregate`, with the outputs of the layers its `sources` name kept for it, its own activation as torch.relu and its norm pair as a per-channel affine)
     -> reducing StatsPooling or AttentiveStatsPooling (its two affines and `attentive_stats_pooling`) -> TDNN (context [0]) ... Parameters start from the layers' current weights; `forward(feats, lens)`
     returns the last layer's output -- (B, T_out, units), or (B, units) behind the pooling -- for `ClassifierHead` (below) or a head and a loss written in torch;
     `export()` writes parameters and moving statistics back into the layers. The layers must be built (a Sequential with an Input, or
@@ -502,12 +582,12 @@ class TrainableSequential(torch.nn.Module):
         dev = ops.default_device() if device is None else torch.device(device)
         self.steps = []                     # (kind, the layer, index into self.params / self.stats)
         self.params = torch.nn.ParameterList()
-        self.keep = set()                   # names of the layers whose output a SqueezeExcite adds as its residual
+        self.keep = set()                   # names of the layers whose output a SqueezeExcite adds as its residual or an Aggregate concatenates
         pooled = False
         f32 = lambda a: torch.nn.Parameter(torch.as_tensor(a, dtype=torch.float32).to(dev).contiguous().clone())  # noqa: E731
         for l in self.seq.layers:
             if not isinstance(l, (_layers.TDNN, _layers.ReLU, _layers.BatchNorm, _layers.StatsPooling, _layers.AttentiveStatsPooling,
-                                  _layers.Res2Conv, _layers.SqueezeExcite)):
+                                  _layers.Res2Conv, _layers.SqueezeExcite, _layers.Aggregate)):
                 raise NotImplementedError(f"layer '{l.name}' ({type(l).__name__}) has no gradient in ktf.autograd")
             if not l.built and not isinstance(l, (_layers.ReLU, _layers.StatsPooling)):
                 raise ValueError(f"layer '{l.name}' is not built: give the Sequential an Input, run it or load its weights first")
@@ -540,6 +620,16 @@ class TrainableSequential(torch.nn.Module):
                     self.seq._plan()
                     self.keep.add(l.residualFrom)
                 self.steps.append(("se", l, at))
+            elif isinstance(l, _layers.Aggregate):
+                if pooled:
+                    raise NotImplementedError(f"layer '{l.name}' (Aggregate behind the pooling) has no gradient in ktf.autograd")
+                at = len(self.params)                              # weight (units, K), bias, norm_scale, norm_shift (those it has)
+                self.params.append(f32(l.kernel.T))
+                for t in ([l.bias] if l.useBias else []) + ([l.normScale, l.normShift] if l.batchNorm else []):
+                    self.params.append(f32(t))
+                self.seq._plan()                                   # (the Sequential's plan checks the names, the widths and the lengths)
+                self.keep.update(l.sources)
+                self.steps.append(("agg", l, at))
             elif isinstance(l, _layers.BatchNorm):
                 at = len(self.params)
                 self.params.append(f32(l.gamma))
@@ -597,7 +687,16 @@ class TrainableSequential(torch.nn.Module):
                 nsc, nsh = rest if l.batchNorm else (None, None)
                 x = res2_conv(x, self.params[at], b, nsc, nsh, l.scale, l.dilation, lens, l.activation, self.gemm)
             elif kind == "se":
-                x = squeeze_excite(x, *self.params[at:at + 4], lens=lens, residual=kept.pop(l.residualFrom) if l.residualFrom else None)
+                x = squeeze_excite(x, *self.params[at:at + 4], lens=lens, residual=kept[l.residualFrom] if l.residualFrom else None)
+            elif kind == "agg":
+                rest = list(self.params[at + 1:at + 1 + int(l.useBias) + 2 * int(l.batchNorm)])
+                b = rest.pop(0) if l.useBias else None
+                x = aggregate([kept[n] for n in l.sources] + [x], self.params[at], b, lens, self.gemm)
+                if isinstance(l.activation, str) and l.activation.lower() == "relu":
+                    held = into_bn
+                    x = x if held else torch.relu(x)
+                if l.batchNorm:
+                    x = x * rest[0] + rest[1]
             elif kind == "bn" and self.fused_norm:
                 x = relu_batch_norm(x, None if pooled else lens, getattr(self, f"moving_mean_{at}"), getattr(self, f"moving_var_{at}"),
                                     self.params[at], l.momentum, l.epsilon, self.training, relu=held)
@@ -632,6 +731,10 @@ class TrainableSequential(torch.nn.Module):
                 l.set_weights([ws[0].reshape(l.scale - 1, 3, l.width, l.width)] + ws[1:], fmt="tensorflow")
             elif kind == "se":
                 l.set_weights([self.params[at + k].detach().cpu().numpy() for k in range(4)], fmt="tensorflow")
+            elif kind == "agg":
+                n = 1 + int(l.useBias) + 2 * int(l.batchNorm)
+                ws = [self.params[at + k].detach().cpu().numpy() for k in range(n)]
+                l.set_weights([ws[0].T] + ws[1:], fmt="tensorflow")
             elif kind == "attn":
                 w1, b1, w2, b2 = (self.params[at + k].detach().cpu().numpy() for k in range(4))
                 l.set_weights([w1[:, 0, :].T, b1, w2[:, 0, :].T, b2], fmt="tensorflow")

@@ -1321,6 +1321,160 @@ class SqueezeExcite(Layer):
         return self.forward(_f32_rows(x), None, None if residual is None else _f32_rows(_to_device(residual)))
 
 
+# =============================================================================== multi-layer feature aggregation
+class Aggregate(Layer):
+    """Multi-layer feature aggregation (include/ktf_agg.h): the 1 x 1 convolution over the channel-wise concatenation of the outputs of
+    the earlier layers named in `sources` (in that order) and of the layer's own input (last), as ONE launch that never forms the
+    concatenation; then `activation` ("relu" or None) and, with `batch_norm`, the folded inference BatchNorm y * norm_scale + norm_shift
+    (`fold_batch_norm`). One to three sources, every width a multiple of 32. Training goes through ktf.autograd.aggregate. The weights
+    in keras order are [kernel (K, units), bias (units,), norm_scale (units,), norm_shift (units,)] (without the ones the layer does not
+    have), K the sum of the widths."""
+
+    MAX_NAMED, MAX_WIDTH, MAX_UNITS = L.AGG_MAX_SOURCES - 1, L.AGG_MAX_WIDTH, L.AGG_MAX_UNITS
+    MODES = Res2Conv.MODES                   # (no f16mx form either: such a call runs the fp32-grade split-bf16)
+    fold_batch_norm = staticmethod(Res2Conv.fold_batch_norm)
+
+    def __init__(self, units, sources, activation=None, use_bias=True, batch_norm=False, name=None, **kwargs):
+        super().__init__(trainable=True, name=name, **kwargs)
+        self.units = int(units)
+        if not 1 <= self.units <= self.MAX_UNITS:
+            raise ValueError(f"'units' must be in [1, {self.MAX_UNITS}], got {units}")
+        if isinstance(sources, str) or not all(isinstance(s, str) for s in sources):
+            raise ValueError(f"'sources' is a list of layer names, got {sources!r}")
+        self.sources = list(sources)
+        if not 1 <= len(self.sources) <= self.MAX_NAMED:
+            raise ValueError(f"layer '{self.name}': 'sources' names {len(self.sources)} layers, one to {self.MAX_NAMED} are expected")
+        act = activation.lower() if isinstance(activation, str) else activation
+        if act not in (None, "linear", "relu"):
+            raise ValueError(f"activation must be 'relu' or None, got {activation!r}")
+        self.activation = activation
+        self.useBias, self.batchNorm = bool(use_bias), bool(batch_norm)
+        self.gemm = "f32"
+        self.batchAxis, self.timeAxis, self.featAxis = 0, 1, -1
+        self.kernel = self.bias = self.normScale = self.normShift = None
+        self.widths = None                   # channels of every concatenated tensor, the layer's own input last
+        self._dev = {}
+        self._version = 0      # bumped whenever the weights change: models refuse stale captured graphs
+
+    def check_widths(self, widths):
+        """The channel counts of the named sources and of the own input (last), as include/ktf_agg.h rule 7 takes them."""
+        widths = [int(c) for c in widths]
+        if len(widths) != len(self.sources) + 1:
+            raise ValueError(f"layer '{self.name}': {len(self.sources)} named sources and the input make {len(self.sources) + 1} widths, got {len(widths)}")
+        for c in widths:
+            if c % 32 or not 32 <= c <= self.MAX_WIDTH:
+                raise ValueError(f"layer '{self.name}': a concatenated width of {c} is not a multiple of 32 in [32, {self.MAX_WIDTH}]")
+        if self.kernel is not None and self.kernel.shape[0] != sum(widths):
+            raise ValueError(f"layer '{self.name}': the kernel has {self.kernel.shape[0]} input channels, the concatenation {sum(widths)}")
+        return widths
+
+    def build(self, input_shape, source_shapes=None):
+        """`source_shapes`: the output shapes of the named sources, in order (a Sequential passes them; outside a model they come from
+        the tensors of the first call)."""
+        if source_shapes is None:
+            raise ValueError(f"layer '{self.name}': the widths of the sources {self.sources} are needed to build it")
+        self.widths = self.check_widths([s[self.featAxis] for s in source_shapes] + [input_shape[self.featAxis]])
+        K, U = sum(self.widths), self.units
+        self.inputDim = K
+        if self.kernel is None:
+            rng = np.random.default_rng(zlib.crc32(self.name.encode()))      # (from the name: every rank draws the same, as TDNN.build)
+            lim = np.sqrt(6.0 / (K + U))
+            self.kernel = rng.uniform(-lim, lim, (K, U)).astype(np.float32)
+            self.bias = np.zeros(U, np.float32) if self.useBias else None
+            self.normScale = np.ones(U, np.float32) if self.batchNorm else None
+            self.normShift = np.zeros(U, np.float32) if self.batchNorm else None
+            self._version += 1
+            WEIGHTS_EPOCH[0] += 1
+        self._dev = {}
+        self.built = True
+
+    def compute_output_shape(self, input_shape):
+        return tuple(input_shape[:-1]) + (self.units,)
+
+    def get_config(self):
+        c = super().get_config()
+        c.update({"units": self.units, "sources": list(self.sources), "activation": self.activation, "use_bias": self.useBias,
+                  "batch_norm": self.batchNorm})
+        return c
+
+    def get_weights(self):
+        if self.kernel is None:
+            return []
+        return [self.kernel] + ([self.bias] if self.useBias else []) + ([self.normScale, self.normShift] if self.batchNorm else [])
+
+    def set_weights(self, weights, fmt="tensorflow"):
+        """[kernel, bias, norm_scale, norm_shift] (without bias / the norm pair where the layer has none). fmt "tensorflow": kernel
+        (K, units), what get_weights() gives; "torch": (units, K) or (units, K, 1), the Conv1d(K, units, 1).weight."""
+        fmt = fmt.lower()
+        if fmt not in ["tensorflow", "torch"]:
+            raise ValueError(f"expected 'fmt' to be either 'tensorflow' or 'torch', got {fmt}")
+        want = 1 + int(self.useBias) + 2 * int(self.batchNorm)
+        if len(weights) != want:
+            raise ValueError(f"expected a weight list of length {want}, got {len(weights)}")
+        arrs = [np.asarray(getattr(a, "detach", lambda: a)(), np.float32) for a in weights]
+        kernel = arrs.pop(0)
+        if fmt == "torch":
+            kernel = kernel[..., 0] if kernel.ndim == 3 and kernel.shape[-1] == 1 else kernel
+            kernel = kernel.T if kernel.ndim == 2 else kernel
+        K = sum(self.widths) if self.widths else (kernel.shape[0] if kernel.ndim == 2 else -1)
+        if kernel.shape != (K, self.units) or K % 32 or K < 64:
+            raise ValueError(f"kernel: expected shape {(K, self.units)} as [in, out] with K a multiple of 32 from 64, got {kernel.shape}")
+        rest = [a.reshape(-1) for a in arrs]
+        for a in rest:
+            if a.shape != (self.units,):
+                raise ValueError(f"bias / norm_scale / norm_shift: expected shape {(self.units,)}, got {a.shape}")
+        self.kernel = np.ascontiguousarray(kernel)
+        self.bias = np.ascontiguousarray(rest.pop(0)) if self.useBias else None
+        self.normScale, self.normShift = (np.ascontiguousarray(a) for a in rest) if self.batchNorm else (None, None)
+        self.inputDim = K
+        self._dev = {}
+        self._version += 1
+        WEIGHTS_EPOCH[0] += 1
+        self.built = self.widths is not None
+
+    def device_weights(self, device):
+        """(w (units, K) as the kernel reads it, bias, norm_scale, norm_shift) on the device, fp32 in every mode (the 16-bit modes
+        split in registers): one set per device, dropped when the weights change."""
+        key = str(device)
+        if key not in self._dev:
+            up = lambda a: None if a is None else ops.to_device_f32(a, device)      # noqa: E731
+            self._dev[key] = (up(self.kernel.T), up(self.bias), up(self.normScale), up(self.normShift))
+        return self._dev[key]
+
+    def forward(self, x, lens=None, sources=(), gemm="f32", out=None, relu=False, bn=None):
+        """The one launch: x and every tensor of `sources` (those of the named layers, in order) (B, T, C_s) fp32 views of rows whose
+        stride is a multiple of 4; lens (B,) int32 or None; `gemm` a mode name or KTF_GEMM_* number; out (B, T, units) fp32 view of rows
+        likewise (default: fresh zeroed rows). Rows at or beyond an utterance's length are left as they are. `relu` / `bn` = (scale,
+        shift) on the device: a ReLU / BatchNorm layer behind this one, run in its epilogue (a layer without activation / norm pair of its own)."""
+        if gemm not in self.MODES:
+            raise ValueError(f"gemm must be one of {sorted(k for k in self.MODES if isinstance(k, str))}")
+        xs = list(sources) + [x]
+        widths = self.check_widths([t.shape[2] for t in xs])
+        if self.widths is not None and widths != self.widths:
+            raise ValueError(f"layer '{self.name}': built for the widths {self.widths}, got {widths}")
+        B, T, _ = x.shape
+        if out is None:
+            out = torch.zeros((B, T, ops.round_up(self.units, 4)), dtype=torch.float32, device=x.device)[:, :, :self.units]      # (ldy % 4 == 0)
+        w, bias, nscale, nshift = self.device_weights(x.device)
+        act = L.ACT_RELU if relu or (isinstance(self.activation, str) and self.activation.lower() == "relu") else L.ACT_NONE
+        if bn is not None:
+            if self.batchNorm:
+                raise ValueError(f"layer '{self.name}' has a norm pair of its own: a BatchNorm behind it is a step of its own")
+            nscale, nshift = bn
+        return ops.agg_conv(xs, lens, w, bias, nscale, nshift, act, self.MODES[gemm], out)
+
+    def __call__(self, inputs, sources=()):
+        x = _to_device(inputs)
+        srcs = [_to_device(s) for s in sources]
+        if x.dim() != 3 or any(s.dim() != 3 for s in srcs):
+            raise ValueError(f"expected (batch, time, feat) tensors, got {[tuple(t.shape) for t in srcs + [x]]}")
+        if not self.built:
+            self.build(tuple(x.shape), [tuple(s.shape) for s in srcs])
+        return self.forward(_f32_rows(x), None, [_f32_rows(s) for s in srcs], self.gemm)
+
+    call = __call__
+
+
 # =============================================================================== stats
 class StatsPooling(Layer):
     """layers/stats/stats_pooling.py:26 — mean (+ std) pooling over the whole utterance or sliding windows."""

@@ -20,7 +20,7 @@ from . import _lib as L
 from . import ops
 from ._host import is_real
 from .io import KaldiNnet3Reader, ReadKaldiArray
-from .layers import (TDNN, AttentiveStatsPooling, BatchNorm, CMVN, Framing, MFCC, ReLU, Res2Conv, SqueezeExcite, StatsPooling, VAD, _GEMM, WEIGHTS_EPOCH,
+from .layers import (TDNN, Aggregate, AttentiveStatsPooling, BatchNorm, CMVN, Framing, MFCC, ReLU, Res2Conv, SqueezeExcite, StatsPooling, VAD, _GEMM, WEIGHTS_EPOCH,
                      _f32_rows)
 from .mx import Planes
 
@@ -44,6 +44,7 @@ _LAYER_KINDS = (
     (("attentive_stats", "attentive_stats_pooling"), AttentiveStatsPooling, "{}", True),
     (("res2_conv",), Res2Conv, "{}", True),
     (("squeeze_excite",), SqueezeExcite, "{}", True),
+    (("aggregate",), Aggregate, "{}", True),
 )
 _KIND_OF = {alias: row for row in _LAYER_KINDS for alias in row[0]}
 
@@ -51,7 +52,7 @@ _KIND_OF = {alias: row for row in _LAYER_KINDS for alias in row[0]}
 def cfg2layers(layerCfg):
     """One entry of `model_config.layers` -> the layers it stands for, in order. `type` is a kind or a list of kinds
     ("affine" | "tdnn", "relu", "batchnorm" | "bn", "stats" | "stats_extraction" | "stats_pooling", "attentive_stats" |
-    "attentive_stats_pooling", "res2_conv", "squeeze_excite"); the entry's `cfg` holds the keyword arguments of its parametrised layer. KeyError without a `type`, ValueError for an unknown one."""
+    "attentive_stats_pooling", "res2_conv", "squeeze_excite", "aggregate"); the entry's `cfg` holds the keyword arguments of its parametrised layer. KeyError without a `type`, ValueError for an unknown one."""
     kinds = layerCfg.get("type") or []
     if isinstance(kinds, str):
         kinds = [kinds]
@@ -140,6 +141,7 @@ class _RunState:
         self.tail_at, self.tail, self.deferred = tail_at, tail, None
         self.mxp = self.planes = self.pending_bn = None
         self.resid = None                                # fp32 rows kept for a SqueezeExcite(residual_from=...)
+        self.kept = {}                                   # step index -> fp32 rows kept for an Aggregate(sources=[...])
         self.x_pair = self.pooled = self.skip = False
         self._rows, self._rows_for = None, None
 
@@ -233,10 +235,18 @@ class Sequential:
         if self.input is None or self.input.shape[-1] is None:
             return
         shape = (self.input.shape[0], self.input.shape[1], self.input.shape[-1])
+        shapes = {}                                      # layer name -> output shape, for Aggregate(sources=[...])
         for l in self.layers:
             if not l.built:
-                l.build(shape)
+                if isinstance(l, Aggregate):
+                    missing = [n for n in l.sources if n not in shapes]
+                    if missing:
+                        raise ValueError(f"layer '{l.name}': sources {missing} name no earlier layer of this model")
+                    l.build(shape, [shapes[n] for n in l.sources])
+                else:
+                    l.build(shape)
             shape = tuple(l.compute_output_shape(shape))
+            shapes[l.name] = shape
 
     def weight_outlier_score(self):
         """Largest |w| / std(w) over the wide frame-level TDNN layers (cached per weights signature)."""
@@ -263,7 +273,7 @@ class Sequential:
     def weights_signature(self):
         """Changes whenever a TDNN / BatchNorm layer's weights change (set_weights, a re-build): captured graphs
         are tied to it."""
-        return tuple((id(l), l._version) for l in self.layers if isinstance(l, (TDNN, BatchNorm, AttentiveStatsPooling, Res2Conv, SqueezeExcite)))
+        return tuple((id(l), l._version) for l in self.layers if isinstance(l, (TDNN, BatchNorm, AttentiveStatsPooling, Res2Conv, SqueezeExcite, Aggregate)))
 
     def get_layer(self, name):
         for l in self.layers:
@@ -289,7 +299,7 @@ class Sequential:
             if not pooled:
                 for k in range(i, len(Ls)):                  # (a TDNN's ReLU / BatchNorm: only the last layer of the step has an output)
                     named.setdefault(Ls[k].name, None)
-                    if not (isinstance(Ls[k], (TDNN, ReLU)) and k + 1 < len(Ls) and isinstance(Ls[k + 1], (ReLU, BatchNorm))):
+                    if not (isinstance(Ls[k], (TDNN, ReLU, Aggregate)) and k + 1 < len(Ls) and isinstance(Ls[k + 1], (ReLU, BatchNorm))):
                         break
             if isinstance(l, SqueezeExcite):
                 if pooled:
@@ -341,6 +351,38 @@ class Sequential:
                 steps.append(("res2", l))
                 named[l.name] = (len(steps) - 1, width, cuts)
                 i += 1
+            elif isinstance(l, Aggregate):
+                # ("agg", layer, fused ReLU?, fused BatchNorm, [steps whose kept outputs are concatenated in front of the input])
+                if pooled:
+                    raise ValueError(f"layer '{l.name}': an Aggregate stands in front of the pooling")
+                srcs, widths = [], []
+                for name in l.sources:
+                    if named.get(name) is None:
+                        raise ValueError(f"layer '{l.name}': source '{name}' names no earlier frame-level layer of this model in front of the "
+                                         "pooling whose output is written (the last layer of a fused TDNN / ReLU / BatchNorm run)")
+                    src, swidth, scuts = named[name]
+                    if scuts != cuts:
+                        raise ValueError(f"layer '{l.name}': a subsampling or context-shrinking layer between '{name}' and this one changes the lengths")
+                    srcs.append(src)
+                    widths.append(swidth)
+                if len(set(srcs)) != len(srcs) or len(steps) - 1 in srcs:
+                    raise ValueError(f"layer '{l.name}': a source is named twice, or is the layer's own input")
+                if width is not None and None not in widths:
+                    widths = l.check_widths(widths + [width])            # (ValueError: a width include/ktf_agg.h refuses)
+                    if l.widths is not None and l.widths != widths:
+                        raise ValueError(f"layer '{l.name}': built for the widths {l.widths}, the model gives {widths}")
+                relu, bn = False, None
+                j = i + 1
+                if l.activation in (None, "linear") and not l.batchNorm and j < len(Ls) and isinstance(Ls[j], ReLU):
+                    relu = True
+                    j += 1
+                if not l.batchNorm and j < len(Ls) and isinstance(Ls[j], BatchNorm):
+                    bn = Ls[j]
+                    j += 1
+                steps.append(("agg", l, relu, bn, srcs))
+                width = l.units
+                named[Ls[j - 1].name] = (len(steps) - 1, width, cuts)
+                i = j
             elif isinstance(l, (ReLU, BatchNorm)):
                 steps.append(("eltwise", l))
                 if not pooled:
@@ -425,6 +467,7 @@ class Sequential:
         tail_at = self._tail_step(steps) if defer_tail else -1
         c = _RunState(self._ws, x, lens, gemm, pairs, tail_at, steps[tail_at][1] if tail_at >= 0 else None)
         sources = {t[2] for t in steps if t[0] == "se"} - {None}      # steps whose output is a SqueezeExcite's residual: fp32 rows, kept
+        agg_sources = {s for t in steps if t[0] == "agg" for s in t[4]}      # ... or one of an Aggregate's sources, held until it has run
         for si, st in enumerate(steps):
             if c.skip:                                   # (pooled in the epilogue of the layer in front of it)
                 c.skip = False
@@ -432,14 +475,16 @@ class Sequential:
             if si == tail_at and c.deferred is not None:
                 return c.deferred
             nxt = steps[si + 1] if si + 1 < len(steps) else None
-            source = si in sources
+            source = si in sources or si in agg_sources
             if source:
                 nxt = ("se", None, si)
             # layer si reads what layer si-1 wrote: two arenas alternate; outputs with pad columns and the single rows
             # after the pooling get arenas of their own, so that in steady state no role changes shape (a change costs a fill)
             out_role = f"act{si & 1}" + ("s" if c.pooled else "") + ("p" if st[0] == "tdnn" and st[1].units % 32 else "")
             if source:                                   # a role of its own, held until the gate has run
-                out_role = "resid" + ("p" if st[0] == "tdnn" and st[1].units % 32 else "")
+                # (an Aggregate's source has a role of ITS own: a later `se` step may write its output over its residual where both live
+                # in "resid", which a source the Aggregate still waits for must not share; a step that is both is written once, here)
+                out_role = (f"agg{si}" if si in agg_sources else "resid") + ("p" if st[0] == "tdnn" and st[1].units % 32 else "")
             own = can_pool = False                       # own: a frame-level layer on the kernels of the call's mode
             if st[0] == "tdnn":
                 _, l, relu, _ = st
@@ -453,7 +498,7 @@ class Sequential:
             if own and gemm == L.GEMM_F16MX:
                 self._step_mx(c, si, st, nxt, can_pool, out_role)
                 if source:
-                    c.resid = c.x
+                    self._keep(c, si, c.x, sources, agg_sources)
                 continue
             if c.mxp is not None:
                 raise RuntimeError("internal: MX planes reached a layer that cannot read them")
@@ -462,7 +507,7 @@ class Sequential:
             if own and gemm == L.GEMM_BF16X3 and self.split_planes and l.units > 128:
                 self._step_planes(c, si, st, nxt, can_pool, out_role)
                 if source:
-                    c.resid = c.x
+                    self._keep(c, si, c.x, sources, agg_sources)
                 continue
             if c.planes is not None:
                 raise RuntimeError("internal: split planes reached a layer that cannot read them")
@@ -476,13 +521,23 @@ class Sequential:
                 self._step_res2(c, st[1], out_role)
             elif st[0] == "se":
                 self._step_se(c, st[1], st[2] is not None, out_role)
+            elif st[0] == "agg":
+                self._step_agg(c, st, out_role)
             else:
                 c.x = st[1](c.x.to(torch.float32).contiguous())
             if source:
-                c.resid = _gemm_rows(c.x, torch.float32)
+                self._keep(c, si, _gemm_rows(c.x, torch.float32), sources, agg_sources)
         if c.pooled:
             return c.x.reshape(c.x.shape[1], 1, c.x.shape[2])
         return c.x
+
+    @staticmethod
+    def _keep(c, si, rows, sources, agg_sources):
+        """Step si's fp32 rows are a SqueezeExcite's residual, an Aggregate's source, or both (written once)."""
+        if si in sources:
+            c.resid = rows
+        if si in agg_sources:
+            c.kept[si] = rows
 
     def _step_mx(self, c, si, st, nxt, can_pool, out_role):
         """f16mx: one half pass + two block-scaled residual passes (csrc/tdnn_mx.hip). Activations travel as four chunk-major planes (half
@@ -596,7 +651,7 @@ class Sequential:
                                    slots, slot_rows, pad_cols=not pair_in)
             return
         g = L.GEMM_F32 if c.pooled else l.effective_gemm(gemm, relu)
-        ydt = torch.float32 if (c.pooled or g != gemm or (nxt is not None and nxt[0] in ("attn", "res2", "se"))) else L.act_torch_dtype(gemm)
+        ydt = torch.float32 if (c.pooled or g != gemm or (nxt is not None and nxt[0] in ("attn", "res2", "se", "agg"))) else L.act_torch_dtype(gemm)
         pair_ok = lambda t, r: t.activation in (None, "linear") or (t.activation == "relu" and not r)  # noqa: E731
         pair_out = (c.pairs and not c.pooled and g == L.GEMM_F32 and pair_ok(l, relu) and nxt is not None and nxt[0] == "tdnn"
                     and pair_ok(nxt[1], nxt[2]) and nxt[1].inputDim == l.units)
@@ -659,6 +714,22 @@ class Sequential:
         gate = c.ws.get("se_gate", (ops.se_gate_floats(B, C),), torch.float32, c.dev, padded=False)
         resid, c.resid = (c.resid, None) if residual else (None, c.resid)
         c.x = l.forward(x, lens=c.lens, residual=resid, out=ybuf[:, :, :C], gate=gate)
+
+    def _step_agg(self, c, st, out_role):
+        """An Aggregate: one launch from the kept fp32 rows of its sources and the fp32 rows in front of it to fp32 rows, in the call's
+        arithmetic (Aggregate.MODES: f16mx runs split-bf16), a ReLU / BatchNorm layer behind it in its epilogue; the lengths stay, and
+        the layer behind starts its route from fp32 rows as a first layer does. No source's buffer is the output's: a kept source lives
+        in a role of its own step, the output in the alternating role of this one."""
+        _, l, relu, bn, srcs = st
+        x = _gemm_rows(c.x, torch.float32)
+        B, T, _ = x.shape
+        ldy = ops.round_up(l.units, 32)
+        ybuf = c.ws.get(out_role + ("p" if ldy != l.units else ""), (B, T, ldy), torch.float32, c.dev, padded=ldy != l.units)
+        kept = [c.kept[s] for s in srcs]
+        if any(k.data_ptr() == ybuf.data_ptr() for k in kept):
+            raise RuntimeError("internal: an Aggregate's output buffer is one of its sources'")
+        c.x = l.forward(x, lens=c.lens, sources=kept, gemm=c.gemm, out=ybuf[:, :, : l.units], relu=relu,
+                        bn=bn.affine_device(c.dev) if bn is not None else None)
 
     def _pool_slots(self, T, flat, mx_flags=None, gemm=None):
         """(slots, slot_rows) of a pooled step's fp64 partial sums over utterances of up to T rows (the slot rule of csrc/pooled_stats.h): on
@@ -1402,7 +1473,7 @@ class XvectorExtractor:
         sig = self.xvec.weights_signature()
         keep = [cap_ws, cap_xws, dict(self._post_dev)]
         for l in self.xvec.layers:
-            if isinstance(l, (TDNN, Res2Conv)):
+            if isinstance(l, (TDNN, Res2Conv, Aggregate)):
                 keep.append(dict(l._dev))
             elif isinstance(l, BatchNorm):
                 keep.append(l._dev)

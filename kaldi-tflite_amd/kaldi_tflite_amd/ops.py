@@ -1962,6 +1962,43 @@ def se_gate_backward(g, x, lens, w1, w2, mean, hid, gate, dx, dw1, db1, dw2, db2
     return dx, dw1, db1, dw2, db2
 
 
+# ----------------------------------------------------------------------------- multi-layer feature aggregation (include/ktf_agg.h)
+def agg_row_tile(units, K, gemm=L.GEMM_F32):
+    """Output rows per workgroup that agg_conv uses for `units` outputs over K concatenated channels."""
+    return _size("ktf_agg_row_tile", int(units), int(K), int(gemm))
+
+
+def agg_conv(xs, lens, w, bias, nscale, nshift, act, gemm, y, widths=None):
+    """y = act(concat(xs) w^T + bias) * nscale + nshift without the concatenation: xs a list of 2 .. 4 (B, T, ld_s) fp32 row tensors of
+    one B and T, each with `widths[s]` channels (default: every column of xs[s]); lens (B,) int32 or None; w (units, ldw) fp32 rows whose
+    first sum(widths) columns are the Conv1d(K, units, 1) weight; bias / nscale / nshift (units,) fp32 or None; act and gemm the
+    KTF_ACT_* / KTF_GEMM_* numbers; y (B, T, ldy) fp32 rows with `units` = w.shape[0] outputs. Rows of y at or beyond an utterance's
+    length and its columns from `units` on are left as they are."""
+    xs = list(xs)
+    if not xs or y.dim() != 3 or any(x.dim() != 3 or x.shape[:2] != y.shape[:2] for x in xs):
+        raise ValueError(f"sources (B, T, ld_s) and y (B, T, ldy) with the same B and T are expected, got {[tuple(x.shape) for x in xs]} and {tuple(y.shape)}")
+    B, T = y.shape[0], y.shape[1]
+    widths = [x.shape[2] for x in xs] if widths is None else [int(c) for c in widths]
+    if len(widths) != len(xs):
+        raise ValueError(f"{len(xs)} sources but {len(widths)} widths")
+    rows = [_attn_rows(f"xs[{s}]", x) for s, x in enumerate(xs)]
+    py, ldy = _attn_rows("y", y)
+    pw, ldw, units = None, sum(widths), y.shape[2]
+    if w is not None:
+        pw, ldw = _attn_mat("w", w)
+        units = w.shape[0]
+    for name, t, shape in (("bias", bias, (units,)), ("nscale", nscale, (units,)), ("nshift", nshift, (units,)), ("lens", lens, (B,))):
+        if t is None:
+            continue
+        _need_dense(name, t)
+        if t.dtype != (torch.int32 if name == "lens" else torch.float32) or tuple(t.shape) != shape:
+            raise ValueError(f"{name}: expected {shape} {'int32' if name == 'lens' else 'fp32'}, got {t.dtype} {tuple(t.shape)}")
+    S = len(xs)
+    table = ((C.c_void_p * S)(*(p.value for p, _ in rows)), (C.c_int32 * S)(*widths), (C.c_int64 * S)(*(ld for _, ld in rows)))
+    _call("ktf_agg_conv", y.device, *table, S, B, T, L.ptr(lens), pw, ldw, L.ptr(bias), L.ptr(nscale), L.ptr(nshift), units, int(act), int(gemm), py, ldy)
+    return y
+
+
 # ----------------------------------------------------------------------------- training examples (include/ktf_egs.h)
 EGS_DTYPES = {torch.float32: L.KTF_F32, torch.float16: L.KTF_F16}
 
