@@ -354,6 +354,14 @@ AGG_PROTOTYPES = {
     "ktf_agg_conv": (C.c_int, [_P, _P, _P, _i32, _i64, _i64, _P, _P, _i64, _P, _P, _P, _i32, _i32, _i32, _P, _i64, _P]),
     "ktf_agg_row_tile": (_i32, [_i32, _i32, _i32]),
 }
+# name -> (restype, argtypes); mirrors include/ktf_gctx.h one to one
+GCTX_PROTOTYPES = {
+    "ktf_gctx_stats": (C.c_int, [_P, _i64, _i64, _i32, _i64, _P, _f32, _P, _P]),
+    "ktf_gctx_bias": (C.c_int, [_P, _i64, _i32, _P, _i64, _P, _i32, _P, _i64, _P]),
+    "ktf_gctx_logits": (C.c_int, [_P, _i64, _i64, _i32, _i64, _P, _P, _i64, _P, _i64, _i32, _i32, _P, _i64, _P, _i32, _i32, _P, _i64, _P]),
+    "ktf_gctx_row_tile": (_i32, [_i32, _i32, _i32]),
+}
+GCTX_MAX_UNITS = 256                # ktf_gctx_*: hidden units of the attention
 AGG_MAX_SOURCES, AGG_MAX_WIDTH, AGG_MAX_UNITS = 4, 4096, 8192   # ktf_agg_*: tensors per call, channels of one, outputs
 ATTN_MAX_BATCH, ATTN_MAX_ROWS, ATTN_MAX_DIM = 65535, 1 << 30, 1 << 20   # ktf_attn_*: utterances, frames and channels per call
 HEAD_MAX_CENTERS, HEAD_MAX_TOPK = 8, 64   # ktf_head_*: sub-centres per class; penalised classes per row
@@ -392,7 +400,7 @@ def load():
                               + list(GRAD_PROTOTYPES.items()) + list(NORM_PROTOTYPES.items()) + list(LOSS_PROTOTYPES.items())
                               + list(EGS_PROTOTYPES.items()) + list(OPTIM_PROTOTYPES.items()) + list(HEAD_PROTOTYPES.items())
                               + list(ATTN_PROTOTYPES.items()) + list(DENSE_PROTOTYPES.items()) + list(RES2_PROTOTYPES.items())
-                              + list(SE_PROTOTYPES.items()) + list(AGG_PROTOTYPES.items())):
+                              + list(SE_PROTOTYPES.items()) + list(AGG_PROTOTYPES.items()) + list(GCTX_PROTOTYPES.items())):
         fn = getattr(lib, name)          # AttributeError = header/library mismatch
         fn.restype = res
         fn.argtypes = args

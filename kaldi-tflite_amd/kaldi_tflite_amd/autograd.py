@@ -647,6 +647,8 @@ class TrainableSequential(torch.nn.Module):
                 if pooled or act not in ("tanh", "relu"):
                     raise NotImplementedError(f"layer '{l.name}' (AttentiveStatsPooling with activation {l.attentionActivation!r}, or a "
                                               "second pooling) has no gradient in ktf.autograd")
+                if l.globalContext:
+                    raise NotImplementedError(f"layer '{l.name}' (AttentiveStatsPooling with global_context) has no gradient in ktf.autograd")
                 pooled = True
                 at = len(self.params)
                 for t in (l.hidden, l.logits):                     # W1 [u, k, d], b1, W2 [u, k, d], b2

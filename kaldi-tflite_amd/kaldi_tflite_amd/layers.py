@@ -1570,15 +1570,32 @@ class AttentiveStatsPooling(Layer):
     """Attentive statistics pooling (Okabe et al. 2018): e = W2^T act(W1^T h + b1) + b2 per frame, a softmax of e over the frames of
     the utterance, and the weighted mean (+ standard deviation) of h under it (include/ktf_attn.h). `heads` = 1: one weight per frame;
     1 < heads < D: channel c is weighted by head c // (D / heads); heads = D: one weight per frame and channel. The two affines are
-    context-[0] TDNN layers held by this layer; the weights in keras order are [W1 (D, A), b1 (A,), W2 (A, H), b2 (H,)]."""
+    context-[0] TDNN layers held by this layer; the weights in keras order are [W1 (D, A), b1 (A,), W2 (A, H), b2 (H,)].
 
-    def __init__(self, attention_units, heads=1, include_std=True, epsilon=1e-10, attention_activation="tanh", name=None, **kwargs):
+    `global_context` (ECAPA-TDNN, include/ktf_gctx.h): the attention reads [h_t ; mu ; sigma], the frame with the unweighted mean and
+    standard deviation sqrt(max(var, 0) + epsilon) of its utterance. W1 is then (3 D, A), rows in that order; the logits come from three
+    launches of their own (attend()) that never form the concatenation, with attention_units <= 256 and a tanh or relu activation.
+    Inference only: ktf.autograd has no gradient of it yet."""
+
+    _GCTX_ACTS = {"tanh": L.ACT_TANH, "relu": L.ACT_RELU}
+
+    def __init__(self, attention_units, heads=1, include_std=True, epsilon=1e-10, attention_activation="tanh", global_context=False,
+                 name=None, **kwargs):
         super().__init__(trainable=True, name=name, **kwargs)
         self.attentionUnits, self.heads = int(attention_units), int(heads)
         if self.attentionUnits < 1 or self.heads < 1:
             raise ValueError("'attention_units' and 'heads' must be >= 1")
         if float(epsilon) < 0 or not np.isfinite(float(epsilon)):
             raise ValueError("'epsilon' must be finite and >= 0")
+        self.globalContext = bool(global_context)
+        if self.globalContext:
+            act = attention_activation.lower() if isinstance(attention_activation, str) else attention_activation
+            if act not in self._GCTX_ACTS:
+                raise ValueError(f"with 'global_context' the attention activation is 'tanh' or 'relu', got {attention_activation!r}")
+            if self.attentionUnits > L.GCTX_MAX_UNITS:
+                raise ValueError(f"with 'global_context' 'attention_units' is at most {L.GCTX_MAX_UNITS}, got {attention_units}")
+        self.contextKernel = None      # global_context: the rows [mu ; sigma] of W1, (2 D, A); the rows of h_t are hidden.kernel
+        self._dev = {}
         self.includeStd = bool(include_std)
         self.epsilon = float(epsilon)
         self.attentionActivation = attention_activation
@@ -1601,6 +1618,12 @@ class AttentiveStatsPooling(Layer):
             self.hidden.build((None, None, D))
         if not self.logits.built:
             self.logits.build((None, None, self.attentionUnits))
+        if self.globalContext and (self.contextKernel is None or self.contextKernel.shape != (2 * D, self.attentionUnits)):
+            rng = np.random.default_rng(zlib.crc32(self.name.encode()))      # (from the name: every rank draws the same, as TDNN.build)
+            lim = np.sqrt(6.0 / (3 * D + self.attentionUnits))
+            self.contextKernel = rng.uniform(-lim, lim, (2 * D, self.attentionUnits)).astype(np.float32)
+            WEIGHTS_EPOCH[0] += 1
+        self._dev = {}
         self.built = True
 
     def compute_output_shape(self, input_shape):
@@ -1611,12 +1634,17 @@ class AttentiveStatsPooling(Layer):
         c = super().get_config()
         c.update({"attention_units": self.attentionUnits, "heads": self.heads, "include_std": self.includeStd, "epsilon": self.epsilon,
                   "attention_activation": self.attentionActivation})
+        if self.globalContext:
+            c["global_context"] = True
         return c
 
     def get_weights(self):
-        if not (self.hidden.built and self.logits.built):
+        if not (self.hidden.built and self.logits.built) or (self.globalContext and self.contextKernel is None):
             return []
-        return [self.hidden.kernel[0, 0], self.hidden.bias, self.logits.kernel[0, 0], self.logits.bias]
+        w1 = self.hidden.kernel[0, 0]
+        if self.globalContext:
+            w1 = np.concatenate([w1, self.contextKernel], 0)
+        return [w1, self.hidden.bias, self.logits.kernel[0, 0], self.logits.bias]
 
     def set_weights(self, weights, fmt="tensorflow"):
         """[W1, b1, W2, b2]; fmt "tensorflow": W1 (D, A), W2 (A, H) as get_weights() gives them, "kaldi": (A, D) and (H, A)."""
@@ -1629,16 +1657,30 @@ class AttentiveStatsPooling(Layer):
         if fmt == "kaldi":
             w1, w2 = w1.T, w2.T
         A, H = self.attentionUnits, self.heads
-        D = self.inputDim if self.built else (w1.shape[0] if w1.ndim == 2 else -1)
-        for name, w, shape in (("W1", w1, (D, A)), ("b1", b1.reshape(-1), (A,)), ("W2", w2, (A, H)), ("b2", b2.reshape(-1), (H,))):
+        nblk = 3 if self.globalContext else 1            # global_context: W1 (3 D, A), the rows of [h_t ; mu ; sigma]
+        D = self.inputDim if self.built else (w1.shape[0] // nblk if w1.ndim == 2 and w1.shape[0] % nblk == 0 else -1)
+        for name, w, shape in (("W1", w1, (nblk * D, A)), ("b1", b1.reshape(-1), (A,)), ("W2", w2, (A, H)), ("b2", b2.reshape(-1), (H,))):
             if w.shape != shape:
                 raise ValueError(f"{name}: expected shape {shape}, got {w.shape}")
         if D % H:
             raise ValueError(f"'heads' = {H} does not divide the {D} input channels")
+        if self.globalContext:
+            w1, self.contextKernel = w1[:D], np.ascontiguousarray(w1[D:])
         self.hidden.set_weights([w1[None, None], b1], fmt="tensorflow")
         self.logits.set_weights([w2[None, None], b2], fmt="tensorflow")
         self.inputDim = D
+        self._dev = {}
         self.built = True
+
+    def device_weights(self, device):
+        """global_context: (W1x (D, A), W1c (2 D, A), b1, W2 (A, H), b2) fp32 on the device, one set per device, dropped when the
+        weights change."""
+        key = (str(device), self._version)
+        if key not in self._dev:
+            self._dev = {k: v for k, v in self._dev.items() if k[1] == self._version}
+            self._dev[key] = tuple(ops.to_device_f32(a, device) for a in (self.hidden.kernel[0, 0], self.contextKernel, self.hidden.bias,
+                                                                          self.logits.kernel[0, 0], self.logits.bias))
+        return self._dev[key]
 
     @staticmethod
     def attention_gemm(gemm):
@@ -1648,12 +1690,21 @@ class AttentiveStatsPooling(Layer):
 
     def attend(self, x, lens=None, gemm=L.GEMM_F32, scratch=None):
         """x (B, T, D) fp32 rows the GEMM can read (TDNN.forward) -> the logits e (B, T, H), a view of a buffer whose pad columns are
-        finite. `scratch(role, shape, dtype)`: where the two outputs go (default: fresh zeroed tensors)."""
-        B, T, _ = x.shape
+        finite. `scratch(role, shape, dtype)`: where the two outputs go (default: fresh zeroed tensors). With global_context: the
+        three launches of include/ktf_gctx.h -- mu and sigma (B, 2, D) fp64, the per-utterance bias (B, A), the logits -- with roles of
+        their own for the first two, no hidden rows anywhere, no host synchronisation."""
+        B, T, D = x.shape
         A, H = self.attentionUnits, self.heads
         lda, lde = ops.round_up(A, 32), ops.round_up(H, 8)
         new = scratch or (lambda role, shape, dtype: torch.zeros(shape, dtype=dtype, device=x.device))
         g = self.attention_gemm(gemm)
+        if self.globalContext:
+            w1x, w1c, b1, w2, b2 = self.device_weights(x.device)
+            ctx = ops.gctx_stats(x, lens, self.epsilon, new("attn_ctx", (B, 2, D), torch.float64), D=D)
+            bias = ops.gctx_bias(ctx, w1c, b1, new("attn_ctx_bias", (B, lda), torch.float32)[:, :A])
+            e = new("attn_logits", (B, T, lde), torch.float32)
+            ops.gctx_logits(x, lens, w1x, bias, self._GCTX_ACTS[self.attentionActivation.lower()], w2, b2, g, e[:, :, :H], D=D)
+            return e[:, :, :H]
         h = self.hidden.forward(x, lens=lens, gemm=g, ldy=lda, out=new("attn_hidden", (B, T, lda), torch.float32))
         e = self.logits.forward(h[:, :, :A], lens=lens, gemm=g, ldy=lde, out=new("attn_logits", (B, T, lde), torch.float32))
         return e[:, :, :H]

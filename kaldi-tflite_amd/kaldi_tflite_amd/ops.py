@@ -1999,6 +1999,81 @@ def agg_conv(xs, lens, w, bias, nscale, nshift, act, gemm, y, widths=None):
     return y
 
 
+# ----------------------------------------------------------------------------- global-context attention (include/ktf_gctx.h)
+def _gctx_vec(name, t, n, dtype=torch.float32):
+    """An optional dense 1-D operand of n elements."""
+    if t is None:
+        return
+    _need_dense(name, t)
+    if t.dtype != dtype or tuple(t.shape) != (n,):
+        raise ValueError(f"{name}: expected ({n},) {dtype}, got {t.dtype} {tuple(t.shape)}")
+
+
+def gctx_row_tile(A, H, gemm=L.GEMM_F32):
+    """Rows per workgroup that gctx_logits uses for A hidden units and H heads."""
+    return _size("ktf_gctx_row_tile", int(A), int(H), int(gemm))
+
+
+def gctx_stats(x, lens, eps, ctx, D=None):
+    """x (B, T, ldx) fp32 rows with D channels (default: every column), lens (B,) int32 or None -> ctx (B, 2, D) fp64 preallocated:
+    the mean and sqrt(max(var, 0) + eps) of every channel over the frames of each utterance."""
+    if x.dim() != 3:
+        raise ValueError(f"x: a (B, T, ldx) tensor is expected, got {tuple(x.shape)}")
+    B, T = x.shape[0], x.shape[1]
+    D = x.shape[2] if D is None else int(D)
+    px, ldx = _attn_rows("x", x)
+    _gctx_vec("lens", lens, B, torch.int32)
+    if ctx is None or ctx.dtype != torch.float64 or tuple(ctx.shape) != (B, 2, D) or not ctx.is_contiguous():
+        raise ValueError(f"ctx: a contiguous ({B}, 2, {D}) fp64 tensor is expected")
+    _call("ktf_gctx_stats", x.device, px, B, T, D, ldx, L.ptr(lens), float(eps), L.ptr(ctx))
+    return ctx
+
+
+def gctx_bias(ctx, w1c, b1, g):
+    """ctx (B, 2, D) fp64 from gctx_stats, w1c (2 D, A) fp32 rows (a view with a row stride will do), b1 (A,) fp32 or None -> g (B, ldg)
+    fp32 rows preallocated, g[:, :A] = b1 + [mu ; sigma] w1c, rounded once from fp64."""
+    if ctx is None or ctx.dim() != 3 or ctx.shape[1] != 2 or ctx.dtype != torch.float64 or not ctx.is_contiguous():
+        raise ValueError("ctx: a contiguous (B, 2, D) fp64 tensor is expected")
+    B, _, D = ctx.shape
+    if w1c is None or w1c.dim() != 2 or w1c.shape[0] != 2 * D:
+        raise ValueError(f"w1c: a ({2 * D}, A) fp32 tensor is expected")
+    A = w1c.shape[1]
+    pw, ldw = _attn_mat("w1c", w1c)
+    pg, ldg = _attn_mat("g", g)
+    if g.shape[0] != B:
+        raise ValueError(f"g: {B} rows are expected, got {tuple(g.shape)}")
+    _gctx_vec("b1", b1, A)
+    _call("ktf_gctx_bias", ctx.device, L.ptr(ctx), B, D, pw, ldw, L.ptr(b1), A, pg, max(ldg, g.shape[1]))
+    return g
+
+
+def gctx_logits(x, lens, w1x, g, act, w2, b2, gemm, e, D=None):
+    """e[b, t] = act(x[b, t] w1x + g[b]) w2 + b2 for t < lens[b] in one launch: x (B, T, ldx) fp32 rows with D channels (default: every
+    column), w1x (D, A) and w2 (A, H) fp32 rows, g (B, ldg >= A) fp32 rows from gctx_bias, b2 (H,) fp32 or None, act KTF_ACT_TANH or
+    _RELU, gemm KTF_GEMM_F32 or _BF16X3; e (B, T, lde) fp32 rows with H = w2.shape[1] columns, preallocated. Rows of e at or beyond an
+    utterance's length are left as they are."""
+    if x.dim() != 3 or e.dim() != 3 or x.shape[:2] != e.shape[:2]:
+        raise ValueError(f"x (B, T, ldx) and e (B, T, lde) with the same B and T are expected, got {tuple(x.shape)} and {tuple(e.shape)}")
+    B, T = x.shape[0], x.shape[1]
+    D = x.shape[2] if D is None else int(D)
+    px, ldx = _attn_rows("x", x)
+    pe, lde = _attn_rows("e", e)
+    if w1x is None or w2 is None or g is None:
+        raise ValueError("w1x, w2 and g: 2-D fp32 tensors are expected")
+    pw1, ldw1 = _attn_mat("w1x", w1x)
+    pw2, ldw2 = _attn_mat("w2", w2)
+    pg, ldg = _attn_mat("g", g)
+    A, H = w1x.shape[1], w2.shape[1]
+    if w1x.shape[0] != D or w2.shape[0] != A or g.shape[0] != B or e.shape[2] != H:
+        raise ValueError(f"expected w1x ({D}, A), w2 (A, H), g ({B}, >= A) and e with H columns, got {tuple(w1x.shape)}, {tuple(w2.shape)}, "
+                         f"{tuple(g.shape)}, {tuple(e.shape)}")
+    _gctx_vec("lens", lens, B, torch.int32)
+    _gctx_vec("b2", b2, H)
+    _call("ktf_gctx_logits", x.device, px, B, T, D, ldx, L.ptr(lens), pw1, ldw1, pg, max(ldg, g.shape[1]), A, int(act), pw2, ldw2, L.ptr(b2), H,
+          int(gemm), pe, lde)
+    return e
+
+
 # ----------------------------------------------------------------------------- training examples (include/ktf_egs.h)
 EGS_DTYPES = {torch.float32: L.KTF_F32, torch.float16: L.KTF_F16}
 
