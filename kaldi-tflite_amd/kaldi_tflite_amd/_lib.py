@@ -362,6 +362,14 @@ GCTX_PROTOTYPES = {
     "ktf_gctx_row_tile": (_i32, [_i32, _i32, _i32]),
 }
 GCTX_MAX_UNITS = 256                # ktf_gctx_*: hidden units of the attention
+# name -> (restype, argtypes); mirrors include/ktf_gcgrad.h one to one
+GCGRAD_PROTOTYPES = {
+    "ktf_gcgrad_hidden": (C.c_int, [_P, _i64, _i64, _i32, _i64, _P, _P, _i64, _P, _i64, _i32, _i32, _P, _i64, _i32, _i32, _P, _i64, _P, _P, _i64, _P]),
+    "ktf_gcgrad_context": (C.c_int, [_P, _i64, _i64, _i32, _i64, _P, _P, _i32, _P, _i64, _f32, _P, _i64, _P, _P, _P, C.c_size_t, _P]),
+    "ktf_gcgrad_data": (C.c_int, [_P, _i64, _i64, _i32, _i64, _P, _P, _i64, _i32, _P, _i64, _P, _P, _i32, _i32, _P, _i64, _P]),
+    "ktf_gcgrad_row_tile": (_i32, [_i32, _i32, _i32]),
+    "ktf_gcgrad_workspace_bytes": (_i64, [_i64, _i32]),
+}
 AGG_MAX_SOURCES, AGG_MAX_WIDTH, AGG_MAX_UNITS = 4, 4096, 8192   # ktf_agg_*: tensors per call, channels of one, outputs
 ATTN_MAX_BATCH, ATTN_MAX_ROWS, ATTN_MAX_DIM = 65535, 1 << 30, 1 << 20   # ktf_attn_*: utterances, frames and channels per call
 HEAD_MAX_CENTERS, HEAD_MAX_TOPK = 8, 64   # ktf_head_*: sub-centres per class; penalised classes per row
@@ -400,7 +408,7 @@ def load():
                               + list(GRAD_PROTOTYPES.items()) + list(NORM_PROTOTYPES.items()) + list(LOSS_PROTOTYPES.items())
                               + list(EGS_PROTOTYPES.items()) + list(OPTIM_PROTOTYPES.items()) + list(HEAD_PROTOTYPES.items())
                               + list(ATTN_PROTOTYPES.items()) + list(DENSE_PROTOTYPES.items()) + list(RES2_PROTOTYPES.items())
-                              + list(SE_PROTOTYPES.items()) + list(AGG_PROTOTYPES.items()) + list(GCTX_PROTOTYPES.items())):
+                              + list(SE_PROTOTYPES.items()) + list(AGG_PROTOTYPES.items()) + list(GCTX_PROTOTYPES.items()) + list(GCGRAD_PROTOTYPES.items())):
         fn = getattr(lib, name)          # AttributeError = header/library mismatch
         fn.restype = res
         fn.argtypes = args

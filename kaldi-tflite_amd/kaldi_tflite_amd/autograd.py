@@ -286,6 +286,106 @@ def attentive_stats_pooling(x, e, lens=None, include_std=True, epsilon=1e-10):
                                         float(epsilon))
 
 
+_GCTX_ACTS = {"tanh": L.ACT_TANH, "relu": L.ACT_RELU}
+
+
+class _GlobalContextAttention(torch.autograd.Function):
+    """include/ktf_gctx.h forward, include/ktf_gcgrad.h backward: saves x, the weights, ctx, g and lens (e is the pooling's to keep) --
+    the hidden rows are recomputed."""
+
+    @staticmethod
+    def forward(ctx, x, w1, b1, w2, b2, lens, act, epsilon, gemm):
+        B, T, D = x.shape
+        A, H = w1.shape[1], w2.shape[1]
+        x, w1, w2 = x.contiguous(), w1.contiguous(), w2.contiguous()
+        stats = ops.gctx_stats(x, lens, epsilon, torch.empty((B, 2, D), dtype=torch.float64, device=x.device))
+        g = ops.gctx_bias(stats, w1[D:], b1, torch.empty((B, A), dtype=torch.float32, device=x.device))
+        e = torch.zeros((B, T, H), dtype=torch.float32, device=x.device)      # rows at and beyond an utterance's length stay zero
+        ops.gctx_logits(x, lens, w1[:D], g, act, w2, b2, gemm, e)
+        ctx.save_for_backward(x, w1, w2, lens, stats, g)
+        ctx.cfg = (act, epsilon, gemm, b1 is not None, b2 is not None)
+        return e
+
+    @staticmethod
+    def backward(ctx, ge):
+        x, w1, w2, lens, stats, g = ctx.saved_tensors
+        act, epsilon, gemm, has_b1, has_b2 = ctx.cfg
+        B, T, D = x.shape
+        A, H = w1.shape[1], w2.shape[1]
+        dev = x.device
+        need = ctx.needs_input_grad
+        dx = torch.zeros_like(x) if need[0] else None
+        dw1 = torch.zeros_like(w1) if need[1] else None
+        db1 = torch.zeros((A,), dtype=torch.float32, device=dev) if has_b1 and need[2] else None
+        dw2 = torch.zeros_like(w2) if need[3] else None
+        db2 = torch.zeros((H,), dtype=torch.float32, device=dev) if has_b2 and need[4] else None
+        if B == 0 or T == 0:
+            return dx, dw1, db1, dw2, db2, None, None, None, None
+        de = ge.to(torch.float32).contiguous()
+        Ap = ops.round_up(A, 32)                                   # the pad columns stay zero: finite, as the weight-gradient GEMM asks
+        dz = torch.zeros((B, T, Ap), dtype=torch.float32, device=dev)
+        h = torch.zeros((B, T, Ap), dtype=torch.float32, device=dev)
+        ops.gcgrad_hidden(x, lens, w1[:D], g, act, w2, gemm, de, dz[:, :, :A], h[:, :, :A])
+        if need[0] or need[1] or db1 is not None:
+            coef = torch.empty((B, 2, D), dtype=torch.float64, device=dev)
+            ops.gcgrad_context(dz[:, :, :A], lens, stats, w1[D:], epsilon, dw1[D:] if need[1] else None, db1, coef,
+                               ops.gcgrad_workspace(B, A, dev))
+            if need[0]:
+                ops.gcgrad_data(dz[:, :, :A], lens, w1[:D], x, stats, coef, gemm, dx, accumulate=False)
+        if need[1]:                                                # dW1x = sum x^T dz: the context-[0] weight gradient over (x, dz)
+            dw1[:D] = _gemm_weight_grad(x, dz, lens, D, A, gemm, None).T
+        if need[3] or db2 is not None:                             # dW2 = sum h^T de, db2 = sum de: ... over (h, de)
+            dw = _gemm_weight_grad(h, de, lens, A, H, gemm, db2)
+            if need[3]:
+                dw2.copy_(dw.T)
+        return dx, dw1, db1, dw2, db2, None, None, None, None
+
+
+def _gemm_weight_grad(x, g, lens, din, units, gemm, dbias):
+    """sum_b sum_{t < len_b} g[b,t,u] x[b,t,d] -> (units, din) by the context-[0] weight call of include/ktf_grad.h in mode `gemm`; dbias
+    (units,) or None receives sum g. x (B, T, >= din) is padded to the GEMM's operand layout only where it does not have it."""
+    B, T = x.shape[0], x.shape[1]
+    d = _desc(units, din, [0], 1, "SAME")
+    Dp, Up = d.din_pad, ops.round_up(units, 256)
+    xp = x if x.shape[2] == Dp and x.is_contiguous() else torch.nn.functional.pad(x[:, :, :din], (0, Dp - din)).contiguous()
+    g = g.contiguous()
+    dwp = torch.empty((Up, Dp), dtype=torch.float32, device=x.device)
+    if gemm == L.GEMM_F32:
+        ops.grad_tdnn_weights(xp, lens, d, g, dwp, dbias, ops.grad_tdnn_workspace(B, T, d, x.device))
+    else:
+        ops.grad_tdnn16_weights(xp, lens, d, g, dwp, dbias, ops.grad_tdnn16_workspace(B, T, d, gemm, x.device), gemm)
+    return dwp[:units, :din]
+
+
+def global_context_attention(x, w1, b1, w2, b2, lens=None, activation="tanh", epsilon=1e-10, gemm="f32"):
+    """The attention logits of AttentiveStatsPooling(global_context=True) (include/ktf_gctx.h), e = W2^T act(W1^T [x_t ; mu ; sigma] + b1) +
+    b2 with mu and sigma = sqrt(max(var, 0) + epsilon) the unweighted statistics of the utterance, differentiable in x, w1, b1, w2 and
+    b2 (include/ktf_gcgrad.h): x (B, T, D) fp32 on the GPU, w1 (3 D, A) with A <= 256, b1 (A,) or None, w2 (A, H), b2 (H,) or None, lens
+    (B,) or None, activation "tanh" or "relu", gemm "f32" or "bf16x3" (the logits go through exp: one-pass bf16 is refused). Returns
+    (B, T, H) with zero rows at and beyond an utterance's length, for `attentive_stats_pooling`. No (B, T, 3 D) tensor is formed; the
+    backward keeps x, e and three per-utterance tensors, recomputes the hidden rows and forms two (B, T, A) tensors while it runs."""
+    code = _gemm_code(gemm)
+    if code not in (L.GEMM_F32, L.GEMM_BF16X3):
+        raise ValueError(f"gemm must be 'f32' or 'bf16x3' for the attention logits, got {gemm!r}")
+    act = activation.lower() if isinstance(activation, str) else activation
+    if act not in _GCTX_ACTS:
+        raise ValueError(f"activation must be 'tanh' or 'relu', got {activation!r}")
+    if not 0.0 <= float(epsilon) < float("inf"):
+        raise ValueError(f"epsilon must be finite and not negative, got {epsilon!r}")
+    if not all(isinstance(t, torch.Tensor) for t in (x, w1, w2)) or x.dim() != 3 or w1.dim() != 2 or w2.dim() != 2 \
+            or w1.shape[0] != 3 * x.shape[2] or w2.shape[0] != w1.shape[1]:
+        raise ValueError(f"expected x (B, T, D), w1 (3 D, A) and w2 (A, H), got shapes {[tuple(getattr(t, 'shape', ())) for t in (x, w1, w2)]}")
+    for name, b, n in (("b1", b1, w1.shape[1]), ("b2", b2, w2.shape[1])):
+        if b is not None and tuple(b.shape) != (n,):
+            raise ValueError(f"{name} shape {tuple(b.shape)} != ({n},)")
+    _on_gpu(x, "x")
+    _on_gpu(w1, "w1")
+    _on_gpu(w2, "w2")
+    f32 = lambda t: None if t is None else t.to(torch.float32).contiguous()  # noqa: E731
+    return _GlobalContextAttention.apply(x.to(torch.float32), f32(w1), f32(b1), f32(w2), f32(b2), _lens(lens, x.shape[0], x.device),
+                                         _GCTX_ACTS[act], float(epsilon), code)
+
+
 class _Res2Conv(torch.autograd.Function):
     """include/ktf_res2.h rules 7 - 13: saves x, y, a (with the norm pair only) and lens."""
 
@@ -562,7 +662,8 @@ class TrainableSequential(torch.nn.Module):
     (in front of the pooling also SqueezeExcite, as `squeeze_excite`, with the output of the layer `residual_from` names kept for it, and Res2Conv, as `res2_conv`: kernel, bias and -- batch_norm=True -- norm_scale / norm_shift trained as a
     per-channel affine; batch statistics inside the block are not taken, since stage i + 1 reads stage i normalised; and Aggregate, as
     `aggregate`, with the outputs of the layers its `sources` name kept for it, its own activation as torch.relu and its norm pair as a per-channel affine)
-    -> reducing StatsPooling or AttentiveStatsPooling (its two affines and `attentive_stats_pooling`) -> TDNN (context [0]) ... Parameters start from the layers' current weights; `forward(feats, lens)`
+    -> reducing StatsPooling or AttentiveStatsPooling (its two affines and `attentive_stats_pooling`; with the layer's global_context, and
+    only under global_context=True here, `global_context_attention` with the four parameters in the layer's get_weights() shapes) -> TDNN (context [0]) ... Parameters start from the layers' current weights; `forward(feats, lens)`
     returns the last layer's output -- (B, T_out, units), or (B, units) behind the pooling -- for `ClassifierHead` (below) or a head and a loss written in torch;
     `export()` writes parameters and moving statistics back into the layers. The layers must be built (a Sequential with an Input, or
     one that has run or loaded weights). gemm: the mode of every TDNN GEMM, forward and backward ("f32", "bf16", "bf16x3": `tdnn_affine`),
@@ -571,11 +672,13 @@ class TrainableSequential(torch.nn.Module):
     a TDNN's activation="relu") that stands immediately in front of it, with relu=False otherwise; a ReLU that no BatchNorm follows
     stays torch.relu. Parameters, buffers, their names and `export()` are the same either way."""
 
-    def __init__(self, seq, device=None, gemm="f32", fused_norm=False):
+    def __init__(self, seq, device=None, gemm="f32", fused_norm=False, global_context=False):
         super().__init__()
         _gemm_code(gemm)
         if not isinstance(fused_norm, bool):
             raise ValueError(f"fused_norm must be True or False, got {fused_norm!r}")
+        if not isinstance(global_context, bool):
+            raise ValueError(f"global_context must be True or False, got {global_context!r}")
         self.gemm = gemm
         self.fused_norm = fused_norm
         self.seq = getattr(seq, "xvec", seq)
@@ -647,10 +750,19 @@ class TrainableSequential(torch.nn.Module):
                 if pooled or act not in ("tanh", "relu"):
                     raise NotImplementedError(f"layer '{l.name}' (AttentiveStatsPooling with activation {l.attentionActivation!r}, or a "
                                               "second pooling) has no gradient in ktf.autograd")
-                if l.globalContext:
-                    raise NotImplementedError(f"layer '{l.name}' (AttentiveStatsPooling with global_context) has no gradient in ktf.autograd")
+                if l.globalContext and not global_context:
+                    raise NotImplementedError(f"layer '{l.name}' (AttentiveStatsPooling with global_context) has no gradient in ktf.autograd "
+                                              "unless TrainableSequential(..., global_context=True) asks for `global_context_attention`")
+                if l.globalContext and gemm == "bf16":
+                    raise NotImplementedError(f"layer '{l.name}' (AttentiveStatsPooling with global_context) trains in gemm 'f32' or 'bf16x3', "
+                                              "not in one-pass 'bf16'")
                 pooled = True
                 at = len(self.params)
+                if l.globalContext:                                # W1 (3 D, A), b1, W2 (A, H), b2: the layer's own get_weights()
+                    for t in l.get_weights():
+                        self.params.append(f32(t))
+                    self.steps.append(("gctx", l, at))
+                    continue
                 for t in (l.hidden, l.logits):                     # W1 [u, k, d], b1, W2 [u, k, d], b2
                     self.params.append(f32(t.kernel[0].transpose(2, 0, 1)))
                     self.params.append(f32(t.bias))
@@ -712,6 +824,11 @@ class TrainableSequential(torch.nn.Module):
                 e = tdnn_affine(h, self.params[at + 2], self.params[at + 3], [0], lens, gemm=self.gemm)
                 x = attentive_stats_pooling(x, e, lens, l.includeStd, l.epsilon)
                 pooled = True
+            elif kind == "gctx":
+                e = global_context_attention(x, *self.params[at:at + 4], lens=lens, activation=l.attentionActivation, epsilon=l.epsilon,
+                                             gemm=self.gemm)
+                x = attentive_stats_pooling(x, e, lens, l.includeStd, l.epsilon)
+                pooled = True
             else:
                 x = stats_pooling(x, lens, l.includeStd, l.epsilon, l.inputPeriod)
                 pooled = True
@@ -740,6 +857,8 @@ class TrainableSequential(torch.nn.Module):
             elif kind == "attn":
                 w1, b1, w2, b2 = (self.params[at + k].detach().cpu().numpy() for k in range(4))
                 l.set_weights([w1[:, 0, :].T, b1, w2[:, 0, :].T, b2], fmt="tensorflow")
+            elif kind == "gctx":
+                l.set_weights([self.params[at + k].detach().cpu().numpy() for k in range(4)], fmt="tensorflow")
         return self.seq
 
 

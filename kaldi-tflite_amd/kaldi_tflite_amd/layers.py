@@ -1575,7 +1575,7 @@ class AttentiveStatsPooling(Layer):
     `global_context` (ECAPA-TDNN, include/ktf_gctx.h): the attention reads [h_t ; mu ; sigma], the frame with the unweighted mean and
     standard deviation sqrt(max(var, 0) + epsilon) of its utterance. W1 is then (3 D, A), rows in that order; the logits come from three
     launches of their own (attend()) that never form the concatenation, with attention_units <= 256 and a tanh or relu activation.
-    Inference only: ktf.autograd has no gradient of it yet."""
+    Training: ktf.autograd.global_context_attention, TrainableSequential(..., global_context=True) (include/ktf_gcgrad.h)."""
 
     _GCTX_ACTS = {"tanh": L.ACT_TANH, "relu": L.ACT_RELU}
 

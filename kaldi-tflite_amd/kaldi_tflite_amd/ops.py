@@ -2074,6 +2074,98 @@ def gctx_logits(x, lens, w1x, g, act, w2, b2, gemm, e, D=None):
     return e
 
 
+# ----------------------------------------------------------------------------- ... and its gradient (include/ktf_gcgrad.h)
+def gcgrad_row_tile(A, H, gemm=L.GEMM_F32):
+    """Rows per workgroup that gcgrad_hidden and gcgrad_data use for A hidden units and H heads."""
+    return _size("ktf_gcgrad_row_tile", int(A), int(H), int(gemm))
+
+
+def gcgrad_workspace(B, A, device):
+    """The workspace gcgrad_context takes for B utterances and A hidden units."""
+    return _workspace("ktf_gcgrad_workspace_bytes", int(B), int(A), device=device)
+
+
+def _gcgrad_ctx(name, t, B, D):
+    if t is None or t.dtype != torch.float64 or tuple(t.shape) != (B, 2, D) or not t.is_contiguous():
+        raise ValueError(f"{name}: a contiguous ({B}, 2, {D}) fp64 tensor is expected")
+
+
+def gcgrad_hidden(x, lens, w1x, g, act, w2, gemm, de, dz, h, D=None):
+    """The operands of gctx_logits and de (B, T, lde) fp32 rows with H = w2.shape[1] heads -> dz = (de w2^T) act'(z) and h = act(z),
+    (B, T, ldz) fp32 rows with A columns and ONE row stride, preallocated; rows at or beyond an utterance's length are written as zero."""
+    if x.dim() != 3 or any(t is None or t.dim() != 3 or t.shape[:2] != x.shape[:2] for t in (de, dz, h)):
+        raise ValueError("x (B, T, ldx), de (B, T, lde), dz and h (B, T, ldz) with the same B and T are expected")
+    B, T = x.shape[0], x.shape[1]
+    D = x.shape[2] if D is None else int(D)
+    px, ldx = _attn_rows("x", x)
+    pde, lde = _attn_rows("de", de)
+    pdz, ldz = _attn_rows("dz", dz)
+    ph, ldh = _attn_rows("h", h)
+    if w1x is None or w2 is None or g is None:
+        raise ValueError("w1x, w2 and g: 2-D fp32 tensors are expected")
+    pw1, ldw1 = _attn_mat("w1x", w1x)
+    pw2, ldw2 = _attn_mat("w2", w2)
+    pg, ldg = _attn_mat("g", g)
+    A, H = w1x.shape[1], w2.shape[1]
+    if w1x.shape[0] != D or w2.shape[0] != A or g.shape[0] != B or de.shape[2] != H or dz.shape[2] != A or h.shape[2] != A or ldh != ldz:
+        raise ValueError(f"expected w1x ({D}, A), w2 (A, H), g ({B}, >= A), de with H columns, dz and h with A columns and one row stride, got "
+                         f"{tuple(w1x.shape)}, {tuple(w2.shape)}, {tuple(g.shape)}, {tuple(de.shape)}, {tuple(dz.shape)}, {tuple(h.shape)}")
+    _gctx_vec("lens", lens, B, torch.int32)
+    _call("ktf_gcgrad_hidden", x.device, px, B, T, D, ldx, L.ptr(lens), pw1, ldw1, pg, max(ldg, g.shape[1]), A, int(act), pw2, ldw2, H, int(gemm),
+          pde, lde, pdz, ph, ldz)
+    return dz, h
+
+
+def gcgrad_context(dz, lens, ctx, w1c, eps, dw1c, db1, coef, workspace):
+    """dz (B, T, ldz) from gcgrad_hidden, ctx (B, 2, D) fp64 from gctx_stats, w1c (2 D, A) fp32 rows -> coef (B, 2, D) fp64, the two
+    per-channel coefficients of gcgrad_data, and dw1c (2 D, A) fp32 rows, db1 (A,) fp32 (either may be None), all preallocated."""
+    if dz is None or dz.dim() != 3 or ctx is None or ctx.dim() != 3:
+        raise ValueError("dz (B, T, ldz) fp32 and ctx (B, 2, D) fp64 are expected")
+    B, T, A = dz.shape
+    D = ctx.shape[2]
+    pdz, ldz = _attn_rows("dz", dz)
+    _gcgrad_ctx("ctx", ctx, B, D)
+    _gcgrad_ctx("coef", coef, B, D)
+    if w1c is None or w1c.dim() != 2 or tuple(w1c.shape) != (2 * D, A):
+        raise ValueError(f"w1c: a ({2 * D}, {A}) fp32 tensor is expected")
+    pw, ldw = _attn_mat("w1c", w1c)
+    pdw, lddw = (None, 0)
+    if dw1c is not None:
+        if dw1c.dim() != 2 or tuple(dw1c.shape) != (2 * D, A):
+            raise ValueError(f"dw1c: a ({2 * D}, {A}) fp32 tensor is expected")
+        pdw, lddw = _attn_mat("dw1c", dw1c)
+    _gctx_vec("lens", lens, B, torch.int32)
+    _gctx_vec("db1", db1, A)
+    _need_dense("workspace", workspace)
+    _call("ktf_gcgrad_context", dz.device, pdz, B, T, A, ldz, L.ptr(lens), L.ptr(ctx), D, pw, ldw, float(eps), pdw, lddw, L.ptr(db1), L.ptr(coef),
+          L.ptr(workspace), 0 if workspace is None else workspace.numel())
+    return coef, dw1c, db1
+
+
+def gcgrad_data(dz, lens, w1x, x, ctx, coef, gemm, dx, accumulate=True, D=None):
+    """dx[b, t] (+)= dz[b, t] w1x^T + coef[b, 0] + coef[b, 1] (x[b, t] - ctx[b, 0]) for t < lens[b], in place: dx (B, T, lddx) fp32 rows
+    with D channels holds the gradient to add to (accumulate=False: it is not read); rows at or beyond an utterance's length are left
+    as they are."""
+    if x.dim() != 3 or any(t is None or t.dim() != 3 or t.shape[:2] != x.shape[:2] for t in (dz, dx)):
+        raise ValueError("x (B, T, ldx), dz (B, T, ldz) and dx (B, T, lddx) with the same B and T are expected")
+    B, T, A = dz.shape
+    D = x.shape[2] if D is None else int(D)
+    px, ldx = _attn_rows("x", x)
+    pdz, ldz = _attn_rows("dz", dz)
+    pdx, lddx = _attn_rows("dx", dx)
+    if w1x is None:
+        raise ValueError("w1x: a 2-D fp32 tensor is expected")
+    pw1, ldw1 = _attn_mat("w1x", w1x)
+    if tuple(w1x.shape) != (D, A) or dx.shape[2] != D:
+        raise ValueError(f"expected w1x ({D}, {A}) and dx with {D} columns, got {tuple(w1x.shape)} and {tuple(dx.shape)}")
+    _gcgrad_ctx("ctx", ctx, B, D)
+    _gcgrad_ctx("coef", coef, B, D)
+    _gctx_vec("lens", lens, B, torch.int32)
+    _call("ktf_gcgrad_data", x.device, pdz, B, T, A, ldz, L.ptr(lens), pw1, ldw1, D, px, ldx, L.ptr(ctx), L.ptr(coef), int(gemm),
+          int(bool(accumulate)), pdx, lddx)
+    return dx
+
+
 # ----------------------------------------------------------------------------- training examples (include/ktf_egs.h)
 EGS_DTYPES = {torch.float32: L.KTF_F32, torch.float16: L.KTF_F16}
 
